@@ -8,7 +8,13 @@ the device pipeline (prepare -> seed -> locate/vote -> pair filter -> Myers -> p
 are already resident in HBM; the 32-byte records and the CIGAR pool stay in HBM.  `--config 1` = configs[1] (10 M 150 bp SE
 reads, 46 Mb genome, -e 0.04), `--config 3` = configs[3]'s per-GPU share (--sensitive), `--config 4` = configs[4] (250 bp).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] ...
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--dump-outputs DIR] [--full] ...
+
+A plain run sets up, warms up, times exactly K steps and prints the result line (`value`, `ms_per_step` = milliseconds of one timed
+step, the roofline of the timed steps' own kernel times).  `--full` adds everything else the bench measures, each on runs of its own:
+the timed region stretched to >= --min-seconds, the single-lane pass, the CPU baseline and the SAM identity check against the
+reference, the PCIe-inclusive, file-to-file and multi-context keys and the secondary / stress keys.  `--dump-outputs DIR` writes
+what the last timed step computed (a fixed sample of its records, see dump_outputs) as DIR/<name>.npy.
 
 N > 1 without WORLD_SIZE in the environment: bench.py starts `python -m torch.distributed.run --nproc-per-node N bench.py ...`
 as a CHILD process before anything touches the GPU and exits with its code (a process that has initialised the GPU is never
@@ -40,7 +46,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 GATHER_CEILING_GREQ = 54.0   # measured on this chip: dependent divergent gathers/s (tools/gather_bench.hip, profiles/r01_gather_bench.txt)
 SECTOR_CEILING_GBS = 3100.0  # the same measurement in bytes: 48.4 G gathers/s over a 34 GB table x one 64-byte sector each
-MIN_TIMED_S = 2.0            # the timed region is stretched to at least this (whole extra passes per step) whatever --steps says
+MIN_TIMED_S = 2.0            # --full: the timed region is stretched to at least this (whole extra passes per step) whatever --steps says
 SECONDARY_MIN_S = 1.0        # ... and that of every secondary key to this
 
 CONFIGS = {
@@ -80,7 +86,13 @@ def parse(argv=None):
     ap.add_argument("--no-single-lane", action="store_true", help="skip the extra single-lane pass that times the kernels alone")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurements (configs[1] SE line, stress keys)")
     ap.add_argument("--no-stress", action="store_true", help="keep the PCIe-inclusive and file-to-file keys, skip the stress keys behind them (other genomes / read sets)")
-    ap.add_argument("--min-seconds", type=float, default=MIN_TIMED_S)
+    ap.add_argument("--min-seconds", type=float, default=None,
+                    help="stretch the timed region to at least this by whole extra passes per step (default: %.1f with --full, 0 without)" % MIN_TIMED_S)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: single-lane pass, CPU baseline and reference check, PCIe / file / multi-context keys, "
+                         "secondary and stress keys (a plain run does only the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed, seeded sample of what the last timed step computed as DIR/<name>.npy (float64 / float32, < 64 MB; e.g. bench_out/dump)")
     ap.add_argument("--host-index", action="store_true", help="build the index with the host builder (bmbs_index_build)")
     ap.add_argument("--dry-run", action="store_true", help="launcher / collective check without a GPU: gloo, no mapping (tests)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="collective backend of the N > 1 run (gloo: tests)")
@@ -90,6 +102,8 @@ def parse(argv=None):
                          "reads drawn from its N-free parts (SURVEY.md 8d); also BMBS_BENCH_FASTA")
     ap.add_argument("--workdir", default=os.environ.get("BMBS_BENCH_DIR", "/tmp/bmbs_bench"))
     a = ap.parse_args(argv)
+    if a.min_seconds is None:
+        a.min_seconds = MIN_TIMED_S if a.full else 0.0
     cfg = dict(CONFIGS[a.config])
     for key, attr in (("units", "units"), ("launches", "launches"), ("genome", "genome"), ("read_len", "read_len"), ("e", "e"),
                       ("pe", "pe"), ("sensitive", "sensitive")):
@@ -199,9 +213,32 @@ def plant_repeat_families(chroms, seed=99, device="cuda"):
     return planted / total
 
 
+def synth_genome(total_len, n_chrom, seed):
+    """synth.make_genome(total_len, n_chrom, seed), the same bytes in a fraction of the time (3.1 Gb: seconds instead of ~20 s).
+    Generator.integers(0, 4, n, dtype=uint8) keeps the top two bits of every byte of the PCG64 stream read as 32-bit words (low word
+    of each 64-bit draw first; Lemire's bounded method never rejects for a power-of-two range), and the chromosomes take consecutive
+    words of that one stream.  So each chromosome is drawn on a thread of its own from a generator advanced to its first word.
+    tests/test_host_logic.py holds this equal to synth.make_genome."""
+    from concurrent.futures import ThreadPoolExecutor
+    from bitmapperbs_amd import synth
+    per = total_len // n_chrom
+    words = (per + 3) // 4                                   # 32-bit words one chromosome consumes
+
+    def one(i):
+        w0 = i * words
+        bg = np.random.PCG64(seed)
+        bg.advance(w0 // 2)
+        b = bg.random_raw((w0 % 2 + words + 1) // 2).view(np.uint32)[w0 % 2:w0 % 2 + words].view(np.uint8)[:per]
+        np.right_shift(b, 6, out=b)
+        return synth._ACGT.take(b)
+    with ThreadPoolExecutor(max(1, min(16, n_chrom, os.cpu_count() or 1))) as ex:
+        chroms = list(ex.map(one, range(n_chrom)))
+    return ["chr%d" % (i + 1) for i in range(n_chrom)], chroms
+
+
 def make_genome(cfg, repeats=0, grch38_like=False):
     from bitmapperbs_amd import synth
-    names, chroms = synth.make_genome(cfg["genome"], cfg["n_chrom"], seed=20240229)
+    names, chroms = synth_genome(cfg["genome"], cfg["n_chrom"], seed=20240229)
     if grch38_like:
         frac = plant_repeat_families(chroms)
         sys.stderr.write("[bench] GRCh38-like repeat families planted: %.1f %% of the bases\n" % (100 * frac))
@@ -704,6 +741,57 @@ def timed(job, steps, warmup, min_seconds, world, dist, torch, cdev="cuda"):
     return dt, passes, kern_ms
 
 
+DUMP_RECORDS = 1 << 17       # --dump-outputs: records sampled from the last timed step (11 fields x 8 B + <= 70 CIGAR ops x 4 B each: < 64 MB)
+DUMP_FIELDS = ("pos", "chrom", "flag", "nm", "score", "status", "mapq", "n_cigar", "path", "n_cand", "tlen")
+
+
+def dump_outputs(path, job, stats):
+    """--dump-outputs DIR: what the timed path handed its caller in the last timed step, for comparing two builds output for output.
+    The step's result records (32 bytes per read, every launch of the step: 3.2 GB at the default size) are sampled at DUMP_RECORDS
+    fixed positions (seeded: the same for the same arguments) and written field by field as float64, records_<field>.npy;
+    sample_index.npy is each sampled record's position in the step (launch x reads per launch + read).  The CIGAR operations of the
+    sampled records (len << 4 | op, what the pool holds at the record's cigar_off) follow one another in cigar_ops.npy (float32),
+    cigar_ops_count.npy gives each record's count there (0 for "<L>M" and for records without an alignment).  cigar_off itself, a
+    position in the pool, is not written: where a record's operations land in the pool is the library's business.  mapstats.npy holds
+    the five counters of the timed steps (float64)."""
+    import torch
+    from bitmapperbs_amd import capi
+    os.makedirs(path, exist_ok=True)
+    nrec = job.reads_per_launch
+    total = nrec * len(job.res_all)
+    pick = np.sort(np.random.default_rng(20240229).choice(total, size=min(DUMP_RECORDS, total), replace=False))
+    recs, ops, counts = [], [], []
+    for b in range(len(job.res_all)):
+        idx = pick[(pick >= b * nrec) & (pick < (b + 1) * nrec)] - b * nrec
+        if idx.size == 0:
+            continue
+        rows = job.res_all[b][torch.from_numpy(idx).to(job.res_all[b].device)].cpu().numpy()
+        r = np.ascontiguousarray(rows).view(capi.RESULT_DTYPE).reshape(-1)
+        n = r["n_cigar"].astype(np.int64)
+        off = r["cigar_off"].astype(np.int64)
+        # only ops that lie inside the pool are read (checked here, on the host, before any index reaches the device)
+        ok = (r["status"] == capi.ST_UNIQUE) & (n > 0) & (n < 255) & (off + n <= job.cig_cap)
+        cnt = np.where(ok, n, 0)
+        if cnt.sum():
+            flat = np.repeat(off[ok], cnt[ok]) + (np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt[ok]) - cnt[ok], cnt[ok]))
+            pool = job.cig_all[b]
+            ops.append(pool[torch.from_numpy(flat).to(pool.device)].cpu().numpy().view(np.uint32))
+        recs.append(r)
+        counts.append(cnt)
+    r = np.concatenate(recs)
+    out = {"records_%s" % f: r[f].astype(np.float64) for f in DUMP_FIELDS}
+    out["sample_index"] = pick.astype(np.float64)
+    out["cigar_ops"] = (np.concatenate(ops) if ops else np.zeros(0, np.uint32)).astype(np.float32)       # ops < 2^24: exact
+    out["cigar_ops_count"] = np.concatenate(counts).astype(np.float64)
+    out["mapstats"] = np.asarray(stats, dtype=np.float64)
+    size = sum(a.nbytes for a in out.values())
+    if size > 64 << 20:
+        raise SystemExit("--dump-outputs: %d bytes would exceed 64 MB" % size)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "files": len(out), "bytes": int(size), "records_sampled": int(pick.size)}
+
+
 def two_context_rate(m, ix, job, cfg, local, torch, steps=6, n_ctx=2):
     """the main configuration's launches dealt to TWO contexts on one attached index (bmbs_index_share: own stream and work buffers
     each), driven by two host threads -- how bmbs_search runs a device by default.  Kernels of different launches overlap (the DP
@@ -1188,11 +1276,14 @@ def main():
 
     dt, passes, kern_ms = timed(job, args.steps, args.warmup, args.min_seconds, world, dist, torch, cdev)
     stats = torch.from_numpy(m.stats()).to(cdev)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, job, m.stats())
     # The same launches once more on ONE lane (a context of its own on the same index, BMBS_LANES=1, outside the timed region): with
     # two lanes the kernels of two chunks share the chip, so a kernel's own duration -- the roofline's denominator -- is longer than
     # it is alone although the job is faster; this gives the duration alone beside it.  Rank 0, N = 1 only.
     single = None
-    if world == 1 and not args.no_single_lane and os.environ.get("BMBS_LANES", "2") != "1":
+    if args.full and world == 1 and not args.no_single_lane and os.environ.get("BMBS_LANES", "2") != "1":
         old_l = os.environ.get("BMBS_LANES")
         os.environ["BMBS_LANES"] = "1"
         try:
@@ -1265,8 +1356,9 @@ def main():
             "library": {"build_id": capi.build_id(), "sources_id": capi.sources_id(), "built_from_these_sources": capi.build_id() == capi.sources_id()},
             "index": {"build_s": round(built_s, 1), "builder": "host" if args.host_index else "gpu", "files_load_s": round(load_s, 1),
                       "attach_s": round(attach_s, 1), "read_synthesis_s": round(synth_s, 1)},
+            "full": args.full, "dump_outputs": dumped,
         }
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             ns = min(job.n, args.cpu_sample or (5_000_000 if pe else 8_000_000))
             host = [x[:ns].cpu().numpy() for x in job.batches[0]]
             cb, ref_sam = cpu_baseline(args, cfg, fa, host, L)
@@ -1310,7 +1402,7 @@ def main():
     del job
     torch.cuda.empty_cache()
     if rank == 0:
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             # secondary keys: the configs[1] line of round 1 and the stress cases (each on its own short timed region)
             sec = {}
             try:        # the driver attaches its own copy of the index: run it now that this process has released its own

@@ -172,6 +172,94 @@ def test_bench_configs_match_baseline_json():
     assert not a1.cfg["pe"] and a1.cfg["units"] == 10_000_000 and abs(a1.cfg["e"] - 0.04) < 1e-12
 
 
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)
+    return b
+
+
+@pytest.mark.parametrize("total,n_chrom", [(12, 3), (390, 3), (652, 5), (999, 7), (3_100_000, 24), (10_000_001, 5)])
+def test_bench_genome_equals_synth_make_genome(total, n_chrom):
+    """bench.py draws its genome from the raw PCG64 stream on several threads: the same bytes as synth.make_genome, chromosomes
+    whose word count is odd (a 64-bit draw split between two of them) included"""
+    from bitmapperbs_amd import synth
+    b = _bench_module()
+    names, chroms = b.synth_genome(total, n_chrom, 20240229)
+    n0, c0 = synth.make_genome(total, n_chrom, seed=20240229)
+    assert names == n0 and len(chroms) == len(c0)
+    for x, y in zip(chroms, c0):
+        assert x.dtype == y.dtype and np.array_equal(x, y)
+
+
+def test_bench_plain_run_times_exactly_the_steps_asked():
+    """a plain run times --steps steps (no stretching) and leaves the extra measurements to --full, which stretches as before"""
+    b = _bench_module()
+    a = b.parse(["--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.min_seconds == 0.0 and a.dump_outputs is None
+    f = b.parse(["--full"])
+    assert f.full and f.min_seconds == b.MIN_TIMED_S
+    assert b.parse(["--full", "--min-seconds", "0"]).min_seconds == 0.0
+    assert b.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+
+
+def test_bench_dump_outputs_writes_a_fixed_sample(tmp_path):
+    """--dump-outputs on a stand-in for the timed job (host tensors): the sampled records field by field in float64, their CIGAR
+    operations in float32, only operations inside the pool read, the same files for the same inputs, < 64 MB"""
+    import torch
+    from bitmapperbs_amd import capi
+    b = _bench_module()
+    rng = np.random.default_rng(5)
+    nrec, launches, ops_per = 70_000, 3, 6
+    cap = nrec * ops_per
+
+    class J:
+        pass
+    job = J()
+    job.reads_per_launch, job.cig_cap = nrec, cap
+    job.res_all, job.cig_all, want = [], [], []
+    for _ in range(launches):
+        r = np.zeros(nrec, dtype=capi.RESULT_DTYPE)
+        r["status"] = rng.integers(0, 3, nrec)
+        r["pos"] = rng.integers(1, 3_000_000_000, nrec)
+        r["chrom"] = rng.integers(-1, 24, nrec)
+        r["n_cigar"] = rng.integers(0, ops_per + 1, nrec)
+        r["cigar_off"] = np.arange(nrec) * ops_per
+        r[-1]["status"] = 1; r[-1]["n_cigar"] = 200          # would run past the pool's end: not read
+        pool = rng.integers(0, 1 << 14, cap).astype(np.int32)
+        job.res_all.append(torch.from_numpy(r.view(np.uint8).reshape(nrec, 32).copy()))
+        job.cig_all.append(torch.from_numpy(pool))
+        want.append((r, pool))
+    stats = np.array([9, 8, 1, 1000, 10], dtype=np.int64)
+    info = b.dump_outputs(str(tmp_path / "a"), job, stats)
+    b.dump_outputs(str(tmp_path / "b"), job, stats)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b")) and info["files"] == len(files)
+    total = 0
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y)
+        total += os.path.getsize(tmp_path / "a" / f)
+    assert total < 64 << 20
+    ld = lambda n: np.load(tmp_path / "a" / (n + ".npy"))
+    idx = ld("sample_index").astype(np.int64)
+    assert idx.size == b.DUMP_RECORDS and np.all(np.diff(idx) > 0) and idx[-1] < launches * nrec
+    assert np.array_equal(ld("mapstats"), stats.astype(np.float64))
+    ops, cnt = ld("cigar_ops").astype(np.int64), ld("cigar_ops_count").astype(np.int64)
+    assert cnt.sum() == ops.size
+    pos, status = ld("records_pos"), ld("records_status")
+    at = 0
+    for j, g in enumerate(idx):
+        r, pool = want[g // nrec]
+        rec = r[g % nrec]
+        assert pos[j] == rec["pos"] and status[j] == rec["status"]
+        n = int(rec["n_cigar"]) if rec["status"] == 1 and 0 < rec["n_cigar"] <= ops_per else 0
+        assert cnt[j] == n
+        off = int(rec["cigar_off"])
+        assert np.array_equal(ops[at:at + n], pool[off:off + n])
+        at += n
+
+
 def _fastq(path, names, lens, rng, at_quals=False):
     with open(path, "wb") as f:
         for nm, L in zip(names, lens):

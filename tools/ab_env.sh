@@ -4,7 +4,7 @@
 ARGS=$1; shift
 for rep in 1 2; do
   for kv in "$@"; do
-    env $kv timeout 900 python bench.py $ARGS --launches 2 --steps 3 --no-cpu --no-secondary --no-single-lane 2>/dev/null | tail -1 | python -c "
+    env $kv timeout 900 python bench.py $ARGS --full --launches 2 --steps 3 --no-cpu --no-secondary --no-single-lane 2>/dev/null | tail -1 | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); k=d.get('kernels_ms_per_launch',{})
 top=sorted(((v,a) for a,v in k.items() if a.startswith('k_')), reverse=True)[:6]
 print('$kv', d['value'], 'ms/launch %.2f' % (d['ms_per_step']/d['config']['launches_per_step']), ' '.join('%s=%.2f'%(a,v) for v,a in top))"

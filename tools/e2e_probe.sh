@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/e2e_probe.sh <outdir> [pairs=10000000] -- file-to-file rates of bmbs_search on the GPU box for a few driver settings (batch size,
-# contexts, output parts, sink).  Needs the bench's 3.1 Gb index and FASTQ sample under $BMBS_BENCH_DIR (python bench.py writes both).
+# contexts, output parts, sink).  Needs the bench's 3.1 Gb index and FASTQ sample under $BMBS_BENCH_DIR (python bench.py --full writes both).
 O=${1:-gpurun_out/e2e}; N=${2:-10000000}
 W=${BMBS_BENCH_DIR:-/tmp/bmbs_bench}
 mkdir -p $O

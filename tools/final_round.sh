@@ -9,4 +9,4 @@ timeout 1200 python tools/fuzz_e2e.py --big --trials 120 --seed 6631 > gpurun_ou
 timeout 900 python tools/fuzz_parity.py --trials 200 --seed 6633 > gpurun_out/${P}_fuzz_parity.txt 2>&1; tail -n 1 gpurun_out/${P}_fuzz_parity.txt
 timeout 900 python tools/fuzz_e2e.py --trials 80 --seed 6632 > gpurun_out/${P}_fuzz_e2e.txt 2>&1; tail -n 1 gpurun_out/${P}_fuzz_e2e.txt
 timeout 900 python tools/fuzz_e2e.py --bound --big --trials 60 --seed 6634 > gpurun_out/${P}_fuzz_bound_big.txt 2>&1; tail -n 1 gpurun_out/${P}_fuzz_bound_big.txt
-python bench.py > gpurun_out/${P}_bench.json 2> gpurun_out/${P}_bench.err; tail -c 300 gpurun_out/${P}_bench.json
+mkdir -p bench_out; python bench.py --full > bench_out/${P}_bench.json 2> bench_out/${P}_bench.err; tail -c 300 bench_out/${P}_bench.json

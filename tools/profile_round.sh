@@ -9,8 +9,8 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/prof_$TAG
 rm -rf "$O"; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py --config $CFG $X ${BENCH_FIRST:---no-stress} > $O/bench.json 2> $O/bench.err
-Q="--config $CFG $X --no-cpu --no-secondary"
+python3 $R/bench.py --full --config $CFG $X ${BENCH_FIRST:---no-stress} > $O/bench.json 2> $O/bench.err
+Q="--config $CFG $X --no-cpu --no-secondary --full"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py $Q > $O/bench_under_rocprof.json 2>/dev/null
 # the counter passes run the call on ONE lane (BMBS_LANES=1): a kernel's last dispatch is then the whole launch, as the algorithmic bytes of
 # the bench line are; the counters of a kernel do not depend on what runs beside it

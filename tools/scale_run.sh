@@ -7,7 +7,7 @@ O=$R/gpurun_out/scale_$G
 mkdir -p $O
 cd $R
 date > $O/log.txt
-( time python bench.py --genome $G --reads 10000000 --no-cpu --steps 2 > $O/bench.json 2> $O/bench.err ) 2>> $O/log.txt
+( time python bench.py --full --genome $G --units 10000000 --no-cpu --steps 2 > $O/bench.json 2> $O/bench.err ) 2>> $O/log.txt
 tail -3 $O/bench.err >> $O/log.txt
 free -g | head -2 >> $O/log.txt
 ( time python tools/e2e_bench.py --genome $G --reads 2000000 --io-threads 32 --ref-threads 32 --out $O/e2e.json > $O/e2e.out 2>&1 ) 2>> $O/log.txt
