@@ -465,7 +465,11 @@ int launch_seeding(Lane* c, const char* d_seq, const ReadGeom& gm, int stride, u
     // few per cent where chains are short -- so they are used once the context has seen long ones (BMBS_KGRAM=2: always, 0: never)
     occ3_want(c);
     const bool kg = c->ix.occ3 && packed_rows && (c->kn.kgram >= 2 || (c->kn.kgram == 1 && c->lr_chain >= 3.0));
-    if (packed_rows && kg) hipLaunchKernelGGL((k_seed_first<true, true>), dim3(chunks), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, (long)n, sc, cnt);
+    // BMBS_SEED_STAGE=1 (default): k_seed_first's results written coalesced through LDS, k_seed_decide_p's exit-A record not stored (0: the round-6 forms)
+    const int stage = c->kn.seed_stage;
+    if (packed_rows && kg && stage) hipLaunchKernelGGL((k_seed_first<true, true, true>), dim3(chunks), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, (long)n, sc, cnt);
+    else if (packed_rows && kg) hipLaunchKernelGGL((k_seed_first<true, true>), dim3(chunks), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, (long)n, sc, cnt);
+    else if (packed_rows && stage) hipLaunchKernelGGL((k_seed_first<true, false, true>), dim3(chunks), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, (long)n, sc, cnt);
     else if (packed_rows) hipLaunchKernelGGL(k_seed_first<true>, dim3(chunks), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, (long)n, sc, cnt);
     else hipLaunchKernelGGL(k_seed_first<false>, dim3(chunks), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, (long)n, sc, cnt);
     prof_end(c);
@@ -476,7 +480,7 @@ int launch_seeding(Lane* c, const char* d_seq, const ReadGeom& gm, int stride, u
     const bool lds_ok = (size_t)64 * (stride + 8) <= 48 * 1024;
     if (packed_rows)
         hipLaunchKernelGGL(k_seed_decide_p, dim3(nblk(n, 64)), dim3(64), (size_t)64 * (pr.pwords + 1) * 8, c->stream, c->ix, d_seq, pr, gm, stride,
-                           (long)n, c->prm.seed_len, pe_mode, st, sc, cnt);
+                           (long)n, c->prm.seed_len, pe_mode, (stage && !(pe_mode && c->prm.sensitive)) ? 1 : 0, st, sc, cnt);   // k_pes_reseed reads it
     else if (lds_ok)
         hipLaunchKernelGGL((k_seed_decide<true, true>), dim3(nblk(n, 64)), dim3(64), (size_t)64 * (stride + 8), c->stream, c->ix, d_seq, gm,
                            stride, (long)n, c->prm.seed_len, pe_mode, st, sc, cnt);

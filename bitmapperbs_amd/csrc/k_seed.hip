@@ -393,12 +393,18 @@ DEVI void wave_stats_add(unsigned long long* sh, u32 v0, u32 v1, u32 v2, u32 v3,
 }
 
 // ---- first seed of every read ------------------------------------------------------------------
-template <bool PACKED, bool KG = false>
+// STAGE (BMBS_SEED_STAGE, default): a lane's first-seed result goes to LDS by its position in the chunk, and the wave writes the
+// chunk's three arrays out at the end with coalesced stores -- instead of three stores per read in the order reads finish, each
+// spread over the lines of the ~64 reads in flight (3.5 KB of LDS per wave: no occupancy lost)
+template <bool PACKED, bool KG = false, bool STAGE = false>
 __global__ void __launch_bounds__(64)
 k_seed_first(DevIndex ix, const char* __restrict__ seq, PackedRows pr, ReadGeom gm, int stride, long n, SeedCarry sc,
              unsigned long long* __restrict__ counters)
 {
     __shared__ u64 s_c3[KG ? 27 : 1];
+    __shared__ u64 s_sp0[STAGE ? SEED_CHUNK : 1];
+    __shared__ u32 s_hits0[STAGE ? SEED_CHUNK : 1];
+    __shared__ u16 s_ml0[STAGE ? SEED_CHUNK : 1];
     const u64* c3 = KG ? kgram_c3(ix, s_c3) : nullptr;
     const WaveLogT wl_t = wavelog_begin();
     int L = gm.L;                                     // length of the lane's current read
@@ -421,7 +427,11 @@ k_seed_first(DevIndex ix, const char* __restrict__ seq, PackedRows pr, ReadGeom 
             const long it = next + rank;
             next += __popcll(pm);
             if (pending) {
-                if (have) { sc.sp0[r] = h.sp; sc.hits0[r] = (u32)h.hits; sc.ml0[r] = (u16)h.ml; have = false; }
+                if (have) {
+                    if (STAGE) { const int q = (int)(r - chunk_begin); s_sp0[q] = h.sp; s_hits0[q] = (u32)h.hits; s_ml0[q] = (u16)h.ml; }
+                    else { sc.sp0[r] = h.sp; sc.hits0[r] = (u32)h.hits; sc.ml0[r] = (u16)h.ml; }
+                    have = false;
+                }
                 if (it < chunk_end) {
                     r = it; have = true; L = gm.rl(r);
                     bool go;
@@ -443,6 +453,12 @@ k_seed_first(DevIndex ix, const char* __restrict__ seq, PackedRows pr, ReadGeom 
             if constexpr (PACKED) fin = search_step_p<false, KG>(ix, L, S, h, lc.n_ext, c3, &lc.n_jump); else fin = search_step<false>(ix, rd, L, S, h, lc.n_ext);
             if (fin) { active = false; pending = true; }
         }
+    }
+    if (STAGE) {
+        // every read of the chunk has been booked (the loop ends with no lane pending): the chunk's results, coalesced
+        __syncthreads();
+        const int cnt = (int)(chunk_end - chunk_begin);
+        for (int q = threadIdx.x & 63; q < cnt; q += 64) { sc.sp0[chunk_begin + q] = s_sp0[q]; sc.hits0[chunk_begin + q] = s_hits0[q]; sc.ml0[chunk_begin + q] = s_ml0[q]; }
     }
     flush_counters(counters, lc, 0);
     wavelog_end(wl_t, 3);
@@ -619,9 +635,11 @@ k_seed_decide(DevIndex ix, const char* __restrict__ seq, ReadGeom gm, int stride
 }
 
 // ---- the same kernel over packed rows: 64 bytes per read through LDS instead of 160, comparisons by whole-word XOR -------------
+// skip_v1 (BMBS_SEED_STAGE, default; not under --sensitive): the first seed's record of a read that leaves by exit A (verdict 1) is
+// not stored -- no kernel reads it (see below).  Half the reads of a 0.5 %-substitution batch leave there: one scattered store each.
 __global__ void __launch_bounds__(64)
 k_seed_decide_p(DevIndex ix, const char* __restrict__ seq, PackedRows pr, ReadGeom gm, int stride, long n, int seed_len, int pe_mode,
-                ReadState st, SeedCarry sc, unsigned long long* __restrict__ counters)
+                int skip_v1, ReadState st, SeedCarry sc, unsigned long long* __restrict__ counters)
 {
     __shared__ unsigned int shc[2];
     if (threadIdx.x < 2) shc[threadIdx.x] = 0;
@@ -670,7 +688,7 @@ k_seed_decide_p(DevIndex ix, const char* __restrict__ seq, PackedRows pr, ReadGe
                 if (sp >> 63) p = sp & ~(1ull << 63);          // the outcome table had the text position
                 else { p = sa_at(ix, sp); n_sa++; }
                 const u64 loc = ix.total - p - ml;
-                seed_record(my, ns, ncand, sp, 1, ml, 0);
+                if (!skip_v1) seed_record(my, ns, ncand, sp, 1, ml, 0);
                 c0 = loc; clen = 1;
                 int error = 0;
                 if (ml > (u64)firstC) ml = (u64)firstC;
@@ -698,6 +716,13 @@ k_seed_decide_p(DevIndex ix, const char* __restrict__ seq, PackedRows pr, ReadGe
                 }
                 get_error = error;
                 if (error == 0) { verdict = 1; st.exit_site[r] = loc; done = true; }
+                // skip_v1: the record was kept back until the verdict was known.  The readers of st.seeds and the verdicts they read
+                // it for: k_vote_fused and the lists it hands to k_vote_mid / k_vote_long (single-end) 3 only; k_vote_pe /
+                // k_vote_pe_fused 3 and 4 (1 and 2: exit_site only) and the lists they hand to k_vote_pe_mid / k_vote_pe_long 3 and 4;
+                // k_pes_order every verdict but 1 and 4; but k_pes_reseed (--sensitive) reads slots 0 .. ps.full - 1 of the mate it
+                // re-seeds whatever its verdict, and ps.full = n_seeds = 1 for exit A -- so --sensitive keeps the store (launch_seeding).
+                // k_pes_vote / k_pes_vote_long read what k_pes_reseed wrote.  The text, file and --pbat entry points run these kernels.
+                if (skip_v1) { if (error == 0) { ns = 1; ncand = 1; } else seed_record(my, ns, ncand, sp, 1, first_ml, 0); }
             }
             if (!done) {
                 mm_site = ml;
