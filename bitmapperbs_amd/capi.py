@@ -23,6 +23,7 @@ SYMBOLS = [
     "bmbs_counters_last", "bmbs_counters_all", "bmbs_index_file_load", "bmbs_index_file_view", "bmbs_index_file_chrom_name",
     "bmbs_index_file_free", "bmbs_index_build", "bmbs_index_build_device", "bmbs_host_alloc", "bmbs_host_free", "bmbs_build_id",
     "bmbs_max_cigar_ops", "bmbs_host_prefault", "bmbs_reserve", "bmbs_host_alloc_kind", "bmbs_retries", "bmbs_text_times", "bmbs_pack_rows", "bmbs_map_se_packed", "bmbs_map_pe_packed", "bmbs_sam_refs", "bmbs_map_se_text", "bmbs_map_pe_text", "bmbs_profile_total", "bmbs_profile_reset", "bmbs_inflate_bgzf", "bmbs_debug_huff_lengths", "bmbs_text_open_bgzf", "bmbs_text_map_open",
+    "bmbs_qual_classes", "bmbs_pack_quals", "bmbs_map_se_packedq", "bmbs_map_pe_packedq",
 ]
 
 
@@ -124,6 +125,15 @@ def lib() -> C.CDLL:
     L.bmbs_map_se_packed.restype = C.c_int
     L.bmbs_map_pe_packed.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i64, vp, vp, i64, C.POINTER(i64)]
     L.bmbs_map_pe_packed.restype = C.c_int
+    if hasattr(L, "bmbs_pack_quals"):                    # (packed quality classes; BMBS_LIB may name an older build, as above)
+        L.bmbs_qual_classes.argtypes = [C.POINTER(Params), vp, vp, C.POINTER(i32)]
+        L.bmbs_qual_classes.restype = C.c_int
+        L.bmbs_pack_quals.argtypes = [C.POINTER(Params), vp, i32, i32, i64, vp, vp, i32, i32, C.POINTER(i64)]
+        L.bmbs_pack_quals.restype = C.c_int
+        L.bmbs_map_se_packedq.argtypes = [vp, vp, i32, vp, i32, vp, i32, i64, vp, vp, i64, C.POINTER(i64)]
+        L.bmbs_map_se_packedq.restype = C.c_int
+        L.bmbs_map_pe_packedq.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, i64, vp, vp, i64, C.POINTER(i64)]
+        L.bmbs_map_pe_packedq.restype = C.c_int
     L.bmbs_map_se_fastq.argtypes = [vp, C.POINTER(FastqView), i64, i32, i32, i32, vp, vp, i64, C.POINTER(i64)]
     L.bmbs_map_pe_fastq.argtypes = [vp, C.POINTER(FastqView), C.POINTER(FastqView), i64, i32, i32, vp, vp, i64, C.POINTER(i64)]
     L.bmbs_sync.argtypes = [vp]
@@ -187,7 +197,7 @@ def lib() -> C.CDLL:
     return L
 
 
-LIB_SRCS = ("bmbs_api.hip", "bmbs_kernels.hip", "k_index.hip", "k_rows.hip", "k_attach.hip", "k_scan.hip", "k_seed.hip", "k_vote.hip", "k_filter.hip", "k_reduce.hip", "k_align.hip", "k_finalize.hip", "k_pe_fast.hip", "k_pe_sensitive.hip",
+LIB_SRCS = ("bmbs_api.hip", "bmbs_kernels.hip", "k_index.hip", "k_rows.hip", "k_qualpack.hip", "k_attach.hip", "k_scan.hip", "k_seed.hip", "k_vote.hip", "k_filter.hip", "k_reduce.hip", "k_align.hip", "k_finalize.hip", "k_pe_fast.hip", "k_pe_sensitive.hip",
             "bmbs_textpath.hip", "bmbs_text.hip", "bmbs_bam.hip", "bmbs_inflate.hip", "bmbs_bytes.h", "bmbs_host.h", "bmbs_dev.h", "bmbs_sort.h", "../../include/bmbs.h",
             "index_io.cpp", "index_io.h", "index_build_gpu.hip", "build_id.cpp")
 

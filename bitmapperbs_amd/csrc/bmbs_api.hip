@@ -106,6 +106,26 @@ int mismatch_penalty(const bmbs_params& P, int Q)
     return (int)(phred * (P.mp_max - P.mp_min)) + P.mp_min;
 }
 
+// The penalty classes of the quality bytes (bmbs_qual_classes): the distinct values of mismatch_penalty over the 256 bytes, largest
+// first, the 16 largest numbered 0..15; class_of[b] = 0xFF for a byte whose penalty is not among them.  rep[c] (may be null) = the
+// smallest byte of class c, what k_qual_expand writes for it (classes that do not exist: rep[0]).
+void qual_class_table(const bmbs_params& P, uint8_t class_of[256], int32_t penalty_of[16], int32_t* n_classes, uint8_t rep[16])
+{
+    int pen[256];
+    for (int b = 0; b < 256; b++) pen[b] = mismatch_penalty(P, b);
+    std::vector<int> v(pen, pen + 256);
+    std::sort(v.begin(), v.end(), [](int a, int b) { return a > b; });
+    v.erase(std::unique(v.begin(), v.end()), v.end());
+    const int nc = (int)std::min<size_t>(16, v.size());
+    for (int c = 0; c < 16; c++) penalty_of[c] = c < nc ? v[(size_t)c] : 0;
+    for (int b = 255; b >= 0; b--) {
+        class_of[b] = 0xFF;
+        for (int c = 0; c < nc; c++) if (pen[b] == v[(size_t)c]) { class_of[b] = (uint8_t)c; if (rep) rep[c] = (uint8_t)b; break; }
+    }
+    if (rep) for (int c = nc; c < 16; c++) rep[c] = rep[0];
+    *n_classes = nc;
+}
+
 // MAP_Calculation (Schema.cpp:168-405) as data.  The reference's ladder of `if`s compares two ratios -- the runner-up's distance in
 // edits over the threshold (rank_error) and the winner's score above the worst admissible score over that range (rank) -- with
 // fixed cut points; the tables below are those cut points and the MAPQ each cell returns.  The ratios are formed and compared in
@@ -664,6 +684,11 @@ Lane* lane_create(int device_id, const bmbs_params& prm, const Knobs& kn, bool f
     (void)hipEventCreateWithFlags(&c->ev_k, hipEventDisableTiming);
     int lut[256];
     for (int q = 0; q < 256; q++) lut[q] = mismatch_penalty(c->prm, q);
+    {
+        uint8_t class_of[256], rep[16]; int32_t penalty_of[16], nc = 0;
+        qual_class_table(c->prm, class_of, penalty_of, &nc, rep);
+        for (int k = 0; k < 8; k++) { c->qrep_lo |= (u64)rep[k] << (8 * k); c->qrep_hi |= (u64)rep[8 + k] << (8 * k); }
+    }
     const size_t shard_bytes = BMBS_SHARDS * BMBS_SHARD_WORDS * 8;
     if (ensure(c, c->pen_lut, sizeof(lut)) || ensure(c, c->stats, shard_bytes) || ensure(c, c->call_stats, shard_bytes) || ensure(c, c->counters, shard_bytes) ||
         ensure(c, c->totals, 32 * 8) || ensure(c, c->flags, BMBS_FLAG_WORDS * 4) || ensure(c, c->tx_info, 64) ||
@@ -732,7 +757,7 @@ void lane_destroy(Lane* c)
                      &c->sd_sp0, &c->sd_hits0, &c->sd_ml0, &c->sd_tm, &c->sd_seed_id, &c->sd_clen, &c->sd_first_ml, &c->sd_flag_c, &c->sd_flag_d,
                      &c->sd_off_c, &c->sd_off_d, &c->sd_list_c, &c->sd_list_d, &c->pe_vround, &c->pe_dead, &c->pe_both, &c->pe_npair, &c->pe_sbd, &c->in_seq2, &c->in_qual2,
                      &c->pe_first, &c->pe_full, &c->pe_R, &c->pe_roff, &c->pe_rflag, &c->pe_rscan, &c->pe_rlist, &c->pe_rcnt, &c->pe_ritem_off, &c->pe_rcand, &c->long_flag, &c->long_off, &c->long_list, &c->vote_list,
-                     &c->mapq_off, &c->klut, &c->in_len, &c->fq_text1, &c->fq_text2, &c->fq_idx, &c->pk_in1, &c->pk_in2, &c->pk_ascii, &c->prow, &c->prow_dirty, &c->pe_mid_flag, &c->pe_mid_list};
+                     &c->mapq_off, &c->klut, &c->in_len, &c->fq_text1, &c->fq_text2, &c->fq_idx, &c->pk_in1, &c->pk_in2, &c->pq_in1, &c->pq_in2, &c->pk_ascii, &c->prow, &c->prow_dirty, &c->pe_mid_flag, &c->pe_mid_list};
     for (DevBuf* b : all) release(*b);
     for (auto& set : c->profset) for (auto& p : set) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     c->arena.free_all();
@@ -743,6 +768,8 @@ void lane_destroy(Lane* c)
       for (DevBuf* b : tx) release(*b); }
     if (c->ev_up) (void)hipEventDestroy(c->ev_up);
     if (c->ev_k) (void)hipEventDestroy(c->ev_k);
+    if (c->ev_qx_a) (void)hipEventDestroy(c->ev_qx_a);
+    if (c->ev_qx_b) (void)hipEventDestroy(c->ev_qx_b);
     if (c->up_stream) (void)hipStreamDestroy(c->up_stream);
     if (c->down_stream) (void)hipStreamDestroy(c->down_stream);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1527,7 +1554,8 @@ int dispatch_device(bmbs_ctx* X, bool pe, uint64_t a0, uint64_t a1, uint64_t a2,
 
 // host entry points: chunk i is uploaded, mapped and read back on lane i % lanes -- its copies run beside the kernels of the
 // chunks on the other lanes (one direction of the link each: 48 GB/s both ways at once on the MI355X boxes, tools/pcie_probe)
-struct HostIn { const char *seq1, *qual1, *seq2, *qual2; const uint16_t *len1, *len2; const uint64_t *rows1 = nullptr, *rows2 = nullptr; int hw = 0; };
+struct HostIn { const char *seq1, *qual1, *seq2, *qual2; const uint16_t *len1, *len2; const uint64_t *rows1 = nullptr, *rows2 = nullptr; int hw = 0;
+                const uint64_t *qrows1 = nullptr, *qrows2 = nullptr; int qw = 0; };      // qw > 0: packed quality classes instead of qual1 / qual2
 int dispatch_host(bmbs_ctx* X, bool pe, const HostIn& in, int32_t L, int32_t stride, int64_t n, bmbs_result* results, uint32_t* cigar_pool, int64_t cigar_cap,
                   int64_t* n_cigar_used)
 {
@@ -1553,6 +1581,14 @@ int dispatch_host(bmbs_ctx* X, bool pe, const HostIn& in, int32_t L, int32_t str
         const u64 retries0 = c->n_retries;
         int rc = lane_settle(c);
         if (rc) return rc;
+        if (c->qx_timed) {                          // k_qual_expand ran in front of the call (outside its event set): into the running sums by hand
+            c->qx_timed = false;
+            float t = 0;
+            if (hipEventElapsedTime(&t, c->ev_qx_a, c->ev_qx_b) != hipSuccess) t = 0.f;
+            bool found = false;
+            for (auto& a : c->acc) if (!strcmp(a.name, "k_qual_expand")) { a.ms += t; found = true; break; }
+            if (!found) c->acc.push_back({"k_qual_expand", (double)t});
+        }
         const bool cs = c->kn.copy_streams && c->up_stream && c->down_stream && c->ev_up && c->ev_k;
         hipStream_t dsn = cs ? c->down_stream : c->stream;
         if (c->n_retries != retries0)               // the chunk was issued again with exact sizes: the records copied behind the first attempt are stale
@@ -1596,16 +1632,39 @@ int dispatch_host(bmbs_ctx* X, bool pe, const HostIn& in, int32_t L, int32_t str
                 HIPCHK(c, hipMemcpyAsync(c->pk_in1.p, in.rows1 + (size_t)off * (size_t)in.hw, pb, hipMemcpyHostToDevice, us));
                 if (pe) { ENS(c, c->pk_in2, pb + 64); HIPCHK(c, hipMemcpyAsync(c->pk_in2.p, in.rows2 + (size_t)off * (size_t)in.hw, pb, hipMemcpyHostToDevice, us)); }
             } else { r1 = upload_rows(c, c->in_seq, in.seq1 + ro, L, stride, um, &ds, us); if (r1) return r1; }
-            r1 = upload_rows(c, c->in_qual, in.qual1 + ro, L, stride, um, &ds, us); if (r1) return r1;
+            if (in.qw) {
+                // packed quality classes: qw words per read go over as they are; k_qual_expand (below) writes the byte rows at the stride
+                // upload_rows would have given them
+                const u64 qb = um * (u64)in.qw * 8;
+                ds = (L + 15) / 16 * 16;
+                ENS(c, c->pq_in1, qb + 64); ENS(c, c->in_qual, um * (u64)ds + 64);
+                HIPCHK(c, hipMemcpyAsync(c->pq_in1.p, in.qrows1 + (size_t)off * (size_t)in.qw, qb, hipMemcpyHostToDevice, us));
+                if (pe) {
+                    ENS(c, c->pq_in2, qb + 64); ENS(c, c->in_qual2, um * (u64)ds + 64);
+                    HIPCHK(c, hipMemcpyAsync(c->pq_in2.p, in.qrows2 + (size_t)off * (size_t)in.qw, qb, hipMemcpyHostToDevice, us));
+                }
+            } else { r1 = upload_rows(c, c->in_qual, in.qual1 + ro, L, stride, um, &ds, us); if (r1) return r1; }
             if (pe) {
                 if (!in.hw) { r1 = upload_rows(c, c->in_seq2, in.seq2 + ro, L, stride, um, &ds, us); if (r1) return r1; }
-                r1 = upload_rows(c, c->in_qual2, in.qual2 + ro, L, stride, um, &ds, us); if (r1) return r1;
+                if (!in.qw) { r1 = upload_rows(c, c->in_qual2, in.qual2 + ro, L, stride, um, &ds, us); if (r1) return r1; }
             }
             if (in.len1) {
                 r1 = upload_lens(c, in.len1 + off, um, 0, um * rpu, L, us); if (r1) return r1;
                 if (pe) { r1 = upload_lens(c, in.len2 + off, um, um, um * rpu, L, us); if (r1) return r1; }
             }
             if (cs) { HIPCHK(c, hipEventRecord(c->ev_up, us)); HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_up, 0)); }
+            if (in.qw) {
+                // on the kernel stream, in front of the call: a chunk that is issued again with exact sizes finds its byte rows in place
+                const int Wq = ds / 16;
+                const u64 words = um * (u64)Wq * (u64)rpu;
+                if (!c->ev_qx_a) { HIPCHK(c, hipEventCreate(&c->ev_qx_a)); HIPCHK(c, hipEventCreate(&c->ev_qx_b)); }
+                const QualRep rep = {c->qrep_lo, c->qrep_hi};
+                HIPCHK(c, hipEventRecord(c->ev_qx_a, c->stream));
+                hipLaunchKernelGGL(k_qual_expand, dim3(std::min<unsigned>(nblk(words, 256), 4096u)), dim3(256), 0, c->stream, c->pq_in1.as<u64>(),
+                                   pe ? c->pq_in2.as<u64>() : (const u64*)nullptr, in.qw, Wq, (long)m, rep, c->in_qual.as<uint4>(), pe ? c->in_qual2.as<uint4>() : (uint4*)nullptr);
+                HIPCHK(c, hipEventRecord(c->ev_qx_b, c->stream));
+                c->qx_timed = true;
+            }
             Pending P;
             P.pe = pe; P.L = L; P.stride = ds; P.n = m;
             P.a[0] = (uint64_t)c->in_seq.p; P.a[1] = (uint64_t)c->in_qual.p; P.a[2] = pe ? (uint64_t)c->in_seq2.p : 0; P.a[3] = pe ? (uint64_t)c->in_qual2.p : 0;
@@ -1731,6 +1790,88 @@ extern "C" int bmbs_map_pe_packed(bmbs_ctx* X, const uint64_t* rows1, const uint
     HostIn in = {nullptr, qual1, nullptr, qual2, len1, len2};
     in.rows1 = rows1; in.rows2 = rows2; in.hw = pwords;
     return dispatch_host(X, true, in, L_max, stride, n_pairs, results, cigar_pool, cigar_cap, n_cigar_used);
+}
+// ---- packed quality classes (include/bmbs.h): a 4-bit penalty class per base instead of the quality byte ------------------------------------
+extern "C" int bmbs_qual_classes(const bmbs_params* params, uint8_t class_of[256], int32_t penalty_of[16], int32_t* n_classes)
+{
+    if (!class_of || !penalty_of || !n_classes) return BMBS_EINVAL;
+    bmbs_params P;
+    if (params) P = *params; else bmbs_default_params(&P);
+    qual_class_table(P, class_of, penalty_of, n_classes, nullptr);
+    return BMBS_OK;
+}
+extern "C" int bmbs_map_se_packedq(bmbs_ctx* X, const uint64_t* rows, int32_t pwords, const uint64_t* qrows, int32_t qwords, const uint16_t* len, int32_t L_max,
+                                   int64_t n_reads, bmbs_result* results, uint32_t* cigar_pool, int64_t cigar_cap, int64_t* n_cigar_used)
+{
+    if (X && (!rows || !qrows || pwords <= 0 || qwords <= 0)) { X->err = "packed reads: NULL rows / quality classes or pwords / qwords <= 0"; return BMBS_EINVAL; }
+    if (X && L_max > 0 && qwords < (L_max + 15) / 16) { X->err = "packed quality classes: qwords is smaller than a row of this length takes"; return BMBS_EINVAL; }
+    HostIn in = {nullptr, nullptr, nullptr, nullptr, len, nullptr};
+    in.rows1 = rows; in.hw = pwords; in.qrows1 = qrows; in.qw = qwords;
+    return dispatch_host(X, false, in, L_max, std::max(L_max, 0), n_reads, results, cigar_pool, cigar_cap, n_cigar_used);
+}
+extern "C" int bmbs_map_pe_packedq(bmbs_ctx* X, const uint64_t* rows1, const uint64_t* rows2, int32_t pwords, const uint64_t* qrows1, const uint64_t* qrows2,
+                                   int32_t qwords, const uint16_t* len1, const uint16_t* len2, int32_t L_max, int64_t n_pairs, bmbs_result* results,
+                                   uint32_t* cigar_pool, int64_t cigar_cap, int64_t* n_cigar_used)
+{
+    if (X && (!rows1 || !rows2 || !qrows1 || !qrows2 || pwords <= 0 || qwords <= 0 || (len1 != nullptr) != (len2 != nullptr))) {
+        X->err = "packed reads: NULL rows / quality classes, pwords / qwords <= 0, or only one of len1 / len2"; return BMBS_EINVAL;
+    }
+    if (X && L_max > 0 && qwords < (L_max + 15) / 16) { X->err = "packed quality classes: qwords is smaller than a row of this length takes"; return BMBS_EINVAL; }
+    HostIn in = {nullptr, nullptr, nullptr, nullptr, len1, len2};
+    in.rows1 = rows1; in.rows2 = rows2; in.hw = pwords; in.qrows1 = qrows1; in.qrows2 = qrows2; in.qw = qwords;
+    return dispatch_host(X, true, in, L_max, std::max(L_max, 0), n_pairs, results, cigar_pool, cigar_cap, n_cigar_used);
+}
+// quality bytes -> packed classes on the host's threads (once per batch, like bmbs_pack_rows).  -> BMBS_OK, or BMBS_EINVAL with *bad_row = the
+// first row that holds a byte without a class (or whose length is 0 or beyond L_max)
+extern "C" int bmbs_pack_quals(const bmbs_params* params, const char* qual, int32_t L_max, int32_t stride, int64_t n, const uint16_t* len, uint64_t* qrows,
+                               int32_t qwords, int32_t threads, int64_t* bad_row)
+{
+    const int Wq = (L_max + 15) / 16;
+    if (bad_row) *bad_row = -1;
+    if (!qual || !qrows || L_max <= 0 || L_max > BMBS_MAX_READ || stride < L_max || qwords < Wq || n < 0) return BMBS_EINVAL;
+    bmbs_params P;
+    if (params) P = *params; else bmbs_default_params(&P);
+    uint8_t cls[256]; int32_t penalty_of[16], nc = 0;
+    qual_class_table(P, cls, penalty_of, &nc, nullptr);
+    // the 256-byte class table, squared: two quality bytes -> their two nibbles in one lookup (the pairs real qualities form touch a few
+    // dozen lines of it); a byte without a class sets the entry's high byte.  One byte at a time the packer ran at 1.3 GB/s per thread
+    std::vector<uint16_t> pair_((size_t)65536);
+    uint16_t* pair = pair_.data();
+    for (int b1 = 0; b1 < 256; b1++)
+        for (int b0 = 0; b0 < 256; b0++)
+            pair[(b1 << 8) | b0] = (uint16_t)((cls[b0] & 15) | ((cls[b1] & 15) << 4) | ((cls[b0] | cls[b1]) & 0xF0 ? 0x100 : 0));
+    const int T = (int)std::max<int64_t>(1, std::min<int64_t>(threads > 0 ? threads : 1, n / 4096 + 1));
+    std::vector<int64_t> bad((size_t)T, -1);
+    auto work = [&](int t) {
+        const int64_t a = n * t / T, e = n * (t + 1) / T;
+        for (int64_t r = a; r < e; r++) {
+            const unsigned char* s = reinterpret_cast<const unsigned char*>(qual) + (size_t)r * (size_t)stride;
+            uint64_t* o = qrows + (size_t)r * (size_t)qwords;
+            const int Lr = len ? (int)len[r] : L_max;
+            if (Lr <= 0 || Lr > L_max) { for (int q = 0; q < qwords; q++) o[q] = 0; if (bad[(size_t)t] < 0) bad[(size_t)t] = r; continue; }
+            unsigned seen = 0;
+            const int full = Lr >> 4;
+            for (int w = 0; w < full; w++, s += 16) {
+                uint64_t in[2], x = 0;
+                memcpy(in, s, 16);
+                for (int h = 0; h < 2; h++)
+                    for (int k = 0; k < 4; k++) { const unsigned c = pair[(in[h] >> (16 * k)) & 0xffffu]; seen |= c; x |= (uint64_t)(c & 0xffu) << (32 * h + 8 * k); }
+                o[w] = x;
+            }
+            int w = full;
+            if (Lr & 15) {
+                uint64_t x = 0;
+                for (int k = 0; k < (Lr & 15); k++) { const unsigned c = cls[s[k]]; seen |= c >> 4 ? 0x100u : 0u; x |= (uint64_t)(c & 15u) << (4 * k); }
+                o[w++] = x;
+            }
+            for (; w < qwords; w++) o[w] = 0;
+            if ((seen & 0x100u) && bad[(size_t)t] < 0) bad[(size_t)t] = r;
+        }
+    };
+    if (T == 1) work(0);
+    else { std::vector<std::thread> th; for (int t = 0; t < T; t++) th.emplace_back(work, t); for (auto& x : th) x.join(); }
+    for (int t = 0; t < T; t++) if (bad[(size_t)t] >= 0) { if (bad_row) *bad_row = bad[(size_t)t]; return BMBS_EINVAL; }
+    return BMBS_OK;
 }
 // ASCII rows -> packed rows on the host's threads (what a caller's reader does once per batch).  -> BMBS_OK, or BMBS_EINVAL with *bad_row =
 // the first row that holds a character other than A C G T N

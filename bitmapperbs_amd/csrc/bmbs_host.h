@@ -185,6 +185,12 @@ struct Lane {
     DevBuf prow, prow_dirty;                            // packed copy of the read rows (k_pack_rows), one dirty byte per read
     double link_up_s = 0, link_down_s = 0, text_call_s = 0; u64 text_calls = 0;       // bmbs_text_times: wall seconds the text calls' copies held the link
     DevBuf pk_in1, pk_in2, pk_ascii;                    // bmbs_map_*_packed: the caller's packed rows as uploaded; single end: the sparse ASCII rows
+    // bmbs_map_*_packedq: the caller's packed quality classes as uploaded (k_qual_expand writes in_qual / in_qual2 from them), the byte
+    // that stands for each class (byte c of qrep_lo, c - 8 of qrep_hi), and the event pair that times the kernel of the chunk in flight
+    DevBuf pq_in1, pq_in2;
+    u64 qrep_lo = 0, qrep_hi = 0;
+    hipEvent_t ev_qx_a = nullptr, ev_qx_b = nullptr;
+    bool qx_timed = false;
     DevBuf fq_text1, fq_text2, fq_idx;                  // bmbs_map_*_fastq: FASTQ text windows and the per-record line index
     // bmbs_map_*_text: newline index built on the device, SAM text written on the device
     DevBuf tx_tilecnt, tx_tileoff, tx_nl[2], tx_rec[2], tx_info, sam_len, sam_off, sam_out, chrom_chars, chrom_off;

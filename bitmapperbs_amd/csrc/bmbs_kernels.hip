@@ -67,6 +67,7 @@ DEVI void wavelog_end(const WaveLogT& t, int kernel_id)
 
 #include "k_index.hip"
 #include "k_rows.hip"
+#include "k_qualpack.hip"
 #include "k_attach.hip"
 #include "k_scan.hip"
 #include "k_seed.hip"

@@ -202,6 +202,42 @@ class Mapper:
                                                capi.ptr(res), capi.ptr(pool), cap, C.byref(used)))
         return res, pool[:used.value]
 
+    # ---- packed quality classes: 4 bits per quality (bmbs_map_*_packedq) -------------------------------
+    def qual_classes(self):
+        """(class_of u8[256], penalty_of i32[n_classes]) under this mapper's mp_max / mp_min / q_base (bmbs_qual_classes): class 0 is the
+        largest penalty, class_of 0xFF marks a byte that cannot be packed"""
+        return qual_classes(self.params)
+
+    def pack_quals(self, qual: np.ndarray, L: int, lens: np.ndarray | None = None, qwords: int | None = None, threads: int = 8) -> np.ndarray:
+        """quality rows [n][stride] -> packed class rows [n][qwords] of u64 (bmbs_pack_quals) under this mapper's parameters; raises when a
+        row holds a byte without a class"""
+        return pack_quals(self.params, qual, L, lens, qwords, threads)
+
+    def map_se_packedq(self, rows: np.ndarray, qrows: np.ndarray, L: int, lens: np.ndarray | None = None):
+        n = rows.shape[0]
+        res = np.zeros(n, dtype=capi.RESULT_DTYPE)
+        cap = max(1, n * self.max_cigar_ops(L))
+        pool = np.zeros(cap, dtype=np.uint32)
+        used = C.c_int64(0)
+        ln = np.ascontiguousarray(lens, dtype=np.uint16) if lens is not None else None
+        self._chk(self._lib.bmbs_map_se_packedq(self._ctx, capi.ptr(rows), rows.shape[1], capi.ptr(qrows), qrows.shape[1],
+                                                capi.ptr(ln) if ln is not None else None, L, n, capi.ptr(res), capi.ptr(pool), cap, C.byref(used)))
+        return res, pool[:used.value]
+
+    def map_pe_packedq(self, rows1: np.ndarray, rows2: np.ndarray, qrows1: np.ndarray, qrows2: np.ndarray, L: int, lens1=None, lens2=None):
+        n = rows1.shape[0]
+        assert qrows1.shape == qrows2.shape and rows1.shape == rows2.shape
+        res = np.zeros(2 * n, dtype=capi.RESULT_DTYPE)
+        cap = max(1, 2 * n * self.max_cigar_ops(L))
+        pool = np.zeros(cap, dtype=np.uint32)
+        used = C.c_int64(0)
+        l1 = np.ascontiguousarray(lens1, dtype=np.uint16) if lens1 is not None else None
+        l2 = np.ascontiguousarray(lens2, dtype=np.uint16) if lens2 is not None else None
+        self._chk(self._lib.bmbs_map_pe_packedq(self._ctx, capi.ptr(rows1), capi.ptr(rows2), rows1.shape[1], capi.ptr(qrows1), capi.ptr(qrows2),
+                                                qrows1.shape[1], capi.ptr(l1) if l1 is not None else None, capi.ptr(l2) if l2 is not None else None,
+                                                L, n, capi.ptr(res), capi.ptr(pool), cap, C.byref(used)))
+        return res, pool[:used.value]
+
     # ---- FASTQ text in, SAM text out (newline index and SAM formatting on the device) ---------------
     TEXT_PBAT, TEXT_UNMAPPED, TEXT_BAM = 1, 2, 16
 
@@ -407,6 +443,34 @@ class Mapper:
         for kid, nm in enumerate(("k_seed_first", "k_seed_second", "k_seed_extra")):
             d[nm] = {"n_hash": int(c[16 + 4 * kid]), "n_ext": int(c[17 + 4 * kid]), "n_sa": int(c[18 + 4 * kid])}
         return d
+
+
+# ---- packed quality classes (host arithmetic only: no device, no Mapper needed) ---------------------
+def qual_classes(params: capi.Params | None = None):
+    """bmbs_qual_classes -> (class_of u8[256], penalty_of i32[n_classes]); params None: the defaults"""
+    class_of = np.zeros(256, dtype=np.uint8)
+    pen = np.zeros(16, dtype=np.int32)
+    nc = C.c_int32(0)
+    rc = capi.lib().bmbs_qual_classes(C.byref(params) if params is not None else None, capi.ptr(class_of), capi.ptr(pen), C.byref(nc))
+    if rc:
+        raise RuntimeError("bmbs_qual_classes failed (%d)" % rc)
+    return class_of, pen[:nc.value].copy()
+
+
+def pack_quals(params, qual: np.ndarray, L: int, lens: np.ndarray | None = None, qwords: int | None = None, threads: int = 8) -> np.ndarray:
+    """bmbs_pack_quals: quality rows [n][stride] -> class rows [n][qwords] of u64 under `params` (None: the defaults)"""
+    a = np.ascontiguousarray(qual, dtype=np.uint8)
+    n, stride = a.shape
+    if qwords is None:
+        qwords = (L + 15) // 16
+    qrows = np.empty((n, qwords), dtype=np.uint64)
+    bad = C.c_int64(-1)
+    ln = np.ascontiguousarray(lens, dtype=np.uint16) if lens is not None else None
+    rc = capi.lib().bmbs_pack_quals(C.byref(params) if params is not None else None, capi.ptr(a), L, stride, n,
+                                    capi.ptr(ln) if ln is not None else None, capi.ptr(qrows), qwords, threads, C.byref(bad))
+    if rc:
+        raise ValueError("bmbs_pack_quals: row %d cannot be packed (rc %d)" % (bad.value, rc))
+    return qrows
 
 
 # ---- SAM text (host emit) --------------------------------------------------------------------------

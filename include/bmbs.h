@@ -232,6 +232,35 @@ int bmbs_map_pe_packed(bmbs_ctx*, const uint64_t* rows1, const uint64_t* rows2, 
                        const uint16_t* len1, const uint16_t* len2, int32_t L_max, int32_t stride, int64_t n_pairs, bmbs_result* results,
                        uint32_t* cigar_pool, int64_t cigar_cap, int64_t* n_cigar_used);
 
+/* ---- packed quality classes: the packed calls with 4 bits per quality going over the link instead of a byte -----------------------------
+ * The mapping path uses a quality byte for one thing, the mismatch penalty MismatchPenaltyByQuality gives it (ksw.h:148-161:
+ * mp_min + (int)(min(Q - q_base, 40) / 40 * (mp_max - mp_min)), evaluated in double), and that function takes few distinct values: 8 over
+ * the 256 bytes with the default penalties, 11 with --phred64.  So a 4-bit penalty CLASS per base carries everything a record needs, and
+ * with bmbs_map_*_packed's 2-bit bases a 150-base read goes up as 64 + 80 bytes instead of 64 + 160:
+ *   classes  the distinct penalties of the 256 bytes, sorted DESCENDING: class 0 is the largest penalty.  *n_classes = min(16, their number),
+ *            penalty_of[c] for c < *n_classes, class_of[b] = the class of byte b, or 0xFF when b's penalty is not among the 16 largest
+ *            ("cannot be packed").  With the defaults every byte has a class; every byte >= q_base has one whenever |mp_max - mp_min| <= 15;
+ *            beyond that some ordinary qualities have none, and such batches take the byte calls (bmbs_map_*_packed), the rule
+ *            bmbs_pack_rows has for letters outside ACGTN.  The bytes that fall off first are those far below q_base.
+ *   row      Wq = ceil(L_max / 16) u64 words: the class of base j in bits 4 (j % 16) .. 4 (j % 16) + 3 of word j / 16; nibbles at and beyond a
+ *            read's length are 0; rows `qwords` (>= Wq) words apart.  150 bases: 10 words = 80 bytes.  Qualities in FASTQ order for BOTH
+ *            mates, exactly what the byte calls take.
+ * bmbs_pack_quals packs a batch on the host's threads and needs no device (BMBS_EINVAL and *bad_row = the first row with a byte that has no
+ * class, or a length of 0 or beyond L_max).  The caller packs with the SAME mp_max / mp_min / q_base the context was created with: a class
+ * number means a penalty only under those.  The device writes, once per chunk, the byte rows its kernels have always read (k_qual_expand:
+ * for class c the smallest byte with that penalty), so results, CIGAR pool, n_cigar_used, statistics, counters and errors are exactly those
+ * of bmbs_map_{se,pe}_packed on the quality bytes the classes stand for (tests/test_packed_quals.py).  A context whose parameters leave
+ * some bytes without a class still serves these calls.  The records do not carry QUAL: SAM's QUAL text is written by the caller from its
+ * own FASTQ line, as for every record-level call; the text calls (bmbs_map_*_text), which print it, keep their bytes.                  */
+int bmbs_qual_classes(const bmbs_params* params /* NULL: defaults */, uint8_t class_of[256], int32_t penalty_of[16], int32_t* n_classes);
+int bmbs_pack_quals(const bmbs_params* params /* NULL: defaults */, const char* qual, int32_t L_max, int32_t stride, int64_t n,
+                    const uint16_t* len /* NULL: uniform */, uint64_t* qrows, int32_t qwords, int32_t threads, int64_t* bad_row /* may be NULL */);
+int bmbs_map_se_packedq(bmbs_ctx*, const uint64_t* rows, int32_t pwords, const uint64_t* qrows, int32_t qwords, const uint16_t* len, int32_t L_max,
+                        int64_t n_reads, bmbs_result* results, uint32_t* cigar_pool, int64_t cigar_cap, int64_t* n_cigar_used);
+int bmbs_map_pe_packedq(bmbs_ctx*, const uint64_t* rows1, const uint64_t* rows2, int32_t pwords, const uint64_t* qrows1, const uint64_t* qrows2,
+                        int32_t qwords, const uint16_t* len1, const uint16_t* len2, int32_t L_max, int64_t n_pairs, bmbs_result* results,
+                        uint32_t* cigar_pool, int64_t cigar_cap, int64_t* n_cigar_used);
+
 /* ---- fused paired-end mapping, default (fast) mode: Map_Pair_Seq_end_to_end_fast (Schema.cpp:18570-19546)
  * = get_candidates x2 (18172), filter_pairs (16052), verify_candidate_locations (18130) on the smaller side,
  * filter_pairs_single_side (16186), new_faster_verify_pairs (15773), calculate_best_map_cigar_end_to_end_return

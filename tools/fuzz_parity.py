@@ -93,16 +93,29 @@ def run_trial(t, env):
                 else:
                     a = (s1, q1, s2, q2, l1, l2) if t["mixed"] else (m1["seq"], m1["qual"], m2["seq"], m2["qual"], None, None)
                     res2, pool2 = m.map_pe_packed(mapper.Mapper.pack_rows(a[0], L, a[4]), mapper.Mapper.pack_rows(a[2], L, a[5]), a[1], a[3], L, a[4], a[5])
-                for f in ("status", "chrom", "pos", "flag", "mapq", "nm", "score", "n_cigar", "tlen", "path"):
-                    if not (res[f] == res2[f]).all():
-                        bad = [("packed entry differs in", f, int(np.nonzero(res[f] != res2[f])[0][0]))]
-                        break
-                if not bad:
-                    for i in np.nonzero(res["n_cigar"] > 0)[0][:20000]:
-                        x, y = res[i], res2[i]
-                        if not (pool[int(x["cigar_off"]):int(x["cigar_off"]) + int(x["n_cigar"])] == pool2[int(y["cigar_off"]):int(y["cigar_off"]) + int(y["n_cigar"])]).all():
-                            bad = [("packed entry differs in the CIGAR of", int(i))]
+                forms = [("packed", res2, pool2)]
+                # ... and with its qualities as 4-bit penalty classes too (bmbs_map_*_packedq), whenever every quality byte has a class
+                try:
+                    if t["mode"] == "se":
+                        forms.append(("packedq",) + m.map_se_packedq(mapper.Mapper.pack_rows(a[0], L, a[2]), m.pack_quals(a[1], L, a[2]), L, a[2]))
+                    else:
+                        forms.append(("packedq",) + m.map_pe_packedq(mapper.Mapper.pack_rows(a[0], L, a[4]), mapper.Mapper.pack_rows(a[2], L, a[5]),
+                                                                     m.pack_quals(a[1], L, a[4]), m.pack_quals(a[3], L, a[5]), L, a[4], a[5]))
+                except ValueError:
+                    pass
+                for name, res2, pool2 in forms:
+                    for f in ("status", "chrom", "pos", "flag", "mapq", "nm", "score", "n_cigar", "tlen", "path"):
+                        if not (res[f] == res2[f]).all():
+                            bad = [(name + " entry differs in", f, int(np.nonzero(res[f] != res2[f])[0][0]))]
                             break
+                    if not bad:
+                        for i in np.nonzero(res["n_cigar"] > 0)[0][:20000]:
+                            x, y = res[i], res2[i]
+                            if not (pool[int(x["cigar_off"]):int(x["cigar_off"]) + int(x["n_cigar"])] == pool2[int(y["cigar_off"]):int(y["cigar_off"]) + int(y["n_cigar"])]).all():
+                                bad = [(name + " entry differs in the CIGAR of", int(i))]
+                                break
+                    if bad:
+                        break
             except ValueError:
                 pass                                   # letters other than A C G T N: the packed format cannot hold them
     finally:
