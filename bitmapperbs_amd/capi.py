@@ -24,6 +24,7 @@ SYMBOLS = [
     "bmbs_index_file_free", "bmbs_index_build", "bmbs_index_build_device", "bmbs_host_alloc", "bmbs_host_free", "bmbs_build_id",
     "bmbs_max_cigar_ops", "bmbs_host_prefault", "bmbs_reserve", "bmbs_host_alloc_kind", "bmbs_retries", "bmbs_text_times", "bmbs_pack_rows", "bmbs_map_se_packed", "bmbs_map_pe_packed", "bmbs_sam_refs", "bmbs_map_se_text", "bmbs_map_pe_text", "bmbs_profile_total", "bmbs_profile_reset", "bmbs_inflate_bgzf", "bmbs_debug_huff_lengths", "bmbs_text_open_bgzf", "bmbs_text_map_open",
     "bmbs_qual_classes", "bmbs_pack_quals", "bmbs_map_se_packedq", "bmbs_map_pe_packedq",
+    "bmbs_text_sorted_index", "bmbs_bam_sort",
 ]
 
 
@@ -173,6 +174,11 @@ def lib() -> C.CDLL:
     L.bmbs_text_map_open.argtypes = [vp, i32, vp, u64, C.POINTER(u64), C.POINTER(i64)]
     L.bmbs_text_map_open.restype = C.c_int
     L.bmbs_map_se_text.restype = C.c_int
+    if hasattr(L, "bmbs_bam_sort"):                      # (coordinate-sorted BAM; BMBS_LIB may name an older build, as above)
+        L.bmbs_text_sorted_index.argtypes = [vp, vp, vp, i64, C.POINTER(i64)]
+        L.bmbs_text_sorted_index.restype = C.c_int
+        L.bmbs_bam_sort.argtypes = [vp, vp, u64, vp, i64, i32, vp, u64, C.POINTER(u64)]
+        L.bmbs_bam_sort.restype = C.c_int
     L.bmbs_map_pe_text.argtypes = [vp, vp, u64, vp, u64, i64, i32, vp, u64, C.POINTER(u64), C.POINTER(i64)]
     L.bmbs_map_pe_text.restype = C.c_int
     L.bmbs_retries.argtypes = [vp]
@@ -198,7 +204,7 @@ def lib() -> C.CDLL:
 
 
 LIB_SRCS = ("bmbs_api.hip", "bmbs_kernels.hip", "k_index.hip", "k_rows.hip", "k_qualpack.hip", "k_attach.hip", "k_scan.hip", "k_seed.hip", "k_vote.hip", "k_filter.hip", "k_reduce.hip", "k_align.hip", "k_finalize.hip", "k_pe_fast.hip", "k_pe_sensitive.hip",
-            "bmbs_textpath.hip", "bmbs_text.hip", "bmbs_bam.hip", "bmbs_inflate.hip", "bmbs_bytes.h", "bmbs_host.h", "bmbs_dev.h", "bmbs_sort.h", "../../include/bmbs.h",
+            "bmbs_textpath.hip", "bmbs_text.hip", "bmbs_bam.hip", "bmbs_inflate.hip", "k_bamsort.hip", "bmbs_bytes.h", "bmbs_host.h", "bmbs_dev.h", "bmbs_sort.h", "../../include/bmbs.h",
             "index_io.cpp", "index_io.h", "index_build_gpu.hip", "build_id.cpp")
 
 

@@ -195,7 +195,12 @@ struct Lane {
     // bmbs_map_*_text: newline index built on the device, SAM text written on the device
     DevBuf tx_tilecnt, tx_tileoff, tx_nl[2], tx_rec[2], tx_info, sam_len, sam_off, sam_out, chrom_chars, chrom_off;
     DevBuf bam_raw, bam_slots, bam_slot_len, bam_off, stats_snap;      // --bam: record stream, deflate scratch, BGZF slots
-    DevBuf z_comp, z_off, z_text, z_err, z_nl, z_comp2, z_off2, z_err2;          // bmbs_inflate_bgzf; (…2: mate 2 of bmbs_text_open_bgzf)
+    // coordinate sort of BAM records (k_bamsort.hip): keys / record numbers before and behind the pair sort, the sorted records' lengths and
+    // offsets, rocPRIM's scratch, the records of bmbs_bam_sort as uploaded and their lengths, the sorted record stream; bs_n = records of the
+    // last BMBS_TEXT_BAM_SORTED call (bmbs_text_sorted_index reads bs_key2 / bs_slen), -1: none
+    DevBuf bs_key, bs_key2, bs_idx, bs_idx2, bs_slen, bs_soff, bs_tmp, bs_in, bs_len, bs_off, bs_sorted;
+    int64_t bs_n = -1;
+    DevBuf z_comp, z_off, z_text, z_err, z_nl, z_comp2, z_off2, z_err2;         // bmbs_inflate_bgzf; (…2: mate 2 of bmbs_text_open_bgzf)
     struct OpenText { bool valid = false, pe = false; u64 bytes1 = 0, bytes2 = 0; int64_t n = 0; } open_text;      // between bmbs_text_open_bgzf and bmbs_text_map_open
     u32* h_info = nullptr;                              // page-locked: 8 info words + 4 totals of the text path
     int n_refs = 0, max_ref_len = 0;

@@ -11,7 +11,9 @@
 //          order kept), --contexts S (contexts per device sharing its index: S batches in flight per GPU so that the copies of
 //          one overlap the kernels of another; default 4), --batch N (records per GPU batch, default 500 k), -t N (host I/O
 //          threads), --out-parts N (the input is cut into N contiguous record ranges, each written to its own file
-//          <out>.part000 ... concurrently; `cat` of the parts in order == the one-file output), --verbose
+//          <out>.part000 ... concurrently; `cat` of the parts in order == the one-file output), --verbose,
+//          --bam --sort [--sort-mem GiB] (ONE coordinate-sorted BAM: its records are the stable sort, by reference / position /
+//          strand, of the records --bam writes; sorted on the device, see "--bam --sort" below; needs --out-parts 1)
 //
 // The reference has ONE reader thread and ONE fprintf sink (Process_Reads.cpp:2057-2260, Process_sam_out.cpp:954-1006), which is
 // what limits it.  Round 2 of this driver indexed the lines and formatted the SAM text with the host's
@@ -722,6 +724,148 @@ void bgzf_append(const char* in, size_t n, std::vector<char>& out)
     } while (done < n);
 }
 
+// ---- --bam --sort: one coordinate-sorted BAM file.  The device sorts (k_bamsort.hip); the host only cuts and concatenates. --------------
+// Pass 1 (while mapping): every batch comes back as uncompressed records sorted by key (BMBS_TEXT_BAM_SORTED) with its key and length
+// arrays (bmbs_text_sorted_index).  The key space is cut into fine bins of equal genomic length plus one for records without a
+// reference; a batch is cut at the bin edges by binary search over its keys and every slice is appended to its bin's store, in
+// Batch.seq order (the writer takes the batches in that order), so a bin holds its records in the order of the unsorted file.
+// Pass 2 (after the last batch): bins in key order, grouped into calls of at most a byte budget, go through bmbs_bam_sort -- a stable
+// sort, so equal keys keep the unsorted file's order whichever context mapped them first -- and come back as BGZF blocks.
+inline uint64_t bam_key_of(const char* r)
+{
+    uint32_t ref, pos; uint16_t flag;
+    memcpy(&ref, r + 4, 4); memcpy(&pos, r + 8, 4); memcpy(&flag, r + 18, 2);
+    return ((uint64_t)ref << 32) | ((uint64_t)(uint32_t)(pos + 1u) << 1) | (uint64_t)((flag >> 4) & 1u);
+}
+struct SortBin { std::vector<char> rec; std::vector<uint32_t> len; };
+struct SortStore {
+    std::vector<uint64_t> edge;                  // bin k holds the keys in [edge[k], edge[k + 1]); the last bin: refID -1
+    std::vector<SortBin> bin;
+    size_t bytes = 0, cap = 0;                   // record bytes + 4 per record held / allowed (--sort-mem)
+    long records = 0;
+    void init(const bmbs_index_view& v, long want_bins)
+    {
+        uint64_t G = 0;
+        for (int i = 0; i < v.n_chrom; i++) G += v.chrom_len[i];
+        const uint64_t nb = (uint64_t)std::max(1l, std::min(want_bins, 1l << 20));
+        const uint64_t W = std::max<uint64_t>(1, (G + nb - 1) / nb);
+        int ref = 0; uint64_t ref_start = 0;
+        edge.clear();
+        for (uint64_t lin = 0; lin < G || edge.empty(); lin += W) {
+            while (ref + 1 < v.n_chrom && lin >= ref_start + v.chrom_len[ref]) { ref_start += v.chrom_len[ref]; ref++; }
+            edge.push_back(lin == 0 ? 0 : ((uint64_t)(uint32_t)ref << 32) | ((lin - ref_start + 1) << 1));
+        }
+        edge.push_back((uint64_t)0xffffffffu << 32);
+        bin.assign(edge.size(), SortBin());
+        edge.push_back(~(uint64_t)0);
+    }
+    // the sorted records of one batch; false: the store's cap would be exceeded
+    bool add(Pool& pool, const char* recs, size_t nbytes, const uint64_t* key, const uint32_t* len, size_t n)
+    {
+        if (bytes + nbytes + 4 * n > cap) return false;
+        struct Slice { size_t k, lo, hi; };
+        std::vector<Slice> sl;
+        for (size_t i = 0; i < n;) {
+            const size_t k = (size_t)(std::upper_bound(edge.begin(), edge.end() - 1, key[i]) - edge.begin()) - 1;
+            const size_t hi = k + 1 < bin.size() ? (size_t)(std::lower_bound(key + i, key + n, edge[k + 1]) - key) : n;
+            sl.push_back({k, i, hi});
+            i = hi;
+        }
+        std::vector<uint64_t> off(n + 1);
+        off[0] = 0;
+        for (size_t i = 0; i < n; i++) off[i + 1] = off[i] + len[i];
+        const int T = std::max(1, std::min<int>(pool.size(), (int)sl.size()));
+        pool.run(T, [&](int t) {
+            for (size_t j = (size_t)t; j < sl.size(); j += (size_t)T) {
+                SortBin& b = bin[sl[j].k];
+                b.rec.insert(b.rec.end(), recs + off[sl[j].lo], recs + off[sl[j].hi]);
+                b.len.insert(b.len.end(), len + sl[j].lo, len + sl[j].hi);
+            }
+        });
+        bytes += nbytes + 4 * n; records += (long)n;
+        return true;
+    }
+};
+// one bmbs_bam_sort call of pass 2: whole bins first .. last, or -- a bin larger than the call budget -- the records of that bin whose
+// keys lie in [k_lo, k_hi], in the bin's order; a single key that is larger than the budget on its own is cut anywhere (`skip` of its
+// records left out, `n` taken): equal keys need no sorting, their order is the bin's
+struct SortUnit { size_t first = 0, last = 0; bool sub = false; uint64_t k_lo = 0, k_hi = 0; size_t skip = 0; size_t bytes = 0, n = 0; };
+void sort_plan(const SortStore& st, size_t budget, std::vector<SortUnit>& units)
+{
+    SortUnit cur; bool open = false;
+    auto flush = [&] { if (open) units.push_back(cur); open = false; };
+    for (size_t k = 0; k < st.bin.size(); k++) {
+        const SortBin& b = st.bin[k];
+        if (b.len.empty()) continue;
+        if (b.rec.size() <= budget) {
+            if (open && cur.bytes + b.rec.size() > budget) flush();
+            if (!open) { cur = SortUnit(); cur.first = k; open = true; }
+            cur.last = k; cur.bytes += b.rec.size(); cur.n += b.len.size();
+            continue;
+        }
+        // skew: this bin alone is over the budget.  Its key range is cut again, at the finest edges there are -- between distinct
+        // keys, wherever the bytes counted in key order reach the budget
+        flush();
+        const size_t n = b.len.size();
+        std::vector<std::pair<uint64_t, uint32_t>> kl(n);
+        { size_t at = 0; for (size_t i = 0; i < n; i++) { kl[i] = {bam_key_of(b.rec.data() + at), b.len[i]}; at += b.len[i]; } }
+        std::vector<std::pair<uint64_t, uint32_t>> in_order = kl;
+        std::sort(kl.begin(), kl.end(), [](const std::pair<uint64_t, uint32_t>& x, const std::pair<uint64_t, uint32_t>& y) { return x.first < y.first; });
+        SortUnit u; bool uopen = false;
+        auto uflush = [&] { if (uopen) units.push_back(u); uopen = false; };
+        for (size_t i = 0; i < n;) {
+            size_t j = i, gb = 0;
+            while (j < n && kl[j].first == kl[i].first) gb += kl[j++].second;
+            const uint64_t key = kl[i].first;
+            if (gb <= budget) {
+                if (uopen && u.bytes + gb > budget) uflush();
+                if (!uopen) { u = SortUnit(); u.first = u.last = k; u.sub = true; u.k_lo = key; uopen = true; }
+                u.k_hi = key; u.bytes += gb; u.n += j - i;
+            } else {
+                uflush();
+                SortUnit one; one.first = one.last = k; one.sub = true; one.k_lo = one.k_hi = key;
+                size_t seen = 0;
+                for (size_t r = 0; r < n; r++) {
+                    if (in_order[r].first != key) continue;
+                    if (one.n && one.bytes + in_order[r].second > budget) { units.push_back(one); one.skip = seen; one.bytes = 0; one.n = 0; }
+                    one.bytes += in_order[r].second; one.n++; seen++;
+                }
+                if (one.n) units.push_back(one);
+            }
+            i = j;
+        }
+        uflush();
+    }
+    flush();
+}
+// the records and lengths of a unit, one behind the other, into a staging buffer
+void sort_stage(const SortStore& st, const SortUnit& u, Pool& pool, char* dst, uint32_t* len)
+{
+    if (!u.sub) {
+        std::vector<size_t> at(u.last - u.first + 2, 0), ln(u.last - u.first + 2, 0);
+        for (size_t k = u.first; k <= u.last; k++) { at[k - u.first + 1] = at[k - u.first] + st.bin[k].rec.size(); ln[k - u.first + 1] = ln[k - u.first] + st.bin[k].len.size(); }
+        const int nb = (int)(u.last - u.first + 1), T = std::max(1, std::min(pool.size(), nb));
+        pool.run(T, [&](int t) {
+            for (int j = t; j < nb; j += T) {
+                const SortBin& b = st.bin[u.first + (size_t)j];
+                if (b.len.empty()) continue;
+                memcpy(dst + at[(size_t)j], b.rec.data(), b.rec.size());
+                memcpy(len + ln[(size_t)j], b.len.data(), b.len.size() * 4);
+            }
+        });
+        return;
+    }
+    const SortBin& b = st.bin[u.first];
+    size_t at = 0, seen = 0, taken = 0;
+    for (size_t i = 0; i < b.len.size() && taken < u.n; at += b.len[i], i++) {
+        const uint64_t key = bam_key_of(b.rec.data() + at);
+        if (key < u.k_lo || key > u.k_hi) continue;
+        if (seen++ < u.skip) continue;
+        memcpy(dst, b.rec.data() + at, b.len[i]); dst += b.len[i];
+        len[taken++] = b.len[i];
+    }
+}
+
 void print_stats(FILE* o, const int64_t st[5])
 {
     long long reads = st[0], uniq = st[1], amb = st[2], unm = st[0] - st[1] - st[2];
@@ -745,6 +889,7 @@ struct Batch {
     Pinned text1, text2, sam;                    // FASTQ windows in, SAM text out
     size_t used1 = 0, used2 = 0;
     uint64_t sam_bytes = 0;
+    std::vector<uint64_t> skey; std::vector<uint32_t> slen; int64_t n_sorted = 0;      // --sort: key and length of each record in `sam`
     std::vector<uint32_t> counts1, counts2;
     bmbs_ctx* open_ctx = nullptr;                // compressed input kept on the device: the context that holds this batch's open window
 };
@@ -802,7 +947,8 @@ int main(int argc, char** argv)
     int device = 0, io_threads = 0, contexts = 4, parts = 1, reader_threads = 0;
     std::vector<int> devices;
     long batch = 500000;
-    bool verbose = false, unmapped_out = false, pbat = false, bam = false, print_parts = false, print_plan = false;
+    bool verbose = false, unmapped_out = false, pbat = false, bam = false, print_parts = false, print_plan = false, sort_out = false;
+    double sort_mem_gib = 0;                     // --sort-mem: cap of the in-memory record store of --sort (0: half of the machine's memory)
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&]() -> const char* { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(2); } return argv[++i]; };
@@ -848,8 +994,12 @@ int main(int argc, char** argv)
         else if (a == "--pbat") pbat = true;                          // Process_CommandLines.cpp:93
         else if (a == "--bam") bam = true;                            // Process_CommandLines.cpp:94-95
         else if (a == "--sam") bam = false;
+        else if (a == "--sort") sort_out = true;                      // --bam --sort: one coordinate-sorted BAM file (sorted on the device)
+        else if (a == "--sort-mem") sort_mem_gib = atof(val());
         else { fprintf(stderr, "bmbs_search: unsupported option %s\n", a.c_str()); return 2; }
     }
+    if (sort_out && !bam) { fprintf(stderr, "bmbs_search: --sort needs --bam\n"); return 2; }
+    if (sort_out && parts > 1) { fprintf(stderr, "bmbs_search: --sort writes one file (--out-parts 1)\n"); return 2; }
     if (!build_fasta.empty()) {
         // bitmapperBS --index <fasta> [--index_folder <dir>]: <fasta>.index* or <dir>/genome.index* (Index.cpp:832-938)
         std::string prefix = build_fasta;
@@ -866,7 +1016,7 @@ int main(int argc, char** argv)
         return 0;
     }
     if (index.empty() || (seq.empty() && (seq1.empty() || seq2.empty()))) {
-        fprintf(stderr, "usage: bmbs_search --index <genome.fa> [--index_folder dir] [-t threads]\n       bmbs_search --search <index> (--seq r.fq | --seq1 a.fq --seq2 b.fq) [-o out.sam] [-e f] [--min n] [--max n] [--sensitive] [--pbat] [--unmapped_out] [--ambiguous_out] [--bam] [--mapstats f] [-t io_threads] [--out-parts n]\n");
+        fprintf(stderr, "usage: bmbs_search --index <genome.fa> [--index_folder dir] [-t threads]\n       bmbs_search --search <index> (--seq r.fq | --seq1 a.fq --seq2 b.fq) [-o out.sam] [-e f] [--min n] [--max n] [--sensitive] [--pbat] [--unmapped_out] [--ambiguous_out] [--bam [--sort [--sort-mem GiB]]] [--mapstats f] [-t io_threads] [--out-parts n]\n");
         return 2;
     }
     if (batch < 1) batch = 1;
@@ -1054,7 +1204,7 @@ int main(int argc, char** argv)
         }
         if (p == 0) {
             // OutPutSAM_Nounheader (Process_sam_out.cpp:1137-1153)
-            std::string h = "@HD\tVN:1.4\tSO:unsorted\n";
+            std::string h = sort_out ? "@HD\tVN:1.4\tSO:coordinate\n" : "@HD\tVN:1.4\tSO:unsorted\n";
             for (int i = 0; i < view.n_chrom; i++) { h += "@SQ\tSN:" + chrom_names[(size_t)i] + "\tLN:"; put_uint(h, view.chrom_len[i]); h += '\n'; }
             h += "@PG\tID:BitMapperBS\tVN:1.0.2.3\tCL:";
             for (int i = 0; i < argc; i++) { h += argv[i]; h += ' '; }
@@ -1090,7 +1240,16 @@ int main(int argc, char** argv)
             });
         for (auto& t : th) t.join();
     }
-    const int32_t flags = (pbat && !pe ? BMBS_TEXT_PBAT : 0) | (unmapped_out ? BMBS_TEXT_UNMAPPED : 0) | (bam ? BMBS_TEXT_BAM : 0);
+    const int32_t flags = (pbat && !pe ? BMBS_TEXT_PBAT : 0) | (unmapped_out ? BMBS_TEXT_UNMAPPED : 0) | (bam ? BMBS_TEXT_BAM : 0) | (sort_out ? BMBS_TEXT_BAM_SORTED : 0);
+    // --sort: the store of pass 1.  Bins: BMBS_SORT_BINS, by default 4096 of equal genomic length (0.76 Mbp of a human genome each) + one
+    // for records without a reference; its cap: --sort-mem, by default half of the machine's memory
+    SortStore sort_store;
+    if (sort_out) {
+        const char* e = getenv("BMBS_SORT_BINS");
+        sort_store.init(view, e ? atol(e) : 4096);
+        const double phys = (double)sysconf(_SC_PHYS_PAGES) * (double)sysconf(_SC_PAGE_SIZE);
+        sort_store.cap = (size_t)(sort_mem_gib > 0 ? sort_mem_gib * 1073741824.0 : phys / 2);
+    }
     const double t_loaded = now();
 
     Chan<Batch*> free_q, gpu_q;
@@ -1297,7 +1456,14 @@ int main(int argc, char** argv)
             const double t0 = now();
             pt->t_wait_w += t0 - tw0;
             const bool end = b->end;
-            if (b->n && !failed && b->sam_bytes) {
+            if (sort_out) {
+                if (b->n && !failed && b->sam_bytes && !sort_store.add(wpool, b->sam.p, (size_t)b->sam_bytes, b->skey.data(), b->slen.data(), (size_t)b->n_sorted)) {
+                    char msg[256];
+                    snprintf(msg, sizeof msg, "--sort-mem: the record store of --sort is used up (%.3f GiB allowed): %ld records fit, the run has more (spilling to disk is not implemented)",
+                             (double)sort_store.cap / 1073741824.0, sort_store.records);
+                    fail(msg);
+                }
+            } else if (b->n && !failed && b->sam_bytes) {
                 const char* text = b->sam.p;
                 const size_t len = (size_t)b->sam_bytes;
                 // One buffered pwrite per batch extends the file under its inode lock at the speed of one memcpy (10 GB/s = 28 M SAM
@@ -1350,6 +1516,10 @@ int main(int argc, char** argv)
                     if (rc == BMBS_ENOMEM && bytes > b->sam.cap && attempt == 0 && b->sam.need((size_t)bytes + 64)) continue;   // reads longer than guessed
                     if (rc) fail(bmbs_last_error(ctx));
                     b->sam_bytes = rc ? 0 : bytes;
+                    if (sort_out && !rc) {
+                        b->skey.resize((size_t)lines + 1); b->slen.resize((size_t)lines + 1);
+                        if (bmbs_text_sorted_index(ctx, b->skey.data(), b->slen.data(), lines, &b->n_sorted)) { fail(bmbs_last_error(ctx)); b->sam_bytes = 0; }
+                    }
                     break;
                 }
             }
@@ -1371,6 +1541,87 @@ int main(int argc, char** argv)
         const Part& pt = *P_[(size_t)p];
         total_records += pt.records; t_read += pt.t_read; t_write += pt.t_write; t_format += pt.t_format; t_wait_r += pt.t_wait_r; t_wait_w += pt.t_wait_w;
     }
+    // ---------------- --sort, pass 2: bins in key order -> bmbs_bam_sort -> BGZF blocks behind the header ------------------------------
+    // Calls of at most BMBS_SORT_CALL_BYTES (default 1 GiB) of records; staged by the I/O threads into page-locked buffers, sorted and
+    // deflated on the device, appended by this thread in call order.  BMBS_SORT_SLOTS staging slots (default 2) on as many contexts:
+    // the staging and upload of one call run beside the kernels and the download of the other.
+    const double t_pass1 = now();
+    size_t sort_calls = 0;
+    if (sort_out && !failed) {
+        Part& pt = *P_[0];
+        const char* e = getenv("BMBS_SORT_CALL_BYTES");
+        const size_t budget = (size_t)std::max(1l, e ? atol(e) : 1l << 30);
+        std::vector<SortUnit> units;
+        sort_plan(sort_store, budget, units);
+        sort_calls = units.size();
+        size_t max_bytes = 0, max_n = 0;
+        for (const SortUnit& u : units) { max_bytes = std::max(max_bytes, u.bytes); max_n = std::max(max_n, u.n); }
+        e = getenv("BMBS_SORT_SLOTS");
+        const int n_slots = (int)std::max<size_t>(1, std::min<size_t>({(size_t)(e ? atoi(e) : 2), ctxs.size(), units.size(), (size_t)4}));
+        struct Slot { Pinned in, out; std::vector<uint32_t> len; size_t unit = 0; uint64_t out_bytes = 0; };
+        std::vector<Slot> slots((size_t)n_slots);
+        if (!units.empty()) {
+            // (the mapping's page-locked windows are of no use here: a call is larger than a batch)
+            for (auto& b : batches) { b.text1.release(); b.text2.release(); b.sam.release(); }
+            std::vector<std::thread> th;
+            std::atomic<bool> ok(true);
+            for (Slot& sl : slots) {
+                sl.in.kind = 1; sl.out.kind = 2; sl.len.resize(max_n + 1);
+                th.emplace_back([&] { if (!sl.in.need(max_bytes + 64)) ok = false; });
+                th.emplace_back([&] { if (!sl.out.need((max_bytes / 0xff00 + 1) * 65536 + 64)) ok = false; });
+            }
+            for (auto& t : th) t.join();
+            if (!ok) fail("cannot allocate page-locked staging memory");
+        }
+        if (!failed && !units.empty()) {
+            Chan<Slot*> free_s, staged_s;
+            OrderedChan<Slot*> done_s;
+            for (Slot& sl : slots) free_s.put(&sl);
+            std::thread stager([&] {
+                Pool spool(std::max(1, std::min(16, io_threads)) - 1);
+                for (size_t i = 0; i < units.size(); i++) {
+                    Slot* sl = free_s.get();
+                    sl->unit = i;
+                    if (!failed) sort_stage(sort_store, units[i], spool, sl->in.p, sl->len.data());
+                    staged_s.put(sl);
+                }
+                for (int i = 0; i < n_slots; i++) staged_s.put(nullptr);
+            });
+            std::vector<std::thread> sorters;
+            for (int w = 0; w < n_slots; w++)
+                sorters.emplace_back([&, w] {
+                    bmbs_ctx* ctx = ctxs[(size_t)w];
+                    for (;;) {
+                        Slot* sl = staged_s.get();
+                        if (!sl) return;
+                        const SortUnit& u = units[sl->unit];
+                        sl->out_bytes = 0;
+                        for (int attempt = 0; attempt < 2 && !failed; attempt++) {
+                            const int rc = bmbs_bam_sort(ctx, sl->in.p, u.bytes, sl->len.data(), (int64_t)u.n, 0, sl->out.p, sl->out.cap, &sl->out_bytes);
+                            if (rc == BMBS_ENOMEM && attempt == 0 && sl->out_bytes > sl->out.cap && sl->out.need((size_t)sl->out_bytes + 64)) continue;
+                            if (rc) { fail(bmbs_last_error(ctx)); sl->out_bytes = 0; }
+                            break;
+                        }
+                        done_s.put((long)sl->unit, sl);
+                    }
+                });
+            for (size_t i = 0; i < units.size(); i++) {
+                Slot* sl = done_s.get();
+                size_t done = 0;
+                while (!failed && done < sl->out_bytes) {
+                    const ssize_t w = pwrite(pt.ofd, sl->out.p + done, (size_t)sl->out_bytes - done, (off_t)(pt.out_off + done));
+                    if (w <= 0) { fail(std::string("write error: ") + strerror(errno)); break; }
+                    done += (size_t)w;
+                }
+                pt.out_off += (size_t)sl->out_bytes;
+                free_s.put(sl);
+            }
+            stager.join();
+            for (auto& t : sorters) t.join();
+        }
+        for (Slot& sl : slots) { sl.in.release(); sl.out.release(); }
+    }
+    const double t_pass2 = now();
     if (bam && !failed) {
         static const unsigned char eof_block[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         Part& lastp = *P_[(size_t)parts - 1];
@@ -1379,6 +1630,7 @@ int main(int argc, char** argv)
     }
     const double t_joined = now();
     for (int p = 0; p < parts; p++) { Part& pt = *P_[(size_t)p]; if (pt.alloc_end > pt.out_off && ftruncate(pt.ofd, (off_t)pt.out_off) != 0) failed = true; ::close(pt.ofd); if (p < live_parts) { pt.s1.close(); if (pe) pt.s2.close(); } }
+    if (failed && sort_out && P_[0]->regular) ::unlink(out.c_str());      // a sorted file is whole or absent (a device or a pipe is left alone)
     if (failed) { fprintf(stderr, "bmbs_search: failed\n"); return 1; }
     int64_t st[5];
     bmbs_stats_allreduce(ctxs.data(), (int)ctxs.size(), st);      // get_mapping_informations: the counters of every worker summed
@@ -1390,6 +1642,9 @@ int main(int argc, char** argv)
         fprintf(stderr, "[bmbs_search] records %ld  load+attach %.3fs  mapping wall %.3fs  (pipeline %.3fs; stage busy, summed over %d part(s): read + newline count %.3fs, gpu calls %.3fs over %d context(s), host format %.3fs, write %.3fs)  %d I/O threads, batch %ld, %zu device(s) x %d context(s), %d output part(s)\n",
                 total_records, t_loaded - t_start, t_end - t_loaded, t_joined - t_loaded, live_parts, t_read, t_gpu, n_ctx, t_format, t_write, io_threads, batch,
                 n_owner, contexts, parts);
+    if (verbose && sort_out)
+        fprintf(stderr, "[bmbs_search] sort: bins %zu (one of them for records without a reference), pass-2 calls %zu, store bytes %zu (%ld records), pass 1 %.3fs (mapping, binning), pass 2 %.3fs (sort, deflate, write)\n",
+                sort_store.bin.size(), sort_calls, sort_store.bytes, sort_store.records, t_pass1 - t_loaded, t_pass2 - t_pass1);
     if (verbose)
         fprintf(stderr, "[bmbs_search] stage idle (waiting for a batch, summed): readers %.3fs, gpu workers %.3fs, writers %.3fs\n", t_wait_r, t_wait_g, t_wait_w);
     if (verbose) {

@@ -1,12 +1,14 @@
 // bitmapperbs_amd/csrc/bmbs_textpath.hip -- the two ends of the file path, their kernels and their entry points (a translation unit of its
 // own since round 5): FASTQ text -> line index -> read rows (bmbs_map_*_fastq, bmbs_map_*_text), BGZF blocks inflated on the device
 // (bmbs_inflate_bgzf, bmbs_text_open_bgzf / bmbs_text_map_open), records -> SAM text or BAM records in BGZF blocks.  The mapping in
-// between is bmbs_api.hip's (lane_enqueue / lane_settle).  Kernels: bmbs_text.hip, bmbs_bam.hip, bmbs_inflate.hip.
+// between is bmbs_api.hip's (lane_enqueue / lane_settle).  Kernels: bmbs_text.hip, bmbs_bam.hip, bmbs_inflate.hip, k_bamsort.hip (the
+// coordinate sort of BAM records: BMBS_TEXT_BAM_SORTED, bmbs_bam_sort).
 #include "bmbs_host.h"
 #define DEVI __device__ __forceinline__
 #include "bmbs_text.hip"
 #include "bmbs_bam.hip"
 #include "bmbs_inflate.hip"
+#include "k_bamsort.hip"
 
 // the constants the kernels of this file read: x^(2^n) mod P of CRC-32 for the BGZF blocks' CRCs (bmbs_bytes.h: crc_x8n); per device
 void textpath_device_init(Lane* c)
@@ -201,9 +203,11 @@ int lane_map_text(Lane* c, bool pe, const char* text1, u64 bytes1, const char* t
     if (!c) return BMBS_EINVAL;
     if (sam_bytes) *sam_bytes = 0;
     if (n_lines_out) *n_lines_out = 0;
+    if ((flags_in & BMBS_TEXT_BAM_SORTED) && !(flags_in & BMBS_TEXT_BAM)) { c->err = "text call: BMBS_TEXT_BAM_SORTED is only valid together with BMBS_TEXT_BAM"; return BMBS_EINVAL; }
+    if (flags_in & BMBS_TEXT_BAM_SORTED) c->bs_n = -1;
     if (!c->attached) { c->err = "no index attached"; return BMBS_ESTATE; }
     if (c->n_refs != c->ix.n_chrom) { c->err = "bmbs_sam_refs has not been given the index's reference names"; return BMBS_ESTATE; }
-    if (n_records <= 0) return BMBS_OK;
+    if (n_records <= 0) { if (flags_in & BMBS_TEXT_BAM_SORTED) c->bs_n = 0; return BMBS_OK; }
     if (!text1 || (pe && !text2) || !sam) { c->err = "text call: NULL buffer"; return BMBS_EINVAL; }
     if (bytes1 >= (1ull << 32) || bytes2 >= (1ull << 32)) { c->err = "a text window has to be smaller than 4 GiB (32-bit offsets)"; return BMBS_EINVAL; }
     HIPCHK(c, hipSetDevice(c->dev));
@@ -269,6 +273,88 @@ static TxwPlan txw_plan(bool pe, u64 text_bytes, u64 n_lines, int hb)
     t.src_cap = tiny ? 16u : (u32)std::min<u64>(need_src(lpb), src_max);
     t.lds = (size_t)t.out_cap + 16 + (pe ? 2 : 1) * ((size_t)t.src_cap + 16);
     return t;
+}
+
+// ---- a record stream on the device -> BGZF blocks of BGZF_IN input bytes (the last one shorter), deflated by one workgroup each into
+// the slots; total_ptr = the stream's size in device memory (what k_bgzf_block reads); *ztotal = the compressed bytes.  bgzf_collect
+// then puts the blocks one behind the other into c->sam_out.
+static int bgzf_deflate(Lane* c, const char* raw, const u64* total_ptr, u64 raw_total, u64* ztotal)
+{
+    const u64 nb = (raw_total + BGZF_IN - 1) / BGZF_IN;
+    ENS(c, c->bam_slots, nb * (u64)BGZF_SLOT);
+    ENS(c, c->bam_slot_len, nb * 4 + 64); ENS(c, c->bam_off, (nb + 1) * 8 + 64);
+    const size_t lds = (size_t)BGZF_THREADS * BGZF_PSTRIDE * 4;                      // the block's bytes (padded segments)
+    HIPCHK(c, hipMemsetAsync(c->bam_slots.p, 0, nb * (u64)BGZF_SLOT, c->stream));      // (k_bgzf_block ORs the shared words of its stream into the slots)
+    static std::once_flag lds_once[16];
+    std::call_once(lds_once[c->dev & 15], [&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_bgzf_block), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
+    prof_begin(c, "k_bgzf_block");
+    hipLaunchKernelGGL(k_bgzf_block, dim3((unsigned)nb), dim3(BGZF_THREADS), lds, c->stream, raw, total_ptr, c->bam_slots.as<char>(), c->bam_slot_len.as<u32>());
+    prof_end(c);
+    const int rc = scan_u32(c, c->bam_slot_len.as<u32>(), nb, c->bam_off.as<u64>(), 20);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->h_info + 26, c->totals.as<u64>() + 20, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *ztotal = *reinterpret_cast<const u64*>(c->h_info + 26);
+    return BMBS_OK;
+}
+static int bgzf_collect(Lane* c, u64 raw_total, u64 ztotal)
+{
+    const u64 nb = (raw_total + BGZF_IN - 1) / BGZF_IN;
+    ENS(c, c->sam_out, ztotal + 64);
+    prof_begin(c, "k_bgzf_gather");
+    hipLaunchKernelGGL(k_bgzf_gather, dim3((unsigned)nb), dim3(256), 0, c->stream, c->bam_slots.as<char>(), c->bam_slot_len.as<u32>(), c->bam_off.as<u64>(), c->sam_out.as<char>());
+    prof_end(c);
+    return BMBS_OK;
+}
+
+// ---- coordinate sort of a record stream on the device (k_bamsort.hip): n entries, entry i = len[i] bytes at raw + off[i] (off: the
+// exclusive scan of len, `total` bytes in all; raw is padded by 16 bytes and more) -> c->bs_sorted: the records stably sorted by key,
+// c->bs_key2 / c->bs_slen their keys and lengths in that order, totals[23] their size.  skip_empty: entries of length 0 are output
+// lines that print nothing, not records (they end up behind the records); *n_records = the others.
+// BMBS_BSG_TINY=1 (test aid): no piece fits the gather kernel's image -- every workgroup takes the plain path.
+static int bam_sort_device(Lane* c, const char* raw, const u64* off, const u32* len, u64 n, u64 total, bool skip_empty, u64* n_records)
+{
+    static const bool tiny = getenv("BMBS_BSG_TINY") != nullptr;
+    ENS(c, c->bs_key, n * 8 + 64); ENS(c, c->bs_key2, n * 8 + 64); ENS(c, c->bs_idx, n * 4 + 64); ENS(c, c->bs_idx2, n * 4 + 64);
+    ENS(c, c->bs_slen, n * 4 + 64); ENS(c, c->bs_soff, (n + 1) * 8 + 64); ENS(c, c->bs_sorted, total + 256);
+    u32* const info = c->tx_info.as<u32>() + 8;
+    HIPCHK(c, hipMemsetAsync(info, 0, 16, c->stream));
+    prof_begin(c, "k_bam_keys");
+    hipLaunchKernelGGL(k_bam_keys, dim3(nblk(n, 256)), dim3(256), 0, c->stream, raw, off, len, (long)n, skip_empty ? 1 : 0, c->bs_key.as<u64>(), c->bs_idx.as<u32>(), info);
+    prof_end(c);
+    HIPCHK(c, hipMemcpyAsync(c->h_info + 8, info, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->h_info[8]) {
+        c->err = "bam sort: the length given for record " + std::to_string(~c->h_info[8]) + " is not its block_size + 4 (or is below the 36 bytes every BAM record has)";
+        return BMBS_EINVAL;
+    }
+    if (n_records) *n_records = n - c->h_info[10];
+    // the key bits that can be set: 33 of position and strand, and those of the largest reference index (-1 is all ones: it stays last
+    // under any number of low bits, because no other index has them all set)
+    int ref_bits = 1;
+    while (ref_bits < 32 && ((u64)c->h_info[9] + 1) >> ref_bits) ref_bits++;
+    const unsigned end_bit = (unsigned)(33 + ref_bits);
+    size_t tmp_bytes = 0;
+    if (rocprim::radix_sort_pairs(nullptr, tmp_bytes, c->bs_key.as<u64>(), c->bs_key2.as<u64>(), c->bs_idx.as<u32>(), c->bs_idx2.as<u32>(), (size_t)n, 0u, end_bit, c->stream) != hipSuccess) {
+        c->err = "bam sort: radix_sort_pairs (size query) failed"; return BMBS_ENODEV;
+    }
+    ENS(c, c->bs_tmp, tmp_bytes + 64);
+    prof_begin(c, "bam_pair_sort");
+    if (rocprim::radix_sort_pairs(c->bs_tmp.p, tmp_bytes, c->bs_key.as<u64>(), c->bs_key2.as<u64>(), c->bs_idx.as<u32>(), c->bs_idx2.as<u32>(), (size_t)n, 0u, end_bit, c->stream) != hipSuccess) {
+        c->err = "bam sort: radix_sort_pairs failed"; return BMBS_ENODEV;
+    }
+    prof_end(c);
+    hipLaunchKernelGGL(k_bam_slen, dim3(nblk(n, 256)), dim3(256), 0, c->stream, len, c->bs_idx2.as<u32>(), (long)n, c->bs_slen.as<u32>());
+    const int rc = scan_u32(c, c->bs_slen.as<u32>(), n, c->bs_soff.as<u64>(), 23);
+    if (rc) return rc;
+    // records per workgroup: three quarters of the image at the stream's mean record size
+    const u64 mean = total / std::max<u64>(n, 1) + 1;
+    const int rpb = (int)std::min<u64>(std::max<u64>((u64)BSG_CAP * 3 / 4 / mean, 1), 1024);
+    prof_begin(c, "k_bam_gather");
+    hipLaunchKernelGGL(k_bam_gather, dim3(nblk(n, (unsigned)rpb)), dim3(BSG_THREADS), 0, c->stream, raw, off, c->bs_idx2.as<u32>(), c->bs_soff.as<u64>(), (long)n, rpb,
+                       tiny ? 0u : (u32)BSG_CAP, c->bs_sorted.as<char>());
+    prof_end(c);
+    return BMBS_OK;
 }
 
 // the text window(s) are on the device (fq_text1 / fq_text2) and their newline positions are being indexed (text_index): record fields,
@@ -367,8 +453,7 @@ int lane_text_finish(Lane* c, bool pe, u64 bytes1, u64 bytes2, int64_t n_records
         const u64 raw_total = *reinterpret_cast<const u64*>(c->h_info + 24);
         if (n_lines_out) *n_lines_out = (int64_t)n2;
         if (c->h_info[3]) { c->err = "output line " + std::to_string(c->h_info[3] - 1) + " of this batch has a read name of more than 254 characters: BAM cannot hold it"; return BMBS_EINVAL; }
-        if (!raw_total) return BMBS_OK;
-        const u64 nb = (raw_total + BGZF_IN - 1) / BGZF_IN;
+        if (!raw_total) { if (flags_in & BMBS_TEXT_BAM_SORTED) c->bs_n = 0; return BMBS_OK; }
         ENS(c, c->bam_raw, raw_total + 256);
         const TxwPlan tw = txw_plan(pe, bytes1 + bytes2, n2, (36 + 4 * std::max(max_ops, 1) + 8 + 15) & ~15);
         if (!tw.lpb) { c->err = "text call: CIGARs too long"; return BMBS_EINVAL; }
@@ -376,27 +461,34 @@ int lane_text_finish(Lane* c, bool pe, u64 bytes1, u64 bytes2, int64_t n_records
         hipLaunchKernelGGL(k_line_write<true>, dim3(nblk(n2, (unsigned)tw.lpb)), dim3(TXW_THREADS), tw.lds, c->stream, in, (long)n2, c->sam_off.as<u64>(), tw.lpb, tw.out_cap, tw.src_cap,
                            c->bam_raw.as<char>());
         prof_end(c);
-        ENS(c, c->bam_slots, nb * (u64)BGZF_SLOT);
-        ENS(c, c->bam_slot_len, nb * 4 + 64); ENS(c, c->bam_off, (nb + 1) * 8 + 64);
-        const size_t lds = (size_t)BGZF_THREADS * BGZF_PSTRIDE * 4;                      // the block's bytes (padded segments)
-        HIPCHK(c, hipMemsetAsync(c->bam_slots.p, 0, nb * (u64)BGZF_SLOT, c->stream));      // (k_bgzf_block ORs the shared words of its stream into the slots)
-        static std::once_flag lds_once[16];
-        std::call_once(lds_once[c->dev & 15], [&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_bgzf_block), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
-        prof_begin(c, "k_bgzf_block");
-        hipLaunchKernelGGL(k_bgzf_block, dim3((unsigned)nb), dim3(BGZF_THREADS), lds, c->stream, c->bam_raw.as<char>(), c->totals.as<u64>() + 19,
-                           c->bam_slots.as<char>(), c->bam_slot_len.as<u32>());
-        prof_end(c);
-        rc = scan_u32(c, c->bam_slot_len.as<u32>(), nb, c->bam_off.as<u64>(), 20);
+        if (flags_in & BMBS_TEXT_BAM_SORTED) {
+            // ---- the uncompressed records in coordinate order (k_bamsort.hip); a driver merges the batches (bmbs_bam_sort)
+            if (sam_bytes) *sam_bytes = raw_total;
+            if (raw_total > sam_cap) return too_small("text call: the BAM buffer is too small (sam_bytes tells what this batch needs)");
+            u64 n_rec = 0;
+            rc = bam_sort_device(c, c->bam_raw.as<char>(), c->sam_off.as<u64>(), c->sam_len.as<u32>(), n2, raw_total, true, &n_rec);
+            if (rc) return rc;
+            c->bs_n = (int64_t)n_rec;
+            if (trace) { HIPCHK(c, hipStreamSynchronize(c->stream)); tp[5] = wall(); }
+            double cs = 0;
+            rc = download_locked(c, sam, c->bs_sorted.as<char>(), raw_total, c->stream, &cs);
+            if (rc) return rc;
+            c->link_down_s += cs;
+            tp[6] = wall();
+            c->text_call_s += tp[6] - tp[0]; c->text_calls++;
+            if (trace)
+                fprintf(stderr, "[text/bam sorted] n=%ld in=%.1fMB records=%.1fMB  upload %.2f lines+records %.2f rows+map %.2f  len+scan %.2f  write+sort %.2f  download %.2f  total %.2f ms\n",
+                        (long)n2, (double)(bytes1 + bytes2) / 1e6, (double)raw_total / 1e6, (tp[7] - tp[0]) * 1e3, (tp[2] - tp[7]) * 1e3, (tp[3] - tp[2]) * 1e3, (tp[4] - tp[3]) * 1e3,
+                        (tp[5] - tp[4]) * 1e3, (tp[6] - tp[5]) * 1e3, (tp[6] - tp[0]) * 1e3);
+            return BMBS_OK;
+        }
+        u64 ztotal = 0;
+        rc = bgzf_deflate(c, c->bam_raw.as<char>(), c->totals.as<u64>() + 19, raw_total, &ztotal);
         if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->h_info + 26, c->totals.as<u64>() + 20, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        const u64 ztotal = *reinterpret_cast<const u64*>(c->h_info + 26);
         if (sam_bytes) *sam_bytes = ztotal;
         if (ztotal > sam_cap) return too_small("text call: the BAM buffer is too small (sam_bytes tells what this batch needs)");
-        ENS(c, c->sam_out, ztotal + 64);
-        prof_begin(c, "k_bgzf_gather");
-        hipLaunchKernelGGL(k_bgzf_gather, dim3((unsigned)nb), dim3(256), 0, c->stream, c->bam_slots.as<char>(), c->bam_slot_len.as<u32>(), c->bam_off.as<u64>(), c->sam_out.as<char>());
-        prof_end(c);
+        rc = bgzf_collect(c, raw_total, ztotal);
+        if (rc) return rc;
         if (trace) { HIPCHK(c, hipStreamSynchronize(c->stream)); tp[5] = wall(); }
         {
             double cs = 0;
@@ -576,6 +668,8 @@ int lane_text_map_open(Lane* c, int32_t flags_in, char* sam, u64 sam_cap, u64* s
     if (!c) return BMBS_EINVAL;
     if (sam_bytes) *sam_bytes = 0;
     if (n_lines_out) *n_lines_out = 0;
+    if ((flags_in & BMBS_TEXT_BAM_SORTED) && !(flags_in & BMBS_TEXT_BAM)) { c->err = "text call: BMBS_TEXT_BAM_SORTED is only valid together with BMBS_TEXT_BAM"; return BMBS_EINVAL; }
+    if (flags_in & BMBS_TEXT_BAM_SORTED) c->bs_n = -1;
     if (!c->open_text.valid) { c->err = "text map: no open batch (bmbs_text_open_bgzf first)"; return BMBS_ESTATE; }
     if (c->n_refs != c->ix.n_chrom) { c->err = "bmbs_sam_refs has not been given the index's reference names"; return BMBS_ESTATE; }
     if (!sam) { c->err = "text call: NULL buffer"; return BMBS_EINVAL; }
@@ -711,6 +805,73 @@ extern "C" int bmbs_text_times(bmbs_ctx* X, double out[4])
     return BMBS_OK;
 }
 
+
+// ---- coordinate sort (k_bamsort.hip): the index of the last sorted text call, and the sort of records the host holds ----------------------
+static int lane_text_sorted_index(Lane* c, uint64_t* key, uint32_t* len, int64_t cap, int64_t* n)
+{
+    if (!n) { c->err = "sorted index: NULL argument"; return BMBS_EINVAL; }
+    *n = 0;
+    if (c->bs_n < 0) { c->err = "sorted index: the context's last text call was not a BMBS_TEXT_BAM_SORTED call that returned records"; return BMBS_ESTATE; }
+    *n = c->bs_n;
+    if (c->bs_n > cap) { c->err = "sorted index: the arrays are too small (n tells what is needed)"; return BMBS_ENOMEM; }
+    if (!c->bs_n) return BMBS_OK;
+    if (!key || !len) { c->err = "sorted index: NULL argument"; return BMBS_EINVAL; }
+    HIPCHK(c, hipSetDevice(c->dev));
+    hipStream_t ds = c->down_stream ? c->down_stream : c->stream;
+    HIPCHK(c, hipMemcpyAsync(key, c->bs_key2.p, (size_t)c->bs_n * 8, hipMemcpyDeviceToHost, ds));
+    HIPCHK(c, hipMemcpyAsync(len, c->bs_slen.p, (size_t)c->bs_n * 4, hipMemcpyDeviceToHost, ds));
+    HIPCHK(c, hipStreamSynchronize(ds));
+    return BMBS_OK;
+}
+
+static int lane_bam_sort(Lane* c, const char* records, uint64_t bytes, const uint32_t* len, int64_t n_in, int32_t flags, char* out, uint64_t out_cap, uint64_t* out_bytes)
+{
+    if (out_bytes) *out_bytes = 0;
+    if (n_in < 0 || n_in >= (1ll << 31) || (flags & ~BMBS_BAMSORT_RAW)) { c->err = "bam sort: bad argument"; return BMBS_EINVAL; }
+    if (n_in && (!records || !len)) { c->err = "bam sort: NULL buffer"; return BMBS_EINVAL; }
+    const u64 n = (u64)n_in;
+    u64 sum = 0;
+    for (u64 i = 0; i < n; i++) {
+        if (len[i] < 36) { c->err = "bam sort: the length given for record " + std::to_string(i) + " is below the 36 bytes every BAM record has"; return BMBS_EINVAL; }
+        sum += len[i];
+    }
+    if (sum != bytes) { c->err = "bam sort: the record lengths add up to " + std::to_string(sum) + " bytes, not to the " + std::to_string(bytes) + " given"; return BMBS_EINVAL; }
+    if (!n) return BMBS_OK;
+    const bool rawout = (flags & BMBS_BAMSORT_RAW) != 0;
+    if (rawout) {
+        if (out_bytes) *out_bytes = bytes;
+        if (bytes > out_cap) { c->err = "bam sort: the output buffer is too small (out_bytes tells what is needed)"; return BMBS_ENOMEM; }
+    }
+    if (!out) { c->err = "bam sort: NULL buffer"; return BMBS_EINVAL; }
+    HIPCHK(c, hipSetDevice(c->dev));
+    c->bs_n = -1;                                         // (the sort's buffers are those of the text calls' sorted index)
+    ENS(c, c->bs_in, bytes + 256); ENS(c, c->bs_len, n * 4 + 64); ENS(c, c->bs_off, (n + 1) * 8 + 64);
+    {
+        std::lock_guard<std::mutex> up(g_h2d_mu[c->dev & 15]);
+        hipStream_t us = c->up_stream ? c->up_stream : c->stream;
+        const u64 piece = 128ull << 20;
+        for (u64 o = 0; o < bytes; o += piece) HIPCHK(c, hipMemcpyAsync(c->bs_in.as<char>() + o, records + o, std::min(piece, bytes - o), hipMemcpyHostToDevice, us));
+        HIPCHK(c, hipMemcpyAsync(c->bs_len.p, len, n * 4, hipMemcpyHostToDevice, us));
+        HIPCHK(c, hipStreamSynchronize(us));
+    }
+    int rc = scan_u32(c, c->bs_len.as<u32>(), n, c->bs_off.as<u64>(), 24);
+    if (rc) return rc;
+    rc = bam_sort_device(c, c->bs_in.as<char>(), c->bs_off.as<u64>(), c->bs_len.as<u32>(), n, bytes, false, nullptr);
+    if (rc) return rc;
+    if (rawout) return download_locked(c, out, c->bs_sorted.as<char>(), bytes, c->stream, nullptr);
+    u64 ztotal = 0;
+    rc = bgzf_deflate(c, c->bs_sorted.as<char>(), c->totals.as<u64>() + 23, bytes, &ztotal);
+    if (rc) return rc;
+    if (out_bytes) *out_bytes = ztotal;
+    if (ztotal > out_cap) { c->err = "bam sort: the output buffer is too small (out_bytes tells what is needed)"; return BMBS_ENOMEM; }
+    rc = bgzf_collect(c, bytes, ztotal);
+    if (rc) return rc;
+    return download_locked(c, out, c->sam_out.as<char>(), ztotal, c->stream, nullptr);
+}
+
+extern "C" int bmbs_text_sorted_index(bmbs_ctx* X, uint64_t* key, uint32_t* len, int64_t cap, int64_t* n) { ON_LANE0(lane_text_sorted_index(c, key, len, cap, n)); }
+extern "C" int bmbs_bam_sort(bmbs_ctx* X, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, int32_t flags, char* out, uint64_t out_cap, uint64_t* out_bytes)
+{ ON_LANE0(lane_bam_sort(c, records, bytes, len, n, flags, out, out_cap, out_bytes)); }
 
 extern "C" int bmbs_sam_refs(bmbs_ctx* X, const char* const* names, int32_t n_names) { ON_LANE0(lane_sam_refs(c, names, n_names)); }
 extern "C" int bmbs_map_se_text(bmbs_ctx* X, const char* text, uint64_t text_bytes, int64_t n_records, int32_t flags, char* sam, uint64_t sam_cap,

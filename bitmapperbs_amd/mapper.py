@@ -55,9 +55,15 @@ class Index:
             pass
 
 
+class BamSortNoRoom(RuntimeError):
+    """Mapper.bam_sort: the output buffer was too small (BMBS_ENOMEM); `needed` = the bytes the library asks for"""
+    needed = 0
+
+
 class Mapper:
     def __init__(self, index: Index, device: int = 0, share: "Mapper | None" = None, **params):
-        """share: another Mapper on the same device whose attached index this one uses (bmbs_index_share) -- for two batches
+        """index None: a context with no index attached (enough for bam_sort and inflate_bgzf).
+        share: another Mapper on the same device whose attached index this one uses (bmbs_index_share) -- for two batches
         in flight from two host threads; `share` has to stay open for as long as this one is used"""
         self._lib = capi.lib()
         self.params = capi.default_params(**params)
@@ -66,7 +72,9 @@ class Mapper:
             raise RuntimeError("bmbs_create failed: no usable HIP device (the mapper has no CPU path)")
         self.index = index
         self._owner = share
-        if share is None:
+        if index is None and share is None:
+            pass                                   # a context without an index: what bam_sort() needs
+        elif share is None:
             self._chk(self._lib.bmbs_index_attach(self._ctx, C.byref(index.view)))
         else:
             self._chk(self._lib.bmbs_index_share(self._ctx, share._ctx))
@@ -240,6 +248,8 @@ class Mapper:
 
     # ---- FASTQ text in, SAM text out (newline index and SAM formatting on the device) ---------------
     TEXT_PBAT, TEXT_UNMAPPED, TEXT_BAM = 1, 2, 16
+    TEXT_BAM_SORTED = 32      # with TEXT_BAM: the batch's uncompressed BAM records, stably sorted by bam_key order (include/bmbs.h)
+    BAMSORT_RAW = 1
 
     def _set_refs(self):
         if getattr(self, "_refs_set", False):
@@ -320,6 +330,36 @@ class Mapper:
         out = np.empty(cap, dtype=np.uint8)
         used = C.c_uint64(0); lines = C.c_int64(0)
         self._chk(self._lib.bmbs_text_map_open(self._ctx, flags, capi.ptr(out), cap, C.byref(used), C.byref(lines)))
+        return out[:used.value].tobytes()
+
+    def sorted_index(self):
+        """(keys u64[n], lengths u32[n]) of the records the last map_text / text_map_open call with TEXT_BAM | TEXT_BAM_SORTED returned, in
+        the order returned (bmbs_text_sorted_index)"""
+        n = C.c_int64(0)
+        rc = self._lib.bmbs_text_sorted_index(self._ctx, None, None, 0, C.byref(n))
+        if rc and rc != -12:
+            self._chk(rc)
+        key = np.empty(max(1, n.value), dtype=np.uint64); ln = np.empty(max(1, n.value), dtype=np.uint32)
+        self._chk(self._lib.bmbs_text_sorted_index(self._ctx, capi.ptr(key), capi.ptr(ln), n.value, C.byref(n)))
+        return key[:n.value], ln[:n.value]
+
+    def bam_sort(self, records: bytes, lens, raw: bool = False, cap: int | None = None) -> bytes:
+        """concatenated BAM records + their sizes -> the records stably sorted by coordinate key (bmbs_bam_sort): BGZF blocks, or the
+        uncompressed records with raw=True.  cap: bytes of the output buffer handed to the library (default: ample); a buffer that is
+        too small raises BamSortNoRoom, whose `needed` is the size the library asks for"""
+        ln = np.ascontiguousarray(lens, dtype=np.uint32)
+        a = np.frombuffer(records, dtype=np.uint8) if len(records) else np.zeros(1, dtype=np.uint8)
+        if cap is None:
+            cap = len(records) + (len(records) // 0xff00 + 2) * 64 + 4096
+        out = np.empty(max(1, cap), dtype=np.uint8)
+        used = C.c_uint64(0)
+        rc = self._lib.bmbs_bam_sort(self._ctx, capi.ptr(a), len(records), capi.ptr(ln) if ln.size else None, ln.size, self.BAMSORT_RAW if raw else 0,
+                                     capi.ptr(out), cap, C.byref(used))
+        if rc == -12:
+            e = BamSortNoRoom(f"bmbs error {rc}: {self._lib.bmbs_last_error(self._ctx).decode()}")
+            e.needed = int(used.value)
+            raise e
+        self._chk(rc)
         return out[:used.value].tobytes()
 
     def sync(self):

@@ -317,6 +317,10 @@ int bmbs_map_pe_fastq(bmbs_ctx*, const bmbs_fastq_view* mate1, const bmbs_fastq_
                                  * behind its header) instead of SAM text: what the reference gets from htslib's sam_parse1 + bam_write1
                                  * per line (bam_prase.cpp:201-221), built and deflated on the device; the INFLATED bytes are the
                                  * reference's, block boundaries and compressed bytes are not.  *sam_bytes = compressed bytes        */
+#define BMBS_TEXT_BAM_SORTED 32 /* --bam --sort, only together with BMBS_TEXT_BAM (BMBS_EINVAL otherwise): `sam` receives the batch's
+                                 * UNCOMPRESSED BAM records, stably sorted by the coordinate key below (equal keys keep the order the
+                                 * unsorted call gives them); *sam_bytes = their size; BMBS_ENOMEM as above.  The records are sorted on
+                                 * the device (csrc/k_bamsort.hip); a driver merges batches with bmbs_bam_sort                       */
 int bmbs_sam_refs(bmbs_ctx*, const char* const* names, int32_t n_names);
 int bmbs_map_se_text(bmbs_ctx*, const char* text, uint64_t text_bytes, int64_t n_records, int32_t flags,
                      char* sam, uint64_t sam_cap, uint64_t* sam_bytes, int64_t* n_lines);
@@ -360,6 +364,26 @@ int bmbs_text_open_bgzf(bmbs_ctx*, const bmbs_ztext* mate1, const bmbs_ztext* ma
 /* (An ordinary .gz file -- ONE deflate stream per member -- is inflated by the driver's block-parallel host inflater, csrc/pgz.h.  Round 4
  * also carried a device form of that scheme, bmbs_inflate_gzip / bmbs_text_open_gzip: exact, and slower than the host's; removed in round 5.) */
 int bmbs_text_map_open(bmbs_ctx*, int32_t flags, char* sam, uint64_t sam_cap, uint64_t* sam_bytes, int64_t* n_lines);
+
+/* ---- coordinate-sorted BAM: the records are sorted on the device (csrc/k_bamsort.hip) ---------------------------------------------------
+ * The sort key of a BAM record -- refID = the int32 at byte 4 of the record (counting its block_size word), pos = the int32 at byte 8,
+ * flag = the uint16 at byte 18 -- is
+ *     key = (uint64)(uint32)refID << 32  |  (uint64)(uint32)(pos + 1) << 1  |  ((flag >> 4) & 1)
+ * reference index, position, strand: coordinate order; refID -1 sorts last, pos -1 gives 0.  Every sort here is STABLE: records with
+ * equal keys keep their input order.
+ * bmbs_text_sorted_index: key and byte length of each record the context's last BMBS_TEXT_BAM_SORTED call returned, in the order
+ * returned; *n = their number (BMBS_ENOMEM with *n set when cap is smaller; BMBS_ESTATE when there was no such call).  A driver cuts a
+ * batch at coordinate boundaries with a binary search over `key`.
+ * bmbs_bam_sort: `records` = n concatenated BAM records in host memory (input order), len[i] = their sizes (block_size + 4 each);
+ * `out` receives the same records stably sorted by key -- as complete BGZF blocks of 0xff00 input bytes (the call's last block
+ * shorter), or uncompressed with BMBS_BAMSORT_RAW; *out_bytes = the bytes written.  Needs no attached index.  BMBS_ENOMEM with
+ * *out_bytes = the size needed when out_cap is too small; BMBS_EINVAL (bmbs_last_error names the record) when a len[i] disagrees with
+ * its record's block_size or is below 36, or when sum(len) != bytes; n = 0 is valid (0 bytes).  Page-locked buffers move at link speed;
+ * the upload takes its turn on the device's upload mutex like every host call.                                                    */
+#define BMBS_BAMSORT_RAW 1
+int bmbs_text_sorted_index(bmbs_ctx*, uint64_t* key, uint32_t* len, int64_t cap, int64_t* n);
+int bmbs_bam_sort(bmbs_ctx*, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, int32_t flags, char* out,
+                  uint64_t out_cap, uint64_t* out_bytes);
 
 /* a21: per-ctx counters of the batches mapped so far = {reads, unique, ambiguous, mapped bases,
  * error bases} (Schema.cpp:25141-25146); bmbs_stats_allreduce sums them over the ctxs one process

@@ -1,0 +1,164 @@
+#!/usr/bin/env python3
+"""tools/sort_probe.py -- what `--bam --sort` costs next to `--bam`, file to file, on one input and one build.
+
+Alternating runs of `bmbs_search --bam` and `bmbs_search --bam --sort` (at least three each), medians and spread of the mapping
+wall (for --sort: both passes); beside the measured ratio the one the link bytes alone predict, (2R + c) / c -- R = raw record
+bytes per read (down in pass 1, up in pass 2), c = compressed bytes per read, both from the runs' own counts.  Then ONE run of its
+own under `rocprofv3 --kernel-trace --stats`: k_bam_gather's bytes/s (2 x record bytes over its kernel time) beside
+k_line_write<true>'s (same records, same count) in the same trace, and the pass-2 kernels' share.  Every GPU step runs under its
+own `timeout`; the script stops at the first failure.
+
+  python tools/sort_probe.py [--reads 4000000] [--loop 8] [--pe] [--runs 3] [--out profiles/sorted_bam_probe.txt]
+"""
+import argparse
+import csv
+import glob
+import os
+import re
+import shutil
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402
+
+
+def step(cmd, limit, **kw):
+    """one GPU step under its own time limit; anything but success ends the probe"""
+    p = subprocess.run(["timeout", "-k", "10", str(limit)] + cmd, capture_output=True, text=True, **kw)
+    if p.returncode:
+        sys.stderr.write("sort_probe: step failed (exit %d): %s\n%s\n" % (p.returncode, " ".join(cmd), p.stderr[-3000:]))
+        sys.exit(1)
+    return p
+
+
+def verbose_numbers(err):
+    out = {}
+    out["wall"] = float(re.search(r"mapping wall ([\d.]+)s", err).group(1))
+    m = re.search(r"sort: bins (\d+) .*pass-2 calls (\d+), store bytes (\d+) \((\d+) records\), pass 1 ([\d.]+)s .*pass 2 ([\d.]+)s", err)
+    if m:
+        out.update(bins=int(m.group(1)), calls=int(m.group(2)), store=int(m.group(3)), records=int(m.group(4)), pass1=float(m.group(5)), pass2=float(m.group(6)))
+    m = re.search(r"busy fractions of the mapping wall: link up ([\d.]+), link down ([\d.]+)", err)
+    if m:
+        out["link_up"], out["link_down"] = float(m.group(1)), float(m.group(2))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reads", type=int, default=4_000_000)
+    ap.add_argument("--loop", type=int, default=8, help="--loop-input: the FASTQ is read this many times over, so that a run maps for seconds")
+    ap.add_argument("--genome", type=int, default=46_000_000)
+    ap.add_argument("--read-len", type=int, default=150)
+    ap.add_argument("-e", type=float, default=0.04)
+    ap.add_argument("--pe", action="store_true")
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--batch", type=int, default=1_000_000)
+    ap.add_argument("--driver-args", default="")
+    ap.add_argument("--workdir", default=os.environ.get("BMBS_BENCH_DIR", "/tmp/bmbs_bench"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sorted_bam_probe.txt"))
+    ap.add_argument("--stats-out", default=os.path.join(ROOT, "profiles", "sorted_bam_kernel_stats.csv"))
+    args = ap.parse_args()
+    import torch
+    from bitmapperbs_amd import gpusynth
+    cfg = dict(genome=args.genome, n_chrom=4 if args.genome < 1_000_000_000 else 24)
+    args.host_index = False
+    fa, names, chroms, _ = bench.ensure_index(args, cfg, 0, 0, 1, None)
+    L = args.read_len
+    stride = (L + 15) // 16 * 16
+    genome_d, lens_d = gpusynth.upload_genome(chroms)
+    wd = args.workdir
+    if not args.pe:
+        s, q = gpusynth.make_reads_se(genome_d, lens_d, args.reads, L, stride, seed=7, sub=0.005)
+        fq = os.path.join(wd, "sortp.fq")
+        bench.write_fastq_sample(fq, s.cpu().numpy(), q.cpu().numpy(), L)
+        in_args = ["--seq", fq]
+    else:
+        s1, q1, s2, q2 = gpusynth.make_reads_pe(genome_d, lens_d, args.reads, L, stride, seed=7, sub=0.005)
+        f1 = os.path.join(wd, "sortp_1.fq"); f2 = os.path.join(wd, "sortp_2.fq")
+        bench.write_fastq_sample(f1, s1.cpu().numpy(), q1.cpu().numpy(), L)
+        bench.write_fastq_sample(f2, s2.cpu().numpy(), q2.cpu().numpy(), L)
+        in_args = ["--seq1", f1, "--seq2", f2]
+    del genome_d
+    torch.cuda.empty_cache()
+    n_reads = args.reads * args.loop * (2 if args.pe else 1)
+    drv = os.path.join(ROOT, "bitmapperbs_amd", "bmbs_search")
+    base = [drv, "--search", fa] + in_args + ["-e", str(args.e), "--bam", "--unmapped_out", "--batch", str(args.batch), "--loop-input", str(args.loop), "--verbose"] + args.driver_args.split()
+    out_u = os.path.join(wd, "sortp_u.bam"); out_s = os.path.join(wd, "sortp_s.bam")
+    runs = {"bam": [], "sort": []}
+    size = {}
+    step(base + ["-o", out_u], 600)                     # warm-up: page cache, index files
+    for _ in range(max(3, args.runs)):
+        for kind, out, extra in (("bam", out_u, []), ("sort", out_s, ["--sort"])):
+            if os.path.exists(out):
+                os.unlink(out)
+            p = step(base + extra + ["-o", out], 600)
+            runs[kind].append(verbose_numbers(p.stderr))
+            size[kind] = os.path.getsize(out)
+    # the same sorted run with ONE staging slot and context in pass 2 (the default is two): what overlapping the calls is worth
+    one = [verbose_numbers(step(base + ["--sort", "-o", out_s], 600, env=dict(os.environ, BMBS_SORT_SLOTS="1")).stderr) for _ in range(3)]
+    lines = []
+    say = lines.append
+    say("sort_probe: %d %s of %d bp x %d passes over the file = %d records per run, genome %d bp, batch %d, %s"
+        % (args.reads, "pairs" if args.pe else "SE reads", L, args.loop, n_reads, args.genome, args.batch, " ".join(base[3:])))
+    med = {}
+    for kind in ("bam", "sort"):
+        w = [r["wall"] for r in runs[kind]]
+        med[kind] = statistics.median(w)
+        say("%-10s mapping wall s: %s   median %.3f  spread (max - min) %.3f   %.1f M records/s at the median   file %d bytes"
+            % ("--bam" + (" --sort" if kind == "sort" else ""), " ".join("%.3f" % x for x in w), med[kind], max(w) - min(w), n_reads / med[kind] / 1e6, size[kind]))
+    last = runs["sort"][-1]
+    say("--sort: bins %d, pass-2 calls %d, store %d bytes, pass 1 %s s, pass 2 %s s (each run)" % (
+        last["bins"], last["calls"], last["store"], " ".join("%.3f" % r["pass1"] for r in runs["sort"]), " ".join("%.3f" % r["pass2"] for r in runs["sort"])))
+    say("pass 2 with BMBS_SORT_SLOTS=1: %s s (walls %s)" % (" ".join("%.3f" % r["pass2"] for r in one), " ".join("%.3f" % r["wall"] for r in one)))
+    R = (last["store"] - 4 * last["records"]) / n_reads
+    c = size["sort"] / n_reads
+    ratio = med["sort"] / med["bam"]
+    spread = max(max(r["wall"] for r in runs[k]) - min(r["wall"] for r in runs[k]) for k in runs) / med["bam"]
+    bound = (2 * R + c) / c
+    say("raw record bytes per read R = %.1f, compressed bytes per read c = %.1f" % (R, c))
+    say("measured ratio sorted / unsorted (medians) = %.3f; the link bytes alone predict (2R + c) / c = %.3f; spread of the walls in this job = %.3f of the unsorted median"
+        % (ratio, bound, spread))
+    say("link busy fractions (per device), last runs: --bam up %.3f down %.3f; --bam --sort up %.3f down %.3f (pass 1 only: the text calls' copies)"
+        % (runs["bam"][-1].get("link_up", 0), runs["bam"][-1].get("link_down", 0), last.get("link_up", 0), last.get("link_down", 0)))
+    # ---- one run of its own under the kernel trace
+    tr = os.path.join(wd, "sortp_trace")
+    shutil.rmtree(tr, ignore_errors=True)
+    if os.path.exists(out_s):
+        os.unlink(out_s)
+    step(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tr, "--"] + base + ["--sort", "-o", out_s], 900)
+    f = glob.glob(os.path.join(tr, "**", "*kernel_stats.csv"), recursive=True)
+    if f:
+        rows = list(csv.DictReader(open(f[0])))
+        tot = sum(int(r["TotalDurationNs"]) for r in rows)
+        os.makedirs(os.path.dirname(args.stats_out), exist_ok=True)
+        with open(args.stats_out, "w") as o:
+            w = csv.writer(o); w.writerow(["Name", "Calls", "TotalDurationNs", "AverageNs", "MinNs", "MaxNs"])
+            for r in rows:
+                w.writerow([r["Name"], r["Calls"], r["TotalDurationNs"], r["AverageNs"], r["MinNs"], r["MaxNs"]])
+        rec_bytes = last["store"] - 4 * last["records"]
+
+        def total_ns(pred):
+            return sum(int(r["TotalDurationNs"]) for r in rows if pred(r["Name"]))
+        g = total_ns(lambda n: "k_bam_gather" in n)
+        lw = total_ns(lambda n: "k_line_write<true>" in n)
+        say("kernel trace (one --bam --sort run under rocprofv3, %s): all kernels %.1f ms" % (os.path.relpath(args.stats_out, ROOT), tot / 1e6))
+        # the gather runs twice over the records (pass 1 per batch, pass 2 per call); k_line_write<true> once
+        if g:
+            say("k_bam_gather: %.2f ms for 2 x %d record bytes read + written (pass 1 and pass 2) = %.0f GB/s" % (g / 1e6, rec_bytes, 2 * 2 * rec_bytes / g))
+        if lw:
+            say("k_line_write<true>: %.2f ms for %d record bytes written = %.0f GB/s counted the same way (2 x record bytes; its source is the FASTQ text)" % (lw / 1e6, rec_bytes, 2 * rec_bytes / lw))
+        for name in ("k_bam_keys", "k_bam_slen", "radix", "onesweep", "k_bgzf_block", "k_bgzf_gather"):
+            t = total_ns(lambda n: name in n.lower() if name in ("radix", "onesweep") else name in n)
+            if t:
+                say("  %-14s %.2f ms" % (name, t / 1e6))
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as o:
+        o.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
+if __name__ == "__main__":
+    main()
