@@ -252,18 +252,12 @@ void launch_sw(Lane* c, const char* d_seq, const char* d_qual, const char* d_qua
 {
     const u64 slots = sw_trace_slots(n_jobs);
     const size_t lds = sw_window_lds(gm, 1);
-    for (u64 base = 0; base < n_jobs; base += slots) {
-        if (!gm.len)
-            hipLaunchKernelGGL((gm.k == KB ? k_align_sw<KB, true, true> : k_align_sw<KB, true, false>), dim3((unsigned)(slots / 64)), dim3(64), lds, c->stream, c->ix, c->sp, c->pen_lut.as<int>(), d_seq,
-                               d_qual, d_qual2, gm, stride, c->totals.as<u64>() + 2, c->sw_job.as<u32>(), jobs, rev_from, c->trace.as<u64>(),
-                               slots, base, d_cigar_pool, max_ops, c->a_start.as<int>(), c->a_end.as<int>(), c->a_nm.as<u32>(),
-                               c->a_score.as<int>(), c->a_nops.as<int>(), prw);
-        else
-            hipLaunchKernelGGL((k_align_sw<KB, false>), dim3((unsigned)(slots / 64)), dim3(64), lds, c->stream, c->ix, c->sp, c->pen_lut.as<int>(), d_seq,
-                               d_qual, d_qual2, gm, stride, c->totals.as<u64>() + 2, c->sw_job.as<u32>(), jobs, rev_from, c->trace.as<u64>(),
-                               slots, base, d_cigar_pool, max_ops, c->a_start.as<int>(), c->a_end.as<int>(), c->a_nm.as<u32>(),
-                               c->a_score.as<int>(), c->a_nops.as<int>(), prw);
-    }
+    auto kern = gm.len ? k_align_sw<KB, false> : gm.k == KB ? k_align_sw<KB, true, true> : k_align_sw<KB, true, false>;
+    for (u64 base = 0; base < n_jobs; base += slots)
+        hipLaunchKernelGGL(kern, dim3((unsigned)(slots / 64)), dim3(64), lds, c->stream, c->ix, c->sp, c->pen_lut.as<int>(), d_seq,
+                           d_qual, d_qual2, gm, stride, c->totals.as<u64>() + 2, c->sw_job.as<u32>(), jobs, rev_from, c->trace.as<u64>(),
+                           slots, base, d_cigar_pool, max_ops, c->a_start.as<int>(), c->a_end.as<int>(), c->a_nm.as<u32>(),
+                           c->a_score.as<int>(), c->a_nops.as<int>(), prw);
 }
 
 // the packed form: two jobs per lane, so a launch of `slots` threads covers 2 * slots jobs
@@ -280,13 +274,31 @@ void launch_sw2(Lane* c, const char* d_seq, const char* d_qual, const char* d_qu
                            c->a_score.as<int>(), c->a_nops.as<int>(), prw);
 }
 
+// the band bounds the register-band DP kernels are instantiated for: f gets the smallest one that holds k, as a compile-time constant.
+// The band loop is unrolled for KB: a tighter bound wastes fewer masked cells (k = 6 in a KB = 8 kernel idles 4 of 17)
+template <class F>
+void with_band_bound(int k, F&& f)
+{
+    if (k <= 2) f(std::integral_constant<int, 2>());
+    else if (k <= 4) f(std::integral_constant<int, 4>());
+    else if (k <= 6) f(std::integral_constant<int, 6>());
+    else if (k <= 8) f(std::integral_constant<int, 8>());
+    else if (k <= 10) f(std::integral_constant<int, 10>());
+    else if (k <= 12) f(std::integral_constant<int, 12>());
+    else if (k <= 16) f(std::integral_constant<int, 16>());
+    else if (k <= 20) f(std::integral_constant<int, 20>());
+    else if (k <= 24) f(std::integral_constant<int, 24>());
+    else f(std::integral_constant<int, 31>());
+}
+
 // K11-K13 over n_jobs jobs: un-gapped recheck for all, scan-compact the ones that need the DP, run the
 // register-band DP kernel instantiated for the smallest KB >= k.  No host round-trip inside.
+// d_qual2: the qualities of the rows from rev_from on (mate 2), or nullptr; pr: the packed copy of the rows -- the empty one: ASCII rows.
 // n_jobs bounds the job arrays and grids; n_jobs_dev (or nullptr) is where the device keeps the real count; sw_bound = the DP jobs the
-// DP launches cover (a call that does not wait for its counts passes capacities here and lets k_guard_count check the last one)
-int run_align(Lane* c, const char* d_seq, const char* d_qual, const ReadGeom& gm, int stride, u64 n_jobs, const Jobs& jobs,
-              u32 rev_from, u32* d_cigar_pool, int max_ops, const char* d_qual2 = nullptr, const PackedRows* pr = nullptr,
-              const u64* n_jobs_dev = nullptr, u64 sw_bound = ~0ull)
+// DP launches cover (a call that does not wait for its counts passes capacities here and lets k_guard_count check the last one;
+// ~0: all of them)
+int run_align(Lane* c, const char* d_seq, const char* d_qual, const char* d_qual2, const ReadGeom& gm, int stride, u64 n_jobs, const Jobs& jobs,
+              u32 rev_from, u32* d_cigar_pool, int max_ops, const PackedRows& pr, const u64* n_jobs_dev, u64 sw_bound)
 {
     if (sw_bound > n_jobs) sw_bound = n_jobs;
     const int L = gm.L, k = gm.k;              // the longest read and the largest threshold size the workspace
@@ -318,10 +330,9 @@ int run_align(Lane* c, const char* d_seq, const char* d_qual, const ReadGeom& gm
         ENS(c, c->trace, slots * (u64)L * nwords * 8);
     }
     unsigned long long* cnt = c->counters.as<unsigned long long>();
-    const PackedRows prw_ = (pr && pr->base) ? *pr : PackedRows{nullptr, nullptr, 0, 0};
     prof_begin(c, "k_align_ungapped");
-    if (pr && pr->base)
-        hipLaunchKernelGGL(k_align_ungapped_p, dim3(nblk(n_jobs, 256)), dim3(256), 0, c->stream, c->ix, c->sp, c->pen_lut.as<int>(), d_seq, *pr,
+    if (pr.base)
+        hipLaunchKernelGGL(k_align_ungapped_p, dim3(nblk(n_jobs, 256)), dim3(256), 0, c->stream, c->ix, c->sp, c->pen_lut.as<int>(), d_seq, pr,
                            d_qual, d_qual2, gm, stride, n_jobs, n_jobs_dev, jobs, rev_from, c->a_start.as<int>(), c->a_end.as<int>(), c->a_nm.as<u32>(),
                            c->a_score.as<int>(), c->a_nops.as<int>(), c->need_sw.as<u32>(), cnt);
     else
@@ -343,7 +354,7 @@ int run_align(Lane* c, const char* d_seq, const char* d_qual, const ReadGeom& gm
         hipLaunchKernelGGL((k_align_sw_wave<LANES>), dim3(nblk(n_jobs, 64 / LANES)), dim3(64), words * 4 * (64 / LANES), c->stream, c->ix, \
                            c->sp, c->pen_lut.as<int>(), d_seq, d_qual, d_qual2, gm, stride, c->totals.as<u64>() + 2, c->sw_job.as<u32>(),   \
                            jobs, rev_from, d_cigar_pool, max_ops, c->a_start.as<int>(), c->a_end.as<int>(), c->a_nm.as<u32>(),          \
-                           c->a_score.as<int>(), c->a_nops.as<int>(), prw_)
+                           c->a_score.as<int>(), c->a_nops.as<int>(), pr)
         if (k <= 7) SWW_LAUNCH(16);
         else if (k <= 15) SWW_LAUNCH(32);
         else SWW_LAUNCH(64);
@@ -351,31 +362,10 @@ int run_align(Lane* c, const char* d_seq, const char* d_qual, const ReadGeom& gm
         prof_end(c);
         return BMBS_OK;
     }
-    if (packed) {
-        if (k <= 2) launch_sw2<2>(c, d_seq, d_qual, d_qual2, gm, stride, sw_bound, jobs, rev_from, d_cigar_pool, max_ops, prw_);
-        else if (k <= 4) launch_sw2<4>(c, d_seq, d_qual, d_qual2, gm, stride, sw_bound, jobs, rev_from, d_cigar_pool, max_ops, prw_);
-        else if (k <= 6) launch_sw2<6>(c, d_seq, d_qual, d_qual2, gm, stride, sw_bound, jobs, rev_from, d_cigar_pool, max_ops, prw_);
-        else if (k <= 8) launch_sw2<8>(c, d_seq, d_qual, d_qual2, gm, stride, sw_bound, jobs, rev_from, d_cigar_pool, max_ops, prw_);
-        else if (k <= 10) launch_sw2<10>(c, d_seq, d_qual, d_qual2, gm, stride, sw_bound, jobs, rev_from, d_cigar_pool, max_ops, prw_);
-        else if (k <= 12) launch_sw2<12>(c, d_seq, d_qual, d_qual2, gm, stride, sw_bound, jobs, rev_from, d_cigar_pool, max_ops, prw_);
-        else if (k <= 16) launch_sw2<16>(c, d_seq, d_qual, d_qual2, gm, stride, sw_bound, jobs, rev_from, d_cigar_pool, max_ops, prw_);
-        else if (k <= 20) launch_sw2<20>(c, d_seq, d_qual, d_qual2, gm, stride, sw_bound, jobs, rev_from, d_cigar_pool, max_ops, prw_);
-        else if (k <= 24) launch_sw2<24>(c, d_seq, d_qual, d_qual2, gm, stride, sw_bound, jobs, rev_from, d_cigar_pool, max_ops, prw_);
-        else launch_sw2<31>(c, d_seq, d_qual, d_qual2, gm, stride, sw_bound, jobs, rev_from, d_cigar_pool, max_ops, prw_);
-        prof_end(c);
-        return BMBS_OK;
-    }
-    // the band loop is unrolled for KB: a tighter bound wastes fewer masked cells (k = 6 in a KB = 8 kernel idles 4 of 17)
-    if (k <= 2) launch_sw<2>(c, d_seq, d_qual, d_qual2, gm, stride, sw_bound, jobs, rev_from, d_cigar_pool, max_ops, prw_);
-    else if (k <= 4) launch_sw<4>(c, d_seq, d_qual, d_qual2, gm, stride, sw_bound, jobs, rev_from, d_cigar_pool, max_ops, prw_);
-    else if (k <= 6) launch_sw<6>(c, d_seq, d_qual, d_qual2, gm, stride, sw_bound, jobs, rev_from, d_cigar_pool, max_ops, prw_);
-    else if (k <= 8) launch_sw<8>(c, d_seq, d_qual, d_qual2, gm, stride, sw_bound, jobs, rev_from, d_cigar_pool, max_ops, prw_);
-    else if (k <= 10) launch_sw<10>(c, d_seq, d_qual, d_qual2, gm, stride, sw_bound, jobs, rev_from, d_cigar_pool, max_ops, prw_);
-    else if (k <= 12) launch_sw<12>(c, d_seq, d_qual, d_qual2, gm, stride, sw_bound, jobs, rev_from, d_cigar_pool, max_ops, prw_);
-    else if (k <= 16) launch_sw<16>(c, d_seq, d_qual, d_qual2, gm, stride, sw_bound, jobs, rev_from, d_cigar_pool, max_ops, prw_);
-    else if (k <= 20) launch_sw<20>(c, d_seq, d_qual, d_qual2, gm, stride, sw_bound, jobs, rev_from, d_cigar_pool, max_ops, prw_);
-    else if (k <= 24) launch_sw<24>(c, d_seq, d_qual, d_qual2, gm, stride, sw_bound, jobs, rev_from, d_cigar_pool, max_ops, prw_);
-    else launch_sw<31>(c, d_seq, d_qual, d_qual2, gm, stride, sw_bound, jobs, rev_from, d_cigar_pool, max_ops, prw_);
+    with_band_bound(k, [&](auto kb) {
+        if (packed) launch_sw2<decltype(kb)::value>(c, d_seq, d_qual, d_qual2, gm, stride, sw_bound, jobs, rev_from, d_cigar_pool, max_ops, pr);
+        else launch_sw<decltype(kb)::value>(c, d_seq, d_qual, d_qual2, gm, stride, sw_bound, jobs, rev_from, d_cigar_pool, max_ops, pr);
+    });
     prof_end(c);
     return BMBS_OK;
 }
@@ -391,10 +381,17 @@ SeedCarry seed_carry(Lane* c)
     return sc;
 }
 
-// packed copy of the read rows for the seeding kernels, k_seed_decide and the un-gapped recheck (default); BMBS_ROWS=ascii keeps the
+// packed copy of the read rows for the seeding kernels, k_seed_decide and the un-gapped recheck (default); BMBS_LEGACY=1 keeps the
 // round-1 forms for A/B runs.  Paired end: the copy is a by-product of k_pe_prepare (+2.5 %); single end: a kernel of its own
 // (k_pack_rows, 0.53 ms per 10 M reads) that the consumers win back (+1.8 %: 1463 -> 1489 M reads/s on configs[1]).
 bool use_packed_rows(const Lane* c) { return !c->kn.rows_ascii; }
+// the lane's packed rows (c->prow once it has been sized for the call) as the kernels take them; the empty one under BMBS_LEGACY=1,
+// which every consumer reads as "ASCII rows"
+PackedRows packed_rows(const Lane* c, const ReadGeom& gm)
+{
+    if (!use_packed_rows(c)) return PackedRows{nullptr, nullptr, 0, 0};
+    return PackedRows{c->prow.as<u64>(), c->prow_dirty.as<u8>(), pack_words(gm.L), pack_base_words(gm.L)};
+}
 
 // trigram rank table: three backward extensions per gather pair (bmbs_dev.h: occ3).  4.5 bytes per row; built from the full SA and
 // the 2-bit text on a stream of its own, checked against three single steps on a million rows before it is used.
@@ -435,7 +432,7 @@ bool occ3_build(Occ3Shared& o, u64 margin)
 }
 // called where a lane decides which seeding kernels to launch, and when a settled call has told it how long its chains are: builds the
 // table once for all users of the index when this lane would use it, and adopts it when someone has built it
-void occ3_want(Lane* c, bool behind_a_call = false)
+void occ3_want(Lane* c, bool behind_a_call)
 {
     if (c->ix.occ3 || !c->o3 || c->kn.kgram < 1 || !use_packed_rows(c)) return;
     const bool wants = c->kn.kgram >= 2 || c->lr_chain >= 3.0;
@@ -453,7 +450,7 @@ void occ3_want(Lane* c, bool behind_a_call = false)
     if (c->o3->occ3) { c->ix.occ3 = reinterpret_cast<const uint4*>(c->o3->occ3); c->ix.c3 = reinterpret_cast<const u64*>(c->o3->c3); c->ix.nb3 = c->o3->nb3; }
 }
 
-int launch_seeding(Lane* c, const char* d_seq, const ReadGeom& gm, int stride, u64 n, int pe_mode, bool prepacked = false)
+int launch_seeding(Lane* c, const char* d_seq, const ReadGeom& gm, int stride, u64 n, int pe_mode, bool prepacked)
 {
     ENS(c, c->sd_sp0, n * 8); ENS(c, c->sd_hits0, n * 4); ENS(c, c->sd_ml0, n * 2); ENS(c, c->sd_tm, n * 2); ENS(c, c->sd_seed_id, n);
     ENS(c, c->sd_clen, n * 4); ENS(c, c->sd_first_ml, n * 2); ENS(c, c->sd_flag_c, n * 4); ENS(c, c->sd_flag_d, n * 4);
@@ -465,32 +462,29 @@ int launch_seeding(Lane* c, const char* d_seq, const ReadGeom& gm, int stride, u
     const unsigned chunks_min = nblk(n, SEED_CHUNK_MIN);      // grid for the device-sized chunks of the two work lists
     const int target_waves = c->kn.seed_waves;
     // packed copy of the rows (2 bits per base + a not-ACGT bit plane, 64 bytes for 150 bases): what the seeding engine and
-    // k_seed_decide read instead of the ASCII rows; BMBS_ROWS=ascii keeps the round-1 forms (A/B runs)
-    const bool packed_rows = use_packed_rows(c);
-    PackedRows pr = {nullptr, nullptr, 0, 0};
-    if (packed_rows) {
+    // k_seed_decide read instead of the ASCII rows; BMBS_LEGACY=1 keeps the round-1 forms (A/B runs)
+    const bool packed = use_packed_rows(c);
+    if (packed && !prepacked) {
         const int pwords = pack_words(gm.L), W = pack_base_words(gm.L);
-        if (!prepacked) {
-            { int rz_ = ensure(c, c->prow, n * (u64)pwords * 8 + 64, true); if (rz_) return rz_; } ENS(c, c->prow_dirty, n + 64);
-            HIPCHK(c, hipMemsetAsync(c->prow_dirty.p, 0, n + 64, c->stream));
-            prof_begin(c, "k_pack_rows");
-            hipLaunchKernelGGL(k_pack_rows, dim3(nblk(n * (u64)(stride / 16), 256)), dim3(256), 0, c->stream, d_seq, gm, stride, (long)n,
-                               c->prow.as<u64>(), pwords, W, c->prow_dirty.as<u32>());
-            prof_end(c);
-        }
-        pr.base = c->prow.as<u64>(); pr.dirty = c->prow_dirty.as<u8>(); pr.pwords = pwords; pr.W = W;
+        { int rz_ = ensure(c, c->prow, n * (u64)pwords * 8 + 64, true); if (rz_) return rz_; } ENS(c, c->prow_dirty, n + 64);
+        HIPCHK(c, hipMemsetAsync(c->prow_dirty.p, 0, n + 64, c->stream));
+        prof_begin(c, "k_pack_rows");
+        hipLaunchKernelGGL(k_pack_rows, dim3(nblk(n * (u64)(stride / 16), 256)), dim3(256), 0, c->stream, d_seq, gm, stride, (long)n,
+                           c->prow.as<u64>(), pwords, W, c->prow_dirty.as<u32>());
+        prof_end(c);
     }
+    const PackedRows pr = packed_rows(c, gm);
     prof_begin(c, "k_seed_first");
     // three-letter index steps (DevIndex::occ3): their kernels hold more registers (one or two waves per SIMD fewer), which costs a
     // few per cent where chains are short -- so they are used once the context has seen long ones (BMBS_KGRAM=2: always, 0: never)
-    occ3_want(c);
-    const bool kg = c->ix.occ3 && packed_rows && (c->kn.kgram >= 2 || (c->kn.kgram == 1 && c->lr_chain >= 3.0));
+    occ3_want(c, false);
+    const bool kg = c->ix.occ3 && packed && (c->kn.kgram >= 2 || (c->kn.kgram == 1 && c->lr_chain >= 3.0));
     // BMBS_SEED_STAGE=1 (default): k_seed_first's results written coalesced through LDS, k_seed_decide_p's exit-A record not stored (0: the round-6 forms)
     const int stage = c->kn.seed_stage;
-    if (packed_rows && kg && stage) hipLaunchKernelGGL((k_seed_first<true, true, true>), dim3(chunks), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, (long)n, sc, cnt);
-    else if (packed_rows && kg) hipLaunchKernelGGL((k_seed_first<true, true>), dim3(chunks), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, (long)n, sc, cnt);
-    else if (packed_rows && stage) hipLaunchKernelGGL((k_seed_first<true, false, true>), dim3(chunks), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, (long)n, sc, cnt);
-    else if (packed_rows) hipLaunchKernelGGL(k_seed_first<true>, dim3(chunks), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, (long)n, sc, cnt);
+    if (packed && kg && stage) hipLaunchKernelGGL((k_seed_first<true, true, true>), dim3(chunks), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, (long)n, sc, cnt);
+    else if (packed && kg) hipLaunchKernelGGL((k_seed_first<true, true>), dim3(chunks), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, (long)n, sc, cnt);
+    else if (packed && stage) hipLaunchKernelGGL((k_seed_first<true, false, true>), dim3(chunks), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, (long)n, sc, cnt);
+    else if (packed) hipLaunchKernelGGL(k_seed_first<true>, dim3(chunks), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, (long)n, sc, cnt);
     else hipLaunchKernelGGL(k_seed_first<false>, dim3(chunks), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, (long)n, sc, cnt);
     prof_end(c);
     prof_begin(c, "k_seed_decide");
@@ -498,7 +492,7 @@ int launch_seeding(Lane* c, const char* d_seq, const ReadGeom& gm, int stride, u
     // 8-lanes-per-read form without staging was measured at 2.07 ms against 1.36 ms; the un-staged and the one-character forms of
     // round 1 were removed in round 4.)
     const bool lds_ok = (size_t)64 * (stride + 8) <= 48 * 1024;
-    if (packed_rows)
+    if (packed)
         hipLaunchKernelGGL(k_seed_decide_p, dim3(nblk(n, 64)), dim3(64), (size_t)64 * (pr.pwords + 1) * 8, c->stream, c->ix, d_seq, pr, gm, stride,
                            (long)n, c->prm.seed_len, pe_mode, (stage && !(pe_mode && c->prm.sensitive)) ? 1 : 0, st, sc, cnt);   // k_pes_reseed reads it
     else if (lds_ok)
@@ -513,8 +507,8 @@ int launch_seeding(Lane* c, const char* d_seq, const ReadGeom& gm, int stride, u
     if (rc) return rc;
     prof_end(c);
     prof_begin(c, "k_seed_second");
-    if (packed_rows && kg) hipLaunchKernelGGL((k_seed_second<true, true>), dim3(chunks_min), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, c->totals.as<u64>() + 3, target_waves, pe_mode, st, sc, cnt);
-    else if (packed_rows) hipLaunchKernelGGL(k_seed_second<true>, dim3(chunks_min), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, c->totals.as<u64>() + 3, target_waves, pe_mode, st, sc, cnt);
+    if (packed && kg) hipLaunchKernelGGL((k_seed_second<true, true>), dim3(chunks_min), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, c->totals.as<u64>() + 3, target_waves, pe_mode, st, sc, cnt);
+    else if (packed) hipLaunchKernelGGL(k_seed_second<true>, dim3(chunks_min), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, c->totals.as<u64>() + 3, target_waves, pe_mode, st, sc, cnt);
     else hipLaunchKernelGGL(k_seed_second<false>, dim3(chunks_min), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, c->totals.as<u64>() + 3, target_waves, pe_mode, st, sc, cnt);
     prof_end(c);
     prof_begin(c, "list_extra");
@@ -532,13 +526,13 @@ int launch_seeding(Lane* c, const char* d_seq, const ReadGeom& gm, int stride, u
         const int rows_in_lds = lds <= 48 * 1024 && !wide_ix;
         // packed rows: the lane's row in its LDS slot (4.6 KB per wave at 150 bases: no occupancy lost); rows too long for 16 KB: from global memory
         const size_t plds = (size_t)64 * (pr.pwords + 1) * 8;
-        if (packed_rows && plds <= 16 * 1024 && kg)
+        if (packed && plds <= 16 * 1024 && kg)
             hipLaunchKernelGGL((k_seed_extra<false, true, true, true>), dim3(chunks_min), dim3(64), plds, c->stream, c->ix, d_seq, pr, gm, stride, c->totals.as<u64>() + 4,
                                target_waves, c->prm.seed_len, pe_mode, st, sc, cnt);
-        else if (packed_rows && plds <= 16 * 1024)
+        else if (packed && plds <= 16 * 1024)
             hipLaunchKernelGGL((k_seed_extra<false, true, true>), dim3(chunks_min), dim3(64), plds, c->stream, c->ix, d_seq, pr, gm, stride, c->totals.as<u64>() + 4,
                                target_waves, c->prm.seed_len, pe_mode, st, sc, cnt);
-        else if (packed_rows)
+        else if (packed)
             hipLaunchKernelGGL((k_seed_extra<false, true>), dim3(chunks_min), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, c->totals.as<u64>() + 4,
                                target_waves, c->prm.seed_len, pe_mode, st, sc, cnt);
         else if (rows_in_lds)
@@ -571,15 +565,13 @@ int cand_total(Lane* c, const ReadState& st, u64 n, bool exact, u64* tot_out)
 }
 
 // stages K1-K6 + votes; leaves the vote segments in c->votes / c->slot_read
-int run_seed_stages(Lane* c, const char* d_seq, const ReadGeom& gm, int stride, u64 n, u64* total_cand, int pe_mode = 0, bool exact = true, bool prepacked = false)
+int run_seed_stages(Lane* c, const char* d_seq, const ReadGeom& gm, int stride, u64 n, u64* total_cand, int pe_mode, bool exact, bool prepacked)
 {
     ReadState st = read_state(c);
-    {
-        int rcs = launch_seeding(c, d_seq, gm, stride, n, pe_mode, prepacked);
-        if (rcs) return rcs;
-    }
+    int rc = launch_seeding(c, d_seq, gm, stride, n, pe_mode, prepacked);
+    if (rc) return rc;
     prof_begin(c, "scan_cand");
-    int rc = scan_u32(c, st.n_cand, n, st.cand_off, 0);
+    rc = scan_u32(c, st.n_cand, n, st.cand_off, 0);
     if (rc) return rc;
     prof_end(c);
     u64 tot = 0;
@@ -590,58 +582,54 @@ int run_seed_stages(Lane* c, const char* d_seq, const ReadGeom& gm, int stride, 
     ENS(c, c->cand, t1 * 8); ENS(c, c->votes, t1 * sizeof(bmbs_vote)); ENS(c, c->slot_read, t1 * 4);
     ENS(c, c->ferr, t1 * 4); ENS(c, c->fend, t1 * 4);
     // locate + sort + votes in one kernel per list-size class (the two-kernel form of round 1, k_locate + k_vote, was removed in round 4)
-    {
-        ENS(c, c->long_flag, n * 4); ENS(c, c->long_off, (n + 1) * 8); ENS(c, c->long_list, n * 4); ENS(c, c->vote_list, n * 4);
-        prof_begin(c, "k_vote_fused");
-        // the reads that have candidates, compacted (the scan's list mode on n_cand != 0), so that the vote kernel's waves are dense
-        HIPCHK(c, hipMemsetAsync(c->long_flag.p, 0, n * 4, c->stream));
-        HIPCHK(c, hipMemsetAsync(st.n_votes, 0, n * 4, c->stream));
-        {
-            int rv = scan_u32(c, st.n_cand, n, c->long_off.as<u64>(), 10, c->vote_list.as<u32>(), 1);
-            if (rv) return rv;
-        }
-        // long reads (up to 25 seeds): lists of 17..32 candidates are the rule, not the repeat case -- they get a kernel of their
-        // own (k_vote_mid); its flag and list live in the seeding work-list buffers, free by now
-        // ... and on a repeat-rich genome also for short reads (seeds with many hits): taken when the last call left more than 0.5 % of
-        // its reads to the long-list kernels (a wave per read)
-        const bool use_mid = gm.L / 10 - 1 > VOTE_REG || c->lr_long > 0.005;
-        u32* mid_flag = use_mid ? c->sd_flag_c.as<u32>() : nullptr;
-        if (use_mid) HIPCHK(c, hipMemsetAsync(mid_flag, 0, n * 4, c->stream));
-        hipLaunchKernelGGL(k_vote_fused, dim3(nblk(n, 64)), dim3(64), 0, c->stream, c->ix, (long)n, gm, st, c->cand.as<u64>(),
-                           c->votes.as<bmbs_vote>(), c->slot_read.as<u32>(), c->long_flag.as<u32>(), c->totals.as<u64>() + 10,
-                           c->vote_list.as<u32>(), mid_flag);
-        prof_end(c);
-        if (use_mid) {
-            prof_begin(c, "k_vote_mid");
-            int rm = scan_u32(c, mid_flag, n, c->long_off.as<u64>(), 11, c->sd_list_c.as<u32>());
-            if (rm) return rm;
-            hipLaunchKernelGGL(k_vote_mid, dim3(nblk(n, 64)), dim3(64), 0, c->stream, c->ix, gm, st, c->totals.as<u64>() + 11, c->sd_list_c.as<u32>(),
-                               c->cand.as<u64>(), c->votes.as<bmbs_vote>(), c->slot_read.as<u32>(), c->counters.as<unsigned long long>());
-            prof_end(c);
-        }
-        // reads with more than 16 candidates (repeats): one block per read
-        prof_begin(c, "k_vote_long");
-        int rl = scan_u32(c, c->long_flag.as<u32>(), n, c->long_off.as<u64>(), 9, c->long_list.as<u32>());
-        if (rl) return rl;
-        // the wave form (lists of up to 256 candidates) walks the list and hands the longer ones to a list of their own (slot 13)
-        ENS(c, c->big_list, n * 4 + 64);
-        unsigned long long* big_count = c->totals.as<unsigned long long>() + 13;
-        HIPCHK(c, hipMemsetAsync(big_count, 0, 8, c->stream));
-        hipLaunchKernelGGL((k_vote_long<VM_CAP, VM_BLOCK, VOTE_REG>), dim3(32768), dim3(VM_BLOCK), 0, c->stream, c->ix, gm, st, c->totals.as<u64>() + 9,
-                           c->long_list.as<u32>(), c->cand.as<u64>(), c->votes.as<bmbs_vote>(), c->slot_read.as<u32>(), c->big_list.as<u32>(), big_count, c->counters.as<unsigned long long>());
-        prof_end(c);
-        prof_begin(c, "k_vote_big");
-        // the handed-over lists in two size classes (as k_vote_pe_long): the <= 1024-key form needs 14 KB of LDS instead of 57 KB, so five
-        // times as many reads are in flight -- the vote order (std::sort's permutation, one partition pass after the other) is a
-        // chain of barriers, not work
-        hipLaunchKernelGGL((k_vote_long<1024, 128, VM_CAP>), dim3(8192), dim3(128), 0, c->stream, c->ix, gm, st, c->totals.as<u64>() + 13,
-                           c->big_list.as<u32>(), c->cand.as<u64>(), c->votes.as<bmbs_vote>(), c->slot_read.as<u32>(), (u32*)nullptr, (unsigned long long*)nullptr, c->counters.as<unsigned long long>());
-        hipLaunchKernelGGL((k_vote_long<2048, 256, 1024>), dim3(4096), dim3(256), 0, c->stream, c->ix, gm, st, c->totals.as<u64>() + 13,
-                           c->big_list.as<u32>(), c->cand.as<u64>(), c->votes.as<bmbs_vote>(), c->slot_read.as<u32>(), (u32*)nullptr, (unsigned long long*)nullptr, c->counters.as<unsigned long long>());
-        hipLaunchKernelGGL((k_vote_long<VL_CAP, VL_BLOCK, 2048>), dim3(2048), dim3(VL_BLOCK), 0, c->stream, c->ix, gm, st, c->totals.as<u64>() + 13,
-                           c->big_list.as<u32>(), c->cand.as<u64>(), c->votes.as<bmbs_vote>(), c->slot_read.as<u32>(), (u32*)nullptr, (unsigned long long*)nullptr, c->counters.as<unsigned long long>());
+    ENS(c, c->long_flag, n * 4); ENS(c, c->long_off, (n + 1) * 8); ENS(c, c->long_list, n * 4); ENS(c, c->vote_list, n * 4);
+    prof_begin(c, "k_vote_fused");
+    // the reads that have candidates, compacted (the scan's list mode on n_cand != 0), so that the vote kernel's waves are dense
+    HIPCHK(c, hipMemsetAsync(c->long_flag.p, 0, n * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(st.n_votes, 0, n * 4, c->stream));
+    rc = scan_u32(c, st.n_cand, n, c->long_off.as<u64>(), 10, c->vote_list.as<u32>(), 1);
+    if (rc) return rc;
+    // long reads (up to 25 seeds): lists of 17..32 candidates are the rule, not the repeat case -- they get a kernel of their
+    // own (k_vote_mid); its flag and list live in the seeding work-list buffers, free by now
+    // ... and on a repeat-rich genome also for short reads (seeds with many hits): taken when the last call left more than 0.5 % of
+    // its reads to the long-list kernels (a wave per read)
+    const bool use_mid = gm.L / 10 - 1 > VOTE_REG || c->lr_long > 0.005;
+    u32* mid_flag = use_mid ? c->sd_flag_c.as<u32>() : nullptr;
+    if (use_mid) HIPCHK(c, hipMemsetAsync(mid_flag, 0, n * 4, c->stream));
+    hipLaunchKernelGGL(k_vote_fused, dim3(nblk(n, 64)), dim3(64), 0, c->stream, c->ix, (long)n, gm, st, c->cand.as<u64>(),
+                       c->votes.as<bmbs_vote>(), c->slot_read.as<u32>(), c->long_flag.as<u32>(), c->totals.as<u64>() + 10,
+                       c->vote_list.as<u32>(), mid_flag);
+    prof_end(c);
+    if (use_mid) {
+        prof_begin(c, "k_vote_mid");
+        rc = scan_u32(c, mid_flag, n, c->long_off.as<u64>(), 11, c->sd_list_c.as<u32>());
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_vote_mid, dim3(nblk(n, 64)), dim3(64), 0, c->stream, c->ix, gm, st, c->totals.as<u64>() + 11, c->sd_list_c.as<u32>(),
+                           c->cand.as<u64>(), c->votes.as<bmbs_vote>(), c->slot_read.as<u32>(), c->counters.as<unsigned long long>());
         prof_end(c);
     }
+    // reads with more than 16 candidates (repeats): one block per read
+    prof_begin(c, "k_vote_long");
+    rc = scan_u32(c, c->long_flag.as<u32>(), n, c->long_off.as<u64>(), 9, c->long_list.as<u32>());
+    if (rc) return rc;
+    // the wave form (lists of up to 256 candidates) walks the list and hands the longer ones to a list of their own (slot 13)
+    ENS(c, c->big_list, n * 4 + 64);
+    unsigned long long* big_count = c->totals.as<unsigned long long>() + 13;
+    HIPCHK(c, hipMemsetAsync(big_count, 0, 8, c->stream));
+    hipLaunchKernelGGL((k_vote_long<VM_CAP, VM_BLOCK, VOTE_REG>), dim3(32768), dim3(VM_BLOCK), 0, c->stream, c->ix, gm, st, c->totals.as<u64>() + 9,
+                       c->long_list.as<u32>(), c->cand.as<u64>(), c->votes.as<bmbs_vote>(), c->slot_read.as<u32>(), c->big_list.as<u32>(), big_count, c->counters.as<unsigned long long>());
+    prof_end(c);
+    prof_begin(c, "k_vote_big");
+    // the handed-over lists in two size classes (as k_vote_pe_long): the <= 1024-key form needs 14 KB of LDS instead of 57 KB, so five
+    // times as many reads are in flight -- the vote order (std::sort's permutation, one partition pass after the other) is a
+    // chain of barriers, not work
+    hipLaunchKernelGGL((k_vote_long<1024, 128, VM_CAP>), dim3(8192), dim3(128), 0, c->stream, c->ix, gm, st, c->totals.as<u64>() + 13,
+                       c->big_list.as<u32>(), c->cand.as<u64>(), c->votes.as<bmbs_vote>(), c->slot_read.as<u32>(), (u32*)nullptr, (unsigned long long*)nullptr, c->counters.as<unsigned long long>());
+    hipLaunchKernelGGL((k_vote_long<2048, 256, 1024>), dim3(4096), dim3(256), 0, c->stream, c->ix, gm, st, c->totals.as<u64>() + 13,
+                       c->big_list.as<u32>(), c->cand.as<u64>(), c->votes.as<bmbs_vote>(), c->slot_read.as<u32>(), (u32*)nullptr, (unsigned long long*)nullptr, c->counters.as<unsigned long long>());
+    hipLaunchKernelGGL((k_vote_long<VL_CAP, VL_BLOCK, 2048>), dim3(2048), dim3(VL_BLOCK), 0, c->stream, c->ix, gm, st, c->totals.as<u64>() + 13,
+                       c->big_list.as<u32>(), c->cand.as<u64>(), c->votes.as<bmbs_vote>(), c->slot_read.as<u32>(), (u32*)nullptr, (unsigned long long*)nullptr, c->counters.as<unsigned long long>());
+    prof_end(c);
     return BMBS_OK;
 }
 
@@ -957,133 +945,13 @@ int call_end(Lane* c, int slot)
 
 // the caller's packed rows (bmbs_map_*_packed) -> the lane's: prow / prow_dirty, and `ascii` (rows `stride` apart) gets the text of the
 // pieces that hold an 'N'.  rc: the rows are reverse-complemented on the way (mate 2).  row0: where these rows sit in the batch
-int rows_from_packed(Lane* c, const u64* src, int hw, const ReadGeom& gm, u64 row0, u64 n, bool rc, char* ascii, int stride)
+// (call_open has checked that hw words hold a row of this length)
+void rows_from_packed(Lane* c, const u64* src, int hw, const ReadGeom& gm, u64 row0, u64 n, bool rc, char* ascii, int stride)
 {
     const int pwords = pack_words(gm.L), W = pack_base_words(gm.L);
-    if (hw < W + (gm.L + 63) / 64) { c->err = "packed rows: pwords is smaller than a row of this length takes"; return BMBS_EINVAL; }
     const unsigned g = nblk(n * (u64)W, 256);
-    if (rc) hipLaunchKernelGGL(k_rows_from_packed<true>, dim3(g), dim3(256), 0, c->stream, src, hw, gm, (long)row0, (long)n, c->prow.as<u64>(), pwords, W, c->prow_dirty.as<u32>(), ascii, stride);
-    else hipLaunchKernelGGL(k_rows_from_packed<false>, dim3(g), dim3(256), 0, c->stream, src, hw, gm, (long)row0, (long)n, c->prow.as<u64>(), pwords, W, c->prow_dirty.as<u32>(), ascii, stride);
-    return BMBS_OK;
-}
-
-// packed_hw > 0: d_seq_ holds the caller's packed rows (packed_hw words apart) instead of ASCII rows
-int map_se_dev(Lane* c, uint64_t d_seq_, uint64_t d_qual_, const u16* d_len, int32_t L, int32_t stride,
-               int64_t n_reads, uint64_t d_results, uint64_t d_cigar_pool, int64_t cigar_cap, bool exact = true, u32 cigar_base = 0, int slot = 0, int packed_hw = 0)
-{
-    if (!c) return BMBS_EINVAL;
-    if (!c->attached) { c->err = "no index attached"; return BMBS_ESTATE; }
-    if (L <= 0 || L > BMBS_MAX_READ || stride < L || n_reads < 0) { c->err = "bad read geometry"; return BMBS_EINVAL; }
-    if ((stride & 15) || (d_seq_ & 15) || (d_qual_ & 15)) { c->err = "device read buffers must be 16-byte aligned with a stride that is a multiple of 16"; return BMBS_EINVAL; }
-    HIPCHK(c, hipSetDevice(c->dev));
-    const char* d_seq = reinterpret_cast<const char*>(d_seq_);
-    const char* d_qual = reinterpret_cast<const char*>(d_qual_);
-    const u64 n = (u64)n_reads;
-    if (n == 0) return BMBS_OK;
-    int rc = prepare_luts(c);
-    if (rc) return rc;
-    const ReadGeom gm = geom(c, L, d_len);
-    const int k = gm.k;
-    const int max_ops = cigar_ops_bound(c->prm, L, k);
-    c->last_max_ops = max_ops;
-    if (max_ops > BMBS_MAX_RECORD_OPS) { c->err = "these gap / mismatch penalties allow alignments with more CIGAR operations than a record holds (254)"; return BMBS_EINVAL; }
-    rc = per_read_workspace(c, n);
-    if (rc) return rc;
-    if (packed_hw && !use_packed_rows(c)) { c->err = "packed reads need the packed-row kernels (BMBS_LEGACY is set)"; return BMBS_EINVAL; }
-    if (packed_hw && packed_hw < pack_base_words(gm.L) + (gm.L + 63) / 64) { c->err = "packed rows: pwords is smaller than a row of this length takes"; return BMBS_EINVAL; }
-    rc = call_begin(c, slot);
-    if (rc) return rc;
-    if (packed_hw) {
-        // the ASCII rows exist only where a piece holds an 'N' (written by k_rows_from_packed into the lane's own buffer)
-        ENS(c, c->pk_ascii, n * (u64)stride + 64);
-        { int rz_ = ensure(c, c->prow, n * (u64)pack_words(gm.L) * 8 + 64, true); if (rz_) return rz_; } ENS(c, c->prow_dirty, n + 64);
-        HIPCHK(c, hipMemsetAsync(c->prow_dirty.p, 0, n + 64, c->stream));
-        prof_begin(c, "k_rows_from_packed");
-        rc = rows_from_packed(c, reinterpret_cast<const u64*>(d_seq_), packed_hw, gm, 0, n, false, c->pk_ascii.as<char>(), stride);
-        if (rc) return rc;
-        prof_end(c);
-        d_seq = c->pk_ascii.as<char>();
-    }
-    ReadState st = read_state(c);
-    unsigned long long* cnt = c->counters.as<unsigned long long>();
-    u64 tot = 0;                     // candidate slots: the count itself (exact) or the capacity the buffers and grids are sized for
-    rc = run_seed_stages(c, d_seq, gm, stride, n, &tot, 0, exact, packed_hw > 0);
-    if (rc) return rc;
-    c->last_total_cand = tot;
-    ENS(c, c->vote_off, (n + 1) * 8);
-    {
-        const u64 t1 = exact ? std::max<u64>(tot, cap_from((double)tot / (double)n, n, n)) : (tot ? tot : 1);
-        ENS(c, c->votes_dense, t1 * sizeof(bmbs_vote)); ENS(c, c->dense_read, t1 * 4);
-    }
-    prof_begin(c, "vote_compact");
-    rc = scan_u32(c, st.n_votes, n, c->vote_off.as<u64>(), 5);
-    if (rc) return rc;
-    if (tot)
-        hipLaunchKernelGGL(k_vote_compact, dim3(nblk(tot, 256)), dim3(256), 0, c->stream, tot, exact ? (const u64*)nullptr : c->totals.as<u64>(), st,
-                           c->vote_off.as<u64>(), c->slot_read.as<u32>(), c->votes.as<bmbs_vote>(), c->votes_dense.as<bmbs_vote>(), c->dense_read.as<u32>());
-    prof_end(c);
-    if (tot) {
-        prof_begin(c, "k_filter");
-        PackedRows prf = {nullptr, nullptr, 0, 0};
-        if (use_packed_rows(c)) { prf.base = c->prow.as<u64>(); prf.dirty = c->prow_dirty.as<u8>(); prf.pwords = pack_words(gm.L); prf.W = pack_base_words(gm.L); }
-        hipLaunchKernelGGL(k_filter, dim3(nblk(tot, 256)), dim3(256), 0, c->stream, c->ix, d_seq, prf, gm, stride, c->totals.as<u64>() + 5,
-                           c->dense_read.as<u32>(), c->votes_dense.as<bmbs_vote>(), c->ferr.as<u32>(), c->fend.as<int>(), cnt);
-        prof_end(c);
-    }
-    prof_begin(c, "k_reduce");
-    {
-        // over the compacted list of reads with candidates the vote stage built
-        const bool listed = true;
-        HIPCHK(c, hipMemsetAsync(st.job_flag, 0, n * 4, c->stream));
-        HIPCHK(c, hipMemsetAsync(st.red_status, 0, n, c->stream));
-        hipLaunchKernelGGL(k_reduce, dim3(nblk(n, 256)), dim3(256), 0, c->stream, (long)n, c->prm.ambiguous_out, st, c->vote_off.as<u64>(),
-                           c->votes_dense.as<bmbs_vote>(), c->ferr.as<u32>(), c->fend.as<int>(), c->totals.as<u64>() + 10,
-                           listed ? c->vote_list.as<u32>() : (const u32*)nullptr);
-    }
-    prof_end(c);
-    prof_begin(c, "scan_jobs");
-    rc = scan_u32(c, st.job_flag, n, st.job_off, 1);
-    if (rc) return rc;
-    prof_end(c);
-    // jobs: the count (exact), or one slot per read with the device-side count bounding every kernel and a guard on the caller's pool
-    u64 n_jobs = n, sw_bound = ~0ull;
-    const u64* n_jobs_dev = nullptr;
-    if (exact) {
-        HIPCHK(c, hipMemcpyAsync(&n_jobs, c->totals.as<u64>() + 1, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if ((u64)cigar_cap < n_jobs * (u64)max_ops) { c->err = "cigar pool too small (it takes bmbs_max_cigar_ops() slots per read)"; return BMBS_ENOMEM; }
-    } else {
-        n_jobs_dev = c->totals.as<u64>() + 1;
-        sw_bound = cap_from(c->lr_sw, n, c->kn.cap_scale < 1.0 ? 64 : 16384, c->kn.cap_scale);
-        if ((u64)cigar_cap < n * (u64)max_ops) {
-            hipLaunchKernelGGL(k_guard_jobs, dim3(nblk(n, 256)), dim3(256), 0, c->stream, n_jobs_dev, (u64)max_ops, (u64)cigar_cap, c->flags.as<u32>(), (long)n, st.job_flag);
-            hipLaunchKernelGGL(k_guard_done, dim3(1), dim3(1), 0, c->stream, c->totals.as<u64>() + 1, c->flags.as<u32>(), BMBS_FLAG_CIGAR);
-        }
-    }
-    c->last_n_jobs = n_jobs;
-    {
-        const u64 nj = n_jobs ? n_jobs : 1;
-        ENS(c, c->job_read, nj * 4); ENS(c, c->job_site, nj * 8); ENS(c, c->job_end, nj * 4); ENS(c, c->job_err, nj * 4);
-        if (n_jobs) {
-            prof_begin(c, "k_job_list");
-            hipLaunchKernelGGL(k_job_list, dim3(nblk(n, 256)), dim3(256), 0, c->stream, (long)n, st, c->job_read.as<u32>(),
-                               c->job_site.as<u64>(), c->job_end.as<int>(), c->job_err.as<u32>());
-            prof_end(c);
-        }
-        Jobs jobs = {c->job_read.as<u32>(), c->job_site.as<u64>(), c->job_end.as<int>(), c->job_err.as<u32>()};
-        PackedRows prw = {nullptr, nullptr, 0, 0};
-        if (use_packed_rows(c)) { prw.base = c->prow.as<u64>(); prw.dirty = c->prow_dirty.as<u8>(); prw.pwords = pack_words(gm.L); prw.W = pack_base_words(gm.L); }
-        rc = run_align(c, d_seq, d_qual, gm, stride, n_jobs, jobs, 0xffffffffu, reinterpret_cast<u32*>(d_cigar_pool), max_ops, nullptr, &prw, n_jobs_dev, sw_bound);
-        if (rc) return rc;
-    }
-    prof_begin(c, "k_finalize");
-    hipLaunchKernelGGL(k_finalize, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->ix, c->sp, c->pen_lut.as<int>(),
-                       c->mapq_lut.as<u8>(), c->mapq_off.as<u32>(), c->mapq_unit, d_seq, d_qual, gm, stride, (long)n, st, c->a_start.as<int>(),
-                       c->a_end.as<int>(), c->a_nm.as<u32>(), c->a_score.as<int>(), c->a_nops.as<int>(), max_ops, cigar_base,
-                       c->prm.ambiguous_out, c->sd_sp0.as<u64>(), c->sd_hits0.as<u32>(),
-                       reinterpret_cast<bmbs_result_dev*>(d_results), c->call_stats.as<unsigned long long>());
-    prof_end(c);
-    return call_end(c, slot);
+    hipLaunchKernelGGL((rc ? k_rows_from_packed<true> : k_rows_from_packed<false>), dim3(g), dim3(256), 0, c->stream, src, hw, gm, (long)row0, (long)n, c->prow.as<u64>(),
+                       pwords, W, c->prow_dirty.as<u32>(), ascii, stride);
 }
 
 // host lengths -> device (u16 per read)
@@ -1096,57 +964,183 @@ int upload_lens(Lane* c, const uint16_t* len, u64 n, u64 at, u64 total, int L, h
     return BMBS_OK;
 }
 
+// ---- the launch sequence of a mapping call ----------------------------------------------------------------------------------------
+// A call is its Pending (bmbs_host.h): the launch sequence reads it and never changes it -- a call whose counts did not fit its
+// capacities is issued again from the same Pending with exact = true (lane_settle).
+//   a[0], a[1]: rows and qualities (mate 1); a[2], a[3]: mate 2 as in the FASTQ file.  packed_hw > 0: a[0] / a[2] hold the caller's
+//   packed rows (packed_hw words apart) instead of ASCII rows.  d_len: NULL, or u16 per row (pairs: the n first mates, then the n second)
 
-// ------------------------------------------------------------------------------------------------
-// paired-end fast mode (Map_Pair_Seq_end_to_end_fast, Schema.cpp:18570)
-// d_len: NULL, or u16[2n] = the lengths of the n first mates followed by those of the n second mates
-// prepared: c->pe_seq already holds the 2n rows (mate 1, then reverse-complemented mate 2) -- the FASTQ-text entry point writes
-// them there straight from the text and k_pe_prepare is not run
-int map_pe_dev(Lane* c, uint64_t d_seq1, uint64_t d_qual1, uint64_t d_seq2, uint64_t d_qual2, const u16* d_len,
-               int32_t L, int32_t stride, int64_t n_pairs, uint64_t d_results, uint64_t d_cigar_pool, int64_t cigar_cap, bool prepared = false,
-               bool exact = true, u32 cigar_base = 0, int slot = 0, int packed_hw = 0)
+// What every call begins with: the argument checks, the tables, the geometry and the CIGAR bound, the per-row workspace of its
+// `reads` rows (n, pairs: 2n) and call_begin.  A call of no reads gets BMBS_OK with nothing set up: the caller returns on P.n == 0.
+int call_open(Lane* c, const Pending& P, u64 reads, ReadGeom* gm, int* max_ops)
 {
     if (!c) return BMBS_EINVAL;
     if (!c->attached) { c->err = "no index attached"; return BMBS_ESTATE; }
-    if (L <= 0 || L > BMBS_MAX_READ || stride < L || n_pairs < 0) { c->err = "bad read geometry"; return BMBS_EINVAL; }
-    if ((stride & 15) || ((d_seq1 | d_qual1 | d_seq2 | d_qual2) & 15)) { c->err = "device read buffers must be 16-byte aligned with a stride that is a multiple of 16"; return BMBS_EINVAL; }
+    if (P.L <= 0 || P.L > BMBS_MAX_READ || P.stride < P.L || P.n < 0) { c->err = "bad read geometry"; return BMBS_EINVAL; }
+    const uint64_t ptrs = P.a[0] | P.a[1] | (P.pe ? P.a[2] | P.a[3] : 0);
+    if ((P.stride & 15) || (ptrs & 15)) { c->err = "device read buffers must be 16-byte aligned with a stride that is a multiple of 16"; return BMBS_EINVAL; }
     HIPCHK(c, hipSetDevice(c->dev));
-    const u64 n = (u64)n_pairs, n2 = 2 * n;
-    if (prepared && c->pe_seq.cap < n2 * (u64)stride + 64) { c->err = "internal: prepared rows missing"; return BMBS_ESTATE; }
-    if (n == 0) return BMBS_OK;
+    // prepared: c->pe_seq already holds the 2n rows (mate 1, then reverse-complemented mate 2) -- the FASTQ-text entry point writes
+    // them there straight from the text
+    if (P.pe && P.prepared && c->pe_seq.cap < reads * (u64)P.stride + 64) { c->err = "internal: prepared rows missing"; return BMBS_ESTATE; }
+    if (P.n == 0) return BMBS_OK;
     int rc = prepare_luts(c);
     if (rc) return rc;
-    const ReadGeom gm = geom(c, L, d_len);
-    const PeIns pi = {c->prm.min_ins, c->prm.max_ins};
-    const int k = gm.k;
-    const int max_ops = cigar_ops_bound(c->prm, L, k);
-    c->last_max_ops = max_ops;
-    if (max_ops > BMBS_MAX_RECORD_OPS) { c->err = "these gap / mismatch penalties allow alignments with more CIGAR operations than a record holds (254)"; return BMBS_EINVAL; }
-    rc = per_read_workspace(c, n2);
+    *gm = geom(c, P.L, P.d_len);
+    *max_ops = cigar_ops_bound(c->prm, P.L, gm->k);
+    c->last_max_ops = *max_ops;
+    if (*max_ops > BMBS_MAX_RECORD_OPS) { c->err = "these gap / mismatch penalties allow alignments with more CIGAR operations than a record holds (254)"; return BMBS_EINVAL; }
+    rc = per_read_workspace(c, reads);
     if (rc) return rc;
-    ENS(c, c->pe_seq, n2 * (u64)stride + 64);
-    ENS(c, c->pe_occ, n2 * 4); ENS(c, c->pe_len, n2 * 4); ENS(c, c->pe_cur, n2); ENS(c, c->pe_vround, n2);
-    ENS(c, c->pe_dead, n); ENS(c, c->pe_both, n); ENS(c, c->pe_npair, n * 4); ENS(c, c->pe_sbd, n * 4);
-    if (packed_hw && !use_packed_rows(c)) { c->err = "packed reads need the packed-row kernels (BMBS_LEGACY is set)"; return BMBS_EINVAL; }
-    if (packed_hw && packed_hw < pack_base_words(gm.L) + (gm.L + 63) / 64) { c->err = "packed rows: pwords is smaller than a row of this length takes"; return BMBS_EINVAL; }
-    rc = call_begin(c, slot);
+    if (P.pe) {
+        const u64 n = (u64)P.n;
+        ENS(c, c->pe_seq, reads * (u64)P.stride + 64);
+        ENS(c, c->pe_occ, reads * 4); ENS(c, c->pe_len, reads * 4); ENS(c, c->pe_cur, reads); ENS(c, c->pe_vround, reads);
+        ENS(c, c->pe_dead, n); ENS(c, c->pe_both, n); ENS(c, c->pe_npair, n * 4); ENS(c, c->pe_sbd, n * 4);
+    }
+    if (P.packed_hw && !use_packed_rows(c)) { c->err = "packed reads need the packed-row kernels (BMBS_LEGACY is set)"; return BMBS_EINVAL; }
+    if (P.packed_hw && P.packed_hw < pack_base_words(gm->L) + (gm->L + 63) / 64) { c->err = "packed rows: pwords is smaller than a row of this length takes"; return BMBS_EINVAL; }
+    return call_begin(c, P.slot);
+}
+
+// What every call ends with, over its `reads` rows: the alignment jobs the reduce / pairing stage flagged -- scan, list, K11-K13.
+// jobs: the count (exact), or one slot per read with the device-side count bounding every kernel and a guard on the caller's pool.
+// Rows from rev_from on (mate 2; 0xffffffff: none) carry FASTQ-order qualities in qual2 for a reverse-complemented read
+// (need_reverse_quality = 1)
+int align_jobs(Lane* c, const Pending& P, const ReadGeom& gm, const ReadState& st, const char* seq, const char* qual1, const char* qual2, u64 reads,
+               u32 rev_from, int max_ops)
+{
+    prof_begin(c, "scan_jobs");
+    int rc = scan_u32(c, st.job_flag, reads, st.job_off, 1);
     if (rc) return rc;
-    char* seq_all = c->pe_seq.as<char>();
-    // the qualities are read where the caller put them (qual_row): mate 1 rows in d_qual1, mate 2 rows in d_qual2
-    const char* qual_1 = reinterpret_cast<const char*>(d_qual1);
-    const char* qual_2 = reinterpret_cast<const char*>(d_qual2);
-    bool prepacked = false;
-    if (packed_hw) {
+    prof_end(c);
+    u64 n_jobs = reads, sw_bound = ~0ull;
+    const u64* n_jobs_dev = nullptr;
+    if (P.exact) {
+        HIPCHK(c, hipMemcpyAsync(&n_jobs, c->totals.as<u64>() + 1, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if ((u64)P.cigar_cap < n_jobs * (u64)max_ops) { c->err = "cigar pool too small (it takes bmbs_max_cigar_ops() slots per read)"; return BMBS_ENOMEM; }
+    } else {
+        n_jobs_dev = c->totals.as<u64>() + 1;
+        sw_bound = cap_from(c->lr_sw, reads, c->kn.cap_scale < 1.0 ? 64 : 16384, c->kn.cap_scale);
+        if ((u64)P.cigar_cap < reads * (u64)max_ops) {
+            hipLaunchKernelGGL(k_guard_jobs, dim3(nblk(reads, 256)), dim3(256), 0, c->stream, n_jobs_dev, (u64)max_ops, (u64)P.cigar_cap, c->flags.as<u32>(), (long)reads, st.job_flag);
+            hipLaunchKernelGGL(k_guard_done, dim3(1), dim3(1), 0, c->stream, c->totals.as<u64>() + 1, c->flags.as<u32>(), BMBS_FLAG_CIGAR);
+        }
+    }
+    c->last_n_jobs = n_jobs;
+    const u64 nj = n_jobs ? n_jobs : 1;
+    ENS(c, c->job_read, nj * 4); ENS(c, c->job_site, nj * 8); ENS(c, c->job_end, nj * 4); ENS(c, c->job_err, nj * 4);
+    if (n_jobs) {
+        prof_begin(c, "k_job_list");
+        hipLaunchKernelGGL(k_job_list, dim3(nblk(reads, 256)), dim3(256), 0, c->stream, (long)reads, st, c->job_read.as<u32>(),
+                           c->job_site.as<u64>(), c->job_end.as<int>(), c->job_err.as<u32>());
+        prof_end(c);
+    }
+    const Jobs jobs = {c->job_read.as<u32>(), c->job_site.as<u64>(), c->job_end.as<int>(), c->job_err.as<u32>()};
+    return run_align(c, seq, qual1, qual2, gm, P.stride, n_jobs, jobs, rev_from, reinterpret_cast<u32*>(P.d_cigar_pool), max_ops, packed_rows(c, gm),
+                     n_jobs_dev, sw_bound);
+}
+
+// ---- single end -------------------------------------------------------------------------------------------------------------------
+// the votes compacted to a dense list, Myers on every candidate (k_filter), the best site(s) of every read (k_reduce).
+// tot: candidate slots -- the count itself (exact) or the capacity the buffers and grids are sized for
+int se_filter_reduce(Lane* c, const ReadGeom& gm, const ReadState& st, const char* d_seq, int stride, u64 n, u64 tot, bool exact)
+{
+    ENS(c, c->vote_off, (n + 1) * 8);
+    {
+        const u64 t1 = exact ? std::max<u64>(tot, cap_from((double)tot / (double)n, n, n)) : (tot ? tot : 1);
+        ENS(c, c->votes_dense, t1 * sizeof(bmbs_vote)); ENS(c, c->dense_read, t1 * 4);
+    }
+    prof_begin(c, "vote_compact");
+    int rc = scan_u32(c, st.n_votes, n, c->vote_off.as<u64>(), 5);
+    if (rc) return rc;
+    if (tot)
+        hipLaunchKernelGGL(k_vote_compact, dim3(nblk(tot, 256)), dim3(256), 0, c->stream, tot, exact ? (const u64*)nullptr : c->totals.as<u64>(), st,
+                           c->vote_off.as<u64>(), c->slot_read.as<u32>(), c->votes.as<bmbs_vote>(), c->votes_dense.as<bmbs_vote>(), c->dense_read.as<u32>());
+    prof_end(c);
+    if (tot) {
+        prof_begin(c, "k_filter");
+        hipLaunchKernelGGL(k_filter, dim3(nblk(tot, 256)), dim3(256), 0, c->stream, c->ix, d_seq, packed_rows(c, gm), gm, stride, c->totals.as<u64>() + 5,
+                           c->dense_read.as<u32>(), c->votes_dense.as<bmbs_vote>(), c->ferr.as<u32>(), c->fend.as<int>(), c->counters.as<unsigned long long>());
+        prof_end(c);
+    }
+    prof_begin(c, "k_reduce");
+    // over the compacted list of reads with candidates the vote stage built
+    HIPCHK(c, hipMemsetAsync(st.job_flag, 0, n * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(st.red_status, 0, n, c->stream));
+    hipLaunchKernelGGL(k_reduce, dim3(nblk(n, 256)), dim3(256), 0, c->stream, (long)n, c->prm.ambiguous_out, st, c->vote_off.as<u64>(),
+                       c->votes_dense.as<bmbs_vote>(), c->ferr.as<u32>(), c->fend.as<int>(), c->totals.as<u64>() + 10, c->vote_list.as<u32>());
+    prof_end(c);
+    return BMBS_OK;
+}
+
+int map_se_dev(Lane* c, const Pending& P)
+{
+    ReadGeom gm = {};
+    int max_ops = 0;
+    int rc = call_open(c, P, (u64)P.n, &gm, &max_ops);
+    if (rc || P.n == 0) return rc;
+    const u64 n = (u64)P.n;
+    const char* d_seq = reinterpret_cast<const char*>(P.a[0]);
+    const char* d_qual = reinterpret_cast<const char*>(P.a[1]);
+    if (P.packed_hw) {
+        // the ASCII rows exist only where a piece holds an 'N' (written by k_rows_from_packed into the lane's own buffer)
+        ENS(c, c->pk_ascii, n * (u64)P.stride + 64);
+        { int rz_ = ensure(c, c->prow, n * (u64)pack_words(gm.L) * 8 + 64, true); if (rz_) return rz_; } ENS(c, c->prow_dirty, n + 64);
+        HIPCHK(c, hipMemsetAsync(c->prow_dirty.p, 0, n + 64, c->stream));
+        prof_begin(c, "k_rows_from_packed");
+        rows_from_packed(c, reinterpret_cast<const u64*>(P.a[0]), P.packed_hw, gm, 0, n, false, c->pk_ascii.as<char>(), P.stride);
+        prof_end(c);
+        d_seq = c->pk_ascii.as<char>();
+    }
+    const ReadState st = read_state(c);
+    u64 tot = 0;
+    rc = run_seed_stages(c, d_seq, gm, P.stride, n, &tot, 0, P.exact, P.packed_hw > 0);
+    if (rc) return rc;
+    c->last_total_cand = tot;
+    rc = se_filter_reduce(c, gm, st, d_seq, P.stride, n, tot, P.exact);
+    if (rc) return rc;
+    rc = align_jobs(c, P, gm, st, d_seq, d_qual, nullptr, n, 0xffffffffu, max_ops);
+    if (rc) return rc;
+    prof_begin(c, "k_finalize");
+    hipLaunchKernelGGL(k_finalize, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->ix, c->sp, c->pen_lut.as<int>(),
+                       c->mapq_lut.as<u8>(), c->mapq_off.as<u32>(), c->mapq_unit, d_seq, d_qual, gm, P.stride, (long)n, st, c->a_start.as<int>(),
+                       c->a_end.as<int>(), c->a_nm.as<u32>(), c->a_score.as<int>(), c->a_nops.as<int>(), max_ops, P.cigar_base,
+                       c->prm.ambiguous_out, c->sd_sp0.as<u64>(), c->sd_hits0.as<u32>(),
+                       reinterpret_cast<bmbs_result_dev*>(P.d_results), c->call_stats.as<unsigned long long>());
+    prof_end(c);
+    return call_end(c, P.slot);
+}
+
+// ---- paired end (fast mode: Map_Pair_Seq_end_to_end_fast, Schema.cpp:18570; --sensitive: Map_Pair_Seq_end_to_end) -----------------
+// what the stages of a paired-end call share: n pairs = n2 rows in seq_all (mate 1, then reverse-complemented mate 2), the candidate
+// lists in A / B (ps.cur says which), tot = candidate slots -- the count itself (exact) or the capacity buffers and grids are sized for
+struct PeCall {
+    Lane* c; ReadGeom gm; PeIns pi; ReadState st; PeState ps; PeCand *A, *B; char* seq_all; u64 n, n2; int stride; bool exact; u64 tot;
+    bool prepacked;              // the lane's packed rows are filled by the row stage (the seeding stage does not pack them itself)
+    int rows(const Pending& P);
+    int seed();
+    int votes();
+    int verify_round(int round, u64 cap, const char* name_f, const char* name_c);
+    int verify_fast();
+    int verify_sensitive();
+};
+
+// the 2n rows in seq_all and their packed copy: from the caller's packed rows, or by k_pe_prepare[_p], or there already (prepared).
+int PeCall::rows(const Pending& P)
+{
+    prepacked = false;
+    if (P.packed_hw) {
         // the caller's packed rows: mate 1 as it is, mate 2 reverse-complemented (bmbs_map_pe_packed); no ASCII rows to read at all
         { int rz_ = ensure(c, c->prow, n2 * (u64)pack_words(gm.L) * 8 + 64, true); if (rz_) return rz_; } ENS(c, c->prow_dirty, n2 + 64);
         HIPCHK(c, hipMemsetAsync(c->prow_dirty.p, 0, n2 + 64, c->stream));
         prof_begin(c, "k_rows_from_packed");
-        rc = rows_from_packed(c, reinterpret_cast<const u64*>(d_seq1), packed_hw, gm, 0, n, false, seq_all, stride);
-        if (!rc) rc = rows_from_packed(c, reinterpret_cast<const u64*>(d_seq2), packed_hw, gm, n, n, true, seq_all, stride);
-        if (rc) return rc;
+        rows_from_packed(c, reinterpret_cast<const u64*>(P.a[0]), P.packed_hw, gm, 0, n, false, seq_all, stride);
+        rows_from_packed(c, reinterpret_cast<const u64*>(P.a[2]), P.packed_hw, gm, n, n, true, seq_all, stride);
         prof_end(c);
         prepacked = true;
-    } else if (!prepared) {
+    } else if (!P.prepared) {
         u64* prow = nullptr; u32* pdirty = nullptr;
         const int pwords = pack_words(gm.L), W = pack_base_words(gm.L);
         if (use_packed_rows(c)) {
@@ -1157,46 +1151,55 @@ int map_pe_dev(Lane* c, uint64_t d_seq1, uint64_t d_qual1, uint64_t d_seq2, uint
         // on packed rows nothing reads the ASCII rows except under a set bit of the mask plane, so only those pieces are written
         // (BMBS_LEGACY=1: no packed rows, the complete ASCII copy)
         const int sparse = prow != nullptr;
+        const char* seq1 = reinterpret_cast<const char*>(P.a[0]);
+        const char* seq2 = reinterpret_cast<const char*>(P.a[2]);
         prof_begin(c, "k_pe_prepare");
         const int ppr = stride / 16;
         if (sparse && ppr <= 256) {
             const int rpb = 256 / ppr;
             hipLaunchKernelGGL(k_pe_prepare_p, dim3(std::min<u64>(nblk(n, rpb), 2048)), dim3(256), (size_t)rpb * (ppr + 1) * 16, c->stream,
-                               reinterpret_cast<const char*>(d_seq1), reinterpret_cast<const char*>(d_seq2), gm, stride, (long)n, seq_all, prow,
-                               pwords, W, pdirty);
+                               seq1, seq2, gm, stride, (long)n, seq_all, prow, pwords, W, pdirty);
         } else
-        hipLaunchKernelGGL(k_pe_prepare, dim3(nblk(n * (stride / 16), 256)), dim3(256), 0, c->stream, reinterpret_cast<const char*>(d_seq1),
-                           reinterpret_cast<const char*>(d_seq2), gm, stride, (long)n, seq_all, prow, pwords, W, pdirty, sparse);
+        hipLaunchKernelGGL(k_pe_prepare, dim3(nblk(n * (stride / 16), 256)), dim3(256), 0, c->stream, seq1, seq2, gm, stride, (long)n, seq_all,
+                           prow, pwords, W, pdirty, sparse);
         prof_end(c);
     }
-    ReadState st = read_state(c);
-    PeState ps;
+    return BMBS_OK;
+}
+
+// the per-row and per-pair state (call_open has sized it; --sensitive: and its buffers), seeding of all 2n reads; candidate slots by
+// scan -> tot, and the per-candidate buffers (A, B)
+int PeCall::seed()
+{
     ps.occ = c->pe_occ.as<int>(); ps.len = c->pe_len.as<u32>(); ps.cur = c->pe_cur.as<u8>(); ps.vround = c->pe_vround.as<u8>();
     ps.dead = c->pe_dead.as<u8>(); ps.both = c->pe_both.as<u8>(); ps.npair = c->pe_npair.as<int>(); ps.sbd = c->pe_sbd.as<u32>();
-    const bool sensitive = c->prm.sensitive != 0;
-    if (sensitive) {
+    if (c->prm.sensitive) {
         ENS(c, c->pe_first, n); ENS(c, c->pe_full, n2); ENS(c, c->pe_roff, n2 * 8); ENS(c, c->pe_rflag, n * 4); ENS(c, c->pe_rscan, (n + 1) * 8);
         ENS(c, c->pe_rlist, n * 4); ENS(c, c->pe_rcnt, n * 4); ENS(c, c->pe_ritem_off, (n + 1) * 8);
     }
     ps.first = c->pe_first.as<u8>(); ps.full = c->pe_full.as<u8>(); ps.R = c->pe_R.as<PeCand>(); ps.roff = c->pe_roff.as<u64>();
     c->last_reseeded = 0; c->last_reseed_cand = 0;
-    unsigned long long* cnt = c->counters.as<unsigned long long>();
-    // seeding of all 2n reads; candidate slots by scan; locate
-    rc = launch_seeding(c, seq_all, gm, stride, n2, 1, prepacked);
+    int rc = launch_seeding(c, seq_all, gm, stride, n2, 1, prepacked);
     if (rc) return rc;
     prof_begin(c, "scan_cand");
     rc = scan_u32(c, st.n_cand, n2, st.cand_off, 0);
     if (rc) return rc;
     prof_end(c);
-    u64 tot = 0;                     // candidate slots: the count itself (exact) or the capacity the buffers and grids are sized for
     rc = cand_total(c, st, n2, exact, &tot);
     if (rc) return rc;
     c->last_total_cand = tot;
     const u64 t1 = exact ? std::max<u64>(tot, cap_from((double)tot / (double)n2, n2, n2)) : (tot ? tot : 1);
     ENS(c, c->cand, t1 * 8); ENS(c, c->votes, t1 * sizeof(PeCand)); ENS(c, c->pe_B, t1 * sizeof(PeCand)); ENS(c, c->slot_read, t1 * 4);
     ENS(c, c->dense_read, t1 * 4); ENS(c, c->ferr, t1 * 4);
-    PeCand* A = c->votes.as<PeCand>();
-    PeCand* B = c->pe_B.as<PeCand>();
+    A = c->votes.as<PeCand>();
+    B = c->pe_B.as<PeCand>();
+    return BMBS_OK;
+}
+
+// locate + sort + votes of every read's candidates, one kernel per list-size class
+int PeCall::votes()
+{
+    unsigned long long* cnt = c->counters.as<unsigned long long>();
     ENS(c, c->long_flag, n2 * 4); ENS(c, c->long_off, (n2 + 1) * 8); ENS(c, c->long_list, n2 * 4);
     // reads of 180 bases and more place up to 25 seeds: lists of 17..32 candidates are the rule there and get a kernel of their own
     // (k_vote_pe_mid; buffers of its own: --sensitive still reads the seeding flags afterwards)
@@ -1211,7 +1214,7 @@ int map_pe_dev(Lane* c, uint64_t d_seq1, uint64_t d_qual1, uint64_t d_seq2, uint
     prof_end(c);
     if (use_mid) {
         prof_begin(c, "k_vote_pe_mid");
-        rc = scan_u32(c, mid_flag, n2, c->long_off.as<u64>(), 11, c->pe_mid_list.as<u32>());
+        int rc = scan_u32(c, mid_flag, n2, c->long_off.as<u64>(), 11, c->pe_mid_list.as<u32>());
         if (rc) return rc;
         hipLaunchKernelGGL(k_vote_pe_mid, dim3(nblk(n2, 64)), dim3(64), 0, c->stream, c->ix, gm, st, ps, c->totals.as<u64>() + 11, c->pe_mid_list.as<u32>(), A, cnt);
         prof_end(c);
@@ -1219,8 +1222,8 @@ int map_pe_dev(Lane* c, uint64_t d_seq1, uint64_t d_qual1, uint64_t d_seq2, uint
     prof_begin(c, "k_vote_pe_long");
     // fast mode: located sites without a partner on the mate's finished list are dropped before the sort (k_pe_fast.hip; --sensitive
     // uses the lists differently, Schema.cpp:19953-21459).  BMBS_PREFILTER=0: off (A/B runs, tests)
-    const int prefilter = (!sensitive && c->kn.prefilter) ? 1 : 0;
-    rc = scan_u32(c, c->long_flag.as<u32>(), n2, c->long_off.as<u64>(), 9, c->long_list.as<u32>());
+    const int prefilter = (!c->prm.sensitive && c->kn.prefilter) ? 1 : 0;
+    int rc = scan_u32(c, c->long_flag.as<u32>(), n2, c->long_off.as<u64>(), 9, c->long_list.as<u32>());
     if (rc) return rc;
     ENS(c, c->big_list, n2 * 4 + 64);
     unsigned long long* big_count = c->totals.as<unsigned long long>() + 13;
@@ -1238,174 +1241,159 @@ int map_pe_dev(Lane* c, uint64_t d_seq1, uint64_t d_qual1, uint64_t d_seq2, uint
     hipLaunchKernelGGL((k_vote_pe_long<VL_CAP, VL_BLOCK, 2048>), dim3(2048), dim3(VL_BLOCK), 0, c->stream, c->ix, gm, st, ps,
                        c->totals.as<u64>() + 13, c->big_list.as<u32>(), A, (u32*)nullptr, (unsigned long long*)nullptr, c->cand.as<u64>(), cnt, (long)n, pi, prefilter, c->long_flag.as<u32>());
     prof_end(c);
-    // one verification round: dense (read, list index) work list of the mates scheduled in `round`, Myers, compaction
-    auto verify_round = [&](int round, u64 cap, const char* name_f, const char* name_c) -> int {
-        if (cap) {
-            prof_begin(c, name_f);
-            u32* wcnt = c->sd_flag_c.as<u32>();
-            u64* woff = c->sd_off_c.as<u64>();
-            hipLaunchKernelGGL(k_pe_count, dim3(nblk(n2, 256)), dim3(256), 0, c->stream, (long)n, (long)n2, round, ps, wcnt);
-            int r_ = scan_u32(c, wcnt, n2, woff, 6);
-            if (r_) return r_;
-            hipLaunchKernelGGL(k_pe_worklist, dim3(nblk(n2, 256)), dim3(256), 0, c->stream, (long)n2, wcnt, woff, c->dense_read.as<u32>(),
-                               c->ferr.as<u32>());
-            PackedRows prf = {nullptr, nullptr, 0, 0};
-            if (use_packed_rows(c)) { prf.base = c->prow.as<u64>(); prf.dirty = c->prow_dirty.as<u8>(); prf.pwords = pack_words(gm.L); prf.W = pack_base_words(gm.L); }
-            hipLaunchKernelGGL(k_filter_pe, dim3(nblk(cap, 256)), dim3(256), 0, c->stream, c->ix, seq_all, prf, gm, stride, st, ps, A, B,
-                               c->totals.as<u64>() + 6, c->dense_read.as<u32>(), c->ferr.as<u32>(), cnt);
-            prof_end(c);
-        }
-        prof_begin(c, name_c);
-        hipLaunchKernelGGL(k_pe_compact, dim3(nblk(n2, 64)), dim3(64), 0, c->stream, (long)n, (long)n2, gm, round, st, ps, A, B);
-        prof_end(c);
-        return BMBS_OK;
-    };
-    if (!sensitive) {
-        prof_begin(c, "k_pe_filter_pairs");
-        // pairs with long candidate lists (repeats) are left to a second kernel, one wave per pair -- on repeat-rich input only (the last
-        // call left more than 0.5 % of its reads to the long-list vote kernels): flag array, scan and the extra launch cost 0.3 ms per
-        // 10 M pairs, 4 % of a launch on a repeat-poor genome.  BMBS_PEF_LONG=0: never, =2: always
-        u32* pef_flag = (c->kn.pef_long == 2 || (c->kn.pef_long == 1 && c->lr_long > 0.005)) ? c->long_flag.as<u32>() : nullptr;
-        if (pef_flag) HIPCHK(c, hipMemsetAsync(pef_flag, 0, n * 4, c->stream));
-        hipLaunchKernelGGL(k_pe_filter_pairs, dim3(nblk(n, 64)), dim3(64), 0, c->stream, (long)n, gm, pi, st, ps, A, B, pef_flag, cnt);
-        if (pef_flag) {
-            rc = scan_u32(c, pef_flag, n, c->long_off.as<u64>(), 12, c->long_list.as<u32>());
-            if (rc) return rc;
-            hipLaunchKernelGGL(k_pe_filter_pairs_long, dim3((unsigned)std::min<u64>(n, 65536)), dim3(64), 0, c->stream, (long)n, gm, pi, st, ps, c->totals.as<u64>() + 12,
-                               c->long_list.as<u32>(), A, B);
-        }
-        prof_end(c);
-        rc = verify_round(1, tot, "k_filter_pe_r1", "k_pe_compact_r1");
+    return BMBS_OK;
+}
+
+// one verification round: dense (read, list index) work list of the mates scheduled in `round`, Myers, compaction.
+// cap: the candidates the Myers grid covers (0: none to verify); name_f / name_c: the profile names of the two halves (literals)
+int PeCall::verify_round(int round, u64 cap, const char* name_f, const char* name_c)
+{
+    if (cap) {
+        prof_begin(c, name_f);
+        u32* wcnt = c->sd_flag_c.as<u32>();
+        u64* woff = c->sd_off_c.as<u64>();
+        hipLaunchKernelGGL(k_pe_count, dim3(nblk(n2, 256)), dim3(256), 0, c->stream, (long)n, (long)n2, round, ps, wcnt);
+        int rc = scan_u32(c, wcnt, n2, woff, 6);
         if (rc) return rc;
-        prof_begin(c, "k_pe_prune");
-        hipLaunchKernelGGL(k_pe_prune, dim3(nblk(n, 64)), dim3(64), 0, c->stream, (long)n, gm, pi, st, ps, A, B);
+        hipLaunchKernelGGL(k_pe_worklist, dim3(nblk(n2, 256)), dim3(256), 0, c->stream, (long)n2, wcnt, woff, c->dense_read.as<u32>(),
+                           c->ferr.as<u32>());
+        hipLaunchKernelGGL(k_filter_pe, dim3(nblk(cap, 256)), dim3(256), 0, c->stream, c->ix, seq_all, packed_rows(c, gm), gm, stride, st, ps, A, B,
+                           c->totals.as<u64>() + 6, c->dense_read.as<u32>(), c->ferr.as<u32>(), c->counters.as<unsigned long long>());
         prof_end(c);
-        rc = verify_round(2, tot, "k_filter_pe_r2", "k_pe_compact_r2");
-        if (rc) return rc;
-    } else {
-        // Map_Pair_Seq_end_to_end: first mate verified in full, second mate filtered by it, rescue by re-seeding
-        prof_begin(c, "k_pes_order");
-        hipLaunchKernelGGL(k_pes_order, dim3(nblk(n, 256)), dim3(256), 0, c->stream, (long)n, st, seed_carry(c), ps);
-        prof_end(c);
-        rc = verify_round(1, tot, "k_filter_pe_r1", "k_pe_compact_r1");
-        if (rc) return rc;
-        prof_begin(c, "k_pes_second");
-        hipLaunchKernelGGL(k_pes_second, dim3(nblk(n, 64)), dim3(64), 0, c->stream, (long)n, gm, pi, st, ps, A, B);
-        prof_end(c);
-        rc = verify_round(2, tot, "k_filter_pe_r2", "k_pe_compact_r2");
-        if (rc) return rc;
-        prof_begin(c, "k_pes_reseed");
-        u32* rflag = c->pe_rflag.as<u32>();
-        u32* rlist = c->pe_rlist.as<u32>();
-        u32* rcnt = c->pe_rcnt.as<u32>();
-        u64* n_reseed = c->totals.as<u64>() + 7;
-        hipLaunchKernelGGL(k_pes_reseed_flag, dim3(nblk(n, 256)), dim3(256), 0, c->stream, (long)n, ps, rflag);
-        rc = scan_u32(c, rflag, n, c->pe_rscan.as<u64>(), 7, rlist);
-        if (rc) return rc;
-        HIPCHK(c, hipMemsetAsync(rcnt, 0, n * 4, c->stream));
-        {
-            PackedRows prs = {nullptr, nullptr, 0, 0};
-            if (use_packed_rows(c)) { prs.base = c->prow.as<u64>(); prs.dirty = c->prow_dirty.as<u8>(); prs.pwords = pack_words(gm.L); prs.W = pack_base_words(gm.L); }
-            const bool kg = c->ix.occ3 && prs.base && (c->kn.kgram >= 2 || (c->kn.kgram == 1 && c->lr_chain >= 3.0));
-            hipLaunchKernelGGL((kg ? k_pes_reseed<true, true> : prs.base ? k_pes_reseed<true> : k_pes_reseed<false>), dim3(nblk(n, 64)), dim3(64), 0, c->stream, c->ix, seq_all, prs, gm, stride,
-                               (long)n, n_reseed, rlist, st, ps, rcnt, cnt);
-        }
-        rc = scan_u32(c, rcnt, n, c->pe_ritem_off.as<u64>(), 8);
-        if (rc) return rc;
-        prof_end(c);
-        u64 rt[2] = {0, 0};          // pairs to re-seed, their candidates: counts (exact) or capacities with a guard
-        if (exact) {
-            HIPCHK(c, hipMemcpyAsync(rt, c->totals.as<u64>() + 7, 16, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-        } else {
-            rt[0] = n; rt[1] = cap_from(c->lr_rcand, n2, c->kn.cap_scale < 1.0 ? 64 : 65536, c->kn.cap_scale);
-            hipLaunchKernelGGL(k_guard_rcand, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->totals.as<u64>() + 8, rt[1], c->flags.as<u32>(), (long)n, rcnt,
-                               c->pe_ritem_off.as<u64>());
-            hipLaunchKernelGGL(k_guard_done, dim3(1), dim3(1), 0, c->stream, c->totals.as<u64>() + 8, c->flags.as<u32>(), BMBS_FLAG_RCAND);
-        }
-        c->last_reseeded = rt[0]; c->last_reseed_cand = rt[1];
-        if (rt[0]) {
-            const u64 rtot = exact ? std::max<u64>(rt[1], cap_from((double)rt[1] / (double)n2, n2, 65536)) : (rt[1] ? rt[1] : 1);
-            ENS(c, c->pe_R, rtot * sizeof(PeCand)); ENS(c, c->pe_rcand, rtot * 8);
-            ENS(c, c->dense_read, rtot * 4); ENS(c, c->ferr, rtot * 4);
-            ps.R = c->pe_R.as<PeCand>();
-            prof_begin(c, "k_pes_vote");
-            // mates with more than PESV_LONG candidates are flagged, listed (slot 14) and sorted by a block each
-            u32* pv_flag = c->long_flag.as<u32>();                                  // n2 words: free again after the vote stage
-            hipLaunchKernelGGL(k_pes_vote, dim3(nblk(rt[0], 64)), dim3(64), 0, c->stream, c->ix, (long)n, gm, pi, n_reseed, rlist,
-                               c->pe_ritem_off.as<u64>(), st, ps, c->pe_rcand.as<u64>(), A, B, pv_flag, cnt);
-            if (pv_flag) {
-                rc = scan_u32(c, pv_flag, rt[0], c->long_off.as<u64>(), 14, c->long_list.as<u32>(), 0, n_reseed);
-                if (rc) return rc;
-                hipLaunchKernelGGL((k_pes_vote_long<1024, 128, PESV_LONG>), dim3(8192), dim3(128), 0, c->stream, c->ix, (long)n, gm, pi, c->totals.as<u64>() + 14,
-                                   c->long_list.as<u32>(), rlist, c->pe_ritem_off.as<u64>(), st, ps, c->pe_rcand.as<u64>(), A, B);
-                // (three size classes, as the vote kernels: a re-seeded mate of 1 025 .. 2 048 candidates in the 4 096-key form held 41 KB of
-                // LDS -- three lists per CU; r6)
-                hipLaunchKernelGGL((k_pes_vote_long<2048, 256, 1024>), dim3(4096), dim3(256), 0, c->stream, c->ix, (long)n, gm, pi, c->totals.as<u64>() + 14,
-                                   c->long_list.as<u32>(), rlist, c->pe_ritem_off.as<u64>(), st, ps, c->pe_rcand.as<u64>(), A, B);
-                hipLaunchKernelGGL((k_pes_vote_long<VL_CAP, VL_BLOCK, 2048>), dim3(2048), dim3(VL_BLOCK), 0, c->stream, c->ix, (long)n, gm, pi, c->totals.as<u64>() + 14,
-                                   c->long_list.as<u32>(), rlist, c->pe_ritem_off.as<u64>(), st, ps, c->pe_rcand.as<u64>(), A, B);
-            }
-            prof_end(c);
-            rc = verify_round(3, rt[1], "k_filter_pe_r3", "k_pe_compact_r3");
-            if (rc) return rc;
-        }
     }
-    prof_begin(c, "k_pe_pair");
-    hipLaunchKernelGGL(k_pe_pair, dim3(nblk(n, 64)), dim3(64), 0, c->stream, c->ix, (long)n, gm, pi, c->prm.ambiguous_out, st, ps, A, B);
+    prof_begin(c, name_c);
+    hipLaunchKernelGGL(k_pe_compact, dim3(nblk(n2, 64)), dim3(64), 0, c->stream, (long)n, (long)n2, gm, round, st, ps, A, B);
     prof_end(c);
-    prof_begin(c, "scan_jobs");
-    rc = scan_u32(c, st.job_flag, n2, st.job_off, 1);
+    return BMBS_OK;
+}
+
+// fast mode: the lists cut down to sites with a partner on the mate's list, verified in two rounds
+int PeCall::verify_fast()
+{
+    prof_begin(c, "k_pe_filter_pairs");
+    // pairs with long candidate lists (repeats) are left to a second kernel, one wave per pair -- on repeat-rich input only (the last
+    // call left more than 0.5 % of its reads to the long-list vote kernels): flag array, scan and the extra launch cost 0.3 ms per
+    // 10 M pairs, 4 % of a launch on a repeat-poor genome.  BMBS_PEF_LONG=0: never, =2: always
+    u32* pef_flag = (c->kn.pef_long == 2 || (c->kn.pef_long == 1 && c->lr_long > 0.005)) ? c->long_flag.as<u32>() : nullptr;
+    if (pef_flag) HIPCHK(c, hipMemsetAsync(pef_flag, 0, n * 4, c->stream));
+    hipLaunchKernelGGL(k_pe_filter_pairs, dim3(nblk(n, 64)), dim3(64), 0, c->stream, (long)n, gm, pi, st, ps, A, B, pef_flag,
+                       c->counters.as<unsigned long long>());
+    if (pef_flag) {
+        int rc = scan_u32(c, pef_flag, n, c->long_off.as<u64>(), 12, c->long_list.as<u32>());
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_pe_filter_pairs_long, dim3((unsigned)std::min<u64>(n, 65536)), dim3(64), 0, c->stream, (long)n, gm, pi, st, ps, c->totals.as<u64>() + 12,
+                           c->long_list.as<u32>(), A, B);
+    }
+    prof_end(c);
+    int rc = verify_round(1, tot, "k_filter_pe_r1", "k_pe_compact_r1");
+    if (rc) return rc;
+    prof_begin(c, "k_pe_prune");
+    hipLaunchKernelGGL(k_pe_prune, dim3(nblk(n, 64)), dim3(64), 0, c->stream, (long)n, gm, pi, st, ps, A, B);
+    prof_end(c);
+    return verify_round(2, tot, "k_filter_pe_r2", "k_pe_compact_r2");
+}
+
+// --sensitive (Map_Pair_Seq_end_to_end): first mate verified in full, second mate filtered by it, rescue by re-seeding (a third round)
+int PeCall::verify_sensitive()
+{
+    unsigned long long* cnt = c->counters.as<unsigned long long>();
+    prof_begin(c, "k_pes_order");
+    hipLaunchKernelGGL(k_pes_order, dim3(nblk(n, 256)), dim3(256), 0, c->stream, (long)n, st, seed_carry(c), ps);
+    prof_end(c);
+    int rc = verify_round(1, tot, "k_filter_pe_r1", "k_pe_compact_r1");
+    if (rc) return rc;
+    prof_begin(c, "k_pes_second");
+    hipLaunchKernelGGL(k_pes_second, dim3(nblk(n, 64)), dim3(64), 0, c->stream, (long)n, gm, pi, st, ps, A, B);
+    prof_end(c);
+    rc = verify_round(2, tot, "k_filter_pe_r2", "k_pe_compact_r2");
+    if (rc) return rc;
+    prof_begin(c, "k_pes_reseed");
+    u32* rflag = c->pe_rflag.as<u32>();
+    u32* rlist = c->pe_rlist.as<u32>();
+    u32* rcnt = c->pe_rcnt.as<u32>();
+    u64* n_reseed = c->totals.as<u64>() + 7;
+    hipLaunchKernelGGL(k_pes_reseed_flag, dim3(nblk(n, 256)), dim3(256), 0, c->stream, (long)n, ps, rflag);
+    rc = scan_u32(c, rflag, n, c->pe_rscan.as<u64>(), 7, rlist);
+    if (rc) return rc;
+    HIPCHK(c, hipMemsetAsync(rcnt, 0, n * 4, c->stream));
+    {
+        const PackedRows prs = packed_rows(c, gm);
+        const bool kg = c->ix.occ3 && prs.base && (c->kn.kgram >= 2 || (c->kn.kgram == 1 && c->lr_chain >= 3.0));
+        hipLaunchKernelGGL((kg ? k_pes_reseed<true, true> : prs.base ? k_pes_reseed<true> : k_pes_reseed<false>), dim3(nblk(n, 64)), dim3(64), 0, c->stream, c->ix, seq_all, prs, gm, stride,
+                           (long)n, n_reseed, rlist, st, ps, rcnt, cnt);
+    }
+    rc = scan_u32(c, rcnt, n, c->pe_ritem_off.as<u64>(), 8);
     if (rc) return rc;
     prof_end(c);
-    u64 n_jobs = n2, sw_bound = ~0ull;
-    const u64* n_jobs_dev = nullptr;
+    u64 rt[2] = {0, 0};          // pairs to re-seed, their candidates: counts (exact) or capacities with a guard
     if (exact) {
-        HIPCHK(c, hipMemcpyAsync(&n_jobs, c->totals.as<u64>() + 1, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(rt, c->totals.as<u64>() + 7, 16, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if ((u64)cigar_cap < n_jobs * (u64)max_ops) { c->err = "cigar pool too small (it takes bmbs_max_cigar_ops() slots per read)"; return BMBS_ENOMEM; }
     } else {
-        n_jobs_dev = c->totals.as<u64>() + 1;
-        sw_bound = cap_from(c->lr_sw, n2, c->kn.cap_scale < 1.0 ? 64 : 16384, c->kn.cap_scale);
-        if ((u64)cigar_cap < n2 * (u64)max_ops) {
-            hipLaunchKernelGGL(k_guard_jobs, dim3(nblk(n2, 256)), dim3(256), 0, c->stream, n_jobs_dev, (u64)max_ops, (u64)cigar_cap, c->flags.as<u32>(), (long)n2, st.job_flag);
-            hipLaunchKernelGGL(k_guard_done, dim3(1), dim3(1), 0, c->stream, c->totals.as<u64>() + 1, c->flags.as<u32>(), BMBS_FLAG_CIGAR);
-        }
+        rt[0] = n; rt[1] = cap_from(c->lr_rcand, n2, c->kn.cap_scale < 1.0 ? 64 : 65536, c->kn.cap_scale);
+        hipLaunchKernelGGL(k_guard_rcand, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->totals.as<u64>() + 8, rt[1], c->flags.as<u32>(), (long)n, rcnt,
+                           c->pe_ritem_off.as<u64>());
+        hipLaunchKernelGGL(k_guard_done, dim3(1), dim3(1), 0, c->stream, c->totals.as<u64>() + 8, c->flags.as<u32>(), BMBS_FLAG_RCAND);
     }
-    c->last_n_jobs = n_jobs;
-    {
-        const u64 nj = n_jobs ? n_jobs : 1;
-        ENS(c, c->job_read, nj * 4); ENS(c, c->job_site, nj * 8); ENS(c, c->job_end, nj * 4); ENS(c, c->job_err, nj * 4);
-        if (n_jobs) {
-            prof_begin(c, "k_job_list");
-            hipLaunchKernelGGL(k_job_list, dim3(nblk(n2, 256)), dim3(256), 0, c->stream, (long)n2, st, c->job_read.as<u32>(),
-                               c->job_site.as<u64>(), c->job_end.as<int>(), c->job_err.as<u32>());
-            prof_end(c);
-        }
-        Jobs jobs = {c->job_read.as<u32>(), c->job_site.as<u64>(), c->job_end.as<int>(), c->job_err.as<u32>()};
-        // mate 2 rows (>= n) carry FASTQ-order qualities for a reverse-complemented read: need_reverse_quality = 1
-        PackedRows prw = {nullptr, nullptr, 0, 0};
-        if (use_packed_rows(c)) { prw.base = c->prow.as<u64>(); prw.dirty = c->prow_dirty.as<u8>(); prw.pwords = pack_words(gm.L); prw.W = pack_base_words(gm.L); }
-        rc = run_align(c, seq_all, qual_1, gm, stride, n_jobs, jobs, (u32)n, reinterpret_cast<u32*>(d_cigar_pool), max_ops, qual_2, &prw, n_jobs_dev, sw_bound);
-        if (rc) return rc;
-    }
+    c->last_reseeded = rt[0]; c->last_reseed_cand = rt[1];
+    if (!rt[0]) return BMBS_OK;
+    const u64 rtot = exact ? std::max<u64>(rt[1], cap_from((double)rt[1] / (double)n2, n2, 65536)) : (rt[1] ? rt[1] : 1);
+    ENS(c, c->pe_R, rtot * sizeof(PeCand)); ENS(c, c->pe_rcand, rtot * 8);
+    ENS(c, c->dense_read, rtot * 4); ENS(c, c->ferr, rtot * 4);
+    ps.R = c->pe_R.as<PeCand>();
+    prof_begin(c, "k_pes_vote");
+    // mates with more than PESV_LONG candidates are flagged, listed (slot 14) and sorted by a block each
+    u32* pv_flag = c->long_flag.as<u32>();                                  // n2 words: free again after the vote stage
+    hipLaunchKernelGGL(k_pes_vote, dim3(nblk(rt[0], 64)), dim3(64), 0, c->stream, c->ix, (long)n, gm, pi, n_reseed, rlist,
+                       c->pe_ritem_off.as<u64>(), st, ps, c->pe_rcand.as<u64>(), A, B, pv_flag, cnt);
+    rc = scan_u32(c, pv_flag, rt[0], c->long_off.as<u64>(), 14, c->long_list.as<u32>(), 0, n_reseed);
+    if (rc) return rc;
+    hipLaunchKernelGGL((k_pes_vote_long<1024, 128, PESV_LONG>), dim3(8192), dim3(128), 0, c->stream, c->ix, (long)n, gm, pi, c->totals.as<u64>() + 14,
+                       c->long_list.as<u32>(), rlist, c->pe_ritem_off.as<u64>(), st, ps, c->pe_rcand.as<u64>(), A, B);
+    // (three size classes, as the vote kernels: a re-seeded mate of 1 025 .. 2 048 candidates in the 4 096-key form held 41 KB of
+    // LDS -- three lists per CU; r6)
+    hipLaunchKernelGGL((k_pes_vote_long<2048, 256, 1024>), dim3(4096), dim3(256), 0, c->stream, c->ix, (long)n, gm, pi, c->totals.as<u64>() + 14,
+                       c->long_list.as<u32>(), rlist, c->pe_ritem_off.as<u64>(), st, ps, c->pe_rcand.as<u64>(), A, B);
+    hipLaunchKernelGGL((k_pes_vote_long<VL_CAP, VL_BLOCK, 2048>), dim3(2048), dim3(VL_BLOCK), 0, c->stream, c->ix, (long)n, gm, pi, c->totals.as<u64>() + 14,
+                       c->long_list.as<u32>(), rlist, c->pe_ritem_off.as<u64>(), st, ps, c->pe_rcand.as<u64>(), A, B);
+    prof_end(c);
+    return verify_round(3, rt[1], "k_filter_pe_r3", "k_pe_compact_r3");
+}
+
+int map_pe_dev(Lane* c, const Pending& P)
+{
+    ReadGeom gm = {};
+    int max_ops = 0;
+    int rc = call_open(c, P, 2 * (u64)P.n, &gm, &max_ops);
+    if (rc || P.n == 0) return rc;
+    PeCall x = {};
+    x.c = c; x.gm = gm; x.pi = {c->prm.min_ins, c->prm.max_ins}; x.st = read_state(c);
+    x.seq_all = c->pe_seq.as<char>(); x.n = (u64)P.n; x.n2 = 2 * x.n; x.stride = P.stride; x.exact = P.exact;
+    // the qualities are read where the caller put them (qual_row): mate 1 rows in a[1], mate 2 rows in a[3]
+    const char* qual_1 = reinterpret_cast<const char*>(P.a[1]);
+    const char* qual_2 = reinterpret_cast<const char*>(P.a[3]);
+    rc = x.rows(P);
+    if (!rc) rc = x.seed();
+    if (!rc) rc = x.votes();
+    if (!rc) rc = c->prm.sensitive ? x.verify_sensitive() : x.verify_fast();
+    if (rc) return rc;
+    prof_begin(c, "k_pe_pair");
+    hipLaunchKernelGGL(k_pe_pair, dim3(nblk(x.n, 64)), dim3(64), 0, c->stream, c->ix, (long)x.n, gm, x.pi, c->prm.ambiguous_out, x.st, x.ps, x.A, x.B);
+    prof_end(c);
+    rc = align_jobs(c, P, gm, x.st, x.seq_all, qual_1, qual_2, x.n2, (u32)x.n, max_ops);
+    if (rc) return rc;
     prof_begin(c, "k_finalize_pe");
-    hipLaunchKernelGGL(k_finalize_pe, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->ix, c->sp, c->pen_lut.as<int>(), seq_all, qual_1, qual_2, stride,
+    hipLaunchKernelGGL(k_finalize_pe, dim3(nblk(x.n, 256)), dim3(256), 0, c->stream, c->ix, c->sp, c->pen_lut.as<int>(), x.seq_all, qual_1, qual_2, P.stride,
                        c->mapq_lut.as<u8>(), c->mapq_off.as<u32>(), c->mapq_unit, gm,
-                       c->prm.min_ins, c->prm.max_ins, c->prm.ambiguous_out, (long)n, st, ps, c->a_start.as<int>(), c->a_end.as<int>(), c->a_nm.as<u32>(),
-                       c->a_score.as<int>(), c->a_nops.as<int>(), max_ops, cigar_base, reinterpret_cast<bmbs_result_dev*>(d_results),
+                       c->prm.min_ins, c->prm.max_ins, c->prm.ambiguous_out, (long)x.n, x.st, x.ps, c->a_start.as<int>(), c->a_end.as<int>(), c->a_nm.as<u32>(),
+                       c->a_score.as<int>(), c->a_nops.as<int>(), max_ops, P.cigar_base, reinterpret_cast<bmbs_result_dev*>(P.d_results),
                        c->call_stats.as<unsigned long long>());
     prof_end(c);
-    return call_end(c, slot);
+    return call_end(c, P.slot);
 }
 
 // ---- calls in flight on a lane ------------------------------------------------------------------------------------------------
-int lane_issue(Lane* c, const Pending& P)
-{
-    return P.pe ? map_pe_dev(c, P.a[0], P.a[1], P.a[2], P.a[3], P.d_len, P.L, P.stride, P.n, P.d_results, P.d_cigar_pool, P.cigar_cap, P.prepared, P.exact,
-                             P.cigar_base, P.slot, P.packed_hw)
-                : map_se_dev(c, P.a[0], P.a[1], P.d_len, P.L, P.stride, P.n, P.d_results, P.d_cigar_pool, P.cigar_cap, P.exact, P.cigar_base, P.slot, P.packed_hw);
-}
+int lane_issue(Lane* c, const Pending& P) { return P.pe ? map_pe_dev(c, P) : map_se_dev(c, P); }
 
 // Wait for the lane, then read what its calls left in their page-locked words: the stage counts (they size the next calls) and the
 // guard flags.  A call whose counts did not fit its capacities has done no harm (the guards took its work away and its counters
@@ -1569,7 +1557,8 @@ int dispatch_host(bmbs_ctx* X, bool pe, const HostIn& in, int32_t L, int32_t str
     const int max_ops = cigar_ops_bound(X->prm, L, threshold_k(X->prm, L));
     const int64_t ch = chunk_units(X, n, cigar_cap, rpu, max_ops, true);
     const int nl = (int)X->lanes.size();
-    const int used_lanes_ = ch == n ? 1 : (int)std::min<int64_t>(nl, (n + ch - 1) / ch);
+    const int64_t n_chunks = (n + ch - 1) / ch;
+    const int used_lanes = ch == n ? 1 : (int)std::min<int64_t>(nl, n_chunks);
     share_needs(X);
     struct Open { bool on = false; int64_t off = 0, m = 0; };
     std::vector<Open> open((size_t)nl);
@@ -1625,7 +1614,7 @@ int dispatch_host(bmbs_ctx* X, bool pe, const HostIn& in, int32_t L, int32_t str
             // copies back to back with no host in between -- measured no better than side-by-side uploads: 172 against 174 / 165 M
             // reads/s, turns 186 / 192; 2 M pairs per call, profiles/HISTORY.md)
             std::unique_lock<std::mutex> up_turn(g_h2d_mu[c->dev & 15], std::defer_lock);
-            if (cs && used_lanes_ > 1 && c->kn.up_turns) up_turn.lock();
+            if (cs && used_lanes > 1 && c->kn.up_turns) up_turn.lock();
             if (in.hw) {
                 // packed rows: hw words per read go over as they are (one block per mate)
                 const u64 pb = um * (u64)in.hw * 8;
@@ -1683,8 +1672,6 @@ int dispatch_host(bmbs_ctx* X, bool pe, const HostIn& in, int32_t L, int32_t str
     // One host thread per lane: a chunk is ~110 kernel launches and a handful of waits, and with all of them issued by one thread the
     // call was bound by that thread on boxes with slower cores (2 M pairs through bmbs_map_pe_packed: 137 M reads/s where the link
     // would give 200).  Chunk k goes to lane k % lanes whoever issues it: the results do not depend on the threads.
-    const int64_t n_chunks = (n + ch - 1) / ch;
-    const int used_lanes = ch == n ? 1 : (int)std::min<int64_t>(nl, n_chunks);
     int rc = BMBS_OK;
     std::mutex err_mu;
     std::atomic<int> stop(0);
@@ -2048,7 +2035,8 @@ static int lane_align_batch(Lane* c, const char* seq, const char* qual, int32_t 
     HIPCHK(c, hipMemsetAsync(c->cig_pool.p, 0, m * (u64)max_ops * 4, c->stream));
     c->cur_slot = 0; c->prof_used[0] = 0;
     Jobs jobs = {c->in_a.as<u32>(), c->in_b.as<u64>(), c->in_c.as<int>(), c->in_d.as<u32>()};
-    int rc = run_align(c, c->in_seq.as<char>(), c->in_qual.as<char>(), geom(c, L, nullptr), stride, m, jobs, 0xffffffffu, c->cig_pool.as<u32>(), max_ops);
+    int rc = run_align(c, c->in_seq.as<char>(), c->in_qual.as<char>(), nullptr, geom(c, L, nullptr), stride, m, jobs, 0xffffffffu, c->cig_pool.as<u32>(), max_ops,
+                       PackedRows{nullptr, nullptr, 0, 0}, nullptr, ~0ull);          // on the ASCII rows
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(start_site, c->a_start.p, m * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(end_site, c->a_end.p, m * 4, hipMemcpyDeviceToHost, c->stream));
@@ -2080,7 +2068,7 @@ static int lane_seed_batch(Lane* c, const char* seq, int32_t L, int32_t stride, 
     HIPCHK(c, hipMemsetAsync(c->counters.p, 0, BMBS_SHARDS * BMBS_SHARD_WORDS * 8, c->stream));
     HIPCHK(c, hipMemsetAsync(c->exit_site.p, 0, n * 8, c->stream));
     u64 tot = 0;
-    rc = run_seed_stages(c, c->in_seq.as<char>(), geom(c, L, nullptr), stride, n, &tot);
+    rc = run_seed_stages(c, c->in_seq.as<char>(), geom(c, L, nullptr), stride, n, &tot, 0, true, false);
     if (rc) return rc;
     if (total_slots) *total_slots = (int64_t)tot;
     if ((u64)vote_cap < tot) { c->err = "vote buffers too small"; (void)hipStreamSynchronize(c->stream); return BMBS_ENOMEM; }

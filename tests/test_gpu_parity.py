@@ -1990,3 +1990,44 @@ def test_very_long_candidate_lists_match_oracle(tmp_path):
             res, pool = m.map_pe(m1["seq"], m1["qual"], m2["seq"], m2["qual"], 150)
             assert not compare_pe(res, pool, recs, 150), (sensitive, rep)
         m.close()
+
+
+# one call of a fresh context each: nothing learned yet, so the call waits for its counts (the exact launch sequence), lr_long is 0 and
+# the stage list depends on the input alone.  A few thousand reads: one lane (far below 2 * BMBS_SPLIT_MIN)
+STAGE_CASES = {
+    "se_L100": dict(pe=False, L=100, n=4000, seed=1201, sub=0.02, prm=dict()),
+    "se_L250": dict(pe=False, L=250, n=3000, seed=1202, sub=0.02, prm=dict()),                # L / 10 - 1 > VOTE_REG: k_vote_mid
+    "pe_fast_L100": dict(pe=True, L=100, n=4000, seed=1203, sub=0.02, prm=dict()),
+    "pe_sensitive_L100": dict(pe=True, L=100, n=4000, seed=1204, sub=0.05, prm=dict(sensitive=1)),      # mates lost to errors: re-seeding
+}
+
+
+def stage_names(chroms, ix, case):
+    """the profile stage names of one mapping call of a fresh Mapper, in launch order (tests/golden/make_stage_names.py records them)"""
+    from bitmapperbs_amd import synth, mapper
+    c = STAGE_CASES[case]
+    m = mapper.Mapper(ix, 0, **c["prm"])
+    if c["pe"]:
+        m1, m2 = synth.make_reads_pe(chroms, n=c["n"], L=c["L"], seed=c["seed"], sub=c["sub"], indel=0.002, qual="random")
+        m.map_pe(m1["seq"], m1["qual"], m2["seq"], m2["qual"], c["L"])
+    else:
+        r = synth.make_reads_se(chroms, n=c["n"], L=c["L"], seed=c["seed"], sub=c["sub"], indel=0.002, qual="random")
+        m.map_se(r["seq"], r["qual"], c["L"])
+    names = [name for name, _ in m.profile()]
+    m.close()
+    return names
+
+
+@pytest.mark.parametrize("case", sorted(STAGE_CASES))
+def test_stage_sequence_is_unchanged(case, env):
+    """the launch sequence as the profile sees it: the stage names of a call and their order equal the recorded ones
+    (tests/golden/stage_names.json, written by tests/golden/make_stage_names.py from the library before the launch path was split
+    into stage functions)"""
+    import json
+    want = json.load(open(os.path.join(GOLD, "stage_names.json")))[case]
+    if case == "se_L250":
+        assert "k_vote_mid" in want
+    if case == "pe_sensitive_L100":
+        assert "k_pes_vote" in want and "k_filter_pe_r3" in want          # the re-seed branch is exercised
+    got = stage_names(env["chroms"], env["ix"], case)
+    assert got == want
