@@ -200,6 +200,15 @@ struct Lane {
     // last BMBS_TEXT_BAM_SORTED call (bmbs_text_sorted_index reads bs_key2 / bs_slen), -1: none
     DevBuf bs_key, bs_key2, bs_idx, bs_idx2, bs_slen, bs_soff, bs_tmp, bs_in, bs_len, bs_off, bs_sorted;
     int64_t bs_n = -1;
+    // .bai pieces of the last bmbs_bam_sort call that returned BGZF blocks (k_bai.hip, bmbs_bam_sort_index): bai_n = its records (-1: none,
+    // or bs_sorted / bs_soff / bam_off have been written since), bai_bytes / bai_z = its uncompressed / compressed size, bai_ref_max = its
+    // largest refID.  bai_a: per-record and per-reference work arrays, bai_b: the chunks and window candidates, bai_out: the three result
+    // arrays (at bai_at), kept (bai_done, bai_cnt = chunks, windows, references, records without a reference) for the call that follows a size query
+    DevBuf bai_a, bai_b, bai_out;
+    int64_t bai_n = -1;
+    u64 bai_bytes = 0, bai_z = 0, bai_cnt[4] = {0, 0, 0, 0}, bai_at[3] = {0, 0, 0};
+    u32 bai_ref_max = 0;
+    bool bai_done = false;
     DevBuf z_comp, z_off, z_text, z_err, z_nl, z_comp2, z_off2, z_err2;         // bmbs_inflate_bgzf; (…2: mate 2 of bmbs_text_open_bgzf)
     struct OpenText { bool valid = false, pe = false; u64 bytes1 = 0, bytes2 = 0; int64_t n = 0; } open_text;      // between bmbs_text_open_bgzf and bmbs_text_map_open
     u32* h_info = nullptr;                              // page-locked: 8 info words + 4 totals of the text path

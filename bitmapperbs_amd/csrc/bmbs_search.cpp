@@ -786,6 +786,96 @@ struct SortStore {
         return true;
     }
 };
+// ---- --bam --sort --bai: the .bai index (SAM specification section 5.2) of the sorted file, from the same run ------------------------------
+// Every pass-2 call leaves the pieces of its own blocks on the device side (bmbs_bam_sort_index: chunks, 16 kb windows, per-reference
+// totals; virtual offsets relative to the call's first block).  The writing thread knows the file offset B at which it appends a
+// call's blocks, adds B << 16 and merges in call order:
+//   chunks of one (ref, bin) one behind the other; two are joined when the earlier one's end is the later one's beg (a run of records
+//   of one bin that went on across the call boundary); a window keeps the first call's offset; a reference keeps the first beg, the
+//   last end and the summed counts.
+// The file written is the NORMAL FORM, so that a BAM file has exactly one index: n_ref of the header; bins in ascending number with
+// their chunks in file order, then the pseudo-bin 37450 with (ref.beg, ref.end) and (n_mapped, n_unmapped); a linear index of 1 + the
+// last window touched, empty windows filled with the previous window's value, leading ones with ref.beg (htslib's update_loff); the
+// count of records without a reference.  Sequences without records: n_bin = 0, n_intv = 0.  htslib's compress_binning (folding small
+// bins into their parents, a size optimisation no reader depends on) is not done.
+struct BaiPieces {
+    std::vector<bmbs_bai_chunk> chunk; std::vector<bmbs_bai_win> win; std::vector<bmbs_bai_ref> ref;
+    int64_t n_chunk = 0, n_win = 0, n_ref = 0; uint64_t n_no_coor = 0;
+    // the pieces of ctx's last bmbs_bam_sort call
+    bool fetch(bmbs_ctx* ctx)
+    {
+        for (int attempt = 0; attempt < 2; attempt++) {
+            const int rc = bmbs_bam_sort_index(ctx, chunk.data(), (int64_t)chunk.size(), &n_chunk, win.data(), (int64_t)win.size(), &n_win, ref.data(), (int64_t)ref.size(),
+                                               &n_ref, &n_no_coor);
+            if (rc == BMBS_OK) return true;
+            if (rc != BMBS_ENOMEM || attempt) return false;
+            if ((size_t)n_chunk > chunk.size()) chunk.resize((size_t)n_chunk + (size_t)n_chunk / 8);
+            if ((size_t)n_win > win.size()) win.resize((size_t)n_win + (size_t)n_win / 8);
+            if ((size_t)n_ref > ref.size()) ref.resize((size_t)n_ref);
+        }
+        return false;
+    }
+};
+struct BaiIndex {
+    struct Ref {
+        std::map<uint32_t, std::vector<std::pair<uint64_t, uint64_t>>> bins;
+        std::vector<uint64_t> lin;                   // window -> offset; ~0: no mapped record overlaps it
+        bool any = false; uint64_t beg = 0, end = 0, n_mapped = 0, n_unmapped = 0;
+    };
+    std::vector<Ref> refs;
+    uint64_t n_no_coor = 0;
+    void init(size_t n_ref) { refs.assign(n_ref, Ref()); }
+    // the pieces of the call whose blocks start at file offset B; false: a reference index outside the header's
+    bool add(const BaiPieces& p, uint64_t B)
+    {
+        const uint64_t sh = B << 16;
+        for (int64_t i = 0; i < p.n_chunk; i++) {
+            const bmbs_bai_chunk& c = p.chunk[(size_t)i];
+            if (c.ref < 0 || (size_t)c.ref >= refs.size()) return false;
+            auto& v = refs[(size_t)c.ref].bins[c.bin];
+            if (!v.empty() && v.back().second == c.beg + sh) v.back().second = c.end + sh;
+            else v.push_back({c.beg + sh, c.end + sh});
+        }
+        for (int64_t i = 0; i < p.n_win; i++) {
+            const bmbs_bai_win& w = p.win[(size_t)i];
+            if (w.ref < 0 || (size_t)w.ref >= refs.size()) return false;
+            auto& lin = refs[(size_t)w.ref].lin;
+            if (lin.size() <= w.win) lin.resize((size_t)w.win + 1, ~(uint64_t)0);
+            if (lin[w.win] == ~(uint64_t)0) lin[w.win] = w.off + sh;
+        }
+        for (int64_t i = 0; i < p.n_ref; i++) {
+            const bmbs_bai_ref& r = p.ref[(size_t)i];
+            if (r.ref < 0 || (size_t)r.ref >= refs.size()) return false;
+            Ref& R = refs[(size_t)r.ref];
+            if (!R.any) { R.any = true; R.beg = r.beg + sh; }
+            R.end = r.end + sh; R.n_mapped += r.n_mapped; R.n_unmapped += r.n_unmapped;
+        }
+        n_no_coor += p.n_no_coor;
+        return true;
+    }
+    size_t n_chunks() const { size_t n = 0; for (const Ref& r : refs) for (const auto& b : r.bins) n += b.second.size(); return n; }
+    size_t n_windows() const { size_t n = 0; for (const Ref& r : refs) n += r.lin.size(); return n; }
+    void serialize(std::string& o) const
+    {
+        auto p32 = [&](uint32_t v) { for (int i = 0; i < 4; i++) o.push_back((char)(v >> (8 * i))); };
+        auto p64 = [&](uint64_t v) { for (int i = 0; i < 8; i++) o.push_back((char)(v >> (8 * i))); };
+        o.assign("BAI\1", 4);
+        p32((uint32_t)refs.size());
+        for (const Ref& r : refs) {
+            if (!r.any) { p32(0); p32(0); continue; }
+            p32((uint32_t)r.bins.size() + 1);
+            for (const auto& b : r.bins) {
+                p32(b.first); p32((uint32_t)b.second.size());
+                for (const auto& c : b.second) { p64(c.first); p64(c.second); }
+            }
+            p32(37450); p32(2); p64(r.beg); p64(r.end); p64(r.n_mapped); p64(r.n_unmapped);
+            p32((uint32_t)r.lin.size());
+            uint64_t prev = r.beg;
+            for (uint64_t v : r.lin) { if (v != ~(uint64_t)0) prev = v; p64(prev); }
+        }
+        p64(n_no_coor);
+    }
+};
 // one bmbs_bam_sort call of pass 2: whole bins first .. last, or -- a bin larger than the call budget -- the records of that bin whose
 // keys lie in [k_lo, k_hi], in the bin's order; a single key that is larger than the budget on its own is cut anywhere (`skip` of its
 // records left out, `n` taken): equal keys need no sorting, their order is the bin's
@@ -947,7 +1037,7 @@ int main(int argc, char** argv)
     int device = 0, io_threads = 0, contexts = 4, parts = 1, reader_threads = 0;
     std::vector<int> devices;
     long batch = 500000;
-    bool verbose = false, unmapped_out = false, pbat = false, bam = false, print_parts = false, print_plan = false, sort_out = false;
+    bool verbose = false, unmapped_out = false, pbat = false, bam = false, print_parts = false, print_plan = false, sort_out = false, bai_out = false;
     double sort_mem_gib = 0;                     // --sort-mem: cap of the in-memory record store of --sort (0: half of the machine's memory)
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -996,10 +1086,17 @@ int main(int argc, char** argv)
         else if (a == "--sam") bam = false;
         else if (a == "--sort") sort_out = true;                      // --bam --sort: one coordinate-sorted BAM file (sorted on the device)
         else if (a == "--sort-mem") sort_mem_gib = atof(val());
+        else if (a == "--bai") bai_out = true;                        // --bam --sort --bai: <out>.bai beside the sorted file, from the same run
         else { fprintf(stderr, "bmbs_search: unsupported option %s\n", a.c_str()); return 2; }
     }
     if (sort_out && !bam) { fprintf(stderr, "bmbs_search: --sort needs --bam\n"); return 2; }
     if (sort_out && parts > 1) { fprintf(stderr, "bmbs_search: --sort writes one file (--out-parts 1)\n"); return 2; }
+    if (bai_out && !sort_out) { fprintf(stderr, "bmbs_search: --bai needs --sort\n"); return 2; }
+    if (bai_out) {
+        // the index lies beside a file: a device or a pipe has no such place
+        struct stat osb;
+        if (stat(out.c_str(), &osb) == 0 && !S_ISREG(osb.st_mode)) { fprintf(stderr, "bmbs_search: --bai needs a regular output file (-o %s is none)\n", out.c_str()); return 2; }
+    }
     if (!build_fasta.empty()) {
         // bitmapperBS --index <fasta> [--index_folder <dir>]: <fasta>.index* or <dir>/genome.index* (Index.cpp:832-938)
         std::string prefix = build_fasta;
@@ -1016,7 +1113,7 @@ int main(int argc, char** argv)
         return 0;
     }
     if (index.empty() || (seq.empty() && (seq1.empty() || seq2.empty()))) {
-        fprintf(stderr, "usage: bmbs_search --index <genome.fa> [--index_folder dir] [-t threads]\n       bmbs_search --search <index> (--seq r.fq | --seq1 a.fq --seq2 b.fq) [-o out.sam] [-e f] [--min n] [--max n] [--sensitive] [--pbat] [--unmapped_out] [--ambiguous_out] [--bam [--sort [--sort-mem GiB]]] [--mapstats f] [-t io_threads] [--out-parts n]\n");
+        fprintf(stderr, "usage: bmbs_search --index <genome.fa> [--index_folder dir] [-t threads]\n       bmbs_search --search <index> (--seq r.fq | --seq1 a.fq --seq2 b.fq) [-o out.sam] [-e f] [--min n] [--max n] [--sensitive] [--pbat] [--unmapped_out] [--ambiguous_out] [--bam [--sort [--sort-mem GiB] [--bai]]] [--mapstats f] [-t io_threads] [--out-parts n]\n");
         return 2;
     }
     if (batch < 1) batch = 1;
@@ -1109,6 +1206,12 @@ int main(int argc, char** argv)
     std::vector<std::string> chrom_names;
     size_t max_chrom = 0;
     for (int i = 0; i < view.n_chrom; i++) { chrom_names.push_back(bmbs_index_file_chrom_name(ixf, i)); max_chrom = std::max(max_chrom, chrom_names.back().size()); }
+    if (bai_out)
+        for (int i = 0; i < view.n_chrom; i++)
+            if (view.chrom_len[i] > (1ull << 29)) {
+                fprintf(stderr, "bmbs_search: --bai: sequence %s is longer than 2^29 bases: a BAI index cannot hold it (CSI is not written)\n", chrom_names[(size_t)i].c_str());
+                return 2;
+            }
     // SAM bytes a batch can need: QNAME + SEQ + QUAL come out of the text, the other columns are bounded per line
     const int L_est = (int)std::min<size_t>(1000, (est0 / 2) + (est0 / 4));
     auto sam_bound = [&](size_t text_bytes, size_t lines, int L) {
@@ -1547,6 +1650,8 @@ int main(int argc, char** argv)
     // the staging and upload of one call run beside the kernels and the download of the other.
     const double t_pass1 = now();
     size_t sort_calls = 0;
+    BaiIndex bai;
+    bai.init((size_t)view.n_chrom);
     if (sort_out && !failed) {
         Part& pt = *P_[0];
         const char* e = getenv("BMBS_SORT_CALL_BYTES");
@@ -1558,7 +1663,7 @@ int main(int argc, char** argv)
         for (const SortUnit& u : units) { max_bytes = std::max(max_bytes, u.bytes); max_n = std::max(max_n, u.n); }
         e = getenv("BMBS_SORT_SLOTS");
         const int n_slots = (int)std::max<size_t>(1, std::min<size_t>({(size_t)(e ? atoi(e) : 2), ctxs.size(), units.size(), (size_t)4}));
-        struct Slot { Pinned in, out; std::vector<uint32_t> len; size_t unit = 0; uint64_t out_bytes = 0; };
+        struct Slot { Pinned in, out; std::vector<uint32_t> len; size_t unit = 0; uint64_t out_bytes = 0; BaiPieces bai; };
         std::vector<Slot> slots((size_t)n_slots);
         if (!units.empty()) {
             // (the mapping's page-locked windows are of no use here: a call is larger than a batch)
@@ -1602,6 +1707,7 @@ int main(int argc, char** argv)
                             if (rc) { fail(bmbs_last_error(ctx)); sl->out_bytes = 0; }
                             break;
                         }
+                        if (bai_out && !failed && !sl->bai.fetch(ctx)) { fail(bmbs_last_error(ctx)); sl->out_bytes = 0; }
                         done_s.put((long)sl->unit, sl);
                     }
                 });
@@ -1613,6 +1719,7 @@ int main(int argc, char** argv)
                     if (w <= 0) { fail(std::string("write error: ") + strerror(errno)); break; }
                     done += (size_t)w;
                 }
+                if (bai_out && !failed && !bai.add(sl->bai, (uint64_t)pt.out_off)) fail("--bai: a record names a sequence the header does not have");
                 pt.out_off += (size_t)sl->out_bytes;
                 free_s.put(sl);
             }
@@ -1630,7 +1737,22 @@ int main(int argc, char** argv)
     }
     const double t_joined = now();
     for (int p = 0; p < parts; p++) { Part& pt = *P_[(size_t)p]; if (pt.alloc_end > pt.out_off && ftruncate(pt.ofd, (off_t)pt.out_off) != 0) failed = true; ::close(pt.ofd); if (p < live_parts) { pt.s1.close(); if (pe) pt.s2.close(); } }
+    // the index: written once the file is complete
+    size_t bai_bytes = 0;
+    if (bai_out && !failed) {
+        if (!P_[0]->regular) { fprintf(stderr, "bmbs_search: --bai needs a regular output file (-o %s is none)\n", out.c_str()); failed = true; }
+        else {
+            std::string ix;
+            bai.serialize(ix);
+            bai_bytes = ix.size();
+            const int fd = ::open((out + ".bai").c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+            size_t done = 0;
+            while (fd >= 0 && done < ix.size()) { const ssize_t w = ::write(fd, ix.data() + done, ix.size() - done); if (w <= 0) break; done += (size_t)w; }
+            if (fd < 0 || done < ix.size() || ::close(fd) != 0) { fprintf(stderr, "bmbs_search: cannot write %s.bai: %s\n", out.c_str(), strerror(errno)); failed = true; }
+        }
+    }
     if (failed && sort_out && P_[0]->regular) ::unlink(out.c_str());      // a sorted file is whole or absent (a device or a pipe is left alone)
+    if (failed && bai_out && P_[0]->regular) ::unlink((out + ".bai").c_str());      // ... and so is its index
     if (failed) { fprintf(stderr, "bmbs_search: failed\n"); return 1; }
     int64_t st[5];
     bmbs_stats_allreduce(ctxs.data(), (int)ctxs.size(), st);      // get_mapping_informations: the counters of every worker summed
@@ -1642,9 +1764,12 @@ int main(int argc, char** argv)
         fprintf(stderr, "[bmbs_search] records %ld  load+attach %.3fs  mapping wall %.3fs  (pipeline %.3fs; stage busy, summed over %d part(s): read + newline count %.3fs, gpu calls %.3fs over %d context(s), host format %.3fs, write %.3fs)  %d I/O threads, batch %ld, %zu device(s) x %d context(s), %d output part(s)\n",
                 total_records, t_loaded - t_start, t_end - t_loaded, t_joined - t_loaded, live_parts, t_read, t_gpu, n_ctx, t_format, t_write, io_threads, batch,
                 n_owner, contexts, parts);
-    if (verbose && sort_out)
-        fprintf(stderr, "[bmbs_search] sort: bins %zu (one of them for records without a reference), pass-2 calls %zu, store bytes %zu (%ld records), pass 1 %.3fs (mapping, binning), pass 2 %.3fs (sort, deflate, write)\n",
-                sort_store.bin.size(), sort_calls, sort_store.bytes, sort_store.records, t_pass1 - t_loaded, t_pass2 - t_pass1);
+    if (verbose && sort_out) {
+        char ixs[128] = "";
+        if (bai_out) snprintf(ixs, sizeof ixs, ", index: chunks %zu, windows %zu, %zu bytes", bai.n_chunks(), bai.n_windows(), bai_bytes);
+        fprintf(stderr, "[bmbs_search] sort: bins %zu (one of them for records without a reference), pass-2 calls %zu, store bytes %zu (%ld records), pass 1 %.3fs (mapping, binning), pass 2 %.3fs (sort, deflate, write)%s\n",
+                sort_store.bin.size(), sort_calls, sort_store.bytes, sort_store.records, t_pass1 - t_loaded, t_pass2 - t_pass1, ixs);
+    }
     if (verbose)
         fprintf(stderr, "[bmbs_search] stage idle (waiting for a batch, summed): readers %.3fs, gpu workers %.3fs, writers %.3fs\n", t_wait_r, t_wait_g, t_wait_w);
     if (verbose) {

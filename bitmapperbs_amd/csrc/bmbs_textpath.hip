@@ -2,13 +2,14 @@
 // own since round 5): FASTQ text -> line index -> read rows (bmbs_map_*_fastq, bmbs_map_*_text), BGZF blocks inflated on the device
 // (bmbs_inflate_bgzf, bmbs_text_open_bgzf / bmbs_text_map_open), records -> SAM text or BAM records in BGZF blocks.  The mapping in
 // between is bmbs_api.hip's (lane_enqueue / lane_settle).  Kernels: bmbs_text.hip, bmbs_bam.hip, bmbs_inflate.hip, k_bamsort.hip (the
-// coordinate sort of BAM records: BMBS_TEXT_BAM_SORTED, bmbs_bam_sort).
+// coordinate sort of BAM records: BMBS_TEXT_BAM_SORTED, bmbs_bam_sort), k_bai.hip (the .bai pieces of a sorted call: bmbs_bam_sort_index).
 #include "bmbs_host.h"
 #define DEVI __device__ __forceinline__
 #include "bmbs_text.hip"
 #include "bmbs_bam.hip"
 #include "bmbs_inflate.hip"
 #include "k_bamsort.hip"
+#include "k_bai.hip"
 
 // the constants the kernels of this file read: x^(2^n) mod P of CRC-32 for the BGZF blocks' CRCs (bmbs_bytes.h: crc_x8n); per device
 void textpath_device_init(Lane* c)
@@ -281,6 +282,7 @@ static TxwPlan txw_plan(bool pe, u64 text_bytes, u64 n_lines, int hb)
 static int bgzf_deflate(Lane* c, const char* raw, const u64* total_ptr, u64 raw_total, u64* ztotal)
 {
     const u64 nb = (raw_total + BGZF_IN - 1) / BGZF_IN;
+    c->bai_n = -1;                                        // (bam_off is rewritten: what bmbs_bam_sort_index would read)
     ENS(c, c->bam_slots, nb * (u64)BGZF_SLOT);
     ENS(c, c->bam_slot_len, nb * 4 + 64); ENS(c, c->bam_off, (nb + 1) * 8 + 64);
     const size_t lds = (size_t)BGZF_THREADS * BGZF_PSTRIDE * 4;                      // the block's bytes (padded segments)
@@ -315,6 +317,7 @@ static int bgzf_collect(Lane* c, u64 raw_total, u64 ztotal)
 static int bam_sort_device(Lane* c, const char* raw, const u64* off, const u32* len, u64 n, u64 total, bool skip_empty, u64* n_records)
 {
     static const bool tiny = getenv("BMBS_BSG_TINY") != nullptr;
+    c->bai_n = -1;                                        // (bs_sorted / bs_soff are rewritten: what bmbs_bam_sort_index would read)
     ENS(c, c->bs_key, n * 8 + 64); ENS(c, c->bs_key2, n * 8 + 64); ENS(c, c->bs_idx, n * 4 + 64); ENS(c, c->bs_idx2, n * 4 + 64);
     ENS(c, c->bs_slen, n * 4 + 64); ENS(c, c->bs_soff, (n + 1) * 8 + 64); ENS(c, c->bs_sorted, total + 256);
     u32* const info = c->tx_info.as<u32>() + 8;
@@ -329,6 +332,7 @@ static int bam_sort_device(Lane* c, const char* raw, const u64* off, const u32* 
         return BMBS_EINVAL;
     }
     if (n_records) *n_records = n - c->h_info[10];
+    c->bai_ref_max = c->h_info[9];
     // the key bits that can be set: 33 of position and strand, and those of the largest reference index (-1 is all ones: it stays last
     // under any number of low bits, because no other index has them all set)
     int ref_bits = 1;
@@ -827,6 +831,7 @@ static int lane_text_sorted_index(Lane* c, uint64_t* key, uint32_t* len, int64_t
 static int lane_bam_sort(Lane* c, const char* records, uint64_t bytes, const uint32_t* len, int64_t n_in, int32_t flags, char* out, uint64_t out_cap, uint64_t* out_bytes)
 {
     if (out_bytes) *out_bytes = 0;
+    c->bai_n = -1;                                        // bmbs_bam_sort_index describes the LAST call
     if (n_in < 0 || n_in >= (1ll << 31) || (flags & ~BMBS_BAMSORT_RAW)) { c->err = "bam sort: bad argument"; return BMBS_EINVAL; }
     if (n_in && (!records || !len)) { c->err = "bam sort: NULL buffer"; return BMBS_EINVAL; }
     const u64 n = (u64)n_in;
@@ -866,12 +871,127 @@ static int lane_bam_sort(Lane* c, const char* records, uint64_t bytes, const uin
     if (ztotal > out_cap) { c->err = "bam sort: the output buffer is too small (out_bytes tells what is needed)"; return BMBS_ENOMEM; }
     rc = bgzf_collect(c, bytes, ztotal);
     if (rc) return rc;
-    return download_locked(c, out, c->sam_out.as<char>(), ztotal, c->stream, nullptr);
+    rc = download_locked(c, out, c->sam_out.as<char>(), ztotal, c->stream, nullptr);
+    if (rc) return rc;
+    c->bai_n = (int64_t)n; c->bai_bytes = bytes; c->bai_z = ztotal; c->bai_done = false;      // (bmbs_bam_sort_index: computed when asked for)
+    return BMBS_OK;
+}
+
+// ---- the .bai pieces of that call (k_bai.hip) from bs_sorted / bs_soff / bam_off -> c->bai_out, counts in c->bai_cnt ------------------------
+static int bai_compute(Lane* c)
+{
+    const u64 n = (u64)c->bai_n, total = c->bai_bytes, nb = (total + BGZF_IN - 1) / BGZF_IN, nw = (n + 63) / 64;
+    const u64 R = (u64)c->bai_ref_max + 1;
+    if (R > (1ull << 24)) { c->err = "bam sort index: reference index " + std::to_string(c->bai_ref_max) + " is beyond the 2^24 sequences this call keeps counts for"; return BMBS_EINVAL; }
+    u64 at = 0;
+    auto take = [&](u64 bytes) { const u64 a = at; at += (bytes + 255) & ~255ull; return a; };
+    const u64 o_rb = take(n * 8), o_rw = take(n * 4), o_wc = take(n * 4), o_woff = take((n + 1) * 8), o_wave = take(nw * 4), o_hoff = take((nw + 1) * 8),
+              o_cnt = take(R * 8), o_has = take(R * 4), o_first = take(R * 4), o_last = take(R * 4), o_rlist = take(R * 4);
+    ENS(c, c->bai_a, at + 64);
+    char* const A = c->bai_a.as<char>();
+    u64* const rb = reinterpret_cast<u64*>(A + o_rb); u64* const woff = reinterpret_cast<u64*>(A + o_woff); u64* const hoff = reinterpret_cast<u64*>(A + o_hoff);
+    u32* const rw = reinterpret_cast<u32*>(A + o_rw); u32* const wc = reinterpret_cast<u32*>(A + o_wc); u32* const wave = reinterpret_cast<u32*>(A + o_wave);
+    u32* const cnt = reinterpret_cast<u32*>(A + o_cnt); u32* const has = reinterpret_cast<u32*>(A + o_has); u32* const first = reinterpret_cast<u32*>(A + o_first);
+    u32* const last = reinterpret_cast<u32*>(A + o_last); u32* const rlist = reinterpret_cast<u32*>(A + o_rlist);
+    u32* const info = c->tx_info.as<u32>() + 8;
+    u64* const tot = c->totals.as<u64>();
+    HIPCHK(c, hipMemsetAsync(info, 0, 32, c->stream));
+    HIPCHK(c, hipMemsetAsync(cnt, 0, o_first - o_cnt, c->stream));                          // cnt and has
+    const BaiVoff v = {c->bs_soff.as<u64>(), c->bam_off.as<u64>(), total, nb};
+    hipLaunchKernelGGL(k_bai_records, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->bs_sorted.as<char>(), c->bs_soff.as<u64>(), (long)n, (u32)R, rb, rw, cnt, info);
+    hipLaunchKernelGGL(k_bai_heads, dim3(nblk(n, 256)), dim3(256), 0, c->stream, rb, rw, (long)n, (u32)R, wave, wc, has, first, last);
+    int rc = scan_u32(c, wave, nw, hoff, 25);
+    if (rc) return rc;
+    rc = scan_u32(c, wc, n, woff, 26);
+    if (rc) return rc;
+    rc = scan_u32(c, has, R, nullptr, 27, rlist);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->h_info, info, 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_info + 16, tot + 25, 24, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->h_info[1]) { c->err = "bam sort index: the read name and CIGAR of record " + std::to_string(~c->h_info[1]) + " (in sorted order) do not fit its length"; return BMBS_EINVAL; }
+    if (c->h_info[0]) {
+        c->err = "bam sort index: record " + std::to_string(~c->h_info[0]) + " (in sorted order) ends behind position 2^29: a BAI index cannot hold it (CSI is not written)";
+        return BMBS_EINVAL;
+    }
+    const u64 nnc = c->h_info[2];
+    const u64 m = reinterpret_cast<const u64*>(c->h_info + 16)[0], T = reinterpret_cast<const u64*>(c->h_info + 16)[1], n_ref = reinterpret_cast<const u64*>(c->h_info + 16)[2];
+    const u64 mr = m - (nnc ? 1 : 0);                    // (the first record without a reference only ends the last run)
+    at = 0;
+    const u64 o_hj = take((m + 1) * 4), o_ckey = take(m * 8), o_ckey2 = take(m * 8), o_cidx = take(m * 4), o_cidx2 = take(m * 4), o_be = take(m * 16),
+              o_wkey = take(T * 8), o_wkey2 = take(T * 8), o_wval = take(T * 4), o_wval2 = take(T * 4), o_wflag = take(T * 4), o_wlist = take(T * 4);
+    ENS(c, c->bai_b, at + 64);
+    char* const B = c->bai_b.as<char>();
+    u32* const hj = reinterpret_cast<u32*>(B + o_hj); u64* const ckey = reinterpret_cast<u64*>(B + o_ckey); u64* const ckey2 = reinterpret_cast<u64*>(B + o_ckey2);
+    u32* const cidx = reinterpret_cast<u32*>(B + o_cidx); u32* const cidx2 = reinterpret_cast<u32*>(B + o_cidx2); u64* const be = reinterpret_cast<u64*>(B + o_be);
+    u64* const wkey = reinterpret_cast<u64*>(B + o_wkey); u64* const wkey2 = reinterpret_cast<u64*>(B + o_wkey2); u32* const wval = reinterpret_cast<u32*>(B + o_wval);
+    u32* const wval2 = reinterpret_cast<u32*>(B + o_wval2); u32* const wflag = reinterpret_cast<u32*>(B + o_wflag); u32* const wlist = reinterpret_cast<u32*>(B + o_wlist);
+    at = 0;
+    c->bai_at[0] = take(mr * sizeof(bmbs_bai_chunk)); c->bai_at[1] = take(T * sizeof(bmbs_bai_win)); c->bai_at[2] = take(n_ref * sizeof(bmbs_bai_ref));
+    ENS(c, c->bai_out, at + 64);
+    char* const O = c->bai_out.as<char>();
+    // the key bits that can be set: those of the largest reference index above the bin's 16 / the window's 15 (as in bam_sort_device)
+    int ref_bits = 1;
+    while (ref_bits < 32 && R >> ref_bits) ref_bits++;
+    hipLaunchKernelGGL(k_bai_emit, dim3(nblk(n, 256)), dim3(256), 0, c->stream, rb, rw, (long)n, hoff, woff, hj, wkey, wval);
+    if (mr) {
+        hipLaunchKernelGGL(k_bai_chunks, dim3(nblk(m, 256)), dim3(256), 0, c->stream, hj, (long)m, (long)n, rb, v, ckey, cidx, be);
+        size_t tmp = 0;
+        if (rocprim::radix_sort_pairs(nullptr, tmp, ckey, ckey2, cidx, cidx2, (size_t)mr, 0u, (unsigned)(16 + ref_bits), c->stream) != hipSuccess) { c->err = "bam sort index: radix_sort_pairs (size query) failed"; return BMBS_ENODEV; }
+        ENS(c, c->bs_tmp, tmp + 64);
+        if (rocprim::radix_sort_pairs(c->bs_tmp.p, tmp, ckey, ckey2, cidx, cidx2, (size_t)mr, 0u, (unsigned)(16 + ref_bits), c->stream) != hipSuccess) { c->err = "bam sort index: radix_sort_pairs failed"; return BMBS_ENODEV; }
+        hipLaunchKernelGGL(k_bai_chunk_out, dim3(nblk(mr, 256)), dim3(256), 0, c->stream, ckey2, cidx2, be, (long)mr, reinterpret_cast<bmbs_bai_chunk*>(O + c->bai_at[0]));
+    }
+    u64 n_win = 0;
+    if (T) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));        // (bs_tmp may be replaced: the chunk sort has to be through with it)
+        size_t tmp = 0;
+        if (rocprim::radix_sort_pairs(nullptr, tmp, wkey, wkey2, wval, wval2, (size_t)T, 0u, (unsigned)(15 + ref_bits), c->stream) != hipSuccess) { c->err = "bam sort index: radix_sort_pairs (size query) failed"; return BMBS_ENODEV; }
+        ENS(c, c->bs_tmp, tmp + 64);
+        if (rocprim::radix_sort_pairs(c->bs_tmp.p, tmp, wkey, wkey2, wval, wval2, (size_t)T, 0u, (unsigned)(15 + ref_bits), c->stream) != hipSuccess) { c->err = "bam sort index: radix_sort_pairs failed"; return BMBS_ENODEV; }
+        hipLaunchKernelGGL(k_bai_win_flag, dim3(nblk(T, 256)), dim3(256), 0, c->stream, wkey2, (long)T, wflag);
+        rc = scan_u32(c, wflag, T, nullptr, 28, wlist);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_bai_win_out, dim3(nblk(T, 256)), dim3(256), 0, c->stream, wlist, tot + 28, wkey2, wval2, v, reinterpret_cast<bmbs_bai_win*>(O + c->bai_at[1]));
+        HIPCHK(c, hipMemcpyAsync(c->h_info + 16, tot + 28, 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (n_ref) hipLaunchKernelGGL(k_bai_ref_out, dim3(nblk(n_ref, 256)), dim3(256), 0, c->stream, rlist, (long)n_ref, first, last, cnt, v, reinterpret_cast<bmbs_bai_ref*>(O + c->bai_at[2]));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    if (T) n_win = reinterpret_cast<const u64*>(c->h_info + 16)[0];
+    c->bai_cnt[0] = mr; c->bai_cnt[1] = n_win; c->bai_cnt[2] = n_ref; c->bai_cnt[3] = nnc;
+    c->bai_done = true;
+    return BMBS_OK;
+}
+
+static int lane_bam_sort_index(Lane* c, bmbs_bai_chunk* chunk, int64_t chunk_cap, int64_t* n_chunk, bmbs_bai_win* win, int64_t win_cap, int64_t* n_win,
+                               bmbs_bai_ref* ref, int64_t ref_cap, int64_t* n_ref, uint64_t* n_no_coor)
+{
+    if (!n_chunk || !n_win || !n_ref || !n_no_coor) { c->err = "bam sort index: NULL argument"; return BMBS_EINVAL; }
+    *n_chunk = *n_win = *n_ref = 0; *n_no_coor = 0;
+    if (c->bai_n < 0) {
+        c->err = "bam sort index: the context's last bmbs_bam_sort call returned no BGZF blocks (none yet, BMBS_BAMSORT_RAW, no records, or it failed), or another call has used its buffers since";
+        return BMBS_ESTATE;
+    }
+    HIPCHK(c, hipSetDevice(c->dev));
+    if (!c->bai_done) { const int rc = bai_compute(c); if (rc) return rc; }
+    *n_chunk = (int64_t)c->bai_cnt[0]; *n_win = (int64_t)c->bai_cnt[1]; *n_ref = (int64_t)c->bai_cnt[2]; *n_no_coor = c->bai_cnt[3];
+    if (*n_chunk > chunk_cap || *n_win > win_cap || *n_ref > ref_cap) { c->err = "bam sort index: an array is too small (n_chunk, n_win and n_ref tell what is needed)"; return BMBS_ENOMEM; }
+    if ((*n_chunk && !chunk) || (*n_win && !win) || (*n_ref && !ref)) { c->err = "bam sort index: NULL argument"; return BMBS_EINVAL; }
+    const char* const O = c->bai_out.as<char>();
+    if (*n_chunk) HIPCHK(c, hipMemcpyAsync(chunk, O + c->bai_at[0], (size_t)*n_chunk * sizeof(bmbs_bai_chunk), hipMemcpyDeviceToHost, c->stream));
+    if (*n_win) HIPCHK(c, hipMemcpyAsync(win, O + c->bai_at[1], (size_t)*n_win * sizeof(bmbs_bai_win), hipMemcpyDeviceToHost, c->stream));
+    if (*n_ref) HIPCHK(c, hipMemcpyAsync(ref, O + c->bai_at[2], (size_t)*n_ref * sizeof(bmbs_bai_ref), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BMBS_OK;
 }
 
 extern "C" int bmbs_text_sorted_index(bmbs_ctx* X, uint64_t* key, uint32_t* len, int64_t cap, int64_t* n) { ON_LANE0(lane_text_sorted_index(c, key, len, cap, n)); }
 extern "C" int bmbs_bam_sort(bmbs_ctx* X, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, int32_t flags, char* out, uint64_t out_cap, uint64_t* out_bytes)
 { ON_LANE0(lane_bam_sort(c, records, bytes, len, n, flags, out, out_cap, out_bytes)); }
+extern "C" int bmbs_bam_sort_index(bmbs_ctx* X, bmbs_bai_chunk* chunk, int64_t chunk_cap, int64_t* n_chunk, bmbs_bai_win* win, int64_t win_cap, int64_t* n_win,
+                                   bmbs_bai_ref* ref, int64_t ref_cap, int64_t* n_ref, uint64_t* n_no_coor)
+{ ON_LANE0(lane_bam_sort_index(c, chunk, chunk_cap, n_chunk, win, win_cap, n_win, ref, ref_cap, n_ref, n_no_coor)); }
 
 extern "C" int bmbs_sam_refs(bmbs_ctx* X, const char* const* names, int32_t n_names) { ON_LANE0(lane_sam_refs(c, names, n_names)); }
 extern "C" int bmbs_map_se_text(bmbs_ctx* X, const char* text, uint64_t text_bytes, int64_t n_records, int32_t flags, char* sam, uint64_t sam_cap,

@@ -362,6 +362,20 @@ class Mapper:
         self._chk(rc)
         return out[:used.value].tobytes()
 
+    def bam_sort_index(self):
+        """the .bai pieces of the last bam_sort() call that returned BGZF blocks (bmbs_bam_sort_index), computed on the device:
+        (chunks BAI_CHUNK_DTYPE ordered by (ref, bin, beg), windows BAI_WIN_DTYPE ordered by (ref, win), references BAI_REF_DTYPE,
+        n_no_coor); virtual offsets are relative to the first byte that call returned"""
+        nc = C.c_int64(0); nw = C.c_int64(0); nr = C.c_int64(0); nn = C.c_uint64(0)
+        rc = self._lib.bmbs_bam_sort_index(self._ctx, None, 0, C.byref(nc), None, 0, C.byref(nw), None, 0, C.byref(nr), C.byref(nn))
+        if rc and rc != -12:
+            self._chk(rc)
+        ch = np.zeros(max(1, nc.value), dtype=capi.BAI_CHUNK_DTYPE); wi = np.zeros(max(1, nw.value), dtype=capi.BAI_WIN_DTYPE)
+        rf = np.zeros(max(1, nr.value), dtype=capi.BAI_REF_DTYPE)
+        self._chk(self._lib.bmbs_bam_sort_index(self._ctx, capi.ptr(ch), nc.value, C.byref(nc), capi.ptr(wi), nw.value, C.byref(nw), capi.ptr(rf), nr.value,
+                                                C.byref(nr), C.byref(nn)))
+        return ch[:nc.value], wi[:nw.value], rf[:nr.value], int(nn.value)
+
     def sync(self):
         self._chk(self._lib.bmbs_sync(self._ctx))
 

@@ -385,6 +385,30 @@ int bmbs_text_sorted_index(bmbs_ctx*, uint64_t* key, uint32_t* len, int64_t cap,
 int bmbs_bam_sort(bmbs_ctx*, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, int32_t flags, char* out,
                   uint64_t out_cap, uint64_t* out_bytes);
 
+/* ---- the .bai index of a sorted BAM (SAM specification section 5.2; csrc/k_bai.hip) -----------------------------------------------------
+ * bmbs_bam_sort_index describes the output of the context's last successful bmbs_bam_sort call that returned BGZF blocks, computed on
+ * the device from the buffers that call left there (bmbs_bam_sort itself does nothing for it).  BMBS_ESTATE: there was no such call,
+ * it used BMBS_BAMSORT_RAW, or another call on the context has used the buffers since.  BMBS_ENOMEM when a cap is too small; *n_chunk,
+ * *n_win and *n_ref are set then too (caps of 0: the size query).
+ * Virtual offsets are relative to the first byte of that call's `out`: the byte at offset u of the uncompressed stream is
+ * (compressed offset of block u / 0xff00) << 16 | u % 0xff00; u = the stream's size gives (compressed bytes of the call) << 16, the
+ * first byte behind the call.  A driver that has put the call's blocks at file offset B adds B << 16 to every offset (exact).
+ * Per record, in sorted order: beg = pos (a pos below 0 counts as 0, as in hts_idx_push), end = pos + the reference length of its
+ * CIGAR (M D N = X), pos + 1 when flag 4 is set, n_cigar_op is 0 or that length is 0; bin = reg2bin(beg, end) (section 5.3).
+ * Records with refID -1 are counted in *n_no_coor and appear nowhere else.  A record with refID >= 0 and end > 2^29 gives BMBS_EINVAL
+ * (bmbs_last_error names it: BAI cannot hold it; CSI is not written).
+ *   chunk  one entry per maximal run of consecutive records with equal (ref, bin), mapped or not: beg = the offset of the run's first
+ *          record, end = that of the record behind the run (or the first byte behind the call); ordered by (ref, bin, beg)
+ *   win    one entry per (ref, 16 kb window) that a MAPPED record overlaps (windows beg >> 14 .. (end - 1) >> 14): off = the smallest
+ *          offset among those records; ordered by (ref, win); no fill
+ *   ref    one entry per refID >= 0 that has records, ordered by ref: beg / end = the offset of its first record / just behind its
+ *          last, n_mapped / n_unmapped = its records by flag 4                                                                    */
+typedef struct bmbs_bai_chunk { int32_t ref; uint32_t bin; uint64_t beg, end; } bmbs_bai_chunk;
+typedef struct bmbs_bai_win   { int32_t ref; uint32_t win; uint64_t off; } bmbs_bai_win;
+typedef struct bmbs_bai_ref   { int32_t ref; uint32_t pad; uint64_t beg, end, n_mapped, n_unmapped; } bmbs_bai_ref;
+int bmbs_bam_sort_index(bmbs_ctx*, bmbs_bai_chunk* chunk, int64_t chunk_cap, int64_t* n_chunk, bmbs_bai_win* win, int64_t win_cap,
+                        int64_t* n_win, bmbs_bai_ref* ref, int64_t ref_cap, int64_t* n_ref, uint64_t* n_no_coor);
+
 /* a21: per-ctx counters of the batches mapped so far = {reads, unique, ambiguous, mapped bases,
  * error bases} (Schema.cpp:25141-25146); bmbs_stats_allreduce sums them over the ctxs one process
  * drives (get_mapping_informations, Schema.cpp:451-476).  Multi-process jobs sum the five int64 with

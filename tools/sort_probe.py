@@ -7,8 +7,10 @@ bytes per read (down in pass 1, up in pass 2), c = compressed bytes per read, bo
 own under `rocprofv3 --kernel-trace --stats`: k_bam_gather's bytes/s (2 x record bytes over its kernel time) beside
 k_line_write<true>'s (same records, same count) in the same trace, and the pass-2 kernels' share.  Every GPU step runs under its
 own `timeout`; the script stops at the first failure.
+--bai: a third leg, `--bam --sort --bai`, alternating with the other two -- its walls beside the sorted runs', the size of the index,
+and the k_bai_* rows of the kernel trace (which then is a --bai run) beside k_bam_gather.
 
-  python tools/sort_probe.py [--reads 4000000] [--loop 8] [--pe] [--runs 3] [--out profiles/sorted_bam_probe.txt]
+  python tools/sort_probe.py [--reads 4000000] [--loop 8] [--pe] [--runs 3] [--bai] [--out profiles/sorted_bam_probe.txt]
 """
 import argparse
 import csv
@@ -40,6 +42,9 @@ def verbose_numbers(err):
     m = re.search(r"sort: bins (\d+) .*pass-2 calls (\d+), store bytes (\d+) \((\d+) records\), pass 1 ([\d.]+)s .*pass 2 ([\d.]+)s", err)
     if m:
         out.update(bins=int(m.group(1)), calls=int(m.group(2)), store=int(m.group(3)), records=int(m.group(4)), pass1=float(m.group(5)), pass2=float(m.group(6)))
+    m = re.search(r"index: (chunks \d+, windows \d+, \d+ bytes)", err)
+    if m:
+        out["index"] = m.group(1)
     m = re.search(r"busy fractions of the mapping wall: link up ([\d.]+), link down ([\d.]+)", err)
     if m:
         out["link_up"], out["link_down"] = float(m.group(1)), float(m.group(2))
@@ -56,6 +61,7 @@ def main():
     ap.add_argument("--pe", action="store_true")
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1_000_000)
+    ap.add_argument("--bai", action="store_true", help="also measure --bam --sort --bai (the index written in the same run)")
     ap.add_argument("--driver-args", default="")
     ap.add_argument("--workdir", default=os.environ.get("BMBS_BENCH_DIR", "/tmp/bmbs_bench"))
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sorted_bam_probe.txt"))
@@ -87,11 +93,16 @@ def main():
     drv = os.path.join(ROOT, "bitmapperbs_amd", "bmbs_search")
     base = [drv, "--search", fa] + in_args + ["-e", str(args.e), "--bam", "--unmapped_out", "--batch", str(args.batch), "--loop-input", str(args.loop), "--verbose"] + args.driver_args.split()
     out_u = os.path.join(wd, "sortp_u.bam"); out_s = os.path.join(wd, "sortp_s.bam")
+    out_b = os.path.join(wd, "sortp_b.bam")
     runs = {"bam": [], "sort": []}
+    legs = [("bam", out_u, []), ("sort", out_s, ["--sort"])]
+    if args.bai:
+        runs["bai"] = []
+        legs.append(("bai", out_b, ["--sort", "--bai"]))
     size = {}
     step(base + ["-o", out_u], 600)                     # warm-up: page cache, index files
     for _ in range(max(3, args.runs)):
-        for kind, out, extra in (("bam", out_u, []), ("sort", out_s, ["--sort"])):
+        for kind, out, extra in legs:
             if os.path.exists(out):
                 os.unlink(out)
             p = step(base + extra + ["-o", out], 600)
@@ -104,11 +115,12 @@ def main():
     say("sort_probe: %d %s of %d bp x %d passes over the file = %d records per run, genome %d bp, batch %d, %s"
         % (args.reads, "pairs" if args.pe else "SE reads", L, args.loop, n_reads, args.genome, args.batch, " ".join(base[3:])))
     med = {}
-    for kind in ("bam", "sort"):
+    label = {"bam": "--bam", "sort": "--bam --sort", "bai": "--bam --sort --bai"}
+    for kind in runs:
         w = [r["wall"] for r in runs[kind]]
         med[kind] = statistics.median(w)
-        say("%-10s mapping wall s: %s   median %.3f  spread (max - min) %.3f   %.1f M records/s at the median   file %d bytes"
-            % ("--bam" + (" --sort" if kind == "sort" else ""), " ".join("%.3f" % x for x in w), med[kind], max(w) - min(w), n_reads / med[kind] / 1e6, size[kind]))
+        say("%-18s mapping wall s: %s   median %.3f  spread (max - min) %.3f   %.1f M records/s at the median   file %d bytes"
+            % (label[kind], " ".join("%.3f" % x for x in w), med[kind], max(w) - min(w), n_reads / med[kind] / 1e6, size[kind]))
     last = runs["sort"][-1]
     say("--sort: bins %d, pass-2 calls %d, store %d bytes, pass 1 %s s, pass 2 %s s (each run)" % (
         last["bins"], last["calls"], last["store"], " ".join("%.3f" % r["pass1"] for r in runs["sort"]), " ".join("%.3f" % r["pass2"] for r in runs["sort"])))
@@ -123,12 +135,17 @@ def main():
         % (ratio, bound, spread))
     say("link busy fractions (per device), last runs: --bam up %.3f down %.3f; --bam --sort up %.3f down %.3f (pass 1 only: the text calls' copies)"
         % (runs["bam"][-1].get("link_up", 0), runs["bam"][-1].get("link_down", 0), last.get("link_up", 0), last.get("link_down", 0)))
+    if args.bai:
+        sw = [r["wall"] for r in runs["sort"]]
+        say("--bai: index %d bytes (%s) beside a file of %d; median wall %.3f s against %.3f s without it = %+.3f s; spread (max - min) of the sorted runs %.3f s; pass 2 %s s"
+            % (os.path.getsize(out_b + ".bai"), runs["bai"][-1].get("index", "?"), size["bai"], med["bai"], med["sort"], med["bai"] - med["sort"], max(sw) - min(sw),
+               " ".join("%.3f" % r["pass2"] for r in runs["bai"])))
     # ---- one run of its own under the kernel trace
     tr = os.path.join(wd, "sortp_trace")
     shutil.rmtree(tr, ignore_errors=True)
     if os.path.exists(out_s):
         os.unlink(out_s)
-    step(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tr, "--"] + base + ["--sort", "-o", out_s], 900)
+    step(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tr, "--"] + base + ["--sort"] + (["--bai"] if args.bai else []) + ["-o", out_s], 900)
     f = glob.glob(os.path.join(tr, "**", "*kernel_stats.csv"), recursive=True)
     if f:
         rows = list(csv.DictReader(open(f[0])))
@@ -154,6 +171,12 @@ def main():
             t = total_ns(lambda n: name in n.lower() if name in ("radix", "onesweep") else name in n)
             if t:
                 say("  %-14s %.2f ms" % (name, t / 1e6))
+        if args.bai:
+            for r in rows:
+                if "k_bai_" in r["Name"]:
+                    say("  %-14s %.3f ms in %s calls" % (r["Name"].split("(")[0], int(r["TotalDurationNs"]) / 1e6, r["Calls"]))
+            say("  k_bai_* together %.3f ms beside k_bam_gather's %.2f ms (the index passes read the fixed fields and the CIGAR of each record, not the record)"
+                % (total_ns(lambda n: "k_bai_" in n) / 1e6, g / 1e6))
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as o:
         o.write("\n".join(lines) + "\n")
