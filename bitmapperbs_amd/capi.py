@@ -25,6 +25,7 @@ SYMBOLS = [
     "bmbs_max_cigar_ops", "bmbs_host_prefault", "bmbs_reserve", "bmbs_host_alloc_kind", "bmbs_retries", "bmbs_text_times", "bmbs_pack_rows", "bmbs_map_se_packed", "bmbs_map_pe_packed", "bmbs_sam_refs", "bmbs_map_se_text", "bmbs_map_pe_text", "bmbs_profile_total", "bmbs_profile_reset", "bmbs_inflate_bgzf", "bmbs_debug_huff_lengths", "bmbs_text_open_bgzf", "bmbs_text_map_open",
     "bmbs_qual_classes", "bmbs_pack_quals", "bmbs_map_se_packedq", "bmbs_map_pe_packedq",
     "bmbs_text_sorted_index", "bmbs_bam_sort", "bmbs_bam_sort_index",
+    "bmbs_bam_dup_sigs", "bmbs_text_sorted_dup", "bmbs_dup_select",
 ]
 
 
@@ -66,6 +67,11 @@ BAI_CHUNK_DTYPE = np.dtype([("ref", "<i4"), ("bin", "<u4"), ("beg", "<u8"), ("en
 BAI_WIN_DTYPE = np.dtype([("ref", "<i4"), ("win", "<u4"), ("off", "<u8")])
 BAI_REF_DTYPE = np.dtype([("ref", "<i4"), ("pad", "<u4"), ("beg", "<u8"), ("end", "<u8"), ("n_mapped", "<u8"), ("n_unmapped", "<u8")])
 assert (BAI_CHUNK_DTYPE.itemsize, BAI_WIN_DTYPE.itemsize, BAI_REF_DTYPE.itemsize) == (24, 16, 40)
+
+# numpy view of bmbs_dup_sig (duplicate marking: bmbs_bam_dup_sigs / bmbs_text_sorted_dup / bmbs_dup_select)
+DUP_SIG_DTYPE = np.dtype([("ref_lo", "<i4"), ("pos_lo", "<i4"), ("ref_hi", "<i4"), ("pos_hi", "<i4"), ("orient", "<u4"), ("score", "<u4")])
+assert DUP_SIG_DTYPE.itemsize == 24
+DUP_NONE = 0x80000000        # in orient: the template has no signature
 
 ST_UNMAPPED, ST_UNIQUE, ST_AMBIG, ST_OFFEND = 0, 1, 2, 3
 
@@ -188,6 +194,13 @@ def lib() -> C.CDLL:
     if hasattr(L, "bmbs_bam_sort_index"):                # (the .bai pieces of the last bmbs_bam_sort call)
         L.bmbs_bam_sort_index.argtypes = [vp, vp, i64, C.POINTER(i64), vp, i64, C.POINTER(i64), vp, i64, C.POINTER(i64), C.POINTER(u64)]
         L.bmbs_bam_sort_index.restype = C.c_int
+    if hasattr(L, "bmbs_dup_select"):                    # (duplicate marking; BMBS_LIB may name an older build, as above)
+        L.bmbs_bam_dup_sigs.argtypes = [vp, vp, u64, vp, i64, i32, vp, i64, C.POINTER(i64)]
+        L.bmbs_bam_dup_sigs.restype = C.c_int
+        L.bmbs_text_sorted_dup.argtypes = [vp, vp, i64, C.POINTER(i64), vp, i64, C.POINTER(i64)]
+        L.bmbs_text_sorted_dup.restype = C.c_int
+        L.bmbs_dup_select.argtypes = [vp, vp, i64, vp, C.POINTER(i64)]
+        L.bmbs_dup_select.restype = C.c_int
     L.bmbs_map_pe_text.argtypes = [vp, vp, u64, vp, u64, i64, i32, vp, u64, C.POINTER(u64), C.POINTER(i64)]
     L.bmbs_map_pe_text.restype = C.c_int
     L.bmbs_retries.argtypes = [vp]
@@ -213,7 +226,7 @@ def lib() -> C.CDLL:
 
 
 LIB_SRCS = ("bmbs_api.hip", "bmbs_kernels.hip", "k_index.hip", "k_rows.hip", "k_qualpack.hip", "k_attach.hip", "k_scan.hip", "k_seed.hip", "k_vote.hip", "k_filter.hip", "k_reduce.hip", "k_align.hip", "k_finalize.hip", "k_pe_fast.hip", "k_pe_sensitive.hip",
-            "bmbs_textpath.hip", "bmbs_text.hip", "bmbs_bam.hip", "bmbs_inflate.hip", "k_bamsort.hip", "k_bai.hip", "bmbs_bytes.h", "bmbs_host.h", "bmbs_dev.h", "bmbs_sort.h", "../../include/bmbs.h",
+            "bmbs_textpath.hip", "bmbs_text.hip", "bmbs_bam.hip", "bmbs_inflate.hip", "k_bamsort.hip", "k_bai.hip", "k_markdup.hip", "bmbs_bytes.h", "bmbs_host.h", "bmbs_dev.h", "bmbs_sort.h", "../../include/bmbs.h",
             "index_io.cpp", "index_io.h", "index_build_gpu.hip", "build_id.cpp")
 
 

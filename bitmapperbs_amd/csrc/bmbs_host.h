@@ -209,6 +209,14 @@ struct Lane {
     u64 bai_bytes = 0, bai_z = 0, bai_cnt[4] = {0, 0, 0, 0}, bai_at[3] = {0, 0, 0};
     u32 bai_ref_max = 0;
     bool bai_done = false;
+    // duplicate marking (k_markdup.hip): the records of bmbs_bam_dup_sigs as uploaded with their lengths and offsets, the signatures, keys /
+    // entry numbers before and behind a pair sort, the marks, the templates of a sorted text call's records.  dup_n2 = output lines of the
+    // last BMBS_TEXT_BAM_SORTED call (-1: none, or bam_raw / sam_off / sam_len / bs_idx2 have been written since), dup_pe: they are pairs;
+    // dup_done: dp_sig / dp_tmpl hold that call's signatures (bmbs_text_sorted_dup: computed when asked for, kept for the call that
+    // follows a size query)
+    DevBuf dp_in, dp_len, dp_off, dp_sig, dp_key, dp_key2, dp_idx, dp_idx2, dp_dup, dp_tmpl;
+    int64_t dup_n2 = -1;
+    bool dup_pe = false, dup_done = false;
     DevBuf z_comp, z_off, z_text, z_err, z_nl, z_comp2, z_off2, z_err2;         // bmbs_inflate_bgzf; (…2: mate 2 of bmbs_text_open_bgzf)
     struct OpenText { bool valid = false, pe = false; u64 bytes1 = 0, bytes2 = 0; int64_t n = 0; } open_text;      // between bmbs_text_open_bgzf and bmbs_text_map_open
     u32* h_info = nullptr;                              // page-locked: 8 info words + 4 totals of the text path

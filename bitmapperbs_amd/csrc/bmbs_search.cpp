@@ -14,6 +14,8 @@
 //          <out>.part000 ... concurrently; `cat` of the parts in order == the one-file output), --verbose,
 //          --bam --sort [--sort-mem GiB] (ONE coordinate-sorted BAM: its records are the stable sort, by reference / position /
 //          strand, of the records --bam writes; sorted on the device, see "--bam --sort" below; needs --out-parts 1)
+//          --bam --sort --markdup (PCR duplicates get flag 0x400 in that file: Picard's pair-level rule, decided on the device, see
+//          "--markdup" below; nothing else in any record changes)
 //
 // The reference has ONE reader thread and ONE fprintf sink (Process_Reads.cpp:2057-2260, Process_sam_out.cpp:954-1006), which is
 // what limits it.  Round 2 of this driver indexed the lines and formatted the SAM text with the host's
@@ -737,12 +739,18 @@ inline uint64_t bam_key_of(const char* r)
     memcpy(&ref, r + 4, 4); memcpy(&pos, r + 8, 4); memcpy(&flag, r + 18, 2);
     return ((uint64_t)ref << 32) | ((uint64_t)(uint32_t)(pos + 1u) << 1) | (uint64_t)((flag >> 4) & 1u);
 }
-struct SortBin { std::vector<char> rec; std::vector<uint32_t> len; };
+// --markdup: beside every record the id of its template (the batch's running template base + the template's index in the batch, batches
+// in Batch.seq order), and a second store of the templates' signatures (bmbs_text_sorted_dup), cut at the SAME edges by the key of
+// (ref_lo, pos_lo) -- templates with equal signatures share a bin, in input order.  Between the passes bmbs_dup_select runs over groups
+// of signature bins and sets a bit per losing template; pass 2 ORs 0x04 into byte 19 (flag 0x400) of the staged copy of its records.
+struct SortBin { std::vector<char> rec; std::vector<uint32_t> len; std::vector<uint64_t> tid; };
+struct SigBin { std::vector<bmbs_dup_sig> sig; std::vector<uint64_t> gid; };
 struct SortStore {
     std::vector<uint64_t> edge;                  // bin k holds the keys in [edge[k], edge[k + 1]); the last bin: refID -1
     std::vector<SortBin> bin;
-    size_t bytes = 0, cap = 0;                   // record bytes + 4 per record held / allowed (--sort-mem)
-    long records = 0;
+    std::vector<SigBin> sbin;                    // --markdup: the signatures, by the same edges
+    size_t bytes = 0, cap = 0;                   // record bytes + 4 per record (--markdup: + 8, and 32 per signature) held / allowed (--sort-mem)
+    long records = 0, templates = 0, with_sig = 0;
     void init(const bmbs_index_view& v, long want_bins)
     {
         uint64_t G = 0;
@@ -757,16 +765,20 @@ struct SortStore {
         }
         edge.push_back((uint64_t)0xffffffffu << 32);
         bin.assign(edge.size(), SortBin());
+        sbin.assign(edge.size(), SigBin());
         edge.push_back(~(uint64_t)0);
     }
-    // the sorted records of one batch; false: the store's cap would be exceeded
-    bool add(Pool& pool, const char* recs, size_t nbytes, const uint64_t* key, const uint32_t* len, size_t n)
+    size_t bin_of(uint64_t key) const { return (size_t)(std::upper_bound(edge.begin(), edge.end() - 1, key) - edge.begin()) - 1; }
+    // the sorted records of one batch (tmpl: the template of each within the batch, base: the batch's first template id; --markdup);
+    // false: the store's cap would be exceeded
+    bool add(Pool& pool, const char* recs, size_t nbytes, const uint64_t* key, const uint32_t* len, size_t n, const uint32_t* tmpl = nullptr, uint64_t base = 0)
     {
-        if (bytes + nbytes + 4 * n > cap) return false;
+        const size_t per = tmpl ? 12 : 4;
+        if (bytes + nbytes + per * n > cap) return false;
         struct Slice { size_t k, lo, hi; };
         std::vector<Slice> sl;
         for (size_t i = 0; i < n;) {
-            const size_t k = (size_t)(std::upper_bound(edge.begin(), edge.end() - 1, key[i]) - edge.begin()) - 1;
+            const size_t k = bin_of(key[i]);
             const size_t hi = k + 1 < bin.size() ? (size_t)(std::lower_bound(key + i, key + n, edge[k + 1]) - key) : n;
             sl.push_back({k, i, hi});
             i = hi;
@@ -780,9 +792,33 @@ struct SortStore {
                 SortBin& b = bin[sl[j].k];
                 b.rec.insert(b.rec.end(), recs + off[sl[j].lo], recs + off[sl[j].hi]);
                 b.len.insert(b.len.end(), len + sl[j].lo, len + sl[j].hi);
+                if (tmpl) for (size_t i = sl[j].lo; i < sl[j].hi; i++) b.tid.push_back(base + tmpl[i]);
             }
         });
-        bytes += nbytes + 4 * n; records += (long)n;
+        bytes += nbytes + per * n; records += (long)n;
+        return true;
+    }
+    // the signatures of one batch's templates, in batch order; those without a signature are counted and not kept
+    bool add_sigs(Pool& pool, const bmbs_dup_sig* sig, size_t nt, uint64_t base)
+    {
+        std::vector<uint32_t> bi(nt);
+        const int T = std::max(1, std::min<int>(pool.size(), (int)(nt / 4096) + 1));
+        std::vector<size_t> kept((size_t)T, 0);
+        pool.run(T, [&](int t) {
+            for (size_t i = nt * (size_t)t / (size_t)T; i < nt * ((size_t)t + 1) / (size_t)T; i++) {
+                if (sig[i].orient & BMBS_DUP_NONE) { bi[i] = ~0u; continue; }
+                bi[i] = (uint32_t)bin_of(((uint64_t)(uint32_t)sig[i].ref_lo << 32) | ((uint64_t)(uint32_t)(sig[i].pos_lo + 1) << 1));
+                kept[(size_t)t]++;
+            }
+        });
+        size_t ns = 0;
+        for (size_t k : kept) ns += k;
+        if (bytes + 32 * ns > cap) return false;
+        pool.run(T, [&](int t) {
+            for (size_t i = 0; i < nt; i++)
+                if (bi[i] != ~0u && bi[i] % (uint32_t)T == (uint32_t)t) { SigBin& b = sbin[bi[i]]; b.sig.push_back(sig[i]); b.gid.push_back(base + i); }
+        });
+        bytes += 32 * ns; templates += (long)nt; with_sig += (long)ns;
         return true;
     }
 };
@@ -929,8 +965,10 @@ void sort_plan(const SortStore& st, size_t budget, std::vector<SortUnit>& units)
     flush();
 }
 // the records and lengths of a unit, one behind the other, into a staging buffer
-void sort_stage(const SortStore& st, const SortUnit& u, Pool& pool, char* dst, uint32_t* len)
+// dup (--markdup, else NULL): a bit per template id; the copy of every record of a marked template gets flag 0x400 (byte 19 |= 0x04)
+void sort_stage(const SortStore& st, const SortUnit& u, Pool& pool, char* dst, uint32_t* len, const uint64_t* dup)
 {
+    auto marked = [&](uint64_t t) { return (dup[t >> 6] >> (t & 63)) & 1; };
     if (!u.sub) {
         std::vector<size_t> at(u.last - u.first + 2, 0), ln(u.last - u.first + 2, 0);
         for (size_t k = u.first; k <= u.last; k++) { at[k - u.first + 1] = at[k - u.first] + st.bin[k].rec.size(); ln[k - u.first + 1] = ln[k - u.first] + st.bin[k].len.size(); }
@@ -941,6 +979,7 @@ void sort_stage(const SortStore& st, const SortUnit& u, Pool& pool, char* dst, u
                 if (b.len.empty()) continue;
                 memcpy(dst + at[(size_t)j], b.rec.data(), b.rec.size());
                 memcpy(len + ln[(size_t)j], b.len.data(), b.len.size() * 4);
+                if (dup) { size_t o = at[(size_t)j]; for (size_t i = 0; i < b.len.size(); o += b.len[i], i++) if (marked(b.tid[i])) dst[o + 19] |= 0x04; }
             }
         });
         return;
@@ -951,7 +990,9 @@ void sort_stage(const SortStore& st, const SortUnit& u, Pool& pool, char* dst, u
         const uint64_t key = bam_key_of(b.rec.data() + at);
         if (key < u.k_lo || key > u.k_hi) continue;
         if (seen++ < u.skip) continue;
-        memcpy(dst, b.rec.data() + at, b.len[i]); dst += b.len[i];
+        memcpy(dst, b.rec.data() + at, b.len[i]);
+        if (dup && marked(b.tid[i])) dst[19] |= 0x04;
+        dst += b.len[i];
         len[taken++] = b.len[i];
     }
 }
@@ -980,6 +1021,7 @@ struct Batch {
     size_t used1 = 0, used2 = 0;
     uint64_t sam_bytes = 0;
     std::vector<uint64_t> skey; std::vector<uint32_t> slen; int64_t n_sorted = 0;      // --sort: key and length of each record in `sam`
+    std::vector<bmbs_dup_sig> sig; std::vector<uint32_t> tmpl; int64_t n_sig = 0;      // --markdup: the batch's signatures, the template of each record in `sam`
     std::vector<uint32_t> counts1, counts2;
     bmbs_ctx* open_ctx = nullptr;                // compressed input kept on the device: the context that holds this batch's open window
 };
@@ -1037,7 +1079,7 @@ int main(int argc, char** argv)
     int device = 0, io_threads = 0, contexts = 4, parts = 1, reader_threads = 0;
     std::vector<int> devices;
     long batch = 500000;
-    bool verbose = false, unmapped_out = false, pbat = false, bam = false, print_parts = false, print_plan = false, sort_out = false, bai_out = false;
+    bool verbose = false, unmapped_out = false, pbat = false, bam = false, print_parts = false, print_plan = false, sort_out = false, bai_out = false, markdup = false;
     double sort_mem_gib = 0;                     // --sort-mem: cap of the in-memory record store of --sort (0: half of the machine's memory)
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -1086,12 +1128,14 @@ int main(int argc, char** argv)
         else if (a == "--sam") bam = false;
         else if (a == "--sort") sort_out = true;                      // --bam --sort: one coordinate-sorted BAM file (sorted on the device)
         else if (a == "--sort-mem") sort_mem_gib = atof(val());
+        else if (a == "--markdup") markdup = true;                   // --bam --sort --markdup: flag 0x400 on PCR duplicates, decided on the device
         else if (a == "--bai") bai_out = true;                        // --bam --sort --bai: <out>.bai beside the sorted file, from the same run
         else { fprintf(stderr, "bmbs_search: unsupported option %s\n", a.c_str()); return 2; }
     }
     if (sort_out && !bam) { fprintf(stderr, "bmbs_search: --sort needs --bam\n"); return 2; }
     if (sort_out && parts > 1) { fprintf(stderr, "bmbs_search: --sort writes one file (--out-parts 1)\n"); return 2; }
     if (bai_out && !sort_out) { fprintf(stderr, "bmbs_search: --bai needs --sort\n"); return 2; }
+    if (markdup && !sort_out) { fprintf(stderr, "bmbs_search: --markdup needs --sort\n"); return 2; }
     if (bai_out) {
         // the index lies beside a file: a device or a pipe has no such place
         struct stat osb;
@@ -1113,7 +1157,7 @@ int main(int argc, char** argv)
         return 0;
     }
     if (index.empty() || (seq.empty() && (seq1.empty() || seq2.empty()))) {
-        fprintf(stderr, "usage: bmbs_search --index <genome.fa> [--index_folder dir] [-t threads]\n       bmbs_search --search <index> (--seq r.fq | --seq1 a.fq --seq2 b.fq) [-o out.sam] [-e f] [--min n] [--max n] [--sensitive] [--pbat] [--unmapped_out] [--ambiguous_out] [--bam [--sort [--sort-mem GiB] [--bai]]] [--mapstats f] [-t io_threads] [--out-parts n]\n");
+        fprintf(stderr, "usage: bmbs_search --index <genome.fa> [--index_folder dir] [-t threads]\n       bmbs_search --search <index> (--seq r.fq | --seq1 a.fq --seq2 b.fq) [-o out.sam] [-e f] [--min n] [--max n] [--sensitive] [--pbat] [--unmapped_out] [--ambiguous_out] [--bam [--sort [--sort-mem GiB] [--markdup] [--bai]]] [--mapstats f] [-t io_threads] [--out-parts n]\n");
         return 2;
     }
     if (batch < 1) batch = 1;
@@ -1551,6 +1595,7 @@ int main(int argc, char** argv)
     };
 
     // ---------------- stage W (one per part): the SAM text (or its BAM form) goes into the part's file, in order -----------------
+    uint64_t tmpl_base = 0;                      // --markdup: template ids run over the batches in Batch.seq order (--sort: one part, one writer)
     auto writer_fn = [&](Part* pt) {
         Pool wpool(std::max(1, std::min(8, io_threads / (2 * live_parts))) - 1);       // slices of a batch written side by side
         for (;;) {
@@ -1560,7 +1605,12 @@ int main(int argc, char** argv)
             pt->t_wait_w += t0 - tw0;
             const bool end = b->end;
             if (sort_out) {
-                if (b->n && !failed && b->sam_bytes && !sort_store.add(wpool, b->sam.p, (size_t)b->sam_bytes, b->skey.data(), b->slen.data(), (size_t)b->n_sorted)) {
+                bool room = true;
+                if (b->n && !failed && markdup) room = sort_store.add_sigs(wpool, b->sig.data(), (size_t)b->n_sig, tmpl_base);
+                if (b->n && !failed && b->sam_bytes && room)
+                    room = sort_store.add(wpool, b->sam.p, (size_t)b->sam_bytes, b->skey.data(), b->slen.data(), (size_t)b->n_sorted, markdup ? b->tmpl.data() : nullptr, tmpl_base);
+                if (b->n && markdup) tmpl_base += (uint64_t)b->n_sig;
+                if (!room) {
                     char msg[256];
                     snprintf(msg, sizeof msg, "--sort-mem: the record store of --sort is used up (%.3f GiB allowed): %ld records fit, the run has more (spilling to disk is not implemented)",
                              (double)sort_store.cap / 1073741824.0, sort_store.records);
@@ -1622,6 +1672,13 @@ int main(int argc, char** argv)
                     if (sort_out && !rc) {
                         b->skey.resize((size_t)lines + 1); b->slen.resize((size_t)lines + 1);
                         if (bmbs_text_sorted_index(ctx, b->skey.data(), b->slen.data(), lines, &b->n_sorted)) { fail(bmbs_last_error(ctx)); b->sam_bytes = 0; }
+                        b->n_sig = 0;
+                        if (markdup && !failed) {
+                            int64_t nt = 0;
+                            b->sig.resize((size_t)b->n + 1); b->tmpl.resize((size_t)lines + 1);
+                            if (bmbs_text_sorted_dup(ctx, b->sig.data(), b->n, &b->n_sig, b->tmpl.data(), lines, &nt)) { fail(bmbs_last_error(ctx)); b->sam_bytes = 0; }
+                            else if (nt != b->n_sorted || b->n_sig != b->n) { fail("--markdup: the batch's templates do not match its records"); b->sam_bytes = 0; }
+                        }
                     }
                     break;
                 }
@@ -1649,13 +1706,39 @@ int main(int argc, char** argv)
     // deflated on the device, appended by this thread in call order.  BMBS_SORT_SLOTS staging slots (default 2) on as many contexts:
     // the staging and upload of one call run beside the kernels and the download of the other.
     const double t_pass1 = now();
-    size_t sort_calls = 0;
+    size_t sort_calls = 0, select_calls = 0, n_dup = 0;
+    std::vector<uint64_t> dup_bits;              // --markdup: a bit per template id, set for duplicates
+    double t_select = t_pass1;
     BaiIndex bai;
     bai.init((size_t)view.n_chrom);
     if (sort_out && !failed) {
         Part& pt = *P_[0];
         const char* e = getenv("BMBS_SORT_CALL_BYTES");
         const size_t budget = (size_t)std::max(1l, e ? atol(e) : 1l << 30);
+        // --markdup, between the passes: bmbs_dup_select over groups of consecutive signature bins of at most the call budget (a template's
+        // group lies in one bin, in input order: bins are filled in Batch.seq order), a bit per losing template
+        if (markdup) {
+            dup_bits.assign(((size_t)sort_store.templates + 63) / 64 + 1, 0);
+            const size_t lim = std::max<size_t>(1, budget / sizeof(bmbs_dup_sig));
+            std::vector<bmbs_dup_sig> gs; std::vector<uint64_t> gg; std::vector<uint8_t> gd;
+            auto run = [&] {
+                if (gs.empty() || failed) { gs.clear(); gg.clear(); return; }
+                gd.assign(gs.size(), 0);
+                int64_t nd = 0;
+                if (bmbs_dup_select(ctxs[0], gs.data(), (int64_t)gs.size(), gd.data(), &nd)) fail(bmbs_last_error(ctxs[0]));
+                else for (size_t i = 0; i < gs.size(); i++) if (gd[i]) dup_bits[gg[i] >> 6] |= (uint64_t)1 << (gg[i] & 63);
+                if (!failed) n_dup += (size_t)nd;
+                select_calls++; gs.clear(); gg.clear();
+            };
+            for (SigBin& sb : sort_store.sbin) {
+                if (sb.sig.empty()) continue;
+                if (!gs.empty() && gs.size() + sb.sig.size() > lim) run();
+                gs.insert(gs.end(), sb.sig.begin(), sb.sig.end()); gg.insert(gg.end(), sb.gid.begin(), sb.gid.end());
+                std::vector<bmbs_dup_sig>().swap(sb.sig); std::vector<uint64_t>().swap(sb.gid);
+            }
+            run();
+        }
+        t_select = now();
         std::vector<SortUnit> units;
         sort_plan(sort_store, budget, units);
         sort_calls = units.size();
@@ -1687,7 +1770,7 @@ int main(int argc, char** argv)
                 for (size_t i = 0; i < units.size(); i++) {
                     Slot* sl = free_s.get();
                     sl->unit = i;
-                    if (!failed) sort_stage(sort_store, units[i], spool, sl->in.p, sl->len.data());
+                    if (!failed) sort_stage(sort_store, units[i], spool, sl->in.p, sl->len.data(), markdup ? dup_bits.data() : nullptr);
                     staged_s.put(sl);
                 }
                 for (int i = 0; i < n_slots; i++) staged_s.put(nullptr);
@@ -1765,8 +1848,11 @@ int main(int argc, char** argv)
                 total_records, t_loaded - t_start, t_end - t_loaded, t_joined - t_loaded, live_parts, t_read, t_gpu, n_ctx, t_format, t_write, io_threads, batch,
                 n_owner, contexts, parts);
     if (verbose && sort_out) {
-        char ixs[128] = "";
+        char ixs[320] = "";
         if (bai_out) snprintf(ixs, sizeof ixs, ", index: chunks %zu, windows %zu, %zu bytes", bai.n_chunks(), bai.n_windows(), bai_bytes);
+        if (markdup)
+            snprintf(ixs + strlen(ixs), sizeof ixs - strlen(ixs), ", markdup: templates %ld, with signature %ld, duplicates %zu (select calls %zu, %.3fs of pass 2)", sort_store.templates,
+                     sort_store.with_sig, n_dup, select_calls, t_select - t_pass1);
         fprintf(stderr, "[bmbs_search] sort: bins %zu (one of them for records without a reference), pass-2 calls %zu, store bytes %zu (%ld records), pass 1 %.3fs (mapping, binning), pass 2 %.3fs (sort, deflate, write)%s\n",
                 sort_store.bin.size(), sort_calls, sort_store.bytes, sort_store.records, t_pass1 - t_loaded, t_pass2 - t_pass1, ixs);
     }

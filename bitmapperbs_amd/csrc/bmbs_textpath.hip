@@ -2,7 +2,8 @@
 // own since round 5): FASTQ text -> line index -> read rows (bmbs_map_*_fastq, bmbs_map_*_text), BGZF blocks inflated on the device
 // (bmbs_inflate_bgzf, bmbs_text_open_bgzf / bmbs_text_map_open), records -> SAM text or BAM records in BGZF blocks.  The mapping in
 // between is bmbs_api.hip's (lane_enqueue / lane_settle).  Kernels: bmbs_text.hip, bmbs_bam.hip, bmbs_inflate.hip, k_bamsort.hip (the
-// coordinate sort of BAM records: BMBS_TEXT_BAM_SORTED, bmbs_bam_sort), k_bai.hip (the .bai pieces of a sorted call: bmbs_bam_sort_index).
+// coordinate sort of BAM records: BMBS_TEXT_BAM_SORTED, bmbs_bam_sort), k_bai.hip (the .bai pieces of a sorted call: bmbs_bam_sort_index),
+// k_markdup.hip (duplicate marking: bmbs_bam_dup_sigs, bmbs_text_sorted_dup, bmbs_dup_select).
 #include "bmbs_host.h"
 #define DEVI __device__ __forceinline__
 #include "bmbs_text.hip"
@@ -10,6 +11,7 @@
 #include "bmbs_inflate.hip"
 #include "k_bamsort.hip"
 #include "k_bai.hip"
+#include "k_markdup.hip"
 
 // the constants the kernels of this file read: x^(2^n) mod P of CRC-32 for the BGZF blocks' CRCs (bmbs_bytes.h: crc_x8n); per device
 void textpath_device_init(Lane* c)
@@ -205,10 +207,10 @@ int lane_map_text(Lane* c, bool pe, const char* text1, u64 bytes1, const char* t
     if (sam_bytes) *sam_bytes = 0;
     if (n_lines_out) *n_lines_out = 0;
     if ((flags_in & BMBS_TEXT_BAM_SORTED) && !(flags_in & BMBS_TEXT_BAM)) { c->err = "text call: BMBS_TEXT_BAM_SORTED is only valid together with BMBS_TEXT_BAM"; return BMBS_EINVAL; }
-    if (flags_in & BMBS_TEXT_BAM_SORTED) c->bs_n = -1;
+    if (flags_in & BMBS_TEXT_BAM_SORTED) { c->bs_n = -1; c->dup_n2 = -1; }
     if (!c->attached) { c->err = "no index attached"; return BMBS_ESTATE; }
     if (c->n_refs != c->ix.n_chrom) { c->err = "bmbs_sam_refs has not been given the index's reference names"; return BMBS_ESTATE; }
-    if (n_records <= 0) { if (flags_in & BMBS_TEXT_BAM_SORTED) c->bs_n = 0; return BMBS_OK; }
+    if (n_records <= 0) { if (flags_in & BMBS_TEXT_BAM_SORTED) { c->bs_n = 0; c->dup_n2 = 0; c->dup_pe = pe; c->dup_done = false; } return BMBS_OK; }
     if (!text1 || (pe && !text2) || !sam) { c->err = "text call: NULL buffer"; return BMBS_EINVAL; }
     if (bytes1 >= (1ull << 32) || bytes2 >= (1ull << 32)) { c->err = "a text window has to be smaller than 4 GiB (32-bit offsets)"; return BMBS_EINVAL; }
     HIPCHK(c, hipSetDevice(c->dev));
@@ -318,6 +320,7 @@ static int bam_sort_device(Lane* c, const char* raw, const u64* off, const u32* 
 {
     static const bool tiny = getenv("BMBS_BSG_TINY") != nullptr;
     c->bai_n = -1;                                        // (bs_sorted / bs_soff are rewritten: what bmbs_bam_sort_index would read)
+    c->dup_n2 = -1;                                       // (bs_idx2 is rewritten: what bmbs_text_sorted_dup would read)
     ENS(c, c->bs_key, n * 8 + 64); ENS(c, c->bs_key2, n * 8 + 64); ENS(c, c->bs_idx, n * 4 + 64); ENS(c, c->bs_idx2, n * 4 + 64);
     ENS(c, c->bs_slen, n * 4 + 64); ENS(c, c->bs_soff, (n + 1) * 8 + 64); ENS(c, c->bs_sorted, total + 256);
     u32* const info = c->tx_info.as<u32>() + 8;
@@ -367,6 +370,7 @@ int lane_text_finish(Lane* c, bool pe, u64 bytes1, u64 bytes2, int64_t n_records
                      int64_t* n_lines_out, double t_start, double t_uploaded)
 {
     const u64 n = (u64)n_records, n2 = pe ? 2 * n : n;
+    c->dup_n2 = -1;                                       // (sam_len / sam_off / bam_raw are rewritten: what bmbs_text_sorted_dup would read)
     static const bool trace = getenv("BMBS_TEXT_TRACE") != nullptr;
     auto wall = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; };
     double tp[8] = {t_start, 0, 0, 0, 0, 0, 0, t_uploaded}, t_uplock = t_start, t_dnlock = 0, t_dnstart = 0;
@@ -457,7 +461,7 @@ int lane_text_finish(Lane* c, bool pe, u64 bytes1, u64 bytes2, int64_t n_records
         const u64 raw_total = *reinterpret_cast<const u64*>(c->h_info + 24);
         if (n_lines_out) *n_lines_out = (int64_t)n2;
         if (c->h_info[3]) { c->err = "output line " + std::to_string(c->h_info[3] - 1) + " of this batch has a read name of more than 254 characters: BAM cannot hold it"; return BMBS_EINVAL; }
-        if (!raw_total) { if (flags_in & BMBS_TEXT_BAM_SORTED) c->bs_n = 0; return BMBS_OK; }
+        if (!raw_total) { if (flags_in & BMBS_TEXT_BAM_SORTED) { c->bs_n = 0; c->dup_n2 = (int64_t)n2; c->dup_pe = pe; c->dup_done = false; } return BMBS_OK; }
         ENS(c, c->bam_raw, raw_total + 256);
         const TxwPlan tw = txw_plan(pe, bytes1 + bytes2, n2, (36 + 4 * std::max(max_ops, 1) + 8 + 15) & ~15);
         if (!tw.lpb) { c->err = "text call: CIGARs too long"; return BMBS_EINVAL; }
@@ -473,6 +477,7 @@ int lane_text_finish(Lane* c, bool pe, u64 bytes1, u64 bytes2, int64_t n_records
             rc = bam_sort_device(c, c->bam_raw.as<char>(), c->sam_off.as<u64>(), c->sam_len.as<u32>(), n2, raw_total, true, &n_rec);
             if (rc) return rc;
             c->bs_n = (int64_t)n_rec;
+            c->dup_n2 = (int64_t)n2; c->dup_pe = pe; c->dup_done = false;         // (bmbs_text_sorted_dup: computed when asked for)
             if (trace) { HIPCHK(c, hipStreamSynchronize(c->stream)); tp[5] = wall(); }
             double cs = 0;
             rc = download_locked(c, sam, c->bs_sorted.as<char>(), raw_total, c->stream, &cs);
@@ -673,7 +678,7 @@ int lane_text_map_open(Lane* c, int32_t flags_in, char* sam, u64 sam_cap, u64* s
     if (sam_bytes) *sam_bytes = 0;
     if (n_lines_out) *n_lines_out = 0;
     if ((flags_in & BMBS_TEXT_BAM_SORTED) && !(flags_in & BMBS_TEXT_BAM)) { c->err = "text call: BMBS_TEXT_BAM_SORTED is only valid together with BMBS_TEXT_BAM"; return BMBS_EINVAL; }
-    if (flags_in & BMBS_TEXT_BAM_SORTED) c->bs_n = -1;
+    if (flags_in & BMBS_TEXT_BAM_SORTED) { c->bs_n = -1; c->dup_n2 = -1; }
     if (!c->open_text.valid) { c->err = "text map: no open batch (bmbs_text_open_bgzf first)"; return BMBS_ESTATE; }
     if (c->n_refs != c->ix.n_chrom) { c->err = "bmbs_sam_refs has not been given the index's reference names"; return BMBS_ESTATE; }
     if (!sam) { c->err = "text call: NULL buffer"; return BMBS_EINVAL; }
@@ -985,6 +990,160 @@ static int lane_bam_sort_index(Lane* c, bmbs_bai_chunk* chunk, int64_t chunk_cap
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return BMBS_OK;
 }
+
+// ---- duplicate marking (k_markdup.hip) -----------------------------------------------------------------------------------------------------
+// the signatures of n_tmpl templates -> c->dp_sig; entry i = len[i] bytes at raw + off[i] (raw is padded by 16 bytes and more)
+static int dup_sig_device(Lane* c, const char* raw, const u64* off, const u32* len, bool paired, u64 n_tmpl)
+{
+    ENS(c, c->dp_sig, n_tmpl * sizeof(bmbs_dup_sig) + 64);
+    u32* const info = c->tx_info.as<u32>() + 8;
+    HIPCHK(c, hipMemsetAsync(info, 0, 32, c->stream));
+    prof_begin(c, "k_dup_sig");
+    hipLaunchKernelGGL(k_dup_sig, dim3(nblk(n_tmpl * DUP_GROUP, 256)), dim3(256), 0, c->stream, raw, off, len, paired ? 1 : 0, (long)n_tmpl, c->dp_sig.as<bmbs_dup_sig>(), info);
+    prof_end(c);
+    HIPCHK(c, hipMemcpyAsync(c->h_info + 8, info, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    if (c->h_info[8]) {
+        c->err = "dup sigs: the length given for record " + std::to_string(~c->h_info[8]) + " is not its block_size + 4 (or is below the 36 bytes every BAM record has)";
+        return BMBS_EINVAL;
+    }
+    if (c->h_info[9]) { c->err = "dup sigs: the read name, CIGAR, sequence and qualities of record " + std::to_string(~c->h_info[9]) + " do not fit its length"; return BMBS_EINVAL; }
+    return BMBS_OK;
+}
+
+static int lane_bam_dup_sigs(Lane* c, const char* records, uint64_t bytes, const uint32_t* len, int64_t n_in, int32_t paired, bmbs_dup_sig* sig, int64_t sig_cap,
+                             int64_t* n_sig)
+{
+    if (!n_sig) { c->err = "dup sigs: NULL argument"; return BMBS_EINVAL; }
+    *n_sig = 0;
+    if (n_in < 0 || n_in >= (1ll << 31)) { c->err = "dup sigs: bad argument"; return BMBS_EINVAL; }
+    if (paired && (n_in & 1)) { c->err = "dup sigs: an odd number of entries (" + std::to_string(n_in) + ") cannot be pairs"; return BMBS_EINVAL; }
+    if (n_in && !len) { c->err = "dup sigs: NULL buffer"; return BMBS_EINVAL; }
+    const u64 n = (u64)n_in;
+    u64 sum = 0;
+    for (u64 i = 0; i < n; i++) {
+        if (len[i] && len[i] < 36) { c->err = "dup sigs: the length given for record " + std::to_string(i) + " is below the 36 bytes every BAM record has"; return BMBS_EINVAL; }
+        sum += len[i];
+    }
+    if (sum != bytes) { c->err = "dup sigs: the record lengths add up to " + std::to_string(sum) + " bytes, not to the " + std::to_string(bytes) + " given"; return BMBS_EINVAL; }
+    const u64 nt = paired ? n / 2 : n;
+    *n_sig = (int64_t)nt;
+    if ((int64_t)nt > sig_cap) { c->err = "dup sigs: the array is too small (n_sig tells what is needed)"; return BMBS_ENOMEM; }
+    if (!nt) return BMBS_OK;
+    if (!sig || (bytes && !records)) { c->err = "dup sigs: NULL buffer"; return BMBS_EINVAL; }
+    HIPCHK(c, hipSetDevice(c->dev));
+    c->dup_done = false;                                  // (dp_sig is rewritten: what bmbs_text_sorted_dup keeps behind a size query)
+    ENS(c, c->dp_in, bytes + 256); ENS(c, c->dp_len, n * 4 + 64); ENS(c, c->dp_off, (n + 1) * 8 + 64);
+    {
+        std::lock_guard<std::mutex> up(g_h2d_mu[c->dev & 15]);
+        hipStream_t us = c->up_stream ? c->up_stream : c->stream;
+        const u64 piece = 128ull << 20;
+        for (u64 o = 0; o < bytes; o += piece) HIPCHK(c, hipMemcpyAsync(c->dp_in.as<char>() + o, records + o, std::min(piece, bytes - o), hipMemcpyHostToDevice, us));
+        HIPCHK(c, hipMemcpyAsync(c->dp_len.p, len, n * 4, hipMemcpyHostToDevice, us));
+        HIPCHK(c, hipStreamSynchronize(us));
+    }
+    int rc = scan_u32(c, c->dp_len.as<u32>(), n, c->dp_off.as<u64>(), 29);
+    if (rc) return rc;
+    rc = dup_sig_device(c, c->dp_in.as<char>(), c->dp_off.as<u64>(), c->dp_len.as<u32>(), paired != 0, nt);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(sig, c->dp_sig.p, nt * sizeof(bmbs_dup_sig), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BMBS_OK;
+}
+
+static int lane_text_sorted_dup(Lane* c, bmbs_dup_sig* sig, int64_t sig_cap, int64_t* n_sig, uint32_t* tmpl, int64_t cap, int64_t* n)
+{
+    if (!n_sig || !n) { c->err = "sorted dup: NULL argument"; return BMBS_EINVAL; }
+    *n_sig = *n = 0;
+    if (c->dup_n2 < 0 || c->bs_n < 0) {
+        c->err = "sorted dup: the context's last text call was not a BMBS_TEXT_BAM_SORTED call that returned records, or another call has used its buffers since";
+        return BMBS_ESTATE;
+    }
+    const u64 nt = (u64)(c->dup_n2 >> (c->dup_pe ? 1 : 0)), nr = (u64)c->bs_n;
+    *n_sig = (int64_t)nt; *n = (int64_t)nr;
+    if ((int64_t)nt > sig_cap || (int64_t)nr > cap) { c->err = "sorted dup: an array is too small (n_sig and n tell what is needed)"; return BMBS_ENOMEM; }
+    if (!nt) return BMBS_OK;
+    if (!sig || (nr && !tmpl)) { c->err = "sorted dup: NULL argument"; return BMBS_EINVAL; }
+    HIPCHK(c, hipSetDevice(c->dev));
+    if (!c->dup_done) {
+        const int rc = dup_sig_device(c, c->bam_raw.as<char>(), c->sam_off.as<u64>(), c->sam_len.as<u32>(), c->dup_pe, nt);
+        if (rc) return rc;
+        if (nr) {
+            ENS(c, c->dp_tmpl, nr * 4 + 64);
+            hipLaunchKernelGGL(k_dup_tmpl, dim3(nblk(nr, 256)), dim3(256), 0, c->stream, c->bs_idx2.as<u32>(), (long)nr, c->dup_pe ? 1 : 0, c->dp_tmpl.as<u32>());
+        }
+        c->dup_done = true;
+    }
+    HIPCHK(c, hipMemcpyAsync(sig, c->dp_sig.p, nt * sizeof(bmbs_dup_sig), hipMemcpyDeviceToHost, c->stream));
+    if (nr) HIPCHK(c, hipMemcpyAsync(tmpl, c->dp_tmpl.p, nr * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BMBS_OK;
+}
+
+static int lane_dup_select(Lane* c, const bmbs_dup_sig* sig, int64_t n_in, uint8_t* dup, int64_t* n_dup)
+{
+    if (n_dup) *n_dup = 0;
+    if (n_in < 0 || n_in >= (1ll << 31)) { c->err = "dup select: bad argument"; return BMBS_EINVAL; }
+    if (!n_in) return BMBS_OK;
+    if (!sig || !dup) { c->err = "dup select: NULL buffer"; return BMBS_EINVAL; }
+    const u64 n = (u64)n_in;
+    HIPCHK(c, hipSetDevice(c->dev));
+    c->dup_done = false;                                  // (dp_sig is rewritten)
+    ENS(c, c->dp_sig, n * sizeof(bmbs_dup_sig) + 64); ENS(c, c->dp_key, n * 8 + 64); ENS(c, c->dp_key2, n * 8 + 64);
+    ENS(c, c->dp_idx, n * 4 + 64); ENS(c, c->dp_idx2, n * 4 + 64); ENS(c, c->dp_dup, n + 64);
+    {
+        std::lock_guard<std::mutex> up(g_h2d_mu[c->dev & 15]);
+        hipStream_t us = c->up_stream ? c->up_stream : c->stream;
+        HIPCHK(c, hipMemcpyAsync(c->dp_sig.p, sig, n * sizeof(bmbs_dup_sig), hipMemcpyHostToDevice, us));
+        HIPCHK(c, hipStreamSynchronize(us));
+    }
+    const bmbs_dup_sig* const ds = c->dp_sig.as<bmbs_dup_sig>();
+    u64* const ka = c->dp_key.as<u64>(); u64* const kb = c->dp_key2.as<u64>();
+    u32* const ia = c->dp_idx.as<u32>(); u32* const ib = c->dp_idx2.as<u32>();
+    u32* const info = c->tx_info.as<u32>() + 8;           // three 64-bit ORs and the count of duplicates
+    HIPCHK(c, hipMemsetAsync(info, 0, 32, c->stream));
+    hipLaunchKernelGGL(k_dup_bits, dim3(nblk(n, 256)), dim3(256), 0, c->stream, ds, (long)n, reinterpret_cast<unsigned long long*>(info));
+    HIPCHK(c, hipMemcpyAsync(c->h_info + 8, info, 24, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    // each pass over the key bits that can be set only
+    unsigned end_bit[3];
+    size_t tmp_bytes = 0;
+    for (int p = 0; p < 3; p++) {
+        u64 bits; memcpy(&bits, c->h_info + 8 + 2 * p, 8);
+        end_bit[p] = 1;
+        while (end_bit[p] < 64 && bits >> end_bit[p]) end_bit[p]++;
+        size_t t = 0;
+        if (rocprim::radix_sort_pairs(nullptr, t, ka, kb, ia, ib, (size_t)n, 0u, end_bit[p], c->stream) != hipSuccess) { c->err = "dup select: radix_sort_pairs (size query) failed"; return BMBS_ENODEV; }
+        tmp_bytes = std::max(tmp_bytes, t);
+    }
+    ENS(c, c->bs_tmp, tmp_bytes + 64);
+    // (key, entry) pairs from the least significant field up; the entry numbers go back and forth between ia and ib
+    prof_begin(c, "dup_pair_sorts");
+    for (int p = 0; p < 3; p++) {
+        u32* const in = p == 1 ? ib : ia; u32* const out = p == 1 ? ia : ib;
+        hipLaunchKernelGGL(k_dup_keys, dim3(nblk(n, 256)), dim3(256), 0, c->stream, ds, p ? in : nullptr, (long)n, p, ka, in);
+        size_t t = tmp_bytes;
+        if (rocprim::radix_sort_pairs(c->bs_tmp.p, t, ka, kb, in, out, (size_t)n, 0u, end_bit[p], c->stream) != hipSuccess) { c->err = "dup select: radix_sort_pairs failed"; return BMBS_ENODEV; }
+    }
+    prof_end(c);
+    prof_begin(c, "k_dup_heads");
+    hipLaunchKernelGGL(k_dup_heads, dim3(nblk(n, 256)), dim3(256), 0, c->stream, ds, ib, (long)n, c->dp_dup.as<uint8_t>(), info + 6);
+    prof_end(c);
+    HIPCHK(c, hipMemcpyAsync(c->h_info + 14, info + 6, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dup, c->dp_dup.p, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    if (n_dup) *n_dup = (int64_t)c->h_info[14];
+    return BMBS_OK;
+}
+
+extern "C" int bmbs_bam_dup_sigs(bmbs_ctx* X, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, int32_t paired, bmbs_dup_sig* sig, int64_t sig_cap,
+                                 int64_t* n_sig)
+{ ON_LANE0(lane_bam_dup_sigs(c, records, bytes, len, n, paired, sig, sig_cap, n_sig)); }
+extern "C" int bmbs_text_sorted_dup(bmbs_ctx* X, bmbs_dup_sig* sig, int64_t sig_cap, int64_t* n_sig, uint32_t* tmpl, int64_t cap, int64_t* n)
+{ ON_LANE0(lane_text_sorted_dup(c, sig, sig_cap, n_sig, tmpl, cap, n)); }
+extern "C" int bmbs_dup_select(bmbs_ctx* X, const bmbs_dup_sig* sig, int64_t n, uint8_t* dup, int64_t* n_dup) { ON_LANE0(lane_dup_select(c, sig, n, dup, n_dup)); }
 
 extern "C" int bmbs_text_sorted_index(bmbs_ctx* X, uint64_t* key, uint32_t* len, int64_t cap, int64_t* n) { ON_LANE0(lane_text_sorted_index(c, key, len, cap, n)); }
 extern "C" int bmbs_bam_sort(bmbs_ctx* X, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, int32_t flags, char* out, uint64_t out_cap, uint64_t* out_bytes)

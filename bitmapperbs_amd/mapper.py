@@ -376,6 +376,39 @@ class Mapper:
                                                 C.byref(nr), C.byref(nn)))
         return ch[:nc.value], wi[:nw.value], rf[:nr.value], int(nn.value)
 
+    def dup_sigs(self, records: bytes, lens, paired: bool = False) -> np.ndarray:
+        """concatenated BAM records in input order + their sizes (0: no record here) -> the duplicate signature of every template
+        (capi.DUP_SIG_DTYPE; bmbs_bam_dup_sigs): one record each, or with paired=True the entries 2p and 2p + 1"""
+        ln = np.ascontiguousarray(lens, dtype=np.uint32)
+        a = np.frombuffer(records, dtype=np.uint8) if len(records) else np.zeros(1, dtype=np.uint8)
+        n = C.c_int64(0)
+        rc = self._lib.bmbs_bam_dup_sigs(self._ctx, capi.ptr(a), len(records), capi.ptr(ln) if ln.size else None, ln.size, int(paired), None, 0, C.byref(n))
+        if rc and rc != -12:
+            self._chk(rc)
+        sig = np.zeros(max(1, n.value), dtype=capi.DUP_SIG_DTYPE)
+        self._chk(self._lib.bmbs_bam_dup_sigs(self._ctx, capi.ptr(a), len(records), capi.ptr(ln) if ln.size else None, ln.size, int(paired), capi.ptr(sig), n.value,
+                                              C.byref(n)))
+        return sig[:n.value]
+
+    def sorted_dup(self):
+        """(signatures DUP_SIG_DTYPE[templates of the batch], tmpl u32[records]) of the last map_text / text_map_open call with TEXT_BAM |
+        TEXT_BAM_SORTED: tmpl[j] = the template of the j-th record that call returned (bmbs_text_sorted_dup)"""
+        ns = C.c_int64(0); n = C.c_int64(0)
+        rc = self._lib.bmbs_text_sorted_dup(self._ctx, None, 0, C.byref(ns), None, 0, C.byref(n))
+        if rc and rc != -12:
+            self._chk(rc)
+        sig = np.zeros(max(1, ns.value), dtype=capi.DUP_SIG_DTYPE); tmpl = np.zeros(max(1, n.value), dtype=np.uint32)
+        self._chk(self._lib.bmbs_text_sorted_dup(self._ctx, capi.ptr(sig), ns.value, C.byref(ns), capi.ptr(tmpl), n.value, C.byref(n)))
+        return sig[:ns.value], tmpl[:n.value]
+
+    def dup_select(self, sig: np.ndarray):
+        """signatures in input order -> (dup u8[n]: 1 where a template loses its group, their number) (bmbs_dup_select)"""
+        s = np.ascontiguousarray(sig, dtype=capi.DUP_SIG_DTYPE)
+        dup = np.zeros(max(1, s.size), dtype=np.uint8)
+        nd = C.c_int64(0)
+        self._chk(self._lib.bmbs_dup_select(self._ctx, capi.ptr(s) if s.size else None, s.size, capi.ptr(dup), C.byref(nd)))
+        return dup[:s.size], int(nd.value)
+
     def sync(self):
         self._chk(self._lib.bmbs_sync(self._ctx))
 

@@ -409,6 +409,42 @@ typedef struct bmbs_bai_ref   { int32_t ref; uint32_t pad; uint64_t beg, end, n_
 int bmbs_bam_sort_index(bmbs_ctx*, bmbs_bai_chunk* chunk, int64_t chunk_cap, int64_t* n_chunk, bmbs_bai_win* win, int64_t win_cap,
                         int64_t* n_win, bmbs_bai_ref* ref, int64_t ref_cap, int64_t* n_ref, uint64_t* n_no_coor);
 
+/* ---- PCR duplicates of a sorted BAM, marked on the device (csrc/k_markdup.hip; `bmbs_search --bam --sort --markdup`) ---------------------
+ * Picard's pair-level rule, per TEMPLATE: one record of a single-end run, the two records of a pair.  A record is USABLE when it is
+ * there, mapped (flag 4 clear), primary (0x100 and 0x800 clear) and has n_cigar_op > 0.  Its 5' coordinate: forward strand pos - (the
+ * leading S and H lengths), reverse strand (flag 0x10) pos + (the sum of its M D N = X lengths) + (the trailing S and H lengths) - 1.
+ *   both records of a pair usable: the two ends (refID, 5' coordinate, strand, is read 1 = flag 0x40); lo = the smaller by (refID,
+ *     coordinate), a tie goes to the forward strand, a further tie to read 1; (ref_lo, pos_lo), (ref_hi, pos_hi) = the two ends,
+ *     orient = strand of lo | strand of hi << 1 | (lo is read 1) << 2 | 8
+ *   a single-end record, or the one usable record of a pair: (ref_lo, pos_lo) = its end, (ref_hi, pos_hi) = (-1, -1), orient = strand
+ *   no usable record: every coordinate -1, orient = BMBS_DUP_NONE, score 0; such a template is never marked
+ * Bit 2 of orient is ALWAYS part of the signature (Picard uses it for FF and RR pairs only): read 1 forward and read 1 reverse come
+ * from different original strands of a bisulfite library and are never copies of one molecule.
+ * score = the sum, over the usable records, of the base qualities that are >= 15 (a quality byte 0xff counts as 0).
+ * Among templates with equal (ref_lo, pos_lo, ref_hi, pos_hi, orient) the one with the highest score stays, among equal scores the
+ * earliest in input order; every other one is a duplicate.  A caller marks a duplicate by `flag |= 0x400` in EVERY record of the
+ * template, which is one byte: record byte 19 (counting the block_size word) |= 0x04 -- its step when it stages records for
+ * bmbs_bam_sort; nothing else in a record changes.
+ * bmbs_bam_dup_sigs: `records` = n entries in host memory (input order), len[i] = their sizes; len[i] == 0: no record here (the text
+ * calls' empty lines).  paired != 0: entries 2p and 2p + 1 are one template (n must be even).  sig[t] = template t; *n_sig = their
+ * number (BMBS_ENOMEM with *n_sig set when sig_cap is smaller; a cap of 0: the size query).  Needs no attached index.  BMBS_EINVAL
+ * (bmbs_last_error names the record) as for bmbs_bam_sort: a len[i] other than 0 below 36 or unlike its record's block_size + 4,
+ * sum(len) != bytes, an odd n with `paired`; also a record whose read name, CIGAR, sequence and qualities do not fit its length.
+ * bmbs_text_sorted_dup: the same for the context's last BMBS_TEXT_BAM_SORTED call, computed when asked for from the buffers that call
+ * left on the device, where the two records of a pair still lie side by side.  sig[t] = template t of the batch in batch order
+ * (*n_sig = the records / pairs handed to the call); tmpl[j] = the template of the j-th record the call returned, in sorted order
+ * (*n = their number, that of bmbs_text_sorted_index).  BMBS_ESTATE: there was no such call, or another call on the context has
+ * rewritten the buffers since; BMBS_ENOMEM when a cap is too small, *n_sig and *n are set then too (caps of 0: the size query).
+ * bmbs_dup_select: dup[i] = 1 when template i loses its group, 0 otherwise; *n_dup = their number; the index is the input order;
+ * n = 0 is valid.  The result for a template depends only on the templates of its group, so a caller may run it on any partition of
+ * the templates by a function of (ref_lo, pos_lo), each part in input order.  Needs no attached index.                            */
+typedef struct bmbs_dup_sig { int32_t ref_lo, pos_lo, ref_hi, pos_hi; uint32_t orient, score; } bmbs_dup_sig;   /* 24 bytes */
+#define BMBS_DUP_NONE 0x80000000u      /* in orient: the template has no signature */
+int bmbs_bam_dup_sigs(bmbs_ctx*, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, int32_t paired,
+                      bmbs_dup_sig* sig, int64_t sig_cap, int64_t* n_sig);
+int bmbs_text_sorted_dup(bmbs_ctx*, bmbs_dup_sig* sig, int64_t sig_cap, int64_t* n_sig, uint32_t* tmpl, int64_t cap, int64_t* n);
+int bmbs_dup_select(bmbs_ctx*, const bmbs_dup_sig* sig, int64_t n, uint8_t* dup, int64_t* n_dup);
+
 /* a21: per-ctx counters of the batches mapped so far = {reads, unique, ambiguous, mapped bases,
  * error bases} (Schema.cpp:25141-25146); bmbs_stats_allreduce sums them over the ctxs one process
  * drives (get_mapping_informations, Schema.cpp:451-476).  Multi-process jobs sum the five int64 with
