@@ -26,6 +26,7 @@ SYMBOLS = [
     "bmbs_qual_classes", "bmbs_pack_quals", "bmbs_map_se_packedq", "bmbs_map_pe_packedq",
     "bmbs_text_sorted_index", "bmbs_bam_sort", "bmbs_bam_sort_index",
     "bmbs_bam_dup_sigs", "bmbs_text_sorted_dup", "bmbs_dup_select",
+    "bmbs_outcome_index",
 ]
 
 
@@ -201,6 +202,9 @@ def lib() -> C.CDLL:
         L.bmbs_text_sorted_dup.restype = C.c_int
         L.bmbs_dup_select.argtypes = [vp, vp, i64, vp, C.POINTER(i64)]
         L.bmbs_dup_select.restype = C.c_int
+    if hasattr(L, "bmbs_outcome_index"):                 # (the balanced outcome table; BMBS_LIB may name an older build, as above)
+        L.bmbs_outcome_index.argtypes = [u64, C.c_uint32, i32, i32, C.POINTER(i32)]
+        L.bmbs_outcome_index.restype = i64
     L.bmbs_map_pe_text.argtypes = [vp, vp, u64, vp, u64, i64, i32, vp, u64, C.POINTER(u64), C.POINTER(i64)]
     L.bmbs_map_pe_text.restype = C.c_int
     L.bmbs_retries.argtypes = [vp]

@@ -811,6 +811,17 @@ extern "C" int32_t bmbs_max_cigar_ops(const bmbs_params* params, int32_t L)
     return cigar_ops_bound(P, L, threshold_k(P, L));
 }
 
+extern "C" int64_t bmbs_outcome_index(uint64_t bases, uint32_t not_acgt, int32_t len, int32_t bits, int32_t* depth)
+{
+    if (bits != 32 && bits != 33) return -2;
+    static const std::vector<u16> tab = [] { std::vector<u16> t(256); for (int v = 0; v < 256; v++) t[v] = th_tab_entry(v); return t; }();
+    int D = 0;
+    u64 idx = 0;
+    const bool ok = th_slot(bases, not_acgt, len, bits, tab.data(), idx, D);
+    if (depth) *depth = D;
+    return ok ? (int64_t)idx : -1;
+}
+
 extern "C" const char* bmbs_last_error(const bmbs_ctx* X) { return X ? X->err.c_str() : "no context (no HIP device?)"; }
 
 static int lane_index_attach(Lane* c, const bmbs_index_view* v)
@@ -885,25 +896,35 @@ static int lane_index_attach(Lane* c, const bmbs_index_view* v)
     ix.C[0] = v->nacgt[0]; ix.C[1] = v->nacgt[1]; ix.C[2] = v->nacgt[2]; ix.n_chrom = v->n_chrom;
     hipLaunchKernelGGL(k_expand_sa, dim3(nblk(std::min<u64>(rows, 1ull << 30), 256)), dim3(256), 0, c->stream, ix, R, rows, wide ? nullptr : c->sa.as<u32>(),
                        wide ? c->sa.as<u64>() : nullptr);
-    // (16 + E)-mer outcome table: E = 5 (3^21 entries, 83.7 GB) for texts of 2^32 symbols and more when the device has the room,
-    // else E = 4 (3^20 entries, 27.9 GB), else none; BMBS_T20=0 turns it off, BMBS_TDEPTH=20|21 forces a depth (A/B runs, tests)
-    ix.t20 = nullptr; ix.t_e = 4;
+    // outcome table.  Texts of 2^32 symbols and more: the balanced table of 2^33 entries (68.7 GB) when the device has the room, else the
+    // ternary one at E = 5 (3^21 entries, 83.7 GB), else E = 4 (3^20 entries, 27.9 GB), else none; smaller texts: E = 4.  BMBS_T20=0 turns it off, BMBS_TDEPTH=20|21 forces a ternary depth and BMBS_TDEPTH=h32|h33 the balanced
+    // table of that many bits on any text (A/B runs, tests)
+    ix.t20 = nullptr; ix.t_e = 4; ix.t_b = 0;
     {
         const char* t20_env = getenv("BMBS_T20");
         const char* td_env = getenv("BMBS_TDEPTH");
         const u64 n_keys = v->hash_entries - 1;                 // 3^16
         size_t free_b = 0, total_b = 0;
         (void)hipMemGetInfo(&free_b, &total_b);
-        int want_e = wide ? 5 : 4;
-        if (td_env) want_e = atoi(td_env) == 21 ? 5 : 4;
+        int want_e = wide ? 5 : 4, want_b = wide ? 33 : 0;
+        if (td_env) {
+            want_b = !strcmp(td_env, "h33") ? 33 : !strcmp(td_env, "h32") ? 32 : 0;
+            want_e = atoi(td_env) == 21 || want_b ? 5 : 4;
+        }
+        const u64 room = 48ull << 30;
         if (!(t20_env && !strcmp(t20_env, "0")) && n_keys == 43046721ull) {
-            for (int e5 = want_e; e5 >= 4; e5--) {
+            if (want_b && free_b > (8ull << want_b) + room && ensure(c, c->t20, 8ull << want_b) == BMBS_OK) {
+                ix.t_b = want_b; ix.t_e = TH_MAX_E;             // (t_e: the most letters a lookup reads ahead)
+                const u64 n_chunks = (1ull << want_b) / TH_CHUNK;
+                hipLaunchKernelGGL(k_build_th, dim3(nblk(std::min<u64>(n_chunks, 1ull << 24), 256)), dim3(256), 0, c->stream, ix, want_b, n_chunks, c->t20.as<u64>());
+                ix.t20 = c->t20.as<u64>();
+            }
+            for (int e5 = want_e; e5 >= 4 && !ix.t20; e5--) {
                 const u64 need = n_keys * t20_width(e5) * 8;
-                if (free_b > need + (48ull << 30) && ensure(c, c->t20, need) == BMBS_OK) {
+                if (free_b > need + room && ensure(c, c->t20, need) == BMBS_OK) {
                     ix.t_e = e5;
                     hipLaunchKernelGGL(k_build_t20, dim3(nblk(n_keys, 256)), dim3(256), 0, c->stream, ix, n_keys, c->t20.as<u64>());
                     ix.t20 = c->t20.as<u64>();
-                    break;
                 }
             }
         }

@@ -24,6 +24,7 @@ typedef uint64_t u64; typedef uint32_t u32; typedef uint16_t u16; typedef uint8_
 //           (bwt.h:2081-2209) has decided after those four backward extensions -- stopped unique at depth 16..19, stopped
 //           because the next letter does not occur, or still going with the depth-20 interval.  One lookup replaces the 16-mer
 //           lookup plus up to four dependent Occ gathers of a seed; 288 GB of HBM is what makes the table affordable;
+//           (texts of 2^32 symbols and more: the balanced form, 2^33 entries indexed by a prefix code of the letters, k_attach.hip);
 //   gen2  : the doubled genome (forward ++ reverse complement) 2 bits/base, 32 bases per u64
 //           LSB-first (A0 C1 G2 T3), so both strands' windows are forward reads;
 //   gen2p : the same bases as two bit planes -- word w = { low half: bit 0 of the letters of bases 32 w .. 32 w + 31, high half: their
@@ -43,6 +44,8 @@ struct DevIndex {
     const u64*   gen2p;
     const u64*   t20;           // optional: outcome of the first t_e extensions of every (16 + t_e)-mer (k_build_t20), else nullptr
     int          t_e;           // letters the table looks ahead: 4 (3^20 entries, 27.9 GB) or 5 (3^21 entries, 83.7 GB; GRCh38-size texts)
+    int          t_b;           // 0: t20 is the ternary table above; 32 | 33: the balanced table of 2^t_b entries (34.4 / 68.7 GB), whose index is a
+                                // prefix code of the letters (T 0, G 10, A 11) and whose depth is 16 .. 32 letters (k_attach.hip; the GRCh38-size default)
     // three backward extensions in one step (round 4): occ3[g * nb3 + row / 96] = { rows before the block whose three preceding text
     // letters are the trigram g, one bit per row of the block for "this row's are" }, g = d1 + 3 d2 + 9 d3 in extension order;
     // c3[g] = first row of the suffixes that begin with the trigram.  LF_d3(LF_d2(LF_d1(row))) = c3[g] + rank_g(row): one 16-byte

@@ -57,7 +57,7 @@ struct Prof { const char* name; hipEvent_t a, b; bool used; };
 // Switches (environment), read ONCE when a context is created -- never on the launch path.  Every form gives identical results and the
 // GPU suite runs each one in single-end and paired-end mode (test_ab_switches_give_identical_records); DESIGN.md section 3 lists them.
 //   forms:      BMBS_LEGACY=1 (the round-1 ASCII-row seeding engine and byte-wise mate preparation, as a whole), BMBS_SW=reg2|reg|wave,
-//               BMBS_KGRAM=0|1|2, BMBS_T20=0, BMBS_TDEPTH=20|21, BMBS_WIDE=1 (+ BMBS_SUPER_SHIFT), BMBS_LANES=n, BMBS_EXACT=1, BMBS_SEED_WAVES=n,
+//               BMBS_KGRAM=0|1|2, BMBS_T20=0, BMBS_TDEPTH=20|21|h32|h33 (ternary outcome table of that depth | balanced one of that many index bits), BMBS_WIDE=1 (+ BMBS_SUPER_SHIFT), BMBS_LANES=n, BMBS_EXACT=1, BMBS_SEED_WAVES=n,
 //               BMBS_SEED_STAGE=0|1
 //   test aids:  BMBS_CAP_SCALE, BMBS_SPLIT_MIN, BMBS_CHUNK, BMBS_PEF_LONG=2 (make small inputs reach the paths large ones take)
 struct Knobs {

@@ -109,6 +109,137 @@ k_build_t20(DevIndex ix, u64 n_keys, u64* __restrict__ t20)
     }
 }
 
+// ---- the balanced outcome table (ix.t_b = B = 32 or 33 bits; BMBS_TDEPTH=h32|h33) ----------------------------------------------
+// The ternary index gives every letter the same depth, but the indexed text is not uniform in its letters: after C->T the doubled
+// text holds T at exactly one half, G and A share the other.  Here the entry index is the first B bits of the prefix code
+// T = 0, G = 10, A = 11 of read[tm], read[tm+1], ... (first code bit = bit B-1 of the index), so every entry carries the same
+// probability mass 2^-B and the table is B bits deep everywhere: D = 16 letters behind a G/A-only pattern, up to 32 behind a T run
+// (the engine holds 32 bases from its one row request).  D = the letters whose code lies completely inside the B bits, at most
+// 32; a last bit 1 that is only the first half of a G/A code belongs to no letter (both such indices hold the depth-D outcome), and
+// so do the bits behind the 32nd letter.  2^33 entries = 68.7 GB (texts of 2^32 symbols and more), 2^32 = 34.4 GB.
+// entry = row (36 bits) | hits (20 bits) << 36 | s (4 bits) << 56 | tag << 60: what the loop described above has decided after the
+// D - 16 letters c16 .. c(D-1).  The reader knows D from the letters it consumed.  Tags:
+//   1   stopped unique before consuming c(16 + s)            (match length 16 + s; the field holds the text position, as above)
+//   2   stopped because c(16 + s) does not occur             (row, hits = interval before, match length 16 + s)
+//   0   all D - 16 letters consumed: row, hits = the depth-D interval (the caller carries on with s = D - 16)
+//   3   all D - 16 letters consumed and that interval is one row (match length D, 1 hit; the field holds the text position)
+//   15  the 16-mer itself does not occur;   14  hits do not fit 20 bits: use the 16-mer path
+#define TH_MAX_E 16
+#define TH_CHUNK 256              // entries per work item of k_build_th: consecutive indices share their leading letters
+DEVI u64 th_entry(u64 row, u64 hits, int s, int tag)
+{
+    return hits >= (1ull << 20) ? (14ull << 60) : (row | (hits << 36) | ((u64)s << 56) | ((u64)tag << 60));
+}
+// index and depth of the 32 bases x (2 bits each, LSB first, A0 C1 G2 T3; C counts as T), four letters per step through a table of
+// 256 entries: tab[v] = the code of the four letters in byte v (letter 0 first = highest bit) | its length (4 .. 8) << 8.  Eight
+// lookups give the code of all 32 letters -- 32 .. 64 bits -- whose first B bits are the index (zeros behind the 32nd letter); D is
+// the largest j with j + (G/A letters among the first j) <= B, found by bisection from 16.  No loop over letters, no divergence:
+// 8 x (extract, lookup, unpack, shift-or, add) + five bisection steps, about 120 instructions for a seed start (a loop over the G/A
+// letters instead takes up to 17 trips of 40 wave instructions, the lanes of a wave waiting for the longest).
+__host__ __device__ inline u16 th_tab_entry(int v)
+{
+    u32 bits = 0, n = 0;
+    for (int j = 0; j < 4; j++) {
+        const int b = (v >> (2 * j)) & 3;
+        if (b & 1) { bits <<= 1; n += 1; }                                // T (C)
+        else { bits = (bits << 2) | 2u | (b == 0 ? 1u : 0u); n += 2; }    // G 10, A 11
+    }
+    return (u16)(bits | (n << 8));
+}
+__host__ __device__ inline u64 th_index(u64 x, int B, const u16* tab, int& D)
+{
+    u64 acc = 0;
+    int n = 0;
+#pragma unroll 1                                          // (unrolled, the eight entries in flight cost k_seed_extra its sixth wave: 81 VGPRs)
+    for (int g = 0; g < 8; g++) {
+        const u32 e = tab[(x >> (8 * g)) & 0xff];
+        acc = (acc << (e >> 8)) | (e & 0xff);
+        n += (int)(e >> 8);
+    }
+    const u64 nt = ~x & 0x5555555555555555ull;            // bit 2j: letter j is G or A
+    int d = 16;
+#pragma unroll
+    for (int step = 8; step >= 1; step >>= 1) {
+        const int c = d + step;                           // <= 31
+#if defined(__HIP_DEVICE_COMPILE__)
+        const int k = __popcll(nt & ((1ull << (2 * c)) - 1));
+#else
+        const int k = __builtin_popcountll(nt & ((1ull << (2 * c)) - 1));
+#endif
+        if (c + k <= B) d = c;
+    }
+    if (n <= B) d = 32;                                   // all 32 letters inside (n = 32 + the G/A letters among them)
+    D = d;
+    return n >= B ? acc >> (n - B) : acc << (B - n);
+}
+// the block's copy of the table: every kernel that starts seeds fills it first (th_tab_fill)
+__shared__ u16 s_th_tab[256];
+DEVI void th_tab_fill(const DevIndex& ix)
+{
+    if (!ix.t_b) return;
+    for (int v = threadIdx.x; v < 256; v += blockDim.x) s_th_tab[v] = th_tab_entry(v);
+    __syncthreads();
+}
+// ... of a seed start: bad = one bit per base that is none of ACGT, len = the bases the seed has.  False when the lookup cannot use
+// the table -- such a letter among the D letters, or fewer than D letters -- and takes the 16-mer path instead.
+__host__ __device__ inline bool th_slot(u64 x, u32 bad, int len, int B, const u16* tab, u64& idx, int& D)
+{
+    idx = th_index(x, B, tab, D);
+    return len >= D && (bad & (u32)((1ull << D) - 1)) == 0;
+}
+
+// Work is dealt out by index ranges (an all-T 16-mer owns 2^(B-16) entries, a G/A-only one owns one or two): a work item is
+// TH_CHUNK consecutive entries, walked in index order.  Depth-first with a memo per level: level l holds the outcome after the
+// letters c16 .. c(15+l), decided by the entry's first 16 + l letters alone, so an entry recomputes only from the first letter in
+// which it differs from the entry before it, and a stopped prefix decides all of its continuations without touching memory.
+__global__ void __launch_bounds__(256)
+k_build_th(DevIndex ix, int B, u64 n_chunks, u64* __restrict__ out)
+{
+    u64 tp[TH_MAX_E + 1], bt[TH_MAX_E + 1], val[TH_MAX_E + 1];
+    bool stop[TH_MAX_E + 1];
+    for (u64 ch = (u64)blockIdx.x * blockDim.x + threadIdx.x; ch < n_chunks; ch += (u64)gridDim.x * blockDim.x) {
+        u64 plet = 0;                  // the letters of the entry before (3-letter digits, 2 bits each, letter 0 lowest)
+        int pD = -1;                   // ... and its depth (-1: none yet)
+        for (u64 i = ch * TH_CHUNK; i < (ch + 1) * TH_CHUNK; i++) {
+            // decode: the D letters of index i
+            u64 let = 0;
+            int D = 0;
+            for (int p = 0; p < B && D < 32;) {
+                if (!((i >> (B - 1 - p)) & 1)) { let |= 1ull << (2 * D); D++; p++; continue; }      // T
+                if (p == B - 1) break;                                                               // half a code
+                if ((i >> (B - 2 - p)) & 1) let |= 2ull << (2 * D);                                  // A (2), else G (0)
+                D++; p += 2;
+            }
+            const int E = D - 16;
+            // levels 0 .. keep stay valid: the letters before 16 + keep are those of the entry before
+            int keep = -1;
+            if (pD >= 0) {
+                const u64 diff = let ^ plet;
+                const int same = diff ? (__ffsll((unsigned long long)diff) - 1) >> 1 : 32;     // leading letters in common
+                const int lim = D < pD ? D : pD;
+                keep = (same < lim ? same : lim) - 16;
+            }
+            int l = keep < 0 ? 0 : keep;
+            if (keep < 0) {
+                u64 key = 0, pw = 1;
+                for (int u = 0; u < 16; u++) { key += ((let >> (2 * u)) & 3) * pw; pw *= 3; }
+                hash_lookup(ix, key, tp[0], bt[0]);
+                stop[0] = bt[0] <= tp[0]; val[0] = 15ull << 60;
+            }
+            for (; l < E; l++) {
+                if (stop[l]) { stop[l + 1] = true; val[l + 1] = val[l]; continue; }
+                if (bt[l] - tp[l] == 1) { val[l + 1] = th_entry(sa_at(ix, tp[l]), 1, l, 1); stop[l + 1] = true; continue; }
+                u64 t = tp[l], b = bt[l];
+                lf_pair(ix, t, b, (int)((let >> (2 * (16 + l))) & 3));
+                if (b <= t) { val[l + 1] = th_entry(tp[l], bt[l] - tp[l], l, 2); stop[l + 1] = true; }
+                else { tp[l + 1] = t; bt[l + 1] = b; stop[l + 1] = false; }
+            }
+            out[i] = stop[E] ? val[E] : (bt[E] - tp[E] == 1 ? th_entry(sa_at(ix, tp[E]), 1, 0, 3) : th_entry(tp[E], bt[E] - tp[E], 0, 0));
+            plet = let; pD = D;
+        }
+    }
+}
+
 // doubled 2-bit genome: d < G forward base, else complement of base 2G-1-d; LSB-first in u64 words
 __global__ void k_build_gen2(RefIndexDev R, u64 G, u64 n_words, u64* out)
 {

@@ -162,6 +162,7 @@ k_pes_reseed(DevIndex ix, const char* __restrict__ seq, PackedRows pr, ReadGeom 
              const u32* __restrict__ plist, ReadState st, PeState ps, u32* __restrict__ rcnt, unsigned long long* __restrict__ counters)
 {
     __shared__ u64 s_c3[KG ? 27 : 1];
+    th_tab_fill(ix);
     const u64* c3 = KG ? kgram_c3(ix, s_c3) : nullptr;
     const long it = (long)blockIdx.x * blockDim.x + threadIdx.x;
     LaneCounters lc = {0, 0, 0, 0, 0};

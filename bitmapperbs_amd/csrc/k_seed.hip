@@ -37,6 +37,43 @@ DEVI void swar_code3(u64 w, u64& digits, u64& bad)
 // four digits (one per byte of x) -> d0 + 3 d1 + 9 d2 + 27 d3 in one multiply
 DEVI u32 base3_of4(u32 x) { return (x * 0x0103091Bu) >> 24; }
 
+// ---- the balanced outcome table (ix.t_b, k_attach.hip): what entry v says about a seed whose table depth is D letters -------------
+// returns 0: use the 16-mer path (tag 14), 1: decided (out filled, search_begin returns false), 2: go on stepping with s = S.s --
+// the caller places its cursor on read[tm + D] -- 3: a single located row (FIXED: the caller verifies it against the genome)
+template <bool FIXED, class SearchT>
+DEVI int th_outcome(u64 v, int D, int len, SearchT& S, SeedHit& out, u32& n_hash)
+{
+    const int tag = (int)(v >> 60);
+    if (tag == 14) return 0;
+    n_hash++;
+    const u64 row = v & ((1ull << 36) - 1), hits = (v >> 36) & ((1ull << 20) - 1);
+    const int s = (int)(v >> 56) & 15, E = D - 16;
+    if (tag == 15) return 1;                                               // hits 0, match length 0
+    if (FIXED) {
+        if (tag == 2) return 1;                                            // count_hash_table: a missing letter is 0 hits
+        if (tag != 0) { S.top = row | (1ull << 63); S.bot = S.top + 1; S.s = tag == 3 ? E : s; return 3; }
+    } else {
+        if (tag == 1) { out.ml = (u64)(16 + s); out.sp = row | (1ull << 63); out.hits = 1; return 1; }      // located (bit 63): text position
+        if (tag == 3) { out.ml = (u64)D; out.sp = row | (1ull << 63); out.hits = 1; return 1; }
+        if (tag == 2) { out.ml = (u64)(16 + s); out.sp = row; out.hits = hits; return 1; }
+    }
+    S.top = row; S.bot = row + hits; S.s = E;
+    if (S.s == S.steps) { out.ml = (u64)len; out.sp = S.top; out.hits = hits; return 1; }
+    return 2;
+}
+// eight ASCII characters -> eight 2-bit bases (A0 C1 G2 T3, the packed rows' code) and one bit per character that is none of ACGT
+DEVI void ascii8_bases(u64 w, u64& bases, u32& bad)
+{
+    u64 d, v;
+    swar_code3(w, d, v);
+    bases = 0; bad = 0;
+    for (int j = 0; j < 8; j++) {
+        const u32 t = (u32)(w >> (8 * j + 1)) & 3u;                      // A0 C1 T2 G3
+        if ((v >> (8 * j)) & 0xffull) bad |= 1u << j;                  // (its base bits stay 0, as in a packed row)
+        else bases |= (u64)(t ^ (t >> 1)) << (2 * j);
+    }
+}
+
 // returns true when the search has to be stepped; false when it is already decided (out filled)
 // LOCATED (with FIXED): the caller finishes single-row intervals against the genome and takes them with the text position
 // in S.top (bit 63 set) -- k_seed_second; without it the full-length search does not touch the 20-mer table.
@@ -55,11 +92,11 @@ DEVI bool search_begin(const DevIndex& ix, const char* rd, int L, int tm, Search
     uint4 B2 = make_uint4(0, 0, 0, 0);
     if (o + 16 + ix.t_e >= 32 && a16 + 32 < L) B2 = *reinterpret_cast<const uint4*>(rd + a16 + 32);
     const u64 q0 = ((u64)B0.y << 32) | B0.x, q1 = ((u64)B0.w << 32) | B0.z, q2 = ((u64)B1.y << 32) | B1.x,
-              q3 = ((u64)B1.w << 32) | B1.z, q4 = ((u64)B2.y << 32) | B2.x;
+              q3 = ((u64)B1.w << 32) | B1.z, q4 = ((u64)B2.y << 32) | B2.x, q5 = ((u64)B2.w << 32) | B2.z;
     const int sh8 = (o & 7) * 8;
     auto funnel = [&](u64 lo, u64 hi) -> u64 { return sh8 ? (lo >> sh8) | (hi << (64 - sh8)) : lo; };
     const bool up = o >= 8;
-    const u64 c0 = up ? q1 : q0, c1 = up ? q2 : q1, c2 = up ? q3 : q2, c3 = up ? q4 : q3;
+    const u64 c0 = up ? q1 : q0, c1 = up ? q2 : q1, c2 = up ? q3 : q2, c3 = up ? q4 : q3, c4 = up ? q5 : q4;
     const u64 w0 = funnel(c0, c1), w1 = funnel(c1, c2);          // read[tm .. tm+7], read[tm+8 .. tm+15]
     u64 d0, v0, d1, v1;
     swar_code3(w0, d0, v0);
@@ -69,7 +106,21 @@ DEVI bool search_begin(const DevIndex& ix, const char* rd, int L, int tm, Search
     const u64 key = base3_of4((u32)d0) + 81u * base3_of4((u32)(d0 >> 32)) + 6561u * base3_of4((u32)d1) + 531441u * base3_of4((u32)(d1 >> 32));
     S.steps = len - 16; S.tm = tm;
     const int E = ix.t_e;
-    if ((!FIXED || LOCATED) && ix.t20 && len >= 16 + E) {
+    if ((!FIXED || LOCATED) && ix.t20 && ix.t_b) {
+        // the balanced table: index and depth from the 32 characters read[tm .. tm+31] (the row is padded to whole 16-byte pieces;
+        // what lies behind the read never counts: len >= D)
+        u64 b0, b1, b2, b3; u32 m0, m1, m2, m3;
+        ascii8_bases(w0, b0, m0); ascii8_bases(w1, b1, m1); ascii8_bases(funnel(c2, c3), b2, m2); ascii8_bases(funnel(c3, c4), b3, m3);
+        int D; u64 idx;
+        if (th_slot(b0 | (b1 << 16) | (b2 << 32) | (b3 << 48), m0 | (m1 << 8) | (m2 << 16) | (m3 << 24), len, ix.t_b, s_th_tab, idx, D)) {
+            S.ptop = ~0ull; S.pbot = ~0ull;
+            const int oc = th_outcome<FIXED>(ix.t20[idx], D, len, S, out, n_hash);
+            if (oc == 1) return false;
+            if (oc == 3) return true;
+            if (oc == 2) { S.cur.seek_with(rd, tm + D, L, o + D < 32 ? B1 : B2); return true; }
+        }
+        // a letter outside the alphabet among them, a seed shorter than the table is deep there, or an oversized interval: the 16-mer path
+    } else if ((!FIXED || LOCATED) && ix.t20 && len >= 16 + E) {
         // the 16-mer lookup and the first E extensions in one table read
         u64 d2, v2;
         const u64 cmask = E == 5 ? 0xffffffffffull : 0xffffffffull;
@@ -170,7 +221,17 @@ DEVI bool search_begin_p(const DevIndex& ix, const u64* row, int W, bool dirty, 
     S.steps = len - 16; S.tm = tm; S.kg = 0;
     S.cur.row = row; S.cur.W = W; S.cur.dirty = dirty;
     const int E = ix.t_e;
-    if ((!FIXED || LOCATED) && ix.t20 && len >= 16 + E) {
+    if ((!FIXED || LOCATED) && ix.t20 && ix.t_b) {
+        // the balanced table: index and depth from the 32 bases of the one row request
+        int D; u64 idx;
+        if (th_slot(x, mbits, len, ix.t_b, s_th_tab, idx, D)) {
+            const int oc = th_outcome<FIXED>(ix.t20[idx], D, len, S, out, n_hash);
+            if (oc == 1) return false;
+            if (oc == 3) return true;
+            if (oc == 2) { S.cur.pos = tm + D; S.cur.buf = D < 32 ? x >> (2 * D) : 0ull; S.cur.have = 32 - D; return true; }      // have = 0: next3 reloads
+        }
+        // a letter outside the alphabet among them, a seed shorter than the table is deep there, or an oversized interval: the 16-mer path
+    } else if ((!FIXED || LOCATED) && ix.t20 && len >= 16 + E) {
         // the 16-mer lookup and the first E extensions in one table read
         if (((mbits >> 16) & ((1u << E) - 1)) == 0) {
             const u32 dE = (u32)(D >> 32);
@@ -405,6 +466,7 @@ k_seed_first(DevIndex ix, const char* __restrict__ seq, PackedRows pr, ReadGeom 
     __shared__ u64 s_sp0[STAGE ? SEED_CHUNK : 1];
     __shared__ u32 s_hits0[STAGE ? SEED_CHUNK : 1];
     __shared__ u16 s_ml0[STAGE ? SEED_CHUNK : 1];
+    th_tab_fill(ix);
     const u64* c3 = KG ? kgram_c3(ix, s_c3) : nullptr;
     const WaveLogT wl_t = wavelog_begin();
     int L = gm.L;                                     // length of the lane's current read
@@ -781,6 +843,7 @@ k_seed_second(DevIndex ix, const char* __restrict__ seq, PackedRows pr, ReadGeom
     const long chunk_begin = (long)blockIdx.x * chunk;
     if (chunk_begin >= total) return;
     __shared__ u64 s_c3[KG ? 27 : 1];
+    th_tab_fill(ix);
     const u64* c3 = KG ? kgram_c3(ix, s_c3) : nullptr;
     const WaveLogT wl_t = wavelog_begin();
     const long chunk_end = chunk_begin + chunk < total ? chunk_begin + chunk : total;
@@ -936,6 +999,7 @@ k_seed_extra(DevIndex ix, const char* __restrict__ seq, PackedRows pr, ReadGeom 
     const long chunk_begin = (long)blockIdx.x * chunk;
     if (chunk_begin >= total) return;
     __shared__ u64 s_c3[KG ? 27 : 1];
+    th_tab_fill(ix);
     const u64* c3 = KG ? kgram_c3(ix, s_c3) : nullptr;
     const WaveLogT wl_t = wavelog_begin();
     const long chunk_end = chunk_begin + chunk < total ? chunk_begin + chunk : total;

@@ -497,6 +497,15 @@ int bmbs_index_build(const char* fasta, const char* prefix, int n_threads);
  * FASTA / .pac preparation.  BMBS_ENODEV without a device (no silent fall-back to the host builder).                       */
 int bmbs_index_build_device(int device_id, const char* fasta, const char* prefix, int n_threads);
 
+/* Index and depth of a seed start in the balanced outcome table (bmbs_index_attach builds it for texts of 2^32 symbols and more,
+ * BMBS_TDEPTH=h32|h33 forces it), as the seeding kernels compute them.  bases = the 32 bases read[tm .. tm+31], 2 bits each from
+ * bit 0 on (A 0, C 1, G 2, T 3; C counts as T), not_acgt = one bit each, set where the character is none of these, len = the
+ * characters read[tm ..] has, bits = 32 or 33.  The index is the first `bits` bits of the code T -> 0, G -> 10, A -> 11 of the
+ * letters (first code bit highest); *depth gets the letters whose code lies completely inside them, 16 .. 32.  Returns the index, or
+ * -1 when the lookup takes the 16-mer path instead: a character outside ACGT among the *depth letters, or len < *depth (-2: bad
+ * `bits`).  Host arithmetic only: needs no context and no device.                                                                */
+int64_t bmbs_outcome_index(uint64_t bases, uint32_t not_acgt, int32_t len, int32_t bits, int32_t* depth);
+
 /* first 16 hex digits of the sha256 over the library's sources (in the Makefile's LIB_SRCS order) at build time: lets a run show
  * that the .so it loaded was built from the sources it sits next to (bitmapperbs_amd.capi.sources_id() recomputes it)          */
 const char* bmbs_build_id(void);
