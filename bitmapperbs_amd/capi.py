@@ -26,6 +26,7 @@ SYMBOLS = [
     "bmbs_qual_classes", "bmbs_pack_quals", "bmbs_map_se_packedq", "bmbs_map_pe_packedq",
     "bmbs_text_sorted_index", "bmbs_bam_sort", "bmbs_bam_sort_index",
     "bmbs_bam_dup_sigs", "bmbs_text_sorted_dup", "bmbs_dup_select",
+    "bmbs_text_sorted_clip", "bmbs_bam_methyl", "bmbs_bam_sort_methyl", "bmbs_methyl_sites",
     "bmbs_outcome_index",
 ]
 
@@ -73,6 +74,15 @@ assert (BAI_CHUNK_DTYPE.itemsize, BAI_WIN_DTYPE.itemsize, BAI_REF_DTYPE.itemsize
 DUP_SIG_DTYPE = np.dtype([("ref_lo", "<i4"), ("pos_lo", "<i4"), ("ref_hi", "<i4"), ("pos_hi", "<i4"), ("orient", "<u4"), ("score", "<u4")])
 assert DUP_SIG_DTYPE.itemsize == 24
 DUP_NONE = 0x80000000        # in orient: the template has no signature
+
+# numpy view of bmbs_methyl_site, and bmbs_methyl_params (methylation counts: bmbs_bam_methyl / bmbs_bam_sort_methyl / bmbs_methyl_sites)
+METHYL_SITE_DTYPE = np.dtype([("ref", "<i4"), ("pos", "<i4"), ("meth", "<u4"), ("unmeth", "<u4"), ("kind", "<u4"), ("pad", "<u4")])
+assert METHYL_SITE_DTYPE.itemsize == 24
+
+
+class MethylParams(C.Structure):
+    _fields_ = [("contexts", C.c_int32), ("min_mapq", C.c_int32), ("min_phred", C.c_int32), ("reserved", C.c_int32)]
+
 
 ST_UNMAPPED, ST_UNIQUE, ST_AMBIG, ST_OFFEND = 0, 1, 2, 3
 
@@ -205,6 +215,15 @@ def lib() -> C.CDLL:
     if hasattr(L, "bmbs_outcome_index"):                 # (the balanced outcome table; BMBS_LIB may name an older build, as above)
         L.bmbs_outcome_index.argtypes = [u64, C.c_uint32, i32, i32, C.POINTER(i32)]
         L.bmbs_outcome_index.restype = i64
+    if hasattr(L, "bmbs_methyl_sites"):                  # (methylation counts; BMBS_LIB may name an older build, as above)
+        L.bmbs_text_sorted_clip.argtypes = [vp, vp, i64, C.POINTER(i64)]
+        L.bmbs_text_sorted_clip.restype = C.c_int
+        L.bmbs_bam_methyl.argtypes = [vp, vp, u64, vp, i64, vp, C.POINTER(MethylParams), C.POINTER(i64)]
+        L.bmbs_bam_methyl.restype = C.c_int
+        L.bmbs_bam_sort_methyl.argtypes = [vp, vp, C.POINTER(MethylParams), C.POINTER(i64)]
+        L.bmbs_bam_sort_methyl.restype = C.c_int
+        L.bmbs_methyl_sites.argtypes = [vp, vp, i64, C.POINTER(i64)]
+        L.bmbs_methyl_sites.restype = C.c_int
     L.bmbs_map_pe_text.argtypes = [vp, vp, u64, vp, u64, i64, i32, vp, u64, C.POINTER(u64), C.POINTER(i64)]
     L.bmbs_map_pe_text.restype = C.c_int
     L.bmbs_retries.argtypes = [vp]
@@ -230,7 +249,7 @@ def lib() -> C.CDLL:
 
 
 LIB_SRCS = ("bmbs_api.hip", "bmbs_kernels.hip", "k_index.hip", "k_rows.hip", "k_qualpack.hip", "k_attach.hip", "k_scan.hip", "k_seed.hip", "k_vote.hip", "k_filter.hip", "k_reduce.hip", "k_align.hip", "k_finalize.hip", "k_pe_fast.hip", "k_pe_sensitive.hip",
-            "bmbs_textpath.hip", "bmbs_text.hip", "bmbs_bam.hip", "bmbs_inflate.hip", "k_bamsort.hip", "k_bai.hip", "k_markdup.hip", "bmbs_bytes.h", "bmbs_host.h", "bmbs_dev.h", "bmbs_sort.h", "../../include/bmbs.h",
+            "bmbs_textpath.hip", "bmbs_text.hip", "bmbs_bam.hip", "bmbs_inflate.hip", "k_bamsort.hip", "k_bai.hip", "k_markdup.hip", "k_methyl.hip", "bmbs_bytes.h", "bmbs_host.h", "bmbs_dev.h", "bmbs_sort.h", "../../include/bmbs.h",
             "index_io.cpp", "index_io.h", "index_build_gpu.hip", "build_id.cpp")
 
 

@@ -217,6 +217,14 @@ struct Lane {
     DevBuf dp_in, dp_len, dp_off, dp_sig, dp_key, dp_key2, dp_idx, dp_idx2, dp_dup, dp_tmpl;
     int64_t dup_n2 = -1;
     bool dup_pe = false, dup_done = false;
+    // methylation counts (k_methyl.hip): the records of bmbs_bam_methyl as uploaded with their lengths, offsets and clips; events per record
+    // and their scan; the (key, value) events before and behind the pair sort; the reduction's work arrays; the sites of earlier slices of
+    // records as pairs (mt_slice: where each slice's lie); the result (bmbs_methyl_sites: mt_sites of them, -1: none); the clips of a sorted
+    // text call.  ms_n = records of the last bmbs_bam_sort call, still in bs_in / bs_off / bs_len (-1: none, as for bai_n)
+    DevBuf mt_in, mt_len, mt_off, mt_clip, mt_cnt, mt_eoff, mt_ev, mt_work, mt_acc, mt_site, mt_cl2;
+    std::vector<std::pair<u64, u64>> mt_slice;
+    int64_t ms_n = -1, mt_sites = -1;
+    u64 ms_bytes = 0;
     DevBuf z_comp, z_off, z_text, z_err, z_nl, z_comp2, z_off2, z_err2;         // bmbs_inflate_bgzf; (…2: mate 2 of bmbs_text_open_bgzf)
     struct OpenText { bool valid = false, pe = false; u64 bytes1 = 0, bytes2 = 0; int64_t n = 0; } open_text;      // between bmbs_text_open_bgzf and bmbs_text_map_open
     u32* h_info = nullptr;                              // page-locked: 8 info words + 4 totals of the text path

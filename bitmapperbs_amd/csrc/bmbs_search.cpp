@@ -16,6 +16,8 @@
 //          strand, of the records --bam writes; sorted on the device, see "--bam --sort" below; needs --out-parts 1)
 //          --bam --sort --markdup (PCR duplicates get flag 0x400 in that file: Picard's pair-level rule, decided on the device, see
 //          "--markdup" below; nothing else in any record changes)
+//          --bam --sort --methyl <prefix> [--CpG] [--CHG] [--CHH] (per-cytosine methylation counts of that file's records, computed on the
+//          device while its blocks are written: <prefix>_CpG.bedGraph ..., see "--methyl" below)
 //
 // The reference has ONE reader thread and ONE fprintf sink (Process_Reads.cpp:2057-2260, Process_sam_out.cpp:954-1006), which is
 // what limits it.  Round 2 of this driver indexed the lines and formatted the SAM text with the host's
@@ -43,6 +45,8 @@
 #include <unistd.h>
 #include <algorithm>
 #include <atomic>
+#include <cctype>
+#include <cstdint>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -743,13 +747,14 @@ inline uint64_t bam_key_of(const char* r)
 // in Batch.seq order), and a second store of the templates' signatures (bmbs_text_sorted_dup), cut at the SAME edges by the key of
 // (ref_lo, pos_lo) -- templates with equal signatures share a bin, in input order.  Between the passes bmbs_dup_select runs over groups
 // of signature bins and sets a bit per losing template; pass 2 ORs 0x04 into byte 19 (flag 0x400) of the staged copy of its records.
-struct SortBin { std::vector<char> rec; std::vector<uint32_t> len; std::vector<uint64_t> tid; };
+// --methyl, pairs: beside every record its mate-overlap clip (bmbs_text_sorted_clip), which pass 2 hands to bmbs_bam_sort_methyl.
+struct SortBin { std::vector<char> rec; std::vector<uint32_t> len; std::vector<uint64_t> tid; std::vector<uint32_t> clip; };
 struct SigBin { std::vector<bmbs_dup_sig> sig; std::vector<uint64_t> gid; };
 struct SortStore {
     std::vector<uint64_t> edge;                  // bin k holds the keys in [edge[k], edge[k + 1]); the last bin: refID -1
     std::vector<SortBin> bin;
     std::vector<SigBin> sbin;                    // --markdup: the signatures, by the same edges
-    size_t bytes = 0, cap = 0;                   // record bytes + 4 per record (--markdup: + 8, and 32 per signature) held / allowed (--sort-mem)
+    size_t bytes = 0, cap = 0;                   // record bytes + 4 per record (--markdup: + 8, and 32 per signature; --methyl of pairs: + 4) held / allowed (--sort-mem)
     long records = 0, templates = 0, with_sig = 0;
     void init(const bmbs_index_view& v, long want_bins)
     {
@@ -769,11 +774,12 @@ struct SortStore {
         edge.push_back(~(uint64_t)0);
     }
     size_t bin_of(uint64_t key) const { return (size_t)(std::upper_bound(edge.begin(), edge.end() - 1, key) - edge.begin()) - 1; }
-    // the sorted records of one batch (tmpl: the template of each within the batch, base: the batch's first template id; --markdup);
-    // false: the store's cap would be exceeded
-    bool add(Pool& pool, const char* recs, size_t nbytes, const uint64_t* key, const uint32_t* len, size_t n, const uint32_t* tmpl = nullptr, uint64_t base = 0)
+    // the sorted records of one batch (tmpl: the template of each within the batch, base: the batch's first template id; --markdup;
+    // clip: the clip of each; --methyl of pairs); false: the store's cap would be exceeded
+    bool add(Pool& pool, const char* recs, size_t nbytes, const uint64_t* key, const uint32_t* len, size_t n, const uint32_t* tmpl = nullptr, uint64_t base = 0,
+             const uint32_t* clip = nullptr)
     {
-        const size_t per = tmpl ? 12 : 4;
+        const size_t per = (tmpl ? 12 : 4) + (clip ? 4 : 0);
         if (bytes + nbytes + per * n > cap) return false;
         struct Slice { size_t k, lo, hi; };
         std::vector<Slice> sl;
@@ -793,6 +799,7 @@ struct SortStore {
                 b.rec.insert(b.rec.end(), recs + off[sl[j].lo], recs + off[sl[j].hi]);
                 b.len.insert(b.len.end(), len + sl[j].lo, len + sl[j].hi);
                 if (tmpl) for (size_t i = sl[j].lo; i < sl[j].hi; i++) b.tid.push_back(base + tmpl[i]);
+                if (clip) b.clip.insert(b.clip.end(), clip + sl[j].lo, clip + sl[j].hi);
             }
         });
         bytes += nbytes + per * n; records += (long)n;
@@ -966,7 +973,8 @@ void sort_plan(const SortStore& st, size_t budget, std::vector<SortUnit>& units)
 }
 // the records and lengths of a unit, one behind the other, into a staging buffer
 // dup (--markdup, else NULL): a bit per template id; the copy of every record of a marked template gets flag 0x400 (byte 19 |= 0x04)
-void sort_stage(const SortStore& st, const SortUnit& u, Pool& pool, char* dst, uint32_t* len, const uint64_t* dup)
+// clip (--methyl of pairs, else NULL): the records' clips, laid out like the lengths
+void sort_stage(const SortStore& st, const SortUnit& u, Pool& pool, char* dst, uint32_t* len, const uint64_t* dup, uint32_t* clip)
 {
     auto marked = [&](uint64_t t) { return (dup[t >> 6] >> (t & 63)) & 1; };
     if (!u.sub) {
@@ -979,6 +987,7 @@ void sort_stage(const SortStore& st, const SortUnit& u, Pool& pool, char* dst, u
                 if (b.len.empty()) continue;
                 memcpy(dst + at[(size_t)j], b.rec.data(), b.rec.size());
                 memcpy(len + ln[(size_t)j], b.len.data(), b.len.size() * 4);
+                if (clip) memcpy(clip + ln[(size_t)j], b.clip.data(), b.clip.size() * 4);
                 if (dup) { size_t o = at[(size_t)j]; for (size_t i = 0; i < b.len.size(); o += b.len[i], i++) if (marked(b.tid[i])) dst[o + 19] |= 0x04; }
             }
         });
@@ -993,8 +1002,83 @@ void sort_stage(const SortStore& st, const SortUnit& u, Pool& pool, char* dst, u
         memcpy(dst, b.rec.data() + at, b.len[i]);
         if (dup && marked(b.tid[i])) dst[19] |= 0x04;
         dst += b.len[i];
+        if (clip) clip[taken] = b.clip[i];
         len[taken++] = b.len[i];
     }
+}
+
+// ---- --bam --sort --methyl <prefix>: methylation counts per cytosine of the sorted file's records -----------------------------------------
+// Every pass-2 call leaves the sites of its own records on the device (bmbs_bam_sort_methyl behind bmbs_bam_sort: the records are still
+// there, duplicates already carry 0x400); only the sites come back.  Calls go in key order and a record reaches at most its span behind
+// its position, so a call's sites overlap only the tail of what the calls before it left: the writing thread merges the two sorted
+// lists from the first new position on and adds the counts of equal (ref, pos).  The result does not depend on how the records were
+// cut into calls.  The files are written once the BAM is complete.
+inline bool site_less(const bmbs_methyl_site& a, const bmbs_methyl_site& b) { return a.ref != b.ref ? a.ref < b.ref : a.pos < b.pos; }
+void methyl_merge(std::vector<bmbs_methyl_site>& all, const bmbs_methyl_site* add, size_t n)
+{
+    if (!n) return;
+    const size_t from = (size_t)(std::lower_bound(all.begin(), all.end(), add[0], site_less) - all.begin());
+    std::vector<bmbs_methyl_site> tail(all.begin() + (long)from, all.end());
+    all.resize(from);
+    size_t i = 0, j = 0;
+    while (i < tail.size() || j < n) {
+        if (j == n || (i < tail.size() && site_less(tail[i], add[j]))) all.push_back(tail[i++]);
+        else if (i == tail.size() || site_less(add[j], tail[i])) all.push_back(add[j++]);
+        else { bmbs_methyl_site s = tail[i++]; s.meth += add[j].meth; s.unmeth += add[j].unmeth; j++; all.push_back(s); }
+    }
+}
+// The index holds a pseudo-random letter for every base of the FASTA that is not A, C, G or T: a site whose position or context window
+// (CpG: the two bases, CHG / CHH: the three) touches such a base says nothing about the genome.  runs[ref] = the [beg, end) runs of
+// such bases of sequence ref, read from the FASTA the way the index builder reads it; false: the file cannot be read, or its
+// sequences are not the index's
+bool non_acgt_runs(const std::string& fasta, const bmbs_index_view& v, std::vector<std::vector<std::pair<int64_t, int64_t>>>& runs)
+{
+    FILE* f = fopen(fasta.c_str(), "rb");
+    if (!f) return false;
+    runs.clear();
+    std::vector<char> buf(1 << 22);
+    bool hdr = false, bol = true;
+    int64_t pos = 0;
+    size_t got;
+    while ((got = fread(buf.data(), 1, buf.size(), f)) > 0)
+        for (size_t i = 0; i < got; i++) {
+            const unsigned char c = (unsigned char)buf[i];
+            if (hdr) { if (c == '\n') { hdr = false; bol = true; } continue; }
+            if (c == '\n') { bol = true; continue; }
+            if (bol && c == '>') { hdr = true; runs.emplace_back(); if (runs.size() > 1 && pos != (int64_t)v.chrom_len[runs.size() - 2]) { fclose(f); return false; } pos = 0; continue; }
+            bol = false;
+            if (c <= ' ') continue;
+            if (runs.empty()) { fclose(f); return false; }
+            const int u = toupper(c);
+            if (u != 'A' && u != 'C' && u != 'G' && u != 'T') {
+                auto& r = runs.back();
+                if (!r.empty() && r.back().second == pos) r.back().second = pos + 1; else r.push_back({pos, pos + 1});
+            }
+            pos++;
+        }
+    fclose(f);
+    return (int)runs.size() == v.n_chrom && pos == (int64_t)v.chrom_len[runs.size() - 1];
+}
+inline bool methyl_touches(const std::vector<std::pair<int64_t, int64_t>>& runs, const bmbs_methyl_site& s)
+{
+    const int64_t w = (s.kind & 3u) == 0 ? 1 : 2;
+    const int64_t lo = (s.kind & 4u) ? s.pos - w : s.pos, hi = (s.kind & 4u) ? s.pos : s.pos + w;       // the window [lo, hi]
+    auto it = std::upper_bound(runs.begin(), runs.end(), std::make_pair(hi, INT64_MAX));                 // the first run that begins behind hi
+    return it != runs.begin() && (it - 1)->second > lo;
+}
+// <prefix>_<context>.bedGraph in MethylDackel's column layout; the percentage is rounded half up in integers
+bool methyl_write(const std::string& path, const std::string& prefix, const char* ctx_name, unsigned ctx, const std::vector<bmbs_methyl_site>& sites, const bmbs_index_file* ixf)
+{
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    fprintf(f, "track type=\"bedGraph\" description=\"%s %s methylation levels\"\n", prefix.c_str(), ctx_name);
+    for (const bmbs_methyl_site& s : sites) {
+        if ((s.kind & 3u) != ctx) continue;
+        const uint64_t m = s.meth, u = s.unmeth;
+        fprintf(f, "%s\t%d\t%d\t%llu\t%u\t%u\n", bmbs_index_file_chrom_name(ixf, s.ref), s.pos, s.pos + 1, (unsigned long long)((200 * m + m + u) / (2 * (m + u))), s.meth, s.unmeth);
+    }
+    const bool ok = !ferror(f);
+    return fclose(f) == 0 && ok;
 }
 
 void print_stats(FILE* o, const int64_t st[5])
@@ -1022,6 +1106,7 @@ struct Batch {
     uint64_t sam_bytes = 0;
     std::vector<uint64_t> skey; std::vector<uint32_t> slen; int64_t n_sorted = 0;      // --sort: key and length of each record in `sam`
     std::vector<bmbs_dup_sig> sig; std::vector<uint32_t> tmpl; int64_t n_sig = 0;      // --markdup: the batch's signatures, the template of each record in `sam`
+    std::vector<uint32_t> clip;                                                         // --methyl of pairs: the mate-overlap clip of each record in `sam`
     std::vector<uint32_t> counts1, counts2;
     bmbs_ctx* open_ctx = nullptr;                // compressed input kept on the device: the context that holds this batch's open window
 };
@@ -1080,6 +1165,8 @@ int main(int argc, char** argv)
     std::vector<int> devices;
     long batch = 500000;
     bool verbose = false, unmapped_out = false, pbat = false, bam = false, print_parts = false, print_plan = false, sort_out = false, bai_out = false, markdup = false;
+    std::string methyl;                          // --methyl <prefix>: <prefix>_CpG.bedGraph ... from the sorted file's records
+    bmbs_methyl_params mpar = {0, 10, 5, 0};     // --CpG (the default) --CHG --CHH, --methyl-min-mapq, --methyl-min-phred
     double sort_mem_gib = 0;                     // --sort-mem: cap of the in-memory record store of --sort (0: half of the machine's memory)
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -1130,12 +1217,23 @@ int main(int argc, char** argv)
         else if (a == "--sort-mem") sort_mem_gib = atof(val());
         else if (a == "--markdup") markdup = true;                   // --bam --sort --markdup: flag 0x400 on PCR duplicates, decided on the device
         else if (a == "--bai") bai_out = true;                        // --bam --sort --bai: <out>.bai beside the sorted file, from the same run
+        else if (a == "--methyl") methyl = val();                     // --bam --sort --methyl <prefix>: methylation counts per cytosine, from the device
+        else if (a == "--CpG") mpar.contexts |= 1;                    // (the reference's names for the contexts of its own extractor)
+        else if (a == "--CHG") mpar.contexts |= 2;
+        else if (a == "--CHH") mpar.contexts |= 4;
+        else if (a == "--methyl-min-mapq") mpar.min_mapq = atoi(val());
+        else if (a == "--methyl-min-phred") mpar.min_phred = atoi(val());
         else { fprintf(stderr, "bmbs_search: unsupported option %s\n", a.c_str()); return 2; }
     }
     if (sort_out && !bam) { fprintf(stderr, "bmbs_search: --sort needs --bam\n"); return 2; }
     if (sort_out && parts > 1) { fprintf(stderr, "bmbs_search: --sort writes one file (--out-parts 1)\n"); return 2; }
     if (bai_out && !sort_out) { fprintf(stderr, "bmbs_search: --bai needs --sort\n"); return 2; }
     if (markdup && !sort_out) { fprintf(stderr, "bmbs_search: --markdup needs --sort\n"); return 2; }
+    const bool methyl_out = !methyl.empty();
+    if (methyl_out && !sort_out) { fprintf(stderr, "bmbs_search: --methyl needs --sort\n"); return 2; }
+    if (!methyl_out && (mpar.contexts || mpar.min_mapq != 10 || mpar.min_phred != 5)) { fprintf(stderr, "bmbs_search: --CpG, --CHG, --CHH, --methyl-min-mapq and --methyl-min-phred need --methyl\n"); return 2; }
+    if (mpar.min_mapq < 0 || mpar.min_mapq > 255 || mpar.min_phred < 0 || mpar.min_phred > 255) { fprintf(stderr, "bmbs_search: --methyl-min-mapq and --methyl-min-phred take 0..255\n"); return 2; }
+    if (!mpar.contexts) mpar.contexts = 1;
     if (bai_out) {
         // the index lies beside a file: a device or a pipe has no such place
         struct stat osb;
@@ -1157,7 +1255,7 @@ int main(int argc, char** argv)
         return 0;
     }
     if (index.empty() || (seq.empty() && (seq1.empty() || seq2.empty()))) {
-        fprintf(stderr, "usage: bmbs_search --index <genome.fa> [--index_folder dir] [-t threads]\n       bmbs_search --search <index> (--seq r.fq | --seq1 a.fq --seq2 b.fq) [-o out.sam] [-e f] [--min n] [--max n] [--sensitive] [--pbat] [--unmapped_out] [--ambiguous_out] [--bam [--sort [--sort-mem GiB] [--markdup] [--bai]]] [--mapstats f] [-t io_threads] [--out-parts n]\n");
+        fprintf(stderr, "usage: bmbs_search --index <genome.fa> [--index_folder dir] [-t threads]\n       bmbs_search --search <index> (--seq r.fq | --seq1 a.fq --seq2 b.fq) [-o out.sam] [-e f] [--min n] [--max n] [--sensitive] [--pbat] [--unmapped_out] [--ambiguous_out] [--bam [--sort [--sort-mem GiB] [--markdup] [--bai] [--methyl prefix [--CpG] [--CHG] [--CHH] [--methyl-min-mapq n] [--methyl-min-phred n]]]] [--mapstats f] [-t io_threads] [--out-parts n]\n");
         return 2;
     }
     if (batch < 1) batch = 1;
@@ -1354,7 +1452,14 @@ int main(int argc, char** argv)
             std::string h = sort_out ? "@HD\tVN:1.4\tSO:coordinate\n" : "@HD\tVN:1.4\tSO:unsorted\n";
             for (int i = 0; i < view.n_chrom; i++) { h += "@SQ\tSN:" + chrom_names[(size_t)i] + "\tLN:"; put_uint(h, view.chrom_len[i]); h += '\n'; }
             h += "@PG\tID:BitMapperBS\tVN:1.0.2.3\tCL:";
-            for (int i = 0; i < argc; i++) { h += argv[i]; h += ' '; }
+            // (--methyl and its options shape no byte of this file, so they stay out of its header: the BAM and its .bai are the same
+            // bytes with and without them)
+            for (int i = 0; i < argc; i++) {
+                const std::string a = argv[i];
+                if (a == "--methyl" || a == "--methyl-min-mapq" || a == "--methyl-min-phred") { i++; continue; }
+                if (a == "--CpG" || a == "--CHG" || a == "--CHH") continue;
+                h += a; h += ' ';
+            }
             h += '\n';
             if (bam) {
                 // BAM header: magic, the same text, the reference dictionary; one BGZF block series
@@ -1608,7 +1713,8 @@ int main(int argc, char** argv)
                 bool room = true;
                 if (b->n && !failed && markdup) room = sort_store.add_sigs(wpool, b->sig.data(), (size_t)b->n_sig, tmpl_base);
                 if (b->n && !failed && b->sam_bytes && room)
-                    room = sort_store.add(wpool, b->sam.p, (size_t)b->sam_bytes, b->skey.data(), b->slen.data(), (size_t)b->n_sorted, markdup ? b->tmpl.data() : nullptr, tmpl_base);
+                    room = sort_store.add(wpool, b->sam.p, (size_t)b->sam_bytes, b->skey.data(), b->slen.data(), (size_t)b->n_sorted, markdup ? b->tmpl.data() : nullptr, tmpl_base,
+                                          methyl_out && pe ? b->clip.data() : nullptr);
                 if (b->n && markdup) tmpl_base += (uint64_t)b->n_sig;
                 if (!room) {
                     char msg[256];
@@ -1679,6 +1785,12 @@ int main(int argc, char** argv)
                             if (bmbs_text_sorted_dup(ctx, b->sig.data(), b->n, &b->n_sig, b->tmpl.data(), lines, &nt)) { fail(bmbs_last_error(ctx)); b->sam_bytes = 0; }
                             else if (nt != b->n_sorted || b->n_sig != b->n) { fail("--markdup: the batch's templates do not match its records"); b->sam_bytes = 0; }
                         }
+                        if (methyl_out && pe && !failed) {
+                            int64_t nc = 0;
+                            b->clip.resize((size_t)lines + 1);
+                            if (bmbs_text_sorted_clip(ctx, b->clip.data(), lines, &nc)) { fail(bmbs_last_error(ctx)); b->sam_bytes = 0; }
+                            else if (nc != b->n_sorted) { fail("--methyl: the batch's clips do not match its records"); b->sam_bytes = 0; }
+                        }
                     }
                     break;
                 }
@@ -1711,6 +1823,7 @@ int main(int argc, char** argv)
     double t_select = t_pass1;
     BaiIndex bai;
     bai.init((size_t)view.n_chrom);
+    std::vector<bmbs_methyl_site> meth_sites;    // --methyl: the sites of the calls so far, merged
     if (sort_out && !failed) {
         Part& pt = *P_[0];
         const char* e = getenv("BMBS_SORT_CALL_BYTES");
@@ -1746,7 +1859,7 @@ int main(int argc, char** argv)
         for (const SortUnit& u : units) { max_bytes = std::max(max_bytes, u.bytes); max_n = std::max(max_n, u.n); }
         e = getenv("BMBS_SORT_SLOTS");
         const int n_slots = (int)std::max<size_t>(1, std::min<size_t>({(size_t)(e ? atoi(e) : 2), ctxs.size(), units.size(), (size_t)4}));
-        struct Slot { Pinned in, out; std::vector<uint32_t> len; size_t unit = 0; uint64_t out_bytes = 0; BaiPieces bai; };
+        struct Slot { Pinned in, out; std::vector<uint32_t> len, clip; size_t unit = 0; uint64_t out_bytes = 0; BaiPieces bai; std::vector<bmbs_methyl_site> site; int64_t n_site = 0; };
         std::vector<Slot> slots((size_t)n_slots);
         if (!units.empty()) {
             // (the mapping's page-locked windows are of no use here: a call is larger than a batch)
@@ -1755,6 +1868,7 @@ int main(int argc, char** argv)
             std::atomic<bool> ok(true);
             for (Slot& sl : slots) {
                 sl.in.kind = 1; sl.out.kind = 2; sl.len.resize(max_n + 1);
+                if (methyl_out && pe) sl.clip.resize(max_n + 1);
                 th.emplace_back([&] { if (!sl.in.need(max_bytes + 64)) ok = false; });
                 th.emplace_back([&] { if (!sl.out.need((max_bytes / 0xff00 + 1) * 65536 + 64)) ok = false; });
             }
@@ -1770,7 +1884,7 @@ int main(int argc, char** argv)
                 for (size_t i = 0; i < units.size(); i++) {
                     Slot* sl = free_s.get();
                     sl->unit = i;
-                    if (!failed) sort_stage(sort_store, units[i], spool, sl->in.p, sl->len.data(), markdup ? dup_bits.data() : nullptr);
+                    if (!failed) sort_stage(sort_store, units[i], spool, sl->in.p, sl->len.data(), markdup ? dup_bits.data() : nullptr, methyl_out && pe ? sl->clip.data() : nullptr);
                     staged_s.put(sl);
                 }
                 for (int i = 0; i < n_slots; i++) staged_s.put(nullptr);
@@ -1791,6 +1905,16 @@ int main(int argc, char** argv)
                             break;
                         }
                         if (bai_out && !failed && !sl->bai.fetch(ctx)) { fail(bmbs_last_error(ctx)); sl->out_bytes = 0; }
+                        // --methyl: the call's records are still on the device (the staged copies: duplicates carry 0x400)
+                        sl->n_site = 0;
+                        if (methyl_out && !failed) {
+                            int64_t ns = 0;
+                            if (bmbs_bam_sort_methyl(ctx, pe ? sl->clip.data() : nullptr, &mpar, &ns)) { fail(bmbs_last_error(ctx)); sl->out_bytes = 0; }
+                            else {
+                                if ((size_t)ns > sl->site.size()) sl->site.resize((size_t)ns + (size_t)ns / 8);
+                                if (bmbs_methyl_sites(ctx, sl->site.data(), (int64_t)sl->site.size(), &sl->n_site)) { fail(bmbs_last_error(ctx)); sl->out_bytes = 0; sl->n_site = 0; }
+                            }
+                        }
                         done_s.put((long)sl->unit, sl);
                     }
                 });
@@ -1803,6 +1927,7 @@ int main(int argc, char** argv)
                     done += (size_t)w;
                 }
                 if (bai_out && !failed && !bai.add(sl->bai, (uint64_t)pt.out_off)) fail("--bai: a record names a sequence the header does not have");
+                if (methyl_out && !failed) methyl_merge(meth_sites, sl->site.data(), (size_t)sl->n_site);
                 pt.out_off += (size_t)sl->out_bytes;
                 free_s.put(sl);
             }
@@ -1834,6 +1959,26 @@ int main(int argc, char** argv)
             if (fd < 0 || done < ix.size() || ::close(fd) != 0) { fprintf(stderr, "bmbs_search: cannot write %s.bai: %s\n", out.c_str(), strerror(errno)); failed = true; }
         }
     }
+    // --methyl: the files, written once the BAM is complete; sites that touch a base the FASTA does not spell A, C, G or T are left out
+    static const char* const ctx_names[3] = {"CpG", "CHG", "CHH"};
+    size_t meth_n[3] = {0, 0, 0}, meth_calls[3] = {0, 0, 0}, meth_dropped = 0;
+    if (methyl_out && !failed) {
+        std::vector<std::vector<std::pair<int64_t, int64_t>>> runs;
+        if (!non_acgt_runs(index, view, runs)) fprintf(stderr, "bmbs_search: --methyl: cannot read the sequences of the index from %s: sites at bases other than A, C, G and T are not filtered out\n", index.c_str());
+        else {
+            size_t kept = 0;
+            for (const bmbs_methyl_site& s : meth_sites) if (runs[(size_t)s.ref].empty() || !methyl_touches(runs[(size_t)s.ref], s)) meth_sites[kept++] = s;
+            meth_dropped = meth_sites.size() - kept;
+            meth_sites.resize(kept);
+        }
+        for (const bmbs_methyl_site& s : meth_sites) { meth_n[s.kind & 3u]++; meth_calls[s.kind & 3u] += (size_t)s.meth + s.unmeth; }
+        for (unsigned x = 0; x < 3 && !failed; x++) {
+            if (!((mpar.contexts >> x) & 1)) continue;
+            const std::string path = methyl + "_" + ctx_names[x] + ".bedGraph";
+            if (!methyl_write(path, methyl, ctx_names[x], x, meth_sites, ixf)) { fprintf(stderr, "bmbs_search: cannot write %s: %s\n", path.c_str(), strerror(errno)); failed = true; }
+        }
+    }
+    if (failed && methyl_out) for (unsigned x = 0; x < 3; x++) if ((mpar.contexts >> x) & 1) ::unlink((methyl + "_" + ctx_names[x] + ".bedGraph").c_str());
     if (failed && sort_out && P_[0]->regular) ::unlink(out.c_str());      // a sorted file is whole or absent (a device or a pipe is left alone)
     if (failed && bai_out && P_[0]->regular) ::unlink((out + ".bai").c_str());      // ... and so is its index
     if (failed) { fprintf(stderr, "bmbs_search: failed\n"); return 1; }
@@ -1848,11 +1993,14 @@ int main(int argc, char** argv)
                 total_records, t_loaded - t_start, t_end - t_loaded, t_joined - t_loaded, live_parts, t_read, t_gpu, n_ctx, t_format, t_write, io_threads, batch,
                 n_owner, contexts, parts);
     if (verbose && sort_out) {
-        char ixs[320] = "";
+        char ixs[640] = "";
         if (bai_out) snprintf(ixs, sizeof ixs, ", index: chunks %zu, windows %zu, %zu bytes", bai.n_chunks(), bai.n_windows(), bai_bytes);
         if (markdup)
             snprintf(ixs + strlen(ixs), sizeof ixs - strlen(ixs), ", markdup: templates %ld, with signature %ld, duplicates %zu (select calls %zu, %.3fs of pass 2)", sort_store.templates,
                      sort_store.with_sig, n_dup, select_calls, t_select - t_pass1);
+        if (methyl_out)
+            snprintf(ixs + strlen(ixs), sizeof ixs - strlen(ixs), ", methyl: sites CpG %zu CHG %zu CHH %zu, calls CpG %zu CHG %zu CHH %zu, sites left out at bases other than ACGT %zu", meth_n[0],
+                     meth_n[1], meth_n[2], meth_calls[0], meth_calls[1], meth_calls[2], meth_dropped);
         fprintf(stderr, "[bmbs_search] sort: bins %zu (one of them for records without a reference), pass-2 calls %zu, store bytes %zu (%ld records), pass 1 %.3fs (mapping, binning), pass 2 %.3fs (sort, deflate, write)%s\n",
                 sort_store.bin.size(), sort_calls, sort_store.bytes, sort_store.records, t_pass1 - t_loaded, t_pass2 - t_pass1, ixs);
     }

@@ -3,7 +3,8 @@
 // (bmbs_inflate_bgzf, bmbs_text_open_bgzf / bmbs_text_map_open), records -> SAM text or BAM records in BGZF blocks.  The mapping in
 // between is bmbs_api.hip's (lane_enqueue / lane_settle).  Kernels: bmbs_text.hip, bmbs_bam.hip, bmbs_inflate.hip, k_bamsort.hip (the
 // coordinate sort of BAM records: BMBS_TEXT_BAM_SORTED, bmbs_bam_sort), k_bai.hip (the .bai pieces of a sorted call: bmbs_bam_sort_index),
-// k_markdup.hip (duplicate marking: bmbs_bam_dup_sigs, bmbs_text_sorted_dup, bmbs_dup_select).
+// k_markdup.hip (duplicate marking: bmbs_bam_dup_sigs, bmbs_text_sorted_dup, bmbs_dup_select), k_methyl.hip (methylation counts per
+// cytosine: bmbs_bam_methyl, bmbs_bam_sort_methyl, bmbs_methyl_sites, bmbs_text_sorted_clip).
 #include "bmbs_host.h"
 #define DEVI __device__ __forceinline__
 #include "bmbs_text.hip"
@@ -12,6 +13,7 @@
 #include "k_bamsort.hip"
 #include "k_bai.hip"
 #include "k_markdup.hip"
+#include "k_methyl.hip"
 
 // the constants the kernels of this file read: x^(2^n) mod P of CRC-32 for the BGZF blocks' CRCs (bmbs_bytes.h: crc_x8n); per device
 void textpath_device_init(Lane* c)
@@ -207,7 +209,7 @@ int lane_map_text(Lane* c, bool pe, const char* text1, u64 bytes1, const char* t
     if (sam_bytes) *sam_bytes = 0;
     if (n_lines_out) *n_lines_out = 0;
     if ((flags_in & BMBS_TEXT_BAM_SORTED) && !(flags_in & BMBS_TEXT_BAM)) { c->err = "text call: BMBS_TEXT_BAM_SORTED is only valid together with BMBS_TEXT_BAM"; return BMBS_EINVAL; }
-    if (flags_in & BMBS_TEXT_BAM_SORTED) { c->bs_n = -1; c->dup_n2 = -1; }
+    if (flags_in & BMBS_TEXT_BAM_SORTED) { c->bs_n = -1; c->dup_n2 = -1; c->ms_n = -1; }
     if (!c->attached) { c->err = "no index attached"; return BMBS_ESTATE; }
     if (c->n_refs != c->ix.n_chrom) { c->err = "bmbs_sam_refs has not been given the index's reference names"; return BMBS_ESTATE; }
     if (n_records <= 0) { if (flags_in & BMBS_TEXT_BAM_SORTED) { c->bs_n = 0; c->dup_n2 = 0; c->dup_pe = pe; c->dup_done = false; } return BMBS_OK; }
@@ -320,7 +322,8 @@ static int bam_sort_device(Lane* c, const char* raw, const u64* off, const u32* 
 {
     static const bool tiny = getenv("BMBS_BSG_TINY") != nullptr;
     c->bai_n = -1;                                        // (bs_sorted / bs_soff are rewritten: what bmbs_bam_sort_index would read)
-    c->dup_n2 = -1;                                       // (bs_idx2 is rewritten: what bmbs_text_sorted_dup would read)
+    c->dup_n2 = -1;                                       // (bs_idx2 is rewritten: what bmbs_text_sorted_dup / bmbs_text_sorted_clip would read)
+    c->ms_n = -1;                                         // (bmbs_bam_sort_methyl reads the LAST bmbs_bam_sort call's records, as bmbs_bam_sort_index does)
     ENS(c, c->bs_key, n * 8 + 64); ENS(c, c->bs_key2, n * 8 + 64); ENS(c, c->bs_idx, n * 4 + 64); ENS(c, c->bs_idx2, n * 4 + 64);
     ENS(c, c->bs_slen, n * 4 + 64); ENS(c, c->bs_soff, (n + 1) * 8 + 64); ENS(c, c->bs_sorted, total + 256);
     u32* const info = c->tx_info.as<u32>() + 8;
@@ -678,7 +681,7 @@ int lane_text_map_open(Lane* c, int32_t flags_in, char* sam, u64 sam_cap, u64* s
     if (sam_bytes) *sam_bytes = 0;
     if (n_lines_out) *n_lines_out = 0;
     if ((flags_in & BMBS_TEXT_BAM_SORTED) && !(flags_in & BMBS_TEXT_BAM)) { c->err = "text call: BMBS_TEXT_BAM_SORTED is only valid together with BMBS_TEXT_BAM"; return BMBS_EINVAL; }
-    if (flags_in & BMBS_TEXT_BAM_SORTED) { c->bs_n = -1; c->dup_n2 = -1; }
+    if (flags_in & BMBS_TEXT_BAM_SORTED) { c->bs_n = -1; c->dup_n2 = -1; c->ms_n = -1; }
     if (!c->open_text.valid) { c->err = "text map: no open batch (bmbs_text_open_bgzf first)"; return BMBS_ESTATE; }
     if (c->n_refs != c->ix.n_chrom) { c->err = "bmbs_sam_refs has not been given the index's reference names"; return BMBS_ESTATE; }
     if (!sam) { c->err = "text call: NULL buffer"; return BMBS_EINVAL; }
@@ -837,6 +840,7 @@ static int lane_bam_sort(Lane* c, const char* records, uint64_t bytes, const uin
 {
     if (out_bytes) *out_bytes = 0;
     c->bai_n = -1;                                        // bmbs_bam_sort_index describes the LAST call
+    c->ms_n = -1;                                         // ... and so does bmbs_bam_sort_methyl
     if (n_in < 0 || n_in >= (1ll << 31) || (flags & ~BMBS_BAMSORT_RAW)) { c->err = "bam sort: bad argument"; return BMBS_EINVAL; }
     if (n_in && (!records || !len)) { c->err = "bam sort: NULL buffer"; return BMBS_EINVAL; }
     const u64 n = (u64)n_in;
@@ -868,7 +872,11 @@ static int lane_bam_sort(Lane* c, const char* records, uint64_t bytes, const uin
     if (rc) return rc;
     rc = bam_sort_device(c, c->bs_in.as<char>(), c->bs_off.as<u64>(), c->bs_len.as<u32>(), n, bytes, false, nullptr);
     if (rc) return rc;
-    if (rawout) return download_locked(c, out, c->bs_sorted.as<char>(), bytes, c->stream, nullptr);
+    if (rawout) {
+        rc = download_locked(c, out, c->bs_sorted.as<char>(), bytes, c->stream, nullptr);
+        if (!rc) { c->ms_n = (int64_t)n; c->ms_bytes = bytes; }
+        return rc;
+    }
     u64 ztotal = 0;
     rc = bgzf_deflate(c, c->bs_sorted.as<char>(), c->totals.as<u64>() + 23, bytes, &ztotal);
     if (rc) return rc;
@@ -879,6 +887,7 @@ static int lane_bam_sort(Lane* c, const char* records, uint64_t bytes, const uin
     rc = download_locked(c, out, c->sam_out.as<char>(), ztotal, c->stream, nullptr);
     if (rc) return rc;
     c->bai_n = (int64_t)n; c->bai_bytes = bytes; c->bai_z = ztotal; c->bai_done = false;      // (bmbs_bam_sort_index: computed when asked for)
+    c->ms_n = (int64_t)n; c->ms_bytes = bytes;                                                // (bmbs_bam_sort_methyl: bs_in / bs_off / bs_len stay as they are)
     return BMBS_OK;
 }
 
@@ -1144,6 +1153,273 @@ extern "C" int bmbs_bam_dup_sigs(bmbs_ctx* X, const char* records, uint64_t byte
 extern "C" int bmbs_text_sorted_dup(bmbs_ctx* X, bmbs_dup_sig* sig, int64_t sig_cap, int64_t* n_sig, uint32_t* tmpl, int64_t cap, int64_t* n)
 { ON_LANE0(lane_text_sorted_dup(c, sig, sig_cap, n_sig, tmpl, cap, n)); }
 extern "C" int bmbs_dup_select(bmbs_ctx* X, const bmbs_dup_sig* sig, int64_t n, uint8_t* dup, int64_t* n_dup) { ON_LANE0(lane_dup_select(c, sig, n, dup, n_dup)); }
+
+// ---- methylation counts per cytosine (k_methyl.hip) -----------------------------------------------------------------------------------------
+// n (key, value) pairs in ka / va (kb / vb: as large, the sort's other side) -> one entry per distinct key with the values' halves added
+// up: bmbs_methyl_site at `site`, or (key, value) pairs at okey / oval; *n_out = their number
+static int meth_reduce(Lane* c, u64* ka, u64* va, u64* kb, u64* vb, u64 n, int pos_bits, int key_bits, bmbs_methyl_site* site, u64* okey, u64* oval, u64* n_out)
+{
+    *n_out = 0;
+    if (!n) return BMBS_OK;
+    const u64 nw = (n + 63) / 64;
+    u64 at = 0;
+    auto take = [&](u64 bytes) { const u64 a = at; at += (bytes + 255) & ~255ull; return a; };
+    const u64 o_wave = take(nw * 4), o_hoff = take((nw + 1) * 8), o_m = take(n * 4), o_u = take(n * 4), o_ms = take((n + 1) * 8), o_us = take((n + 1) * 8), o_hpos = take(n * 4);
+    ENS(c, c->mt_work, at + 64);
+    char* const A = c->mt_work.as<char>();
+    u32* const wave = reinterpret_cast<u32*>(A + o_wave); u64* const hoff = reinterpret_cast<u64*>(A + o_hoff); u32* const m = reinterpret_cast<u32*>(A + o_m);
+    u32* const u = reinterpret_cast<u32*>(A + o_u); u64* const ms = reinterpret_cast<u64*>(A + o_ms); u64* const us = reinterpret_cast<u64*>(A + o_us);
+    u32* const hpos = reinterpret_cast<u32*>(A + o_hpos);
+    size_t tmp = 0;
+    if (rocprim::radix_sort_pairs(nullptr, tmp, ka, kb, va, vb, (size_t)n, 0u, (unsigned)key_bits, c->stream) != hipSuccess) { c->err = "methyl: radix_sort_pairs (size query) failed"; return BMBS_ENODEV; }
+    HIPCHK(c, hipStreamSynchronize(c->stream));           // (bs_tmp may be replaced: an earlier sort has to be through with it)
+    ENS(c, c->bs_tmp, tmp + 64);
+    prof_begin(c, "meth_pair_sort");
+    if (rocprim::radix_sort_pairs(c->bs_tmp.p, tmp, ka, kb, va, vb, (size_t)n, 0u, (unsigned)key_bits, c->stream) != hipSuccess) { c->err = "methyl: radix_sort_pairs failed"; return BMBS_ENODEV; }
+    prof_end(c);
+    prof_begin(c, "k_meth_heads");
+    hipLaunchKernelGGL(k_meth_heads, dim3(nblk(n, 256)), dim3(256), 0, c->stream, kb, vb, (long)n, wave, m, u);
+    prof_end(c);
+    int rc = scan_u32(c, wave, nw, hoff, 30);
+    if (rc) return rc;
+    rc = scan_u32(c, m, n, ms, 31);
+    if (rc) return rc;
+    rc = scan_u32(c, u, n, us, 31);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->h_info + 28, c->totals.as<u64>() + 30, 8, hipMemcpyDeviceToHost, c->stream));
+    hipLaunchKernelGGL(k_meth_hpos, dim3(nblk(n, 256)), dim3(256), 0, c->stream, kb, (long)n, hoff, hpos);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const u64 nh = *reinterpret_cast<const u64*>(c->h_info + 28);
+    if (nh > n) { c->err = "methyl: more run heads than entries"; return BMBS_ESTATE; }
+    *n_out = nh;
+    prof_begin(c, "k_meth_sites");
+    hipLaunchKernelGGL(k_meth_sites, dim3(nblk(nh, 256)), dim3(256), 0, c->stream, c->ix.gen2p, c->ix.chrom_start, kb, hpos, (long)nh, (long)n, ms, us, pos_bits, site, okey, oval);
+    prof_end(c);
+    return BMBS_OK;
+}
+
+// the records at raw / off / len (device; off = the exclusive scan of len), their clips (device, or NULL) -> c->mt_site, c->mt_sites
+static int methyl_device(Lane* c, const char* raw, const u64* off, const u32* len, const u32* clip, u64 n, const bmbs_methyl_params* par_in, int64_t* n_site)
+{
+    // BMBS_METHYL_EVENTS (test aid): the events a slice of records may hold
+    static const u64 slice_cap = [] { const char* e = getenv("BMBS_METHYL_EVENTS"); const long long v = e ? atoll(e) : 0; return v > 0 ? (u64)v : (u64)1 << 26; }();
+    bmbs_methyl_params pp = {1, 10, 5, 0};
+    if (par_in) pp = *par_in;
+    if (pp.contexts < 1 || pp.contexts > 7 || pp.min_mapq < 0 || pp.min_mapq > 255 || pp.min_phred < 0 || pp.min_phred > 255 || pp.reserved) {
+        c->err = "methyl: bad parameters (contexts 1..7, min_mapq and min_phred 0..255, reserved 0)"; return BMBS_EINVAL;
+    }
+    c->mt_sites = -1;
+    MethPar par;
+    par.contexts = (u32)pp.contexts; par.min_mapq = (u32)pp.min_mapq; par.min_phred = (u32)pp.min_phred; par.n_chrom = c->ix.n_chrom;
+    int pos_bits = 1, ref_bits = 1;
+    while (pos_bits < 40 && c->ix.G >> pos_bits) pos_bits++;
+    while (ref_bits < 24 && (u64)c->ix.n_chrom >> ref_bits) ref_bits++;
+    par.pos_bits = pos_bits;
+    ENS(c, c->mt_cnt, n * 4 + 64); ENS(c, c->mt_eoff, (n + 1) * 8 + 64);
+    u32* const info = c->tx_info.as<u32>() + 8;
+    HIPCHK(c, hipMemsetAsync(info, 0, 32, c->stream));
+    const unsigned grid = nblk(n * METH_GROUP, 256);
+    prof_begin(c, "k_meth_count");
+    hipLaunchKernelGGL(k_meth_events<false>, dim3(grid), dim3(256), 0, c->stream, c->ix.gen2p, c->ix.chrom_start, raw, off, len, clip, 0l, (long)n, par, c->mt_cnt.as<u32>(),
+                       (const u64*)nullptr, (u64*)nullptr, (u64*)nullptr, info);
+    prof_end(c);
+    int rc = scan_u32(c, c->mt_cnt.as<u32>(), n, c->mt_eoff.as<u64>(), 30);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->h_info + 8, info, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_info + 28, c->totals.as<u64>() + 30, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    if (c->h_info[8]) { c->err = "methyl: the length given for record " + std::to_string(~c->h_info[8]) + " is not its block_size + 4 (or is below the 36 bytes every BAM record has)"; return BMBS_EINVAL; }
+    if (c->h_info[9]) { c->err = "methyl: the read name, CIGAR, sequence and qualities of record " + std::to_string(~c->h_info[9]) + " do not fit its length"; return BMBS_EINVAL; }
+    if (c->h_info[10]) { c->err = "methyl: the refID of record " + std::to_string(~c->h_info[10]) + " is beyond the " + std::to_string(c->ix.n_chrom) + " sequences of the index"; return BMBS_EINVAL; }
+    if (c->h_info[11]) { c->err = "methyl: the reference span of record " + std::to_string(~c->h_info[11]) + " runs off its sequence"; return BMBS_EINVAL; }
+    const u64 n_ev = *reinterpret_cast<const u64*>(c->h_info + 28);
+    const u64* const eoff = c->mt_eoff.as<u64>();
+    u64 n_acc = 0, n_sites = 0;
+    bool sliced = false;
+    for (u64 start = 0; start < n && n_ev;) {
+        // a slice of records [start, end) with at most slice_cap events (a record with more is a slice of its own)
+        u64 end = n, e0 = 0, e1 = n_ev;
+        if (n_ev > slice_cap) {
+            sliced = true;
+            hipLaunchKernelGGL(k_meth_cut, dim3(1), dim3(64), 0, c->stream, eoff, (long)start, (long)n, slice_cap, reinterpret_cast<u64*>(info));
+            HIPCHK(c, hipMemcpyAsync(c->h_info + 8, info, 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(c->h_info + 10, eoff + start, 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            end = *reinterpret_cast<const u64*>(c->h_info + 8); e0 = *reinterpret_cast<const u64*>(c->h_info + 10);
+            if (end <= start || end > n) { c->err = "methyl: bad slice"; return BMBS_ESTATE; }
+            HIPCHK(c, hipMemcpyAsync(c->h_info + 10, eoff + end, 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            e1 = *reinterpret_cast<const u64*>(c->h_info + 10);
+        }
+        const u64 ne = e1 - e0;
+        if (ne >= (1ull << 32)) { c->err = "methyl: a record with 2^32 events and more"; return BMBS_EINVAL; }
+        if (ne) {
+            const u64 q = (ne * 8 + 255) & ~255ull;
+            ENS(c, c->mt_ev, 4 * q + 64);
+            char* const E = c->mt_ev.as<char>();
+            u64* const ka = reinterpret_cast<u64*>(E); u64* const kb = reinterpret_cast<u64*>(E + q); u64* const va = reinterpret_cast<u64*>(E + 2 * q); u64* const vb = reinterpret_cast<u64*>(E + 3 * q);
+            prof_begin(c, "k_meth_emit");
+            hipLaunchKernelGGL(k_meth_events<true>, dim3(nblk((end - start) * METH_GROUP, 256)), dim3(256), 0, c->stream, c->ix.gen2p, c->ix.chrom_start, raw, off, len, clip, (long)start,
+                               (long)(end - start), par, (u32*)nullptr, eoff + start, ka, va, info + 4);
+            prof_end(c);
+            u64 got = 0;
+            if (!sliced) {
+                ENS(c, c->mt_site, ne * sizeof(bmbs_methyl_site) + 64);
+                rc = meth_reduce(c, ka, va, kb, vb, ne, pos_bits, pos_bits + ref_bits, c->mt_site.as<bmbs_methyl_site>(), nullptr, nullptr, &got);
+                if (rc) return rc;
+                n_sites = got;
+            } else {
+                // the slice's sites as pairs behind those of the slices before (the buffer grows: what it holds is copied over)
+                if (c->mt_acc.cap < (n_acc + ne) * 16 + 64) {
+                    DevBuf grown;
+                    ENS(c, grown, (n_acc + ne) * 16 * 2 + 64);
+                    if (n_acc) HIPCHK(c, hipMemcpyAsync(grown.p, c->mt_acc.p, n_acc * 16, hipMemcpyDeviceToDevice, c->stream));
+                    HIPCHK(c, hipStreamSynchronize(c->stream));
+                    release(c->mt_acc); c->mt_acc = grown;
+                }
+                // (pairs interleaved as key, value would need another kernel: keys in the first half of each slice's piece, values behind)
+                ENS(c, c->mt_site, ne * 16 + 64);
+                u64* const sk = c->mt_site.as<u64>(); u64* const sv = sk + ne;
+                rc = meth_reduce(c, ka, va, kb, vb, ne, pos_bits, pos_bits + ref_bits, nullptr, sk, sv, &got);
+                if (rc) return rc;
+                HIPCHK(c, hipMemcpyAsync(c->mt_acc.as<u64>() + 2 * n_acc, sk, got * 8, hipMemcpyDeviceToDevice, c->stream));
+                HIPCHK(c, hipMemcpyAsync(c->mt_acc.as<u64>() + 2 * n_acc + got, sv, got * 8, hipMemcpyDeviceToDevice, c->stream));
+                HIPCHK(c, hipStreamSynchronize(c->stream));
+                c->mt_slice.push_back({n_acc, got});
+                n_acc += got;
+            }
+        }
+        start = end;
+    }
+    if (sliced) {
+        // the slices' sites, one more reduction: keys and values gathered into the two sides of the event buffer
+        const u64 q = (n_acc * 8 + 255) & ~255ull;
+        ENS(c, c->mt_ev, 4 * q + 64);
+        char* const E = c->mt_ev.as<char>();
+        u64* const ka = reinterpret_cast<u64*>(E); u64* const kb = reinterpret_cast<u64*>(E + q); u64* const va = reinterpret_cast<u64*>(E + 2 * q); u64* const vb = reinterpret_cast<u64*>(E + 3 * q);
+        for (const auto& s : c->mt_slice) {
+            HIPCHK(c, hipMemcpyAsync(ka + s.first, c->mt_acc.as<u64>() + 2 * s.first, s.second * 8, hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(va + s.first, c->mt_acc.as<u64>() + 2 * s.first + s.second, s.second * 8, hipMemcpyDeviceToDevice, c->stream));
+        }
+        c->mt_slice.clear();
+        ENS(c, c->mt_site, n_acc * sizeof(bmbs_methyl_site) + 64);
+        rc = meth_reduce(c, ka, va, kb, vb, n_acc, pos_bits, pos_bits + ref_bits, c->mt_site.as<bmbs_methyl_site>(), nullptr, nullptr, &n_sites);
+        if (rc) return rc;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    c->mt_sites = (int64_t)n_sites;
+    if (n_site) *n_site = (int64_t)n_sites;
+    return BMBS_OK;
+}
+
+static int lane_bam_methyl(Lane* c, const char* records, uint64_t bytes, const uint32_t* len, int64_t n_in, const uint32_t* clip, const bmbs_methyl_params* par, int64_t* n_site)
+{
+    if (n_site) *n_site = 0;
+    c->mt_sites = -1;
+    c->mt_slice.clear();
+    if (!c->attached) { c->err = "methyl: no index attached"; return BMBS_ESTATE; }
+    if (n_in < 0 || n_in >= (1ll << 31)) { c->err = "methyl: bad argument"; return BMBS_EINVAL; }
+    if (n_in && !len) { c->err = "methyl: NULL buffer"; return BMBS_EINVAL; }
+    const u64 n = (u64)n_in;
+    u64 sum = 0;
+    for (u64 i = 0; i < n; i++) {
+        if (len[i] && len[i] < 36) { c->err = "methyl: the length given for record " + std::to_string(i) + " is below the 36 bytes every BAM record has"; return BMBS_EINVAL; }
+        sum += len[i];
+    }
+    if (sum != bytes) { c->err = "methyl: the record lengths add up to " + std::to_string(sum) + " bytes, not to the " + std::to_string(bytes) + " given"; return BMBS_EINVAL; }
+    if (!n) { c->mt_sites = 0; return BMBS_OK; }
+    if (bytes && !records) { c->err = "methyl: NULL buffer"; return BMBS_EINVAL; }
+    HIPCHK(c, hipSetDevice(c->dev));
+    ENS(c, c->mt_in, bytes + 256); ENS(c, c->mt_len, n * 4 + 64); ENS(c, c->mt_off, (n + 1) * 8 + 64);
+    if (clip) ENS(c, c->mt_clip, n * 4 + 64);
+    {
+        std::lock_guard<std::mutex> up(g_h2d_mu[c->dev & 15]);
+        hipStream_t us = c->up_stream ? c->up_stream : c->stream;
+        const u64 piece = 128ull << 20;
+        for (u64 o = 0; o < bytes; o += piece) HIPCHK(c, hipMemcpyAsync(c->mt_in.as<char>() + o, records + o, std::min(piece, bytes - o), hipMemcpyHostToDevice, us));
+        HIPCHK(c, hipMemcpyAsync(c->mt_len.p, len, n * 4, hipMemcpyHostToDevice, us));
+        if (clip) HIPCHK(c, hipMemcpyAsync(c->mt_clip.p, clip, n * 4, hipMemcpyHostToDevice, us));
+        HIPCHK(c, hipStreamSynchronize(us));
+    }
+    const int rc = scan_u32(c, c->mt_len.as<u32>(), n, c->mt_off.as<u64>(), 29);
+    if (rc) return rc;
+    return methyl_device(c, c->mt_in.as<char>(), c->mt_off.as<u64>(), c->mt_len.as<u32>(), clip ? c->mt_clip.as<u32>() : nullptr, n, par, n_site);
+}
+
+static int lane_bam_sort_methyl(Lane* c, const uint32_t* clip, const bmbs_methyl_params* par, int64_t* n_site)
+{
+    if (n_site) *n_site = 0;
+    c->mt_sites = -1;
+    c->mt_slice.clear();
+    if (!c->attached) { c->err = "sort methyl: no index attached"; return BMBS_ESTATE; }
+    if (c->ms_n < 0) {
+        c->err = "sort methyl: no bmbs_bam_sort call's records are resident (none yet, no records, or it failed), or another call has used its buffers since";
+        return BMBS_ESTATE;
+    }
+    const u64 n = (u64)c->ms_n;
+    HIPCHK(c, hipSetDevice(c->dev));
+    if (clip) {
+        ENS(c, c->mt_clip, n * 4 + 64);
+        std::lock_guard<std::mutex> up(g_h2d_mu[c->dev & 15]);
+        hipStream_t us = c->up_stream ? c->up_stream : c->stream;
+        HIPCHK(c, hipMemcpyAsync(c->mt_clip.p, clip, n * 4, hipMemcpyHostToDevice, us));
+        HIPCHK(c, hipStreamSynchronize(us));
+    }
+    return methyl_device(c, c->bs_in.as<char>(), c->bs_off.as<u64>(), c->bs_len.as<u32>(), clip ? c->mt_clip.as<u32>() : nullptr, n, par, n_site);
+}
+
+static int lane_methyl_sites(Lane* c, bmbs_methyl_site* site, int64_t cap, int64_t* n)
+{
+    if (!n) { c->err = "methyl sites: NULL argument"; return BMBS_EINVAL; }
+    *n = 0;
+    if (c->mt_sites < 0) { c->err = "methyl sites: the context's last bmbs_bam_methyl / bmbs_bam_sort_methyl call left no result"; return BMBS_ESTATE; }
+    *n = c->mt_sites;
+    if (c->mt_sites > cap) { c->err = "methyl sites: the array is too small (n tells what is needed)"; return BMBS_ENOMEM; }
+    if (!c->mt_sites) return BMBS_OK;
+    if (!site) { c->err = "methyl sites: NULL argument"; return BMBS_EINVAL; }
+    HIPCHK(c, hipSetDevice(c->dev));
+    hipStream_t ds = c->down_stream ? c->down_stream : c->stream;
+    HIPCHK(c, hipMemcpyAsync(site, c->mt_site.p, (size_t)c->mt_sites * sizeof(bmbs_methyl_site), hipMemcpyDeviceToHost, ds));
+    HIPCHK(c, hipStreamSynchronize(ds));
+    return BMBS_OK;
+}
+
+static int lane_text_sorted_clip(Lane* c, uint32_t* clip, int64_t cap, int64_t* n)
+{
+    if (!n) { c->err = "sorted clip: NULL argument"; return BMBS_EINVAL; }
+    *n = 0;
+    if (c->dup_n2 < 0 || c->bs_n < 0) {
+        c->err = "sorted clip: the context's last text call was not a BMBS_TEXT_BAM_SORTED call that returned records, or another call has used its buffers since";
+        return BMBS_ESTATE;
+    }
+    const u64 nr = (u64)c->bs_n;
+    *n = (int64_t)nr;
+    if ((int64_t)nr > cap) { c->err = "sorted clip: the array is too small (n tells what is needed)"; return BMBS_ENOMEM; }
+    if (!nr) return BMBS_OK;
+    if (!clip) { c->err = "sorted clip: NULL argument"; return BMBS_EINVAL; }
+    HIPCHK(c, hipSetDevice(c->dev));
+    ENS(c, c->mt_cl2, nr * 4 + 64);
+    u32* const info = c->tx_info.as<u32>() + 8;
+    HIPCHK(c, hipMemsetAsync(info, 0, 32, c->stream));
+    prof_begin(c, "k_meth_clip");
+    hipLaunchKernelGGL(k_meth_clip, dim3(nblk(nr, 256)), dim3(256), 0, c->stream, c->bam_raw.as<char>(), c->sam_off.as<u64>(), c->sam_len.as<u32>(), c->bs_idx2.as<u32>(), (long)nr,
+                       c->dup_pe ? 1 : 0, c->mt_cl2.as<u32>(), info);
+    prof_end(c);
+    HIPCHK(c, hipMemcpyAsync(c->h_info + 8, info, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(clip, c->mt_cl2.p, nr * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    if (c->h_info[8]) { c->err = "sorted clip: the overlap of record " + std::to_string(~c->h_info[8]) + " (in sorted order) with its mate does not fit 16 bits"; return BMBS_EINVAL; }
+    return BMBS_OK;
+}
+
+extern "C" int bmbs_bam_methyl(bmbs_ctx* X, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, const uint32_t* clip, const bmbs_methyl_params* par, int64_t* n_site)
+{ ON_LANE0(lane_bam_methyl(c, records, bytes, len, n, clip, par, n_site)); }
+extern "C" int bmbs_bam_sort_methyl(bmbs_ctx* X, const uint32_t* clip, const bmbs_methyl_params* par, int64_t* n_site) { ON_LANE0(lane_bam_sort_methyl(c, clip, par, n_site)); }
+extern "C" int bmbs_methyl_sites(bmbs_ctx* X, bmbs_methyl_site* site, int64_t cap, int64_t* n) { ON_LANE0(lane_methyl_sites(c, site, cap, n)); }
+extern "C" int bmbs_text_sorted_clip(bmbs_ctx* X, uint32_t* clip, int64_t cap, int64_t* n) { ON_LANE0(lane_text_sorted_clip(c, clip, cap, n)); }
 
 extern "C" int bmbs_text_sorted_index(bmbs_ctx* X, uint64_t* key, uint32_t* len, int64_t cap, int64_t* n) { ON_LANE0(lane_text_sorted_index(c, key, len, cap, n)); }
 extern "C" int bmbs_bam_sort(bmbs_ctx* X, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, int32_t flags, char* out, uint64_t out_cap, uint64_t* out_bytes)

@@ -409,6 +409,54 @@ class Mapper:
         self._chk(self._lib.bmbs_dup_select(self._ctx, capi.ptr(s) if s.size else None, s.size, capi.ptr(dup), C.byref(nd)))
         return dup[:s.size], int(nd.value)
 
+    def sorted_clip(self) -> np.ndarray:
+        """clip u32[records] of the last map_text / text_map_open call with TEXT_BAM | TEXT_BAM_SORTED: the mate-overlap clip of the j-th
+        record that call returned (bmbs_text_sorted_clip)"""
+        n = C.c_int64(0)
+        rc = self._lib.bmbs_text_sorted_clip(self._ctx, None, 0, C.byref(n))
+        if rc and rc != -12:
+            self._chk(rc)
+        clip = np.zeros(max(1, n.value), dtype=np.uint32)
+        self._chk(self._lib.bmbs_text_sorted_clip(self._ctx, capi.ptr(clip), n.value, C.byref(n)))
+        return clip[:n.value]
+
+    @staticmethod
+    def _methyl_params(contexts, min_mapq, min_phred):
+        return capi.MethylParams(int(contexts), int(min_mapq), int(min_phred), 0)
+
+    def methyl_sites(self) -> np.ndarray:
+        """the sites (capi.METHYL_SITE_DTYPE) the last bam_methyl / bam_sort_methyl call left on the device (bmbs_methyl_sites)"""
+        n = C.c_int64(0)
+        rc = self._lib.bmbs_methyl_sites(self._ctx, None, 0, C.byref(n))
+        if rc and rc != -12:
+            self._chk(rc)
+        site = np.zeros(max(1, n.value), dtype=capi.METHYL_SITE_DTYPE)
+        self._chk(self._lib.bmbs_methyl_sites(self._ctx, capi.ptr(site), n.value, C.byref(n)))
+        return site[:n.value]
+
+    def bam_methyl(self, records: bytes, lens, clip=None, contexts: int = 1, min_mapq: int = 10, min_phred: int = 5) -> np.ndarray:
+        """concatenated BAM records + their sizes (0: no record here) [+ their mate-overlap clips] -> the methylation counts of every
+        cytosine of the selected contexts (1 CpG | 2 CHG | 4 CHH) that a record calls, ordered by (ref, pos) (bmbs_bam_methyl)"""
+        ln = np.ascontiguousarray(lens, dtype=np.uint32)
+        a = np.frombuffer(records, dtype=np.uint8) if len(records) else np.zeros(1, dtype=np.uint8)
+        cl = None if clip is None else np.ascontiguousarray(clip, dtype=np.uint32)
+        if cl is not None and cl.size != ln.size:
+            raise ValueError("bam_methyl: one clip per record")
+        par = self._methyl_params(contexts, min_mapq, min_phred)
+        n = C.c_int64(0)
+        self._chk(self._lib.bmbs_bam_methyl(self._ctx, capi.ptr(a), len(records), capi.ptr(ln) if ln.size else None, ln.size,
+                                            capi.ptr(cl) if cl is not None and cl.size else None, C.byref(par), C.byref(n)))
+        return self.methyl_sites()
+
+    def bam_sort_methyl(self, clip=None, contexts: int = 1, min_mapq: int = 10, min_phred: int = 5) -> np.ndarray:
+        """the same for the records of the last bam_sort call, which are still on the device; clip in that call's input order
+        (bmbs_bam_sort_methyl)"""
+        cl = None if clip is None else np.ascontiguousarray(clip, dtype=np.uint32)
+        par = self._methyl_params(contexts, min_mapq, min_phred)
+        n = C.c_int64(0)
+        self._chk(self._lib.bmbs_bam_sort_methyl(self._ctx, capi.ptr(cl) if cl is not None and cl.size else None, C.byref(par), C.byref(n)))
+        return self.methyl_sites()
+
     def sync(self):
         self._chk(self._lib.bmbs_sync(self._ctx))
 

@@ -445,6 +445,40 @@ int bmbs_bam_dup_sigs(bmbs_ctx*, const char* records, uint64_t bytes, const uint
 int bmbs_text_sorted_dup(bmbs_ctx*, bmbs_dup_sig* sig, int64_t sig_cap, int64_t* n_sig, uint32_t* tmpl, int64_t cap, int64_t* n);
 int bmbs_dup_select(bmbs_ctx*, const bmbs_dup_sig* sig, int64_t n, uint8_t* dup, int64_t* n_dup);
 
+/* ---- methylation counts per cytosine from BAM records, on the device (csrc/k_methyl.hip; `bmbs_search --bam --sort --methyl`) ---------------
+ * The genome is the attached index's (two bits a base; a non-ACGT base of the FASTA is whatever letter the index holds for it), refID its
+ * sequence number.  Contexts are defined on the genome alone.  A forward-strand C at p: CpG if p + 1 is inside the sequence and is G,
+ * otherwise CHG if p + 2 is inside and is G, otherwise CHH if p + 2 is inside, otherwise none.  A G at p (a cytosine of the reverse
+ * strand), mirrored: CpG if p - 1 is inside and is C, otherwise CHG if p - 2 is inside and is C, otherwise CHH if p - 2 is inside.
+ * A record COUNTS when refID >= 0, flag 4 is clear, flag & 0xF00 == 0 (MethylDackel's default: no secondary, QC-fail, duplicate or
+ * supplementary record), n_cigar_op > 0, MAPQ >= min_mapq, and flag 0x2 is set if flag 0x1 is.  Its strand comes from the flags alone:
+ * paired -- read 1 reverse or read 2 forward is OB, otherwise OT; single -- reverse is OB, otherwise OT.
+ * The CIGAR pairs read bases with reference positions (M = X; I S consume the read, D N the reference, H P nothing).  An OT record is
+ * called at forward-strand C of a selected context: read base C is methylated, T unmethylated, anything else nothing; an OB record at
+ * forward-strand G: G methylated, A unmethylated.  A call counts when the base quality is >= min_phred (a quality byte 0xff is 0).
+ * clip[i] (mate overlap, Bismark's --no_overlap): record i is not called at the reference positions pos + (clip >> 16) ..
+ * pos + (clip >> 16) + (clip & 0xffff) - 1.  bmbs_text_sorted_clip computes it for the records of the context's last
+ * BMBS_TEXT_BAM_SORTED call while the two records of a pair (output lines 2p, 2p + 1) still lie side by side: for a read-2 record
+ * (flag 0x80) whose mate and itself are there, mapped, have a CIGAR and share refID, (beg - pos) << 16 | (end - beg) with [beg, end) the
+ * intersection of the two reference spans; 0 for every other record.  clip[j] belongs to the j-th record the call returned (*n = that
+ * of bmbs_text_sorted_index); BMBS_ESTATE / BMBS_ENOMEM as for bmbs_text_sorted_dup; BMBS_EINVAL: an offset or length of 65536 and more.
+ * bmbs_bam_methyl: `records` = n entries in host memory, len[i] their sizes (0: no record here), clip in the same order or NULL.
+ * bmbs_bam_sort_methyl: the same for the records of the context's last bmbs_bam_sort call, which are still on the device, clip in THAT
+ * call's input order (BMBS_BAMSORT_RAW or not).  Both leave one site per (ref, pos) of a selected context with meth + unmeth > 0 on the
+ * device, ordered by (ref, pos), *n_site of them; bmbs_methyl_sites fetches the last result (BMBS_ENOMEM with *n set when cap is
+ * smaller; a cap of 0: the size query).  params NULL: CpG, MAPQ 10, quality 5.
+ * BMBS_ESTATE: no index attached; bmbs_bam_sort_methyl: no bmbs_bam_sort call's records are resident (none yet, it failed or had no
+ * records), or another call has used its buffers since.  BMBS_EINVAL (bmbs_last_error names the record): the length checks of
+ * bmbs_bam_dup_sigs, a refID beyond the index's sequences, a mapped record with a CIGAR whose reference span runs off its sequence.
+ * n = 0 is valid.                                                                                                                  */
+typedef struct bmbs_methyl_params { int32_t contexts /* 1 CpG | 2 CHG | 4 CHH */, min_mapq, min_phred, reserved; } bmbs_methyl_params;
+typedef struct bmbs_methyl_site   { int32_t ref, pos; uint32_t meth, unmeth, kind /* context 0..2 | strand << 2 */, pad; } bmbs_methyl_site;   /* 24 bytes */
+int bmbs_text_sorted_clip(bmbs_ctx*, uint32_t* clip, int64_t cap, int64_t* n);
+int bmbs_bam_methyl(bmbs_ctx*, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, const uint32_t* clip,
+                    const bmbs_methyl_params* params, int64_t* n_site);
+int bmbs_bam_sort_methyl(bmbs_ctx*, const uint32_t* clip, const bmbs_methyl_params* params, int64_t* n_site);
+int bmbs_methyl_sites(bmbs_ctx*, bmbs_methyl_site* site, int64_t cap, int64_t* n);
+
 /* a21: per-ctx counters of the batches mapped so far = {reads, unique, ambiguous, mapped bases,
  * error bases} (Schema.cpp:25141-25146); bmbs_stats_allreduce sums them over the ctxs one process
  * drives (get_mapping_informations, Schema.cpp:451-476).  Multi-process jobs sum the five int64 with

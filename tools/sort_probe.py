@@ -11,8 +11,10 @@ own `timeout`; the script stops at the first failure.
 and the k_bai_* rows of the kernel trace (which then is a --bai run) beside k_bam_gather.
 --markdup: a leg `--bam --sort --markdup`, alternating with the others -- its walls beside the sorted runs', the counts of the
 driver's markdup line, and the k_dup_* rows of the kernel trace (which then is a --markdup run) beside k_bam_gather.
+--methyl: a leg `--bam --sort --methyl <prefix> --CpG --CHG --CHH`, alternating with the others -- its walls beside the sorted runs' on the
+same build, the counts of the driver's methyl line, and the k_meth_* rows of the kernel trace (which then is a --methyl run).
 
-  python tools/sort_probe.py [--reads 4000000] [--loop 8] [--pe] [--runs 3] [--bai] [--markdup] [--out profiles/sorted_bam_probe.txt]
+  python tools/sort_probe.py [--reads 4000000] [--loop 8] [--pe] [--runs 3] [--bai] [--markdup] [--methyl] [--out profiles/sorted_bam_probe.txt]
 """
 import argparse
 import csv
@@ -50,6 +52,9 @@ def verbose_numbers(err):
     m = re.search(r"(markdup: templates \d+, with signature \d+, duplicates \d+ \(select calls \d+, [\d.]+s of pass 2\))", err)
     if m:
         out["markdup"] = m.group(1)
+    m = re.search(r"(methyl: sites CpG \d+ CHG \d+ CHH \d+, calls CpG \d+ CHG \d+ CHH \d+)", err)
+    if m:
+        out["methyl"] = m.group(1)
     m = re.search(r"busy fractions of the mapping wall: link up ([\d.]+), link down ([\d.]+)", err)
     if m:
         out["link_up"], out["link_down"] = float(m.group(1)), float(m.group(2))
@@ -68,6 +73,7 @@ def main():
     ap.add_argument("--batch", type=int, default=1_000_000)
     ap.add_argument("--bai", action="store_true", help="also measure --bam --sort --bai (the index written in the same run)")
     ap.add_argument("--markdup", action="store_true", help="also measure --bam --sort --markdup (PCR duplicates flagged in the same run)")
+    ap.add_argument("--methyl", action="store_true", help="also measure --bam --sort --methyl (methylation counts per cytosine from the same run)")
     ap.add_argument("--driver-args", default="")
     ap.add_argument("--workdir", default=os.environ.get("BMBS_BENCH_DIR", "/tmp/bmbs_bench"))
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sorted_bam_probe.txt"))
@@ -108,6 +114,10 @@ def main():
     if args.markdup:
         runs["markdup"] = []
         legs.append(("markdup", out_m, ["--sort", "--markdup"]))
+    meth_args = ["--methyl", os.path.join(wd, "sortp_meth"), "--CpG", "--CHG", "--CHH"]
+    if args.methyl:
+        runs["methyl"] = []
+        legs.append(("methyl", os.path.join(wd, "sortp_y.bam"), ["--sort"] + meth_args))
     size = {}
     step(base + ["-o", out_u], 600)                     # warm-up: page cache, index files
     for _ in range(max(3, args.runs)):
@@ -124,7 +134,7 @@ def main():
     say("sort_probe: %d %s of %d bp x %d passes over the file = %d records per run, genome %d bp, batch %d, %s"
         % (args.reads, "pairs" if args.pe else "SE reads", L, args.loop, n_reads, args.genome, args.batch, " ".join(base[3:])))
     med = {}
-    label = {"bam": "--bam", "sort": "--bam --sort", "bai": "--bam --sort --bai", "markdup": "--bam --sort --markdup"}
+    label = {"bam": "--bam", "sort": "--bam --sort", "bai": "--bam --sort --bai", "markdup": "--bam --sort --markdup", "methyl": "--bam --sort --methyl"}
     for kind in runs:
         w = [r["wall"] for r in runs[kind]]
         med[kind] = statistics.median(w)
@@ -154,12 +164,17 @@ def main():
         say("--markdup: %s; median wall %.3f s against %.3f s without it = %+.3f s; spread (max - min) of the sorted runs %.3f s; pass 1 %s s, pass 2 %s s"
             % (runs["markdup"][-1].get("markdup", "?"), med["markdup"], med["sort"], med["markdup"] - med["sort"], max(sw) - min(sw),
                " ".join("%.3f" % r["pass1"] for r in runs["markdup"]), " ".join("%.3f" % r["pass2"] for r in runs["markdup"])))
+    if args.methyl:
+        sw = [r["wall"] for r in runs["sort"]]
+        say("--methyl: %s; median wall %.3f s against %.3f s without it = %+.3f s; spread (max - min) of the sorted runs %.3f s; pass 1 %s s, pass 2 %s s"
+            % (runs["methyl"][-1].get("methyl", "?"), med["methyl"], med["sort"], med["methyl"] - med["sort"], max(sw) - min(sw),
+               " ".join("%.3f" % r["pass1"] for r in runs["methyl"]), " ".join("%.3f" % r["pass2"] for r in runs["methyl"])))
     # ---- one run of its own under the kernel trace
     tr = os.path.join(wd, "sortp_trace")
     shutil.rmtree(tr, ignore_errors=True)
     if os.path.exists(out_s):
         os.unlink(out_s)
-    step(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tr, "--"] + base + ["--sort"] + (["--bai"] if args.bai else []) + (["--markdup"] if args.markdup else []) + ["-o", out_s], 900)
+    step(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tr, "--"] + base + ["--sort"] + (["--bai"] if args.bai else []) + (["--markdup"] if args.markdup else []) + (meth_args if args.methyl else []) + ["-o", out_s], 900)
     f = glob.glob(os.path.join(tr, "**", "*kernel_stats.csv"), recursive=True)
     if f:
         rows = list(csv.DictReader(open(f[0])))
@@ -197,6 +212,12 @@ def main():
                     say("  %-14s %.3f ms in %s calls" % (r["Name"].split("(")[0], int(r["TotalDurationNs"]) / 1e6, r["Calls"]))
             say("  k_dup_* together %.3f ms beside k_bam_gather's %.2f ms (k_dup_sig reads the qualities of every record once more, the others 24-byte signatures)"
                 % (total_ns(lambda n: "k_dup_" in n) / 1e6, g / 1e6))
+        if args.methyl:
+            for r in rows:
+                if "k_meth_" in r["Name"]:
+                    say("  %-14s %.3f ms in %s calls" % (r["Name"].split("(")[0], int(r["TotalDurationNs"]) / 1e6, r["Calls"]))
+            say("  k_meth_* together %.3f ms beside k_bam_gather's %.2f ms (the event passes read the fixed fields, the CIGAR and, at cytosines only, bases and qualities)"
+                % (total_ns(lambda n: "k_meth_" in n) / 1e6, g / 1e6))
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as o:
         o.write("\n".join(lines) + "\n")
