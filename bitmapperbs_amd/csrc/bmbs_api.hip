@@ -1232,8 +1232,11 @@ int PeCall::votes()
     u32* mid_flag = use_mid ? c->pe_mid_flag.as<u32>() : nullptr;
     if (use_mid) HIPCHK(c, hipMemsetAsync(mid_flag, 0, n2 * 4, c->stream));
     prof_begin(c, "k_vote_pe_fused");
-    hipLaunchKernelGGL(k_vote_pe_fused, dim3(nblk(n2, 64)), dim3(64), 0, c->stream, c->ix, (long)n2, gm, st, ps, c->cand.as<u64>(), A,
-                       c->slot_read.as<u32>(), c->long_flag.as<u32>(), mid_flag);
+    // the reads that have lists are compacted onto dense lanes inside each block of 256 (BMBS_VOTE_DENSE=0: one lane per read)
+    if (c->kn.vote_dense)
+        hipLaunchKernelGGL(k_vote_pe_dense, dim3(nblk(n2, VOTE_DENSE_BLOCK)), dim3(VOTE_DENSE_BLOCK), 0, c->stream, c->ix, (long)n2, gm, st, ps, A, c->long_flag.as<u32>(), mid_flag);
+    else
+        hipLaunchKernelGGL(k_vote_pe_fused, dim3(nblk(n2, 64)), dim3(64), 0, c->stream, c->ix, (long)n2, gm, st, ps, A, c->long_flag.as<u32>(), mid_flag);
     prof_end(c);
     if (use_mid) {
         prof_begin(c, "k_vote_pe_mid");

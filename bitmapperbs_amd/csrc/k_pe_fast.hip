@@ -201,63 +201,35 @@ k_pe_prepare_p(const char* __restrict__ s1, const char* __restrict__ s2raw, Read
 }
 
 
-// get_candidates' list construction (Schema.cpp:18510-18545): site-sorted votes (NOT re-sorted by vote)
-__global__ void __launch_bounds__(64)
-k_vote_pe(long n2, ReadGeom gm, ReadState st, PeState ps, u64* __restrict__ cand, PeCand* __restrict__ A, u32* __restrict__ slot_read)
+// get_candidates' list construction (Schema.cpp:18510-18545): site-sorted votes (NOT re-sorted by vote).
+// k_locate + the list construction for lists of up to VOTE_REG candidates: located into registers, sorted by the same network as
+// k_vote_fused; general reads emit one entry per distinct site (no vote order), exact-ambiguous reads every hit.
+//
+// What every read gets whatever its verdict (the prologue); returns whether the read has a list to locate (verdict 3 or 4).
+// long_flag of a read that has none is final here; the lane that runs vote_pe_heavy for a read writes that read's.
+DEVI bool vote_pe_light(long r, const ReadGeom& gm, const ReadState& st, const PeState& ps, PeCand* __restrict__ A, u32* __restrict__ long_flag)
 {
-    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n2) return;
-    const int L = gm.rl(r), k = gm.rk(L);
     const int v = st.verdict[r];
-    const u64 off = st.cand_off[r];
-    for (u64 g = off; g < st.cand_off[r + 1]; g++) slot_read[g] = (u32)r;
     ps.cur[r] = 0; ps.vround[r] = 0;
-    if (v == 1 || v == 2) {
-        A[off].site = st.exit_site[r]; A[off].err = v == 1 ? 0u : 1u; A[off].end = L - 1;
-        ps.occ[r] = 1; ps.len[r] = 1;
-    } else if (v == 4) {
-        const long nc = (long)st.n_cand[r];
-        sort_u64_asc(cand + off, nc);
-        for (long i = 0; i < nc; i++) { A[off + i].site = cand[off + i]; A[off + i].err = 0; A[off + i].end = L - 1; }
-        ps.occ[r] = (int)nc; ps.len[r] = (u32)nc;
-    } else if (v == 3) {
-        const long nc = (long)st.n_cand[r];
-        u64* c = cand + off;
-        sort_u64_asc(c, nc);
-        PeCand* o = A + off;
-        long nv = 0;
-        u64 pre = c[0];
-        for (long i = 1; i < nc; i++)
-            if (c[i] != pre) { o[nv].site = pre < (u64)k ? 0 : pre - (u64)k; o[nv].err = 0; o[nv].end = 0; nv++; pre = c[i]; }
-        o[nv].site = pre >= (u64)k ? pre - (u64)k : 0; o[nv].err = 0; o[nv].end = 0; nv++;
-        ps.occ[r] = -1; ps.len[r] = (u32)nv;
-    } else { ps.occ[r] = 0; ps.len[r] = 0; }
-}
-
-// k_locate + k_vote_pe for lists of up to VOTE_REG candidates: located into registers, sorted by the same network as
-// k_vote_fused; general reads emit one entry per distinct site (no vote order), exact-ambiguous reads every hit
-__global__ void __launch_bounds__(64)
-k_vote_pe_fused(DevIndex ix, long n2, ReadGeom gm, ReadState st, PeState ps, u64* __restrict__ cand, PeCand* __restrict__ A,
-                u32* __restrict__ slot_read, u32* __restrict__ long_flag, u32* __restrict__ mid_flag)
-{
-    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n2) return;
+    if (v == 3 || v == 4) return true;
     long_flag[r] = 0;
+    if (v == 1 || v == 2) {
+        const u64 off = st.cand_off[r];
+        A[off].site = st.exit_site[r]; A[off].err = v == 1 ? 0u : 1u; A[off].end = gm.rl(r) - 1;
+        ps.occ[r] = 1; ps.len[r] = 1;
+    } else { ps.occ[r] = 0; ps.len[r] = 0; }
+    return false;
+}
+// a read of verdict 3 or 4: its list of up to VOTE_REG candidates, or the hand-over to the kernel of its size class
+DEVI void vote_pe_heavy(const DevIndex& ix, long r, const ReadGeom& gm, const ReadState& st, const PeState& ps, PeCand* __restrict__ A,
+                        u32* __restrict__ long_flag, u32* __restrict__ mid_flag)
+{
     const int L = gm.rl(r), k = gm.rk(L);
     const int v = st.verdict[r];
-    const u64 off = st.cand_off[r];
-    (void)slot_read;             // nothing downstream of the paired-end vote stage reads the slot -> read map (49 M scattered stores per launch)
-    ps.cur[r] = 0; ps.vround[r] = 0;
-    if (v == 1 || v == 2) {
-        A[off].site = st.exit_site[r]; A[off].err = v == 1 ? 0u : 1u; A[off].end = L - 1;
-        ps.occ[r] = 1; ps.len[r] = 1;
-        return;
-    }
-    if (v != 3 && v != 4) { ps.occ[r] = 0; ps.len[r] = 0; return; }
     const long nc = (long)st.n_cand[r];
     const SeedRec* my = st.seeds + (size_t)r * BMBS_MAX_SEEDS;
     const int ns = st.n_seeds[r];
-    PeCand* o = A + off;
+    PeCand* o = A + st.cand_off[r];
     if (nc <= VOTE_REG) {
         u64 c[VOTE_REG];
         int sidx = 0; u32 h = 0;
@@ -296,10 +268,54 @@ k_vote_pe_fused(DevIndex ix, long n2, ReadGeom gm, ReadState st, PeState ps, u64
         }
         if (v == 4) { ps.occ[r] = (int)nc; ps.len[r] = (u32)nc; }
         else { ps.occ[r] = -1; ps.len[r] = (u32)nv; }
+        long_flag[r] = 0;
         return;
     }
-    if (mid_flag && nc <= VOTE_MID) { mid_flag[r] = 1; return; }      // 17..32 candidates, the rule for reads of 180 bases and more: k_vote_pe_mid
+    if (mid_flag && nc <= VOTE_MID) { mid_flag[r] = 1; long_flag[r] = 0; return; }      // 17..32 candidates, the rule for reads of 180 bases and more: k_vote_pe_mid
     long_flag[r] = 1;                                         // repeats: k_vote_pe_long sorts the list out of LDS (beyond its capacity: in tiles)
+}
+
+// One lane per read (BMBS_VOTE_DENSE=0).  Mates sit at r and r + n, so the reads that have lists -- one in five on the uniform genome
+// -- fall at random: every wave of 64 consecutive reads holds some, and runs the whole locate chain, the network and the emit for
+// about 12 busy lanes.
+__global__ void __launch_bounds__(64)
+k_vote_pe_fused(DevIndex ix, long n2, ReadGeom gm, ReadState st, PeState ps, PeCand* __restrict__ A, u32* __restrict__ long_flag,
+                u32* __restrict__ mid_flag)
+{
+    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n2) return;
+    if (vote_pe_light(r, gm, st, ps, A, long_flag)) vote_pe_heavy(ix, r, gm, st, ps, A, long_flag, mid_flag);
+}
+
+// The default form: the block's reads that have lists are compacted onto its first lanes (ballot + prefix count per wave, the wave
+// totals through LDS -- no pass over memory, no flag array, no scan), so that the locate chain runs in as many waves as they fill:
+// one of four in a block of 256 at one read in five.  Every read is still computed by the same code on the same inputs and
+// writes only its own slots; only which lane runs it changes.
+#define VOTE_DENSE_BLOCK 256       // (512: the same time, 1.11 against 1.10-1.14 ms per 20 M reads)
+__global__ void __launch_bounds__(VOTE_DENSE_BLOCK)
+k_vote_pe_dense(DevIndex ix, long n2, ReadGeom gm, ReadState st, PeState ps, PeCand* __restrict__ A, u32* __restrict__ long_flag,
+                u32* __restrict__ mid_flag)
+{
+    constexpr int BLOCK = VOTE_DENSE_BLOCK, NW = BLOCK / 64;
+    __shared__ u16 sh_idx[BLOCK];           // wave w's heavy threads, in order, from sh_idx[64 w]
+    __shared__ int sh_tot[NW];
+    const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const long row0 = (long)blockIdx.x * BLOCK;
+    const long r = row0 + tid;
+    const bool heavy = r < n2 && vote_pe_light(r, gm, st, ps, A, long_flag);         // (no thread leaves before the barrier)
+    const unsigned long long m = __ballot(heavy);
+    if (heavy) sh_idx[w * 64 + __popcll(m & ((1ull << lane) - 1))] = (u16)tid;
+    if (lane == 0) sh_tot[w] = __popcll(m);
+    __syncthreads();
+    int base = 0, src = -1;
+#pragma unroll
+    for (int q = 0; q < NW; q++) {
+        const int t = sh_tot[q];
+        if (src < 0 && tid < base + t) src = q * 64 + tid - base;
+        base += t;
+    }
+    if (src < 0) return;                    // tid >= the block's heavy count (whole waves beyond it end here)
+    vote_pe_heavy(ix, row0 + sh_idx[src], gm, st, ps, A, long_flag, mid_flag);
 }
 
 // lists of 17..32 candidates (reads of 180 bases and more place up to 25 seeds): one lane per read over the compacted list,
@@ -438,7 +454,7 @@ k_vote_pe_long(DevIndex ix, ReadGeom gm, ReadState st, PeState ps, const u64* __
     __shared__ u64 sh_mate[PREF_STAGE];
     constexpr int EMAX = (CAP + BLOCK - 1) / BLOCK;
     auto in_class = [](long nc) { return nc > LO && (CAP == VL_CAP || nc <= CAP); };
-    // is read x's list built by one of these size-class kernels at all (k_vote_pe_fused / _mid wrote the others before this launch)
+    // is read x's list built by one of these size-class kernels at all (k_vote_pe_fused / _dense / _mid wrote the others before this launch)
     auto listed = [&](long x) { return long_flag[x] != 0; };
     const long total_items = (long)*count_ptr;
     for (long item = blockIdx.x; item < total_items; item += gridDim.x) {

@@ -4,7 +4,7 @@
 // Paired-end sensitive mode (Map_Pair_Seq_end_to_end, Schema.cpp:19953-21459)
 // ================================================================================================
 // Seeding of both mates is the same state machine as fast mode (first seed, 1-mismatch second seed, remaining
-// seeds; process_rest_seed[_filter]_debug, Schema.cpp:17574 / 16298), so k_seed_* + k_locate + k_vote_pe are
+// seeds; process_rest_seed[_filter]_debug, Schema.cpp:17574 / 16298), so k_seed_* and the k_vote_pe_* kernels are
 // shared.  What differs is the order of verification -- the mate with fewer first-seed candidates is verified
 // completely (round 1), the other mate's votes are kept only where a verified hit of the first lies within the
 // insert window (select_suit_candidates, 4775) and verified (round 2) -- and the rescue: a mate left without a

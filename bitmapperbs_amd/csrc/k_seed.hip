@@ -779,8 +779,8 @@ k_seed_decide_p(DevIndex ix, const char* __restrict__ seq, PackedRows pr, ReadGe
                 get_error = error;
                 if (error == 0) { verdict = 1; st.exit_site[r] = loc; done = true; }
                 // skip_v1: the record was kept back until the verdict was known.  The readers of st.seeds and the verdicts they read
-                // it for: k_vote_fused and the lists it hands to k_vote_mid / k_vote_long (single-end) 3 only; k_vote_pe /
-                // k_vote_pe_fused 3 and 4 (1 and 2: exit_site only) and the lists they hand to k_vote_pe_mid / k_vote_pe_long 3 and 4;
+                // it for: k_vote_fused and the lists it hands to k_vote_mid / k_vote_long (single-end) 3 only; k_vote_pe_fused /
+                // k_vote_pe_dense 3 and 4 (1 and 2: exit_site only) and the lists they hand to k_vote_pe_mid / k_vote_pe_long 3 and 4;
                 // k_pes_order every verdict but 1 and 4; but k_pes_reseed (--sensitive) reads slots 0 .. ps.full - 1 of the mate it
                 // re-seeds whatever its verdict, and ps.full = n_seeds = 1 for exit A -- so --sensitive keeps the store (launch_seeding).
                 // k_pes_vote / k_pes_vote_long read what k_pes_reseed wrote.  The text, file and --pbat entry points run these kernels.
