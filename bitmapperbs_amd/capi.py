@@ -27,6 +27,7 @@ SYMBOLS = [
     "bmbs_text_sorted_index", "bmbs_bam_sort", "bmbs_bam_sort_index",
     "bmbs_bam_dup_sigs", "bmbs_text_sorted_dup", "bmbs_dup_select",
     "bmbs_text_sorted_clip", "bmbs_bam_methyl", "bmbs_bam_sort_methyl", "bmbs_methyl_sites",
+    "bmbs_bam_methyl_opts", "bmbs_bam_sort_methyl_opts", "bmbs_methyl_mbias",
     "bmbs_outcome_index",
 ]
 
@@ -83,6 +84,17 @@ assert METHYL_SITE_DTYPE.itemsize == 24
 class MethylParams(C.Structure):
     _fields_ = [("contexts", C.c_int32), ("min_mapq", C.c_int32), ("min_phred", C.c_int32), ("reserved", C.c_int32)]
 
+
+# bmbs_methyl_opts (read-end trimming and the M-bias table: bmbs_bam_methyl_opts / bmbs_bam_sort_methyl_opts / bmbs_methyl_mbias)
+class MethylOpts(C.Structure):
+    _fields_ = [("contexts", C.c_int32), ("min_mapq", C.c_int32), ("min_phred", C.c_int32), ("flags", C.c_int32),
+                ("ignore_5p", C.c_int32 * 2), ("ignore_3p", C.c_int32 * 2)]
+
+
+assert C.sizeof(MethylOpts) == 32
+METHYL_MBIAS = 1             # in MethylOpts.flags
+MBIAS_CYCLES = 1024
+MBIAS_SHAPE = (2, 2, 3, 2, MBIAS_CYCLES)      # mate, strand (0 OT, 1 OB), context, (0 unmethylated, 1 methylated), cycle
 
 ST_UNMAPPED, ST_UNIQUE, ST_AMBIG, ST_OFFEND = 0, 1, 2, 3
 
@@ -224,6 +236,13 @@ def lib() -> C.CDLL:
         L.bmbs_bam_sort_methyl.restype = C.c_int
         L.bmbs_methyl_sites.argtypes = [vp, vp, i64, C.POINTER(i64)]
         L.bmbs_methyl_sites.restype = C.c_int
+    if hasattr(L, "bmbs_methyl_mbias"):                  # (read-end trimming and the M-bias table; BMBS_LIB may name an older build, as above)
+        L.bmbs_bam_methyl_opts.argtypes = [vp, vp, u64, vp, i64, vp, C.POINTER(MethylOpts), C.POINTER(i64)]
+        L.bmbs_bam_methyl_opts.restype = C.c_int
+        L.bmbs_bam_sort_methyl_opts.argtypes = [vp, vp, C.POINTER(MethylOpts), C.POINTER(i64)]
+        L.bmbs_bam_sort_methyl_opts.restype = C.c_int
+        L.bmbs_methyl_mbias.argtypes = [vp, vp, i64, C.POINTER(i64)]
+        L.bmbs_methyl_mbias.restype = C.c_int
     L.bmbs_map_pe_text.argtypes = [vp, vp, u64, vp, u64, i64, i32, vp, u64, C.POINTER(u64), C.POINTER(i64)]
     L.bmbs_map_pe_text.restype = C.c_int
     L.bmbs_retries.argtypes = [vp]

@@ -755,7 +755,7 @@ void lane_destroy(Lane* c)
                      &c->bam_raw, &c->bam_slots, &c->bam_slot_len, &c->bam_off, &c->stats_snap, &c->z_comp, &c->z_off, &c->z_text, &c->z_err, &c->z_nl, &c->z_comp2, &c->z_off2, &c->z_err2,
                      &c->bs_key, &c->bs_key2, &c->bs_idx, &c->bs_idx2, &c->bs_slen, &c->bs_soff, &c->bs_tmp, &c->bs_in, &c->bs_len, &c->bs_off, &c->bs_sorted, &c->bai_a, &c->bai_b, &c->bai_out,
                      &c->dp_in, &c->dp_len, &c->dp_off, &c->dp_sig, &c->dp_key, &c->dp_key2, &c->dp_idx, &c->dp_idx2, &c->dp_dup, &c->dp_tmpl,
-                     &c->mt_in, &c->mt_len, &c->mt_off, &c->mt_clip, &c->mt_cnt, &c->mt_eoff, &c->mt_ev, &c->mt_work, &c->mt_acc, &c->mt_site, &c->mt_cl2};
+                     &c->mt_in, &c->mt_len, &c->mt_off, &c->mt_clip, &c->mt_cnt, &c->mt_eoff, &c->mt_ev, &c->mt_work, &c->mt_acc, &c->mt_site, &c->mt_cl2, &c->mt_mbias};
       for (DevBuf* b : tx) release(*b); }
     if (c->ev_up) (void)hipEventDestroy(c->ev_up);
     if (c->ev_k) (void)hipEventDestroy(c->ev_k);

@@ -223,10 +223,14 @@ struct Lane {
     // methylation counts (k_methyl.hip): the records of bmbs_bam_methyl as uploaded with their lengths, offsets and clips; events per record
     // and their scan; the (key, value) events before and behind the pair sort; the reduction's work arrays; the sites of earlier slices of
     // records as pairs (mt_slice: where each slice's lie); the result (bmbs_methyl_sites: mt_sites of them, -1: none); the clips of a sorted
-    // text call.  ms_n = records of the last bmbs_bam_sort call, still in bs_in / bs_off / bs_len (-1: none, as for bai_n)
-    DevBuf mt_in, mt_len, mt_off, mt_clip, mt_cnt, mt_eoff, mt_ev, mt_work, mt_acc, mt_site, mt_cl2;
+    // text call.  ms_n = records of the last bmbs_bam_sort call, still in bs_in / bs_off / bs_len (-1: none, as for bai_n).
+    // mt_mbias: the M-bias table of the last call (bmbs_methyl_mbias) if mt_has_mbias (mt_mbias_zero: a call without records, the table
+    // is all zero and not on the device); mt_cus: the device's compute units (0: not asked yet)
+    DevBuf mt_in, mt_len, mt_off, mt_clip, mt_cnt, mt_eoff, mt_ev, mt_work, mt_acc, mt_site, mt_cl2, mt_mbias;
     std::vector<std::pair<u64, u64>> mt_slice;
     int64_t ms_n = -1, mt_sites = -1;
+    bool mt_has_mbias = false, mt_mbias_zero = false;
+    int mt_cus = 0;
     u64 ms_bytes = 0;
     DevBuf z_comp, z_off, z_text, z_err, z_nl, z_comp2, z_off2, z_err2;         // bmbs_inflate_bgzf; (…2: mate 2 of bmbs_text_open_bgzf)
     struct OpenText { bool valid = false, pe = false; u64 bytes1 = 0, bytes2 = 0; int64_t n = 0; } open_text;      // between bmbs_text_open_bgzf and bmbs_text_map_open

@@ -18,6 +18,9 @@
 //          "--markdup" below; nothing else in any record changes)
 //          --bam --sort --methyl <prefix> [--CpG] [--CHG] [--CHH] (per-cytosine methylation counts of that file's records, computed on the
 //          device while its blocks are written: <prefix>_CpG.bedGraph ..., see "--methyl" below)
+//          --methyl ... [--methyl-ignore n] [--methyl-ignore-3prime n] [--methyl-ignore-r2 n] [--methyl-ignore-3prime-r2 n] (cycles left
+//          out of the calls at the 5' / 3' end of read 1 (or a single-end read) / read 2: Bismark's --ignore options) [--mbias]
+//          (<prefix>_mbias.tsv: the calls by context, strand, read and cycle, before the trim)
 //
 // The reference has ONE reader thread and ONE fprintf sink (Process_Reads.cpp:2057-2260, Process_sam_out.cpp:954-1006), which is
 // what limits it.  Round 2 of this driver indexed the lines and formatted the SAM text with the host's
@@ -69,10 +72,14 @@ struct Options {
     bool verbose = false, unmapped_out = false, pbat = false, bam = false, print_parts = false, print_plan = false;
     bool sort = false, bai = false, markdup = false;
     bmbs_methyl_params mpar = {0, 10, 5, 0};     // --CpG (the default) --CHG --CHH, --methyl-min-mapq, --methyl-min-phred
+    long ignore[4] = {0, 0, 0, 0};               // --methyl-ignore, --methyl-ignore-r2 (5' of mate 0, 1), --methyl-ignore-3prime, --methyl-ignore-3prime-r2 (3')
+    bool ignore_given = false, mbias = false;    // --mbias: <prefix>_mbias.tsv
     double sort_mem_gib = 0;                     // --sort-mem: cap of the in-memory record store of --sort (0: half of the machine's memory)
     // derived once
     bool pe = false, gz_in = false, methyl_out = false;
     bool methyl_clip = false;                    // --methyl of pairs: the records carry their mate-overlap clips
+    bool methyl_use_opts = false;                // a trim or --mbias: pass 2 calls bmbs_bam_sort_methyl_opts with mopt (else bmbs_bam_sort_methyl, as ever)
+    bmbs_methyl_opts mopt = {1, 10, 5, 0, {0, 0}, {0, 0}};
     std::string in1;                             // the first (or only) read file
     int live_parts = 1;                          // a .gz stream cannot be entered in the middle: everything goes through part 0, the other part files stay empty
     int32_t flags = 0;                           // BMBS_TEXT_* of every mapping call
@@ -169,7 +176,10 @@ struct Run {
 };
 
 // ---- --sort, pass 2: main, its stager and its sorters ----------------------------------------------------------------------------------
-struct Slot { Pinned in, out; std::vector<uint32_t> len, clip; size_t unit = 0; uint64_t out_bytes = 0; BaiPieces bai; std::vector<bmbs_methyl_site> site; int64_t n_site = 0; };
+struct Slot {
+    Pinned in, out; std::vector<uint32_t> len, clip; size_t unit = 0; uint64_t out_bytes = 0; BaiPieces bai; std::vector<bmbs_methyl_site> site; int64_t n_site = 0;
+    std::vector<uint64_t> mbias;                 // --mbias: the call's table
+};
 // (a slot belongs to one thread at a time: free_s -> stager -> staged_s -> a sorter -> done_s -> main)
 struct Pass2 {
     std::vector<SortUnit> units;                 // written by main before the threads start, read-only then
@@ -180,6 +190,8 @@ struct Pass2 {
     std::vector<uint64_t> dup_bits;              // --markdup: a bit per template id, set for duplicates; dup_select_pass writes, the stager reads
     BaiIndex bai;                                // main alone (the calls' pieces, in call order)
     std::vector<bmbs_methyl_site> meth_sites;    // --methyl: the sites of the calls so far, merged; main alone
+    std::vector<uint64_t> mbias;                 // --mbias: the tables of the calls so far, added up; main alone
+    uint64_t mbias_calls = 0;                    // ... and its total
     size_t sort_calls = 0, select_calls = 0, n_dup = 0, bai_bytes = 0;
     size_t meth_n[3] = {0, 0, 0}, meth_calls[3] = {0, 0, 0}, meth_dropped = 0;
     double t_select = 0;
@@ -251,6 +263,15 @@ Options parse_options(int argc, char** argv)
         else if (a == "--CHH") mpar.contexts |= 4;
         else if (a == "--methyl-min-mapq") mpar.min_mapq = atoi(val());
         else if (a == "--methyl-min-phred") mpar.min_phred = atoi(val());
+        else if (a == "--methyl-ignore" || a == "--methyl-ignore-r2" || a == "--methyl-ignore-3prime" || a == "--methyl-ignore-3prime-r2") {
+            char* end = nullptr;
+            const char* v = val();
+            const long x = strtol(v, &end, 10);
+            if (end == v || *end || x < 0 || x > 65535) { fprintf(stderr, "bmbs_search: %s takes 0..65535\n", a.c_str()); exit(2); }
+            o.ignore[(a.find("3prime") != std::string::npos ? 2 : 0) + (a.size() > 3 && a.compare(a.size() - 3, 3, "-r2") == 0 ? 1 : 0)] = x;
+            o.ignore_given = true;
+        }
+        else if (a == "--mbias") o.mbias = true;                      // --methyl ... --mbias: <prefix>_mbias.tsv
         else { fprintf(stderr, "bmbs_search: unsupported option %s\n", a.c_str()); exit(2); }
     }
     if (o.sort && !o.bam) refuse("bmbs_search: --sort needs --bam\n");
@@ -261,7 +282,11 @@ Options parse_options(int argc, char** argv)
     if (o.methyl_out && !o.sort) refuse("bmbs_search: --methyl needs --sort\n");
     if (!o.methyl_out && (mpar.contexts || mpar.min_mapq != 10 || mpar.min_phred != 5)) refuse("bmbs_search: --CpG, --CHG, --CHH, --methyl-min-mapq and --methyl-min-phred need --methyl\n");
     if (mpar.min_mapq < 0 || mpar.min_mapq > 255 || mpar.min_phred < 0 || mpar.min_phred > 255) refuse("bmbs_search: --methyl-min-mapq and --methyl-min-phred take 0..255\n");
+    if (!o.methyl_out && o.ignore_given) refuse("bmbs_search: --methyl-ignore, --methyl-ignore-3prime, --methyl-ignore-r2 and --methyl-ignore-3prime-r2 need --methyl\n");
+    if (!o.methyl_out && o.mbias) refuse("bmbs_search: --mbias needs --methyl\n");
     if (!mpar.contexts) mpar.contexts = 1;
+    o.methyl_use_opts = o.mbias || o.ignore[0] || o.ignore[1] || o.ignore[2] || o.ignore[3];
+    o.mopt = bmbs_methyl_opts{mpar.contexts, mpar.min_mapq, mpar.min_phred, o.mbias ? BMBS_METHYL_MBIAS : 0, {(int32_t)o.ignore[0], (int32_t)o.ignore[1]}, {(int32_t)o.ignore[2], (int32_t)o.ignore[3]}};
     if (o.bai) {
         // the index lies beside a file: a device or a pipe has no such place
         struct stat osb;
@@ -269,7 +294,7 @@ Options parse_options(int argc, char** argv)
     }
     if (!o.build_fasta.empty()) return o;            // --index: nothing below applies
     if (o.index.empty() || (o.seq.empty() && (o.seq1.empty() || o.seq2.empty())))
-        refuse("usage: bmbs_search --index <genome.fa> [--index_folder dir] [-t threads]\n       bmbs_search --search <index> (--seq r.fq | --seq1 a.fq --seq2 b.fq) [-o out.sam] [-e f] [--min n] [--max n] [--sensitive] [--pbat] [--unmapped_out] [--ambiguous_out] [--bam [--sort [--sort-mem GiB] [--markdup] [--bai] [--methyl prefix [--CpG] [--CHG] [--CHH] [--methyl-min-mapq n] [--methyl-min-phred n]]]] [--mapstats f] [-t io_threads] [--out-parts n]\n");
+        refuse("usage: bmbs_search --index <genome.fa> [--index_folder dir] [-t threads]\n       bmbs_search --search <index> (--seq r.fq | --seq1 a.fq --seq2 b.fq) [-o out.sam] [-e f] [--min n] [--max n] [--sensitive] [--pbat] [--unmapped_out] [--ambiguous_out] [--bam [--sort [--sort-mem GiB] [--markdup] [--bai] [--methyl prefix [--CpG] [--CHG] [--CHH] [--methyl-min-mapq n] [--methyl-min-phred n] [--methyl-ignore n] [--methyl-ignore-3prime n] [--methyl-ignore-r2 n] [--methyl-ignore-3prime-r2 n] [--mbias]]]] [--mapstats f] [-t io_threads] [--out-parts n]\n");
     if (o.batch < 1) o.batch = 1;
     if (o.io_threads <= 0) {
         // plain text needs few threads to read at memory speed; compressed input is inflated by them (csrc/pgz.h): more pay off
@@ -481,7 +506,8 @@ std::string sam_header_text(bool sorted, const std::vector<std::string>& chrom_n
     for (size_t i = 0; i < args.size(); i++) {
         const std::string& a = args[i];
         if (a == "--methyl" || a == "--methyl-min-mapq" || a == "--methyl-min-phred") { i++; continue; }
-        if (a == "--CpG" || a == "--CHG" || a == "--CHH") continue;
+        if (a == "--methyl-ignore" || a == "--methyl-ignore-r2" || a == "--methyl-ignore-3prime" || a == "--methyl-ignore-3prime-r2") { i++; continue; }
+        if (a == "--CpG" || a == "--CHG" || a == "--CHH" || a == "--mbias") continue;
         h += a; h += ' ';
     }
     h += '\n';
@@ -950,12 +976,16 @@ void pass2_sorter(Run& R, Pass2& S, bmbs_ctx* ctx)
         if (o.bai && !R.failed && !sl->bai.fetch(ctx)) { R.fail(bmbs_last_error(ctx)); sl->out_bytes = 0; }
         // --methyl: the call's records are still on the device (the staged copies: duplicates carry 0x400)
         sl->n_site = 0;
+        if (o.mbias) std::fill(sl->mbias.begin(), sl->mbias.end(), 0);      // (a call that fails leaves no table of the call before)
         if (o.methyl_out && !R.failed) {
             int64_t ns = 0;
-            if (bmbs_bam_sort_methyl(ctx, o.pe ? sl->clip.data() : nullptr, &o.mpar, &ns)) { R.fail(bmbs_last_error(ctx)); sl->out_bytes = 0; }
+            const uint32_t* const clip = o.pe ? sl->clip.data() : nullptr;
+            if (o.methyl_use_opts ? bmbs_bam_sort_methyl_opts(ctx, clip, &o.mopt, &ns) : bmbs_bam_sort_methyl(ctx, clip, &o.mpar, &ns)) { R.fail(bmbs_last_error(ctx)); sl->out_bytes = 0; }
             else {
                 if ((size_t)ns > sl->site.size()) sl->site.resize((size_t)ns + (size_t)ns / 8);
                 if (bmbs_methyl_sites(ctx, sl->site.data(), (int64_t)sl->site.size(), &sl->n_site)) { R.fail(bmbs_last_error(ctx)); sl->out_bytes = 0; sl->n_site = 0; }
+                int64_t nt = 0;
+                if (o.mbias && !R.failed && bmbs_methyl_mbias(ctx, sl->mbias.data(), (int64_t)sl->mbias.size(), &nt)) { R.fail(bmbs_last_error(ctx)); sl->out_bytes = 0; }
             }
         }
         S.done_s.put((long)sl->unit, sl);
@@ -973,6 +1003,7 @@ void sort_pass2(Run& R, Pass2& S)
     const char* e = getenv("BMBS_SORT_CALL_BYTES");
     const size_t budget = (size_t)std::max(1l, e ? atol(e) : 1l << 30);
     if (o.markdup) dup_select_pass(R, S, budget);
+    if (o.mbias) S.mbias.assign((size_t)24 * BMBS_MBIAS_CYCLES, 0);
     S.t_select = now();
     sort_plan(R.sort_store, budget, S.units);
     S.sort_calls = S.units.size();
@@ -989,6 +1020,7 @@ void sort_pass2(Run& R, Pass2& S)
         for (Slot& sl : S.slots) {
             sl.in.kind = 1; sl.out.kind = 2; sl.len.resize(max_n + 1);
             if (o.methyl_clip) sl.clip.resize(max_n + 1);
+            if (o.mbias) sl.mbias.assign((size_t)24 * BMBS_MBIAS_CYCLES, 0);
             Slot* s = &sl;
             th.emplace_back([s, &ok, max_bytes] { if (!s->in.need(max_bytes + 64)) ok = false; });
             th.emplace_back([s, &ok, max_bytes] { if (!s->out.need((max_bytes / 0xff00 + 1) * 65536 + 64)) ok = false; });
@@ -1006,6 +1038,7 @@ void sort_pass2(Run& R, Pass2& S)
             if (!R.failed && !pwrite_all(pt.ofd, sl->out.p, (size_t)sl->out_bytes, pt.out_off)) R.fail(std::string("write error: ") + strerror(errno));
             if (o.bai && !R.failed && !S.bai.add(sl->bai, (uint64_t)pt.out_off)) R.fail("--bai: a record names a sequence the header does not have");
             if (o.methyl_out && !R.failed) methyl_merge(S.meth_sites, sl->site.data(), (size_t)sl->n_site);
+            if (o.mbias && !R.failed) for (size_t k = 0; k < S.mbias.size(); k++) S.mbias[k] += sl->mbias[k];
             pt.out_off += (size_t)sl->out_bytes;
             S.free_s.put(sl);
         }
@@ -1067,6 +1100,13 @@ void write_methyl(Run& R, Pass2& S)
         const std::string path = o.methyl + "_" + ctx_names[x] + ".bedGraph";
         if (!methyl_write(path, o.methyl, ctx_names[x], x, sites, R.ixf)) { fprintf(stderr, "bmbs_search: cannot write %s: %s\n", path.c_str(), strerror(errno)); R.failed = true; }
     }
+    // --mbias: the table as the device made it (calls at bases the FASTA does not spell A, C, G or T are in it: only sites are filtered)
+    if (o.mbias && !R.failed) {
+        S.mbias.resize((size_t)24 * BMBS_MBIAS_CYCLES, 0);               // (a run without a pass-2 call: all zero)
+        for (const uint64_t v : S.mbias) S.mbias_calls += v;
+        const std::string path = o.methyl + "_mbias.tsv";
+        if (!mbias_write(path, S.mbias)) { fprintf(stderr, "bmbs_search: cannot write %s: %s\n", path.c_str(), strerror(errno)); R.failed = true; }
+    }
 }
 
 // a failed run leaves no half-made sorted file, index or bedGraph behind
@@ -1074,6 +1114,7 @@ int give_up(Run& R)
 {
     const Options& o = R.o;
     if (o.methyl_out) for (unsigned x = 0; x < 3; x++) if ((o.mpar.contexts >> x) & 1) ::unlink((o.methyl + "_" + ctx_names[x] + ".bedGraph").c_str());
+    if (o.mbias) ::unlink((o.methyl + "_mbias.tsv").c_str());
     if (o.sort && R.parts[0]->regular) ::unlink(o.out.c_str());      // a sorted file is whole or absent (a device or a pipe is left alone)
     if (o.bai && R.parts[0]->regular) ::unlink((o.out + ".bai").c_str());      // ... and so is its index
     fprintf(stderr, "bmbs_search: failed\n");
@@ -1111,6 +1152,7 @@ void report(const Run& R, const Pass2& S)
         if (o.methyl_out)
             snprintf(ixs + strlen(ixs), sizeof ixs - strlen(ixs), ", methyl: sites CpG %zu CHG %zu CHH %zu, calls CpG %zu CHG %zu CHH %zu, sites left out at bases other than ACGT %zu", S.meth_n[0],
                      S.meth_n[1], S.meth_n[2], S.meth_calls[0], S.meth_calls[1], S.meth_calls[2], S.meth_dropped);
+        if (o.mbias) snprintf(ixs + strlen(ixs), sizeof ixs - strlen(ixs), ", mbias calls %llu", (unsigned long long)S.mbias_calls);
         fprintf(stderr, "[bmbs_search] sort: bins %zu (one of them for records without a reference), pass-2 calls %zu, store bytes %zu (%ld records), pass 1 %.3fs (mapping, binning), pass 2 %.3fs (sort, deflate, write)%s\n",
                 store.bin.size(), S.sort_calls, store.bytes, store.records, R.t_pass1 - R.t_loaded, R.t_pass2 - R.t_pass1, ixs);
     }

@@ -4,7 +4,8 @@
 // between is bmbs_api.hip's (lane_enqueue / lane_settle).  Kernels: bmbs_text.hip, bmbs_bam.hip, bmbs_inflate.hip, k_bamsort.hip (the
 // coordinate sort of BAM records: BMBS_TEXT_BAM_SORTED, bmbs_bam_sort), k_bai.hip (the .bai pieces of a sorted call: bmbs_bam_sort_index),
 // k_markdup.hip (duplicate marking: bmbs_bam_dup_sigs, bmbs_text_sorted_dup, bmbs_dup_select), k_methyl.hip (methylation counts per
-// cytosine: bmbs_bam_methyl, bmbs_bam_sort_methyl, bmbs_methyl_sites, bmbs_text_sorted_clip).
+// cytosine, read-end trimming, M-bias table: bmbs_bam_methyl[_opts], bmbs_bam_sort_methyl[_opts], bmbs_methyl_sites, bmbs_methyl_mbias,
+// bmbs_text_sorted_clip).
 #include "bmbs_host.h"
 #define DEVI __device__ __forceinline__
 #include "bmbs_text.hip"
@@ -1198,19 +1199,43 @@ static int meth_reduce(Lane* c, u64* ka, u64* va, u64* kb, u64* vb, u64 n, int p
     return BMBS_OK;
 }
 
-// the records at raw / off / len (device; off = the exclusive scan of len), their clips (device, or NULL) -> c->mt_site, c->mt_sites
-static int methyl_device(Lane* c, const char* raw, const u64* off, const u32* len, const u32* clip, u64 n, const bmbs_methyl_params* par_in, int64_t* n_site)
+static int methyl_params_as_opts(Lane* c, const bmbs_methyl_params* par, bmbs_methyl_opts* o)
+{
+    *o = bmbs_methyl_opts{1, 10, 5, 0, {0, 0}, {0, 0}};
+    if (!par) return BMBS_OK;
+    if (par->contexts < 1 || par->contexts > 7 || par->min_mapq < 0 || par->min_mapq > 255 || par->min_phred < 0 || par->min_phred > 255 || par->reserved) {
+        c->err = "methyl: bad parameters (contexts 1..7, min_mapq and min_phred 0..255, reserved 0)"; return BMBS_EINVAL;
+    }
+    o->contexts = par->contexts; o->min_mapq = par->min_mapq; o->min_phred = par->min_phred;
+    return BMBS_OK;
+}
+
+// the options of a call: *opts if given (the _opts calls), else the old calls' parameters with no flags and no trim (NULL: the defaults)
+static int methyl_get_opts(Lane* c, const bmbs_methyl_params* par, const bmbs_methyl_opts* opts, bmbs_methyl_opts* out)
+{
+    if (!opts) return methyl_params_as_opts(c, par, out);
+    const bmbs_methyl_opts& o = *out = *opts;
+    bool bad = o.contexts < 1 || o.contexts > 7 || o.min_mapq < 0 || o.min_mapq > 255 || o.min_phred < 0 || o.min_phred > 255 || (o.flags & ~BMBS_METHYL_MBIAS);
+    for (int m = 0; m < 2; m++) bad = bad || o.ignore_5p[m] < 0 || o.ignore_5p[m] > 65535 || o.ignore_3p[m] < 0 || o.ignore_3p[m] > 65535;
+    if (bad) { c->err = "methyl: bad parameters (contexts 1..7, min_mapq and min_phred 0..255, flags BMBS_METHYL_MBIAS or 0, ignore values 0..65535)"; return BMBS_EINVAL; }
+    return BMBS_OK;
+}
+
+// the records at raw / off / len (device; off = the exclusive scan of len), their clips (device, or NULL) -> c->mt_site, c->mt_sites;
+// with BMBS_METHYL_MBIAS the M-bias table of all n records -> c->mt_mbias too (once, whatever the slices).  Options: methyl_get_opts
+static int methyl_device(Lane* c, const char* raw, const u64* off, const u32* len, const u32* clip, u64 n, const bmbs_methyl_params* par_in, const bmbs_methyl_opts* opts,
+                         int64_t* n_site)
 {
     // BMBS_METHYL_EVENTS (test aid): the events a slice of records may hold
     static const u64 slice_cap = [] { const char* e = getenv("BMBS_METHYL_EVENTS"); const long long v = e ? atoll(e) : 0; return v > 0 ? (u64)v : (u64)1 << 26; }();
-    bmbs_methyl_params pp = {1, 10, 5, 0};
-    if (par_in) pp = *par_in;
-    if (pp.contexts < 1 || pp.contexts > 7 || pp.min_mapq < 0 || pp.min_mapq > 255 || pp.min_phred < 0 || pp.min_phred > 255 || pp.reserved) {
-        c->err = "methyl: bad parameters (contexts 1..7, min_mapq and min_phred 0..255, reserved 0)"; return BMBS_EINVAL;
-    }
+    bmbs_methyl_opts pp;
+    if (int rc = methyl_get_opts(c, par_in, opts, &pp)) return rc;
     c->mt_sites = -1;
     MethPar par;
     par.contexts = (u32)pp.contexts; par.min_mapq = (u32)pp.min_mapq; par.min_phred = (u32)pp.min_phred; par.n_chrom = c->ix.n_chrom;
+    for (int m = 0; m < 2; m++) { par.ig5[m] = (u32)pp.ignore_5p[m]; par.ig3[m] = (u32)pp.ignore_3p[m]; }
+    const bool trim = par.ig5[0] || par.ig5[1] || par.ig3[0] || par.ig3[1];
+    const bool mbias = (pp.flags & BMBS_METHYL_MBIAS) != 0;
     int pos_bits = 1, ref_bits = 1;
     while (pos_bits < 40 && c->ix.G >> pos_bits) pos_bits++;
     while (ref_bits < 24 && (u64)c->ix.n_chrom >> ref_bits) ref_bits++;
@@ -1219,9 +1244,12 @@ static int methyl_device(Lane* c, const char* raw, const u64* off, const u32* le
     u32* const info = c->tx_info.as<u32>() + 8;
     HIPCHK(c, hipMemsetAsync(info, 0, 32, c->stream));
     const unsigned grid = nblk(n * METH_GROUP, 256);
+    // (without a trim: the kernels as they were before there was one)
+    const auto k_count = trim ? k_meth_events<false, true> : k_meth_events<false, false>;
+    const auto k_emit = trim ? k_meth_events<true, true> : k_meth_events<true, false>;
     prof_begin(c, "k_meth_count");
-    hipLaunchKernelGGL(k_meth_events<false>, dim3(grid), dim3(256), 0, c->stream, c->ix.gen2p, c->ix.chrom_start, raw, off, len, clip, 0l, (long)n, par, c->mt_cnt.as<u32>(),
-                       (const u64*)nullptr, (u64*)nullptr, (u64*)nullptr, info);
+    hipLaunchKernelGGL(k_count, dim3(grid), dim3(256), 0, c->stream, c->ix.gen2p, c->ix.chrom_start, raw, off, len, clip, 0l,
+                       (long)n, par, c->mt_cnt.as<u32>(), (const u64*)nullptr, (u64*)nullptr, (u64*)nullptr, info);
     prof_end(c);
     int rc = scan_u32(c, c->mt_cnt.as<u32>(), n, c->mt_eoff.as<u64>(), 30);
     if (rc) return rc;
@@ -1233,6 +1261,19 @@ static int methyl_device(Lane* c, const char* raw, const u64* off, const u32* le
     if (c->h_info[9]) { c->err = "methyl: the read name, CIGAR, sequence and qualities of record " + std::to_string(~c->h_info[9]) + " do not fit its length"; return BMBS_EINVAL; }
     if (c->h_info[10]) { c->err = "methyl: the refID of record " + std::to_string(~c->h_info[10]) + " is beyond the " + std::to_string(c->ix.n_chrom) + " sequences of the index"; return BMBS_EINVAL; }
     if (c->h_info[11]) { c->err = "methyl: the reference span of record " + std::to_string(~c->h_info[11]) + " runs off its sequence"; return BMBS_EINVAL; }
+    if (mbias) {
+        // 6 blocks per CU, each with its own tally in LDS (k_methyl.hip): the 6 waves per SIMD its registers allow, and 144 of the CU's 160
+        // KiB of LDS -- the walk waits on memory most of its time, so resident waves are what it runs on.  The count pass above has
+        // found nothing to refuse
+        if (!c->mt_cus) { int cus = 0; HIPCHK(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->dev)); c->mt_cus = cus > 0 ? cus : 1; }
+        ENS(c, c->mt_mbias, METH_MBIAS_ROWS * BMBS_MBIAS_CYCLES * 8 + 64);
+        HIPCHK(c, hipMemsetAsync(c->mt_mbias.p, 0, METH_MBIAS_ROWS * BMBS_MBIAS_CYCLES * 8, c->stream));
+        const unsigned mgrid = (unsigned)std::min<u64>((u64)c->mt_cus * 6, nblk(n * METH_GROUP, 256));
+        prof_begin(c, "k_meth_mbias");
+        hipLaunchKernelGGL(k_meth_mbias, dim3(mgrid), dim3(256), 0, c->stream, c->ix.gen2p, c->ix.chrom_start, raw, off, len, clip, (long)n, par,
+                           c->mt_mbias.as<unsigned long long>());
+        prof_end(c);
+    }
     const u64 n_ev = *reinterpret_cast<const u64*>(c->h_info + 28);
     const u64* const eoff = c->mt_eoff.as<u64>();
     u64 n_acc = 0, n_sites = 0;
@@ -1260,8 +1301,8 @@ static int methyl_device(Lane* c, const char* raw, const u64* off, const u32* le
             char* const E = c->mt_ev.as<char>();
             u64* const ka = reinterpret_cast<u64*>(E); u64* const kb = reinterpret_cast<u64*>(E + q); u64* const va = reinterpret_cast<u64*>(E + 2 * q); u64* const vb = reinterpret_cast<u64*>(E + 3 * q);
             prof_begin(c, "k_meth_emit");
-            hipLaunchKernelGGL(k_meth_events<true>, dim3(nblk((end - start) * METH_GROUP, 256)), dim3(256), 0, c->stream, c->ix.gen2p, c->ix.chrom_start, raw, off, len, clip, (long)start,
-                               (long)(end - start), par, (u32*)nullptr, eoff + start, ka, va, info + 4);
+            hipLaunchKernelGGL(k_emit, dim3(nblk((end - start) * METH_GROUP, 256)), dim3(256), 0, c->stream, c->ix.gen2p,
+                               c->ix.chrom_start, raw, off, len, clip, (long)start, (long)(end - start), par, (u32*)nullptr, eoff + start, ka, va, info + 4);
             prof_end(c);
             u64 got = 0;
             if (!sliced) {
@@ -1310,14 +1351,16 @@ static int methyl_device(Lane* c, const char* raw, const u64* off, const u32* le
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
     c->mt_sites = (int64_t)n_sites;
+    c->mt_has_mbias = mbias;
     if (n_site) *n_site = (int64_t)n_sites;
     return BMBS_OK;
 }
 
-static int lane_bam_methyl(Lane* c, const char* records, uint64_t bytes, const uint32_t* len, int64_t n_in, const uint32_t* clip, const bmbs_methyl_params* par, int64_t* n_site)
+static int lane_bam_methyl(Lane* c, const char* records, uint64_t bytes, const uint32_t* len, int64_t n_in, const uint32_t* clip, const bmbs_methyl_params* par,
+                           const bmbs_methyl_opts* opts, int64_t* n_site)
 {
     if (n_site) *n_site = 0;
-    c->mt_sites = -1;
+    c->mt_sites = -1; c->mt_has_mbias = c->mt_mbias_zero = false;
     c->mt_slice.clear();
     if (!c->attached) { c->err = "methyl: no index attached"; return BMBS_ESTATE; }
     if (n_in < 0 || n_in >= (1ll << 31)) { c->err = "methyl: bad argument"; return BMBS_EINVAL; }
@@ -1329,7 +1372,13 @@ static int lane_bam_methyl(Lane* c, const char* records, uint64_t bytes, const u
         sum += len[i];
     }
     if (sum != bytes) { c->err = "methyl: the record lengths add up to " + std::to_string(sum) + " bytes, not to the " + std::to_string(bytes) + " given"; return BMBS_EINVAL; }
-    if (!n) { c->mt_sites = 0; return BMBS_OK; }
+    if (!n) {
+        // (no record: no device work; an _opts call still has its options checked, and its table is all zero)
+        bmbs_methyl_opts pp;
+        if (opts) { if (int rc = methyl_get_opts(c, par, opts, &pp)) return rc; c->mt_has_mbias = c->mt_mbias_zero = (pp.flags & BMBS_METHYL_MBIAS) != 0; }
+        c->mt_sites = 0;
+        return BMBS_OK;
+    }
     if (bytes && !records) { c->err = "methyl: NULL buffer"; return BMBS_EINVAL; }
     HIPCHK(c, hipSetDevice(c->dev));
     ENS(c, c->mt_in, bytes + 256); ENS(c, c->mt_len, n * 4 + 64); ENS(c, c->mt_off, (n + 1) * 8 + 64);
@@ -1345,13 +1394,13 @@ static int lane_bam_methyl(Lane* c, const char* records, uint64_t bytes, const u
     }
     const int rc = scan_u32(c, c->mt_len.as<u32>(), n, c->mt_off.as<u64>(), 29);
     if (rc) return rc;
-    return methyl_device(c, c->mt_in.as<char>(), c->mt_off.as<u64>(), c->mt_len.as<u32>(), clip ? c->mt_clip.as<u32>() : nullptr, n, par, n_site);
+    return methyl_device(c, c->mt_in.as<char>(), c->mt_off.as<u64>(), c->mt_len.as<u32>(), clip ? c->mt_clip.as<u32>() : nullptr, n, par, opts, n_site);
 }
 
-static int lane_bam_sort_methyl(Lane* c, const uint32_t* clip, const bmbs_methyl_params* par, int64_t* n_site)
+static int lane_bam_sort_methyl(Lane* c, const uint32_t* clip, const bmbs_methyl_params* par, const bmbs_methyl_opts* opts, int64_t* n_site)
 {
     if (n_site) *n_site = 0;
-    c->mt_sites = -1;
+    c->mt_sites = -1; c->mt_has_mbias = c->mt_mbias_zero = false;
     c->mt_slice.clear();
     if (!c->attached) { c->err = "sort methyl: no index attached"; return BMBS_ESTATE; }
     if (c->ms_n < 0) {
@@ -1367,7 +1416,7 @@ static int lane_bam_sort_methyl(Lane* c, const uint32_t* clip, const bmbs_methyl
         HIPCHK(c, hipMemcpyAsync(c->mt_clip.p, clip, n * 4, hipMemcpyHostToDevice, us));
         HIPCHK(c, hipStreamSynchronize(us));
     }
-    return methyl_device(c, c->bs_in.as<char>(), c->bs_off.as<u64>(), c->bs_len.as<u32>(), clip ? c->mt_clip.as<u32>() : nullptr, n, par, n_site);
+    return methyl_device(c, c->bs_in.as<char>(), c->bs_off.as<u64>(), c->bs_len.as<u32>(), clip ? c->mt_clip.as<u32>() : nullptr, n, par, opts, n_site);
 }
 
 static int lane_methyl_sites(Lane* c, bmbs_methyl_site* site, int64_t cap, int64_t* n)
@@ -1382,6 +1431,26 @@ static int lane_methyl_sites(Lane* c, bmbs_methyl_site* site, int64_t cap, int64
     HIPCHK(c, hipSetDevice(c->dev));
     hipStream_t ds = c->down_stream ? c->down_stream : c->stream;
     HIPCHK(c, hipMemcpyAsync(site, c->mt_site.p, (size_t)c->mt_sites * sizeof(bmbs_methyl_site), hipMemcpyDeviceToHost, ds));
+    HIPCHK(c, hipStreamSynchronize(ds));
+    return BMBS_OK;
+}
+
+static int lane_methyl_mbias(Lane* c, uint64_t* table, int64_t cap, int64_t* n)
+{
+    if (!n) { c->err = "methyl mbias: NULL argument"; return BMBS_EINVAL; }
+    *n = 0;
+    if (c->mt_sites < 0 || !c->mt_has_mbias) {
+        c->err = "methyl mbias: the context's last bmbs_bam_methyl_opts / bmbs_bam_sort_methyl_opts call left no table (none yet, it failed, or BMBS_METHYL_MBIAS was not set)";
+        return BMBS_ESTATE;
+    }
+    const int64_t entries = (int64_t)METH_MBIAS_ROWS * BMBS_MBIAS_CYCLES;
+    *n = entries;
+    if (entries > cap) { c->err = "methyl mbias: the array is too small (n tells what is needed)"; return BMBS_ENOMEM; }
+    if (!table) { c->err = "methyl mbias: NULL argument"; return BMBS_EINVAL; }
+    if (c->mt_mbias_zero) { memset(table, 0, (size_t)entries * 8); return BMBS_OK; }
+    HIPCHK(c, hipSetDevice(c->dev));
+    hipStream_t ds = c->down_stream ? c->down_stream : c->stream;
+    HIPCHK(c, hipMemcpyAsync(table, c->mt_mbias.p, (size_t)entries * 8, hipMemcpyDeviceToHost, ds));
     HIPCHK(c, hipStreamSynchronize(ds));
     return BMBS_OK;
 }
@@ -1416,8 +1485,12 @@ static int lane_text_sorted_clip(Lane* c, uint32_t* clip, int64_t cap, int64_t* 
 }
 
 extern "C" int bmbs_bam_methyl(bmbs_ctx* X, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, const uint32_t* clip, const bmbs_methyl_params* par, int64_t* n_site)
-{ ON_LANE0(lane_bam_methyl(c, records, bytes, len, n, clip, par, n_site)); }
-extern "C" int bmbs_bam_sort_methyl(bmbs_ctx* X, const uint32_t* clip, const bmbs_methyl_params* par, int64_t* n_site) { ON_LANE0(lane_bam_sort_methyl(c, clip, par, n_site)); }
+{ ON_LANE0(lane_bam_methyl(c, records, bytes, len, n, clip, par, nullptr, n_site)); }
+extern "C" int bmbs_bam_sort_methyl(bmbs_ctx* X, const uint32_t* clip, const bmbs_methyl_params* par, int64_t* n_site) { ON_LANE0(lane_bam_sort_methyl(c, clip, par, nullptr, n_site)); }
+extern "C" int bmbs_bam_methyl_opts(bmbs_ctx* X, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, const uint32_t* clip, const bmbs_methyl_opts* opts, int64_t* n_site)
+{ ON_LANE0(lane_bam_methyl(c, records, bytes, len, n, clip, nullptr, opts, n_site)); }
+extern "C" int bmbs_bam_sort_methyl_opts(bmbs_ctx* X, const uint32_t* clip, const bmbs_methyl_opts* opts, int64_t* n_site) { ON_LANE0(lane_bam_sort_methyl(c, clip, nullptr, opts, n_site)); }
+extern "C" int bmbs_methyl_mbias(bmbs_ctx* X, uint64_t* table, int64_t cap, int64_t* n) { ON_LANE0(lane_methyl_mbias(c, table, cap, n)); }
 extern "C" int bmbs_methyl_sites(bmbs_ctx* X, bmbs_methyl_site* site, int64_t cap, int64_t* n) { ON_LANE0(lane_methyl_sites(c, site, cap, n)); }
 extern "C" int bmbs_text_sorted_clip(bmbs_ctx* X, uint32_t* clip, int64_t cap, int64_t* n) { ON_LANE0(lane_text_sorted_clip(c, clip, cap, n)); }
 

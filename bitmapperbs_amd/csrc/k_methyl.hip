@@ -1,13 +1,15 @@
 // bitmapperbs_amd/csrc/k_methyl.hip -- per-cytosine methylation counts from BAM records on the device (`--bam --sort --methyl`,
-// bmbs_bam_methyl, bmbs_bam_sort_methyl, bmbs_methyl_sites, bmbs_text_sorted_clip).  The rule is in include/bmbs.h; tests/methyl_spec.py
-// restates it.
+// bmbs_bam_methyl[_opts], bmbs_bam_sort_methyl[_opts], bmbs_methyl_sites, bmbs_methyl_mbias, bmbs_text_sorted_clip).  The rule is in
+// include/bmbs.h; tests/methyl_spec.py restates the sites, tests/mbias_spec.py the read-end trim and the M-bias table.
 //
 // Record i = len[i] bytes at raw + off[i] (len 0: no record), the layout of k_markdup.hip.  An EVENT is one call of one read base:
 // key = refID << pos_bits | pos, value = 1 << 32 (methylated) or 1 (unmethylated) -- the same (key, value) form a SITE has once its
 // events are added up, so that one reduction serves the events of a slice of records and the sites of several slices.
 //   k_meth_events<false>  a group of METH_GROUP lanes per record: checks it, decides whether it counts, and counts its events
 //   (scan_u32)            where each record's events go
-//   k_meth_events<true>   the same walk again, writing the events
+//   k_meth_events<true>   the same walk again, writing the events  (<.., true>: both passes leave out the calls of trimmed cycles)
+//   k_meth_mbias          the same walk once more when the M-bias table is asked for: a histogram of the calls by (mate, strand,
+//                         context, methylated, cycle), trimmed or not
 //   k_meth_cut            where a slice of records ends that holds at most a given number of events
 //   (pair sort)           rocPRIM radix_sort_pairs over (key, value), stable, over the key bits that can be set only
 //   k_meth_heads          run heads of equal keys per wave by ballot + popcount; the two halves of the values as 32-bit words for the scans
@@ -16,13 +18,23 @@
 //                         again) or a (key, value) pair for the merge of slices
 //   k_meth_clip           the mate-overlap clip of every record of a sorted text call, in sorted order
 // The context masks are bit-parallel on the planes of DevIndex::gen2p, 32 reference bases a word; read bases and qualities are fetched
-// only where a mask bit is set.  No kernel here uses LDS; every store is an ordinary vector store.
+// only where a mask bit is set.  k_meth_mbias keeps a block's tally in LDS; no other kernel here uses LDS.  Every store is an ordinary
+// vector store, every add an atomicAdd of plain C++; there is no inline assembly.
 #ifndef K_METHYL_HIP
 #define K_METHYL_HIP
 
 #define METH_GROUP 16                     // lanes per record: a lane takes one 32-base word of the record's reference span at a time
 
-struct MethPar { u32 contexts, min_mapq, min_phred; int n_chrom, pos_bits; };
+#define METH_MBIAS_ROWS 24                // mate x strand x context x (unmethylated, methylated)
+#define METH_MBIAS_LDS 256                // k_meth_mbias: cycles below this are tallied in the block's LDS table
+
+// ig5 / ig3: the cycles left out at the 5' / 3' end of a record of mate 0 / 1 (read only where TRIM is set)
+struct MethPar { u32 contexts, min_mapq, min_phred; int n_chrom, pos_bits; u32 ig5[2], ig3[2]; };
+
+// mate of a record: 1 for read 2 of a pair (flags 0x1 and 0x80), else 0
+DEVI u32 meth_mate(u32 flag) { return (flag & 0x81u) == 0x81u ? 1u : 0u; }
+// cycle of read base ri: its position in sequencing order (SEQ is stored reversed for flag 0x10)
+DEVI long meth_cycle(u32 flag, u32 l_seq, long ri) { return (flag & 0x10u) ? (long)l_seq - 1 - ri : ri; }
 
 // bits k of a 64-bit window whose bit 0 is position b0, for the positions in [lo, hi)  (the window is at most 63 bits wide in use)
 DEVI u64 meth_range(long b0, long lo, long hi, int width)
@@ -55,7 +67,10 @@ DEVI void meth_masks(const u64* __restrict__ gen2p, long W, long lo, long hi, u3
 // sequence and qualities do not fit its length), info[2] = ~(the first whose refID is beyond the index's sequences), info[3] = ~(the
 // first mapped record whose reference span runs off its sequence) (0: none).  Nothing is read behind a record.
 // EMIT false: cnt[i - first] = the events of record i.  EMIT true: they are written at eoff[i - first] - eoff[0].
-template <bool EMIT>
+// TRIM: a call of cycle c of a record of mate m is an event only if par.ig5[m] <= c < l_seq - par.ig3[m]; both passes of a call run
+// the same TRIM.  <.., false> is the kernel as it was before there was a trim: none of this is compiled into it.
+// k_meth_mbias below holds a COPY of the record checks and of the walk: a change to the rule here has to be made there too.
+template <bool EMIT, bool TRIM>
 __global__ void __launch_bounds__(256)
 k_meth_events(const u64* __restrict__ gen2p, const u64* __restrict__ chrom_start, const char* __restrict__ raw, const u64* __restrict__ off,
               const u32* __restrict__ len, const u32* __restrict__ clip, long first, long n, MethPar par, u32* __restrict__ cnt,
@@ -110,6 +125,7 @@ k_meth_events(const u64* __restrict__ gen2p, const u64* __restrict__ chrom_start
     const char* const ql = sq + ((u64)l_seq + 1) / 2;
     const u32 want_m = ob ? 4u : 2u, want_u = ob ? 1u : 8u;               // G / A for OB, C / T for OT (BAM's 4-bit codes)
     const long W0 = a0 >> 5, W1 = counts && span ? (a1 - 1) >> 5 : W0 - 1;
+    const long t_lo = TRIM ? (long)par.ig5[meth_mate(flag)] : 0, t_hi = TRIM ? (long)l_seq - (long)par.ig3[meth_mate(flag)] : 0;
     for (long base = W0; base <= W1; base += METH_GROUP) {                  // (uniform within the group)
         const long W = base + gl;
         u32 mb = 0, ub = 0;
@@ -140,6 +156,7 @@ k_meth_events(const u64* __restrict__ gen2p, const u64* __restrict__ chrom_start
                     }
                 }
                 if (ri < 0 || ri >= (long)l_seq) continue;
+                if (TRIM) { const long cy = meth_cycle(flag, l_seq, ri); if (cy < t_lo || cy >= t_hi) continue; }
                 const u32 q = (u32)(unsigned char)ql[ri];
                 if ((q == 255u ? 0u : q) < par.min_phred) continue;
                 const u32 by = (u32)(unsigned char)sq[ri >> 1];
@@ -168,6 +185,114 @@ k_meth_events(const u64* __restrict__ gen2p, const u64* __restrict__ chrom_start
         total += all;
     }
     if (!EMIT && t < n && gl == 0) cnt[t] = total;
+}
+
+// The M-bias table: table[row * BMBS_MBIAS_CYCLES + min(cycle, BMBS_MBIAS_CYCLES - 1)] += 1 for every call of records 0 .. n - 1, with
+// row = ((mate * 2 + strand) * 3 + context) * 2 + methylated.  A call is what k_meth_events<.., false> makes an event of: the trim is
+// not looked at.  The walk is that kernel's, written out again: the tally needs the read index and the context of a call where the
+// innermost loop has them, and a walk shared through a function would have to leave k_meth_events' code as it is.  It
+// runs behind a count pass that found nothing to refuse; the checks stay, so that nothing is read behind a record, and report nothing.
+// A fixed grid strides over the records, a group of METH_GROUP lanes per record.  Each block tallies the cycles below METH_MBIAS_LDS in
+// its own u32 table in LDS (24 rows x 256 x 4 B = 24 KiB) with adds that return nothing, and adds its non-zero counters to the global
+// table when it is through; later cycles go to the global table at once.  A record has every cycle once, so it adds at most 1 to any
+// one counter: with n < 2^31 records no u32 counter of a block can wrap.  Integer adds: the table does not depend on their order.
+__global__ void __launch_bounds__(256)
+k_meth_mbias(const u64* __restrict__ gen2p, const u64* __restrict__ chrom_start, const char* __restrict__ raw, const u64* __restrict__ off,
+             const u32* __restrict__ len, const u32* __restrict__ clip, long n, MethPar par, unsigned long long* __restrict__ table)
+{
+    __shared__ u32 tally[METH_MBIAS_ROWS * METH_MBIAS_LDS];
+    for (int x = (int)threadIdx.x; x < METH_MBIAS_ROWS * METH_MBIAS_LDS; x += 256) tally[x] = 0;
+    __syncthreads();
+    const int gl = threadIdx.x % METH_GROUP;
+    const long per_block = 256 / METH_GROUP, step = (long)gridDim.x * per_block;
+    for (long first = (long)blockIdx.x * per_block; first < n; first += step) {          // (uniform within the block)
+        const long i = first + threadIdx.x / METH_GROUP;
+        bool live = i < n;
+        const u32 l = live ? len[i] : 0;
+        if (l < 36) live = false;
+        const char* const p = raw + (live ? off[i] : 0);
+        if (live && bs_ld32(p) + 4u != l) live = false;
+        int ref = -1, pos = 0;
+        u32 l_name = 0, mapq = 0, n_cig = 0, flag = 4, l_seq = 0;
+        if (live) {
+            ref = (int)bs_ld32(p + 4); pos = (int)bs_ld32(p + 8);
+            l_name = (u32)(unsigned char)p[12]; mapq = (u32)(unsigned char)p[13];
+            n_cig = (u32)(unsigned char)p[16] | ((u32)(unsigned char)p[17] << 8);
+            flag = (u32)(unsigned char)p[18] | ((u32)(unsigned char)p[19] << 8);
+            l_seq = bs_ld32(p + 20);
+            if (36ull + l_name + 4ull * n_cig + ((u64)l_seq + 1) / 2 + l_seq > (u64)l) live = false;
+        }
+        if (live && ref >= par.n_chrom) live = false;
+        const bool mapped = live && ref >= 0 && !(flag & 4u) && n_cig > 0;
+        const char* const cg = p + 36 + l_name;
+        u64 span = 0;
+        if (mapped)
+            for (u32 k = (u32)gl; k < n_cig; k += METH_GROUP) { const u32 c = bs_ld32(cg + 4 * (u64)k); if ((0x18du >> (c & 15u)) & 1u) span += c >> 4; }
+        for (int d = METH_GROUP / 2; d; d >>= 1) {
+            const u32 lo = (u32)__shfl_xor((int)(u32)span, d), hi = (u32)__shfl_xor((int)(u32)(span >> 32), d);
+            span += ((u64)hi << 32) | lo;
+        }
+        long s_lo = 0, s_hi = 0;
+        bool counts = mapped;
+        if (mapped) {
+            s_lo = (long)chrom_start[ref]; s_hi = (long)chrom_start[ref + 1];
+            if (pos < 0 || (u64)pos + span > (u64)(s_hi - s_lo)) counts = false;
+        }
+        counts = counts && !(flag & 0xF00u) && mapq >= par.min_mapq && (!(flag & 1u) || (flag & 2u));
+        const bool ob = (flag & 1u) ? (((flag & 0x40u) && (flag & 0x10u)) || ((flag & 0x80u) && !(flag & 0x10u))) : (flag & 0x10u) != 0;
+        const long a0 = s_lo + pos, a1 = a0 + (long)span;
+        const u32 cw = (counts && clip) ? clip[i] : 0;
+        const long c_lo = a0 + (long)(cw >> 16), c_hi = c_lo + (long)(cw & 0xffffu);
+        const bool all_m = counts && n_cig == 1 && ((0x181u >> (bs_ld32(cg) & 15u)) & 1u);
+        const char* const sq = cg + 4 * (u64)n_cig;
+        const char* const ql = sq + ((u64)l_seq + 1) / 2;
+        const u32 want_m = ob ? 4u : 2u, want_u = ob ? 1u : 8u;
+        const u32 row0 = (meth_mate(flag) * 2u + (ob ? 1u : 0u)) * 6u;              // + 2 context + methylated
+        const long W0 = a0 >> 5, W1 = counts && span ? (a1 - 1) >> 5 : W0 - 1;
+        for (long W = W0 + gl; W <= W1; W += METH_GROUP) {
+            u32 m[6];
+            meth_masks(gen2p, W, s_lo, s_hi, m);
+            const u32 m0 = m[ob ? 3 : 0], m1 = m[ob ? 4 : 1];
+            u32 sel = 0;
+#pragma unroll
+            for (int x = 0; x < 3; x++) if ((par.contexts >> x) & 1u) sel |= m[(ob ? 3 : 0) + x];
+            sel &= (u32)meth_range(32 * W, a0, a1, 32) & ~(u32)meth_range(32 * W, c_lo, c_hi, 32);
+            u32 k = 0; long r_at = 0, i_at = 0;
+            while (sel) {
+                const int b = __ffs((int)sel) - 1;
+                sel &= sel - 1;
+                const long ro = 32 * W + b - a0;
+                long ri = -1;
+                if (all_m) ri = ro;
+                else {
+                    while (k < n_cig) {
+                        const u32 c = bs_ld32(cg + 4 * (u64)k);
+                        const u32 op = c & 15u; const long ln = (long)(c >> 4);
+                        const bool on_ref = (0x18du >> op) & 1u, on_read = (0x193u >> op) & 1u;
+                        if (on_ref && ro < r_at + ln) { if (on_read) ri = i_at + (ro - r_at); break; }
+                        if (on_ref) r_at += ln;
+                        if (on_read) i_at += ln;
+                        k++;
+                    }
+                }
+                if (ri < 0 || ri >= (long)l_seq) continue;
+                const u32 q = (u32)(unsigned char)ql[ri];
+                if ((q == 255u ? 0u : q) < par.min_phred) continue;
+                const u32 by = (u32)(unsigned char)sq[ri >> 1];
+                const u32 code = (ri & 1) ? (by & 15u) : (by >> 4);
+                if (code != want_m && code != want_u) continue;
+                const u32 row = row0 + 2u * (((m0 >> b) & 1u) ? 0u : ((m1 >> b) & 1u) ? 1u : 2u) + (code == want_m ? 1u : 0u);
+                const long cy = meth_cycle(flag, l_seq, ri);                        // 0 .. l_seq - 1
+                if (cy < METH_MBIAS_LDS) atomicAdd(&tally[row * METH_MBIAS_LDS + (u32)cy], 1u);
+                else atomicAdd(&table[row * BMBS_MBIAS_CYCLES + (u32)(cy < BMBS_MBIAS_CYCLES ? cy : BMBS_MBIAS_CYCLES - 1)], 1ull);
+            }
+        }
+    }
+    __syncthreads();
+    for (int x = (int)threadIdx.x; x < METH_MBIAS_ROWS * METH_MBIAS_LDS; x += 256) {
+        const u32 v = tally[x];
+        if (v) atomicAdd(&table[(x / METH_MBIAS_LDS) * BMBS_MBIAS_CYCLES + x % METH_MBIAS_LDS], (unsigned long long)v);
+    }
 }
 
 // *end = the largest r in (start, n] with eoff[r] - eoff[start] <= cap, start + 1 at the least (one thread)

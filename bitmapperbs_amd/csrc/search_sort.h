@@ -388,3 +388,25 @@ inline bool methyl_write(const std::string& path, const std::string& prefix, con
     const bool ok = !ferror(f);
     return fclose(f) == 0 && ok;
 }
+// <prefix>_mbias.tsv (--mbias): the M-bias table, table[2 mate][2 strand][3 context][2 (unmethylated, methylated)][BMBS_MBIAS_CYCLES] --
+// the pass-2 calls' tables (bmbs_methyl_mbias) added up, which does not depend on how the records were cut into calls.  One line per
+// (context, strand, read, cycle) with calls, in that order, cycles 1-based, the percentage rounded as in the bedGraphs
+inline bool mbias_write(const std::string& path, const std::vector<uint64_t>& table)
+{
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    static const char* const ctx_name[3] = {"CpG", "CHG", "CHH"};
+    fputs("#context\tstrand\tread\tcycle\tmethylated\tunmethylated\tpercent\n", f);
+    for (size_t ctx = 0; ctx < 3; ctx++)
+        for (size_t strand = 0; strand < 2; strand++)
+            for (size_t mate = 0; mate < 2; mate++) {
+                const uint64_t* const un = table.data() + (((mate * 2 + strand) * 3 + ctx) * 2) * BMBS_MBIAS_CYCLES, * const me = un + BMBS_MBIAS_CYCLES;
+                for (size_t cy = 0; cy < BMBS_MBIAS_CYCLES; cy++) {
+                    const uint64_t m = me[cy], u = un[cy];
+                    if (m + u) fprintf(f, "%s\t%s\t%zu\t%zu\t%llu\t%llu\t%llu\n", ctx_name[ctx], strand ? "OB" : "OT", mate + 1, cy + 1, (unsigned long long)m, (unsigned long long)u,
+                                       (unsigned long long)((200 * m + m + u) / (2 * (m + u))));
+                }
+            }
+    const bool ok = !ferror(f);
+    return fclose(f) == 0 && ok;
+}

@@ -434,27 +434,55 @@ class Mapper:
         self._chk(self._lib.bmbs_methyl_sites(self._ctx, capi.ptr(site), n.value, C.byref(n)))
         return site[:n.value]
 
-    def bam_methyl(self, records: bytes, lens, clip=None, contexts: int = 1, min_mapq: int = 10, min_phred: int = 5) -> np.ndarray:
+    @staticmethod
+    def _methyl_opts(contexts, min_mapq, min_phred, ignore_5p, ignore_3p, mbias):
+        """None with the defaults of the three new keywords (the call then goes to the entry point without options), else MethylOpts"""
+        i5, i3 = tuple(int(x) for x in ignore_5p), tuple(int(x) for x in ignore_3p)
+        if len(i5) != 2 or len(i3) != 2:
+            raise ValueError("ignore_5p and ignore_3p: one value per mate")
+        if not mbias and i5 == (0, 0) and i3 == (0, 0):
+            return None
+        return capi.MethylOpts(int(contexts), int(min_mapq), int(min_phred), capi.METHYL_MBIAS if mbias else 0, (C.c_int32 * 2)(*i5), (C.c_int32 * 2)(*i3))
+
+    def methyl_mbias(self) -> np.ndarray:
+        """the M-bias table the last bam_methyl / bam_sort_methyl call with mbias=True left: uint64 [mate][strand][context][0 unmethylated,
+        1 methylated][cycle] (capi.MBIAS_SHAPE), every call that passed every filter but the trim (bmbs_methyl_mbias)"""
+        n = C.c_int64(0)
+        rc = self._lib.bmbs_methyl_mbias(self._ctx, None, 0, C.byref(n))
+        if rc and rc != -12:
+            self._chk(rc)
+        table = np.zeros(max(1, n.value), dtype=np.uint64)
+        self._chk(self._lib.bmbs_methyl_mbias(self._ctx, capi.ptr(table), n.value, C.byref(n)))
+        return table[:n.value].reshape(capi.MBIAS_SHAPE)
+
+    def bam_methyl(self, records: bytes, lens, clip=None, contexts: int = 1, min_mapq: int = 10, min_phred: int = 5, ignore_5p=(0, 0), ignore_3p=(0, 0),
+                   mbias: bool = False) -> np.ndarray:
         """concatenated BAM records + their sizes (0: no record here) [+ their mate-overlap clips] -> the methylation counts of every
-        cytosine of the selected contexts (1 CpG | 2 CHG | 4 CHH) that a record calls, ordered by (ref, pos) (bmbs_bam_methyl)"""
+        cytosine of the selected contexts (1 CpG | 2 CHG | 4 CHH) that a record calls, ordered by (ref, pos) (bmbs_bam_methyl).
+        ignore_5p / ignore_3p = (read 1 or single end, read 2): cycles left out at either end of a read; mbias: keep the M-bias table for
+        methyl_mbias() (bmbs_bam_methyl_opts)"""
         ln = np.ascontiguousarray(lens, dtype=np.uint32)
         a = np.frombuffer(records, dtype=np.uint8) if len(records) else np.zeros(1, dtype=np.uint8)
         cl = None if clip is None else np.ascontiguousarray(clip, dtype=np.uint32)
         if cl is not None and cl.size != ln.size:
             raise ValueError("bam_methyl: one clip per record")
+        opts = self._methyl_opts(contexts, min_mapq, min_phred, ignore_5p, ignore_3p, mbias)
         par = self._methyl_params(contexts, min_mapq, min_phred)
         n = C.c_int64(0)
-        self._chk(self._lib.bmbs_bam_methyl(self._ctx, capi.ptr(a), len(records), capi.ptr(ln) if ln.size else None, ln.size,
-                                            capi.ptr(cl) if cl is not None and cl.size else None, C.byref(par), C.byref(n)))
+        call = self._lib.bmbs_bam_methyl if opts is None else self._lib.bmbs_bam_methyl_opts
+        self._chk(call(self._ctx, capi.ptr(a), len(records), capi.ptr(ln) if ln.size else None, ln.size,
+                       capi.ptr(cl) if cl is not None and cl.size else None, C.byref(par if opts is None else opts), C.byref(n)))
         return self.methyl_sites()
 
-    def bam_sort_methyl(self, clip=None, contexts: int = 1, min_mapq: int = 10, min_phred: int = 5) -> np.ndarray:
+    def bam_sort_methyl(self, clip=None, contexts: int = 1, min_mapq: int = 10, min_phred: int = 5, ignore_5p=(0, 0), ignore_3p=(0, 0), mbias: bool = False) -> np.ndarray:
         """the same for the records of the last bam_sort call, which are still on the device; clip in that call's input order
-        (bmbs_bam_sort_methyl)"""
+        (bmbs_bam_sort_methyl, bmbs_bam_sort_methyl_opts)"""
         cl = None if clip is None else np.ascontiguousarray(clip, dtype=np.uint32)
+        opts = self._methyl_opts(contexts, min_mapq, min_phred, ignore_5p, ignore_3p, mbias)
         par = self._methyl_params(contexts, min_mapq, min_phred)
         n = C.c_int64(0)
-        self._chk(self._lib.bmbs_bam_sort_methyl(self._ctx, capi.ptr(cl) if cl is not None and cl.size else None, C.byref(par), C.byref(n)))
+        call = self._lib.bmbs_bam_sort_methyl if opts is None else self._lib.bmbs_bam_sort_methyl_opts
+        self._chk(call(self._ctx, capi.ptr(cl) if cl is not None and cl.size else None, C.byref(par if opts is None else opts), C.byref(n)))
         return self.methyl_sites()
 
     def sync(self):

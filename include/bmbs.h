@@ -470,14 +470,41 @@ int bmbs_dup_select(bmbs_ctx*, const bmbs_dup_sig* sig, int64_t n, uint8_t* dup,
  * BMBS_ESTATE: no index attached; bmbs_bam_sort_methyl: no bmbs_bam_sort call's records are resident (none yet, it failed or had no
  * records), or another call has used its buffers since.  BMBS_EINVAL (bmbs_last_error names the record): the length checks of
  * bmbs_bam_dup_sigs, a refID beyond the index's sequences, a mapped record with a CIGAR whose reference span runs off its sequence.
- * n = 0 is valid.                                                                                                                  */
+ * n = 0 is valid.
+ *
+ * Read-end trimming and the M-bias table (bmbs_bam_methyl_opts, bmbs_bam_sort_methyl_opts, bmbs_methyl_mbias; tests/mbias_spec.py).
+ * The CYCLE of a call is the 0-based position of the called read base in sequencing order: with ri the base's index in SEQ as the
+ * record stores it (soft-clipped and inserted bases count; H and P are not part of SEQ and shift nothing), cycle = ri for a forward
+ * record and l_seq - 1 - ri for a record with flag 0x10.  The MATE of a record is 1 when flags 0x1 and 0x80 are both set (read 2 of a
+ * pair), else 0 (single end, read 1, no read number).  A call of a record of mate m counts towards the sites iff
+ * ignore_5p[m] <= cycle < l_seq - ignore_3p[m] (Bismark's --ignore, --ignore_3prime, --ignore_r2, --ignore_3prime_r2; each 0..65535;
+ * all zero: no trim).  A record all of whose cycles are ignored contributes nothing and is no error.  The mate-overlap clip stays
+ * geometric and does not look at the trim: read 2 is still clipped where read 1 covers a position, even if read 1's call there was
+ * trimmed away (Bismark does the same).
+ * flags & BMBS_METHYL_MBIAS: the call also leaves uint64 table[2 mate][2 strand (0 OT, 1 OB)][3 context][2 (0 unmethylated,
+ * 1 methylated)][BMBS_MBIAS_CYCLES] on the device, which counts every call that passes every filter EXCEPT the trim (record flags,
+ * MAPQ, proper pair, base quality, selected contexts, overlap clip): one run gives the untrimmed curve and the trimmed sites.  Calls at
+ * cycle >= BMBS_MBIAS_CYCLES are tallied in the last bin (the trim still uses the true cycle); rows of contexts that are not selected
+ * stay zero; n = 0 leaves an all-zero table.  The table is made from the index's genome: calls at bases the FASTA does not spell A, C,
+ * G or T, where the index holds a pseudo-random letter, are in it (bmbs_search filters their SITES out of the bedGraph, not the table).
+ * bmbs_methyl_mbias fetches the table of the context's last methylation call: *n = 24 * BMBS_MBIAS_CYCLES; BMBS_ESTATE if that call
+ * did not set BMBS_METHYL_MBIAS, failed, or there was none; BMBS_ENOMEM with *n set when cap (entries) is smaller, a cap of 0 being
+ * the size query.  BMBS_EINVAL ("bad parameters") for unknown flags bits or an ignore value outside 0..65535.
+ * bmbs_bam_methyl / bmbs_bam_sort_methyl are the _opts calls with flags 0 and no trim.                                           */
+#define BMBS_MBIAS_CYCLES 1024
+#define BMBS_METHYL_MBIAS 1            /* in bmbs_methyl_opts.flags */
 typedef struct bmbs_methyl_params { int32_t contexts /* 1 CpG | 2 CHG | 4 CHH */, min_mapq, min_phred, reserved; } bmbs_methyl_params;
+typedef struct bmbs_methyl_opts   { int32_t contexts, min_mapq, min_phred, flags; int32_t ignore_5p[2], ignore_3p[2]; } bmbs_methyl_opts;   /* 32 bytes */
 typedef struct bmbs_methyl_site   { int32_t ref, pos; uint32_t meth, unmeth, kind /* context 0..2 | strand << 2 */, pad; } bmbs_methyl_site;   /* 24 bytes */
 int bmbs_text_sorted_clip(bmbs_ctx*, uint32_t* clip, int64_t cap, int64_t* n);
 int bmbs_bam_methyl(bmbs_ctx*, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, const uint32_t* clip,
                     const bmbs_methyl_params* params, int64_t* n_site);
 int bmbs_bam_sort_methyl(bmbs_ctx*, const uint32_t* clip, const bmbs_methyl_params* params, int64_t* n_site);
+int bmbs_bam_methyl_opts(bmbs_ctx*, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, const uint32_t* clip,
+                         const bmbs_methyl_opts* opts, int64_t* n_site);
+int bmbs_bam_sort_methyl_opts(bmbs_ctx*, const uint32_t* clip, const bmbs_methyl_opts* opts, int64_t* n_site);
 int bmbs_methyl_sites(bmbs_ctx*, bmbs_methyl_site* site, int64_t cap, int64_t* n);
+int bmbs_methyl_mbias(bmbs_ctx*, uint64_t* table, int64_t cap, int64_t* n);
 
 /* a21: per-ctx counters of the batches mapped so far = {reads, unique, ambiguous, mapped bases,
  * error bases} (Schema.cpp:25141-25146); bmbs_stats_allreduce sums them over the ctxs one process

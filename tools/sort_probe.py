@@ -13,8 +13,15 @@ and the k_bai_* rows of the kernel trace (which then is a --bai run) beside k_ba
 driver's markdup line, and the k_dup_* rows of the kernel trace (which then is a --markdup run) beside k_bam_gather.
 --methyl: a leg `--bam --sort --methyl <prefix> --CpG --CHG --CHH`, alternating with the others -- its walls beside the sorted runs' on the
 same build, the counts of the driver's methyl line, and the k_meth_* rows of the kernel trace (which then is a --methyl run).
+--mbias (with --methyl): a leg `--methyl ... --mbias` beside the --methyl leg -- its walls beside that leg's, the `mbias calls` figure,
+and k_meth_mbias's kernel time beside the counting pass's (k_meth_events<false, ..>, the same walk) in the trace (then a --mbias run).
+--other-driver <bmbs_search of another build> (with --methyl): that build's `--methyl` leg alternates with this build's, to show that
+a run which asks for neither the table nor a trim costs what it did: this build's median against the other's median and spread.
+(The other build's runs write the same sortp_y.bam and bedGraphs as this build's --methyl leg, one after the other.)
+With --mbias the report goes to profiles/mbias_probe.txt and the kernel rows to profiles/mbias_kernel_stats.csv unless --out /
+--stats-out name other files.
 
-  python tools/sort_probe.py [--reads 4000000] [--loop 8] [--pe] [--runs 3] [--bai] [--markdup] [--methyl] [--out profiles/sorted_bam_probe.txt]
+  python tools/sort_probe.py [--reads 4000000] [--loop 8] [--pe] [--runs 3] [--bai] [--markdup] [--methyl [--mbias] [--other-driver path]] [--out profiles/sorted_bam_probe.txt | profiles/mbias_probe.txt]
 """
 import argparse
 import csv
@@ -55,6 +62,9 @@ def verbose_numbers(err):
     m = re.search(r"(methyl: sites CpG \d+ CHG \d+ CHH \d+, calls CpG \d+ CHG \d+ CHH \d+)", err)
     if m:
         out["methyl"] = m.group(1)
+    m = re.search(r"mbias calls (\d+)", err)
+    if m:
+        out["mbias"] = int(m.group(1))
     m = re.search(r"busy fractions of the mapping wall: link up ([\d.]+), link down ([\d.]+)", err)
     if m:
         out["link_up"], out["link_down"] = float(m.group(1)), float(m.group(2))
@@ -74,11 +84,16 @@ def main():
     ap.add_argument("--bai", action="store_true", help="also measure --bam --sort --bai (the index written in the same run)")
     ap.add_argument("--markdup", action="store_true", help="also measure --bam --sort --markdup (PCR duplicates flagged in the same run)")
     ap.add_argument("--methyl", action="store_true", help="also measure --bam --sort --methyl (methylation counts per cytosine from the same run)")
+    ap.add_argument("--mbias", action="store_true", help="with --methyl: also measure --methyl ... --mbias (the M-bias table from the same run)")
+    ap.add_argument("--other-driver", default="", help="with --methyl: bmbs_search of another build, whose --methyl leg alternates with this build's")
     ap.add_argument("--driver-args", default="")
     ap.add_argument("--workdir", default=os.environ.get("BMBS_BENCH_DIR", "/tmp/bmbs_bench"))
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sorted_bam_probe.txt"))
-    ap.add_argument("--stats-out", default=os.path.join(ROOT, "profiles", "sorted_bam_kernel_stats.csv"))
+    ap.add_argument("--out", default="")
+    ap.add_argument("--stats-out", default="")
     args = ap.parse_args()
+    stem = "mbias" if args.methyl and args.mbias else "sorted_bam"
+    args.out = args.out or os.path.join(ROOT, "profiles", stem + "_probe.txt")
+    args.stats_out = args.stats_out or os.path.join(ROOT, "profiles", stem + "_kernel_stats.csv")
     import torch
     from bitmapperbs_amd import gpusynth
     cfg = dict(genome=args.genome, n_chrom=4 if args.genome < 1_000_000_000 else 24)
@@ -118,13 +133,19 @@ def main():
     if args.methyl:
         runs["methyl"] = []
         legs.append(("methyl", os.path.join(wd, "sortp_y.bam"), ["--sort"] + meth_args))
+        if args.mbias:
+            runs["mbias"] = []
+            legs.append(("mbias", os.path.join(wd, "sortp_y.bam"), ["--sort"] + meth_args + ["--mbias"]))
+        if args.other_driver:
+            runs["methyl_other"] = []
+            legs.append(("methyl_other", os.path.join(wd, "sortp_y.bam"), ["--sort"] + meth_args))
     size = {}
     step(base + ["-o", out_u], 600)                     # warm-up: page cache, index files
     for _ in range(max(3, args.runs)):
         for kind, out, extra in legs:
             if os.path.exists(out):
                 os.unlink(out)
-            p = step(base + extra + ["-o", out], 600)
+            p = step(([args.other_driver] + base[1:] if kind == "methyl_other" else base) + extra + ["-o", out], 600)
             runs[kind].append(verbose_numbers(p.stderr))
             size[kind] = os.path.getsize(out)
     # the same sorted run with ONE staging slot and context in pass 2 (the default is two): what overlapping the calls is worth
@@ -134,7 +155,8 @@ def main():
     say("sort_probe: %d %s of %d bp x %d passes over the file = %d records per run, genome %d bp, batch %d, %s"
         % (args.reads, "pairs" if args.pe else "SE reads", L, args.loop, n_reads, args.genome, args.batch, " ".join(base[3:])))
     med = {}
-    label = {"bam": "--bam", "sort": "--bam --sort", "bai": "--bam --sort --bai", "markdup": "--bam --sort --markdup", "methyl": "--bam --sort --methyl"}
+    label = {"bam": "--bam", "sort": "--bam --sort", "bai": "--bam --sort --bai", "markdup": "--bam --sort --markdup", "methyl": "--bam --sort --methyl",
+             "mbias": "... --methyl --mbias", "methyl_other": "--methyl, other build"}
     for kind in runs:
         w = [r["wall"] for r in runs[kind]]
         med[kind] = statistics.median(w)
@@ -169,12 +191,21 @@ def main():
         say("--methyl: %s; median wall %.3f s against %.3f s without it = %+.3f s; spread (max - min) of the sorted runs %.3f s; pass 1 %s s, pass 2 %s s"
             % (runs["methyl"][-1].get("methyl", "?"), med["methyl"], med["sort"], med["methyl"] - med["sort"], max(sw) - min(sw),
                " ".join("%.3f" % r["pass1"] for r in runs["methyl"]), " ".join("%.3f" % r["pass2"] for r in runs["methyl"])))
+    if args.methyl and args.mbias:
+        mw = [r["wall"] for r in runs["methyl"]]
+        say("--mbias: mbias calls %s; median wall %.3f s against %.3f s of --methyl without it = %+.3f s; spread (max - min) of the --methyl runs %.3f s; pass 2 %s s"
+            % (runs["mbias"][-1].get("mbias", "?"), med["mbias"], med["methyl"], med["mbias"] - med["methyl"], max(mw) - min(mw), " ".join("%.3f" % r["pass2"] for r in runs["mbias"])))
+    if args.methyl and args.other_driver:
+        ow = [r["wall"] for r in runs["methyl_other"]]
+        say("--methyl on this build against the other build (%s): median wall %.3f s against %.3f s = %+.3f s; the other build's own spread (max - min) %.3f s: %s"
+            % (args.other_driver, med["methyl"], med["methyl_other"], med["methyl"] - med["methyl_other"], max(ow) - min(ow),
+               "within it" if abs(med["methyl"] - med["methyl_other"]) <= max(ow) - min(ow) else "OUTSIDE it"))
     # ---- one run of its own under the kernel trace
     tr = os.path.join(wd, "sortp_trace")
     shutil.rmtree(tr, ignore_errors=True)
     if os.path.exists(out_s):
         os.unlink(out_s)
-    step(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tr, "--"] + base + ["--sort"] + (["--bai"] if args.bai else []) + (["--markdup"] if args.markdup else []) + (meth_args if args.methyl else []) + ["-o", out_s], 900)
+    step(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tr, "--"] + base + ["--sort"] + (["--bai"] if args.bai else []) + (["--markdup"] if args.markdup else []) + (meth_args if args.methyl else []) + (["--mbias"] if args.methyl and args.mbias else []) + ["-o", out_s], 900)
     f = glob.glob(os.path.join(tr, "**", "*kernel_stats.csv"), recursive=True)
     if f:
         rows = list(csv.DictReader(open(f[0])))
@@ -218,6 +249,9 @@ def main():
                     say("  %-14s %.3f ms in %s calls" % (r["Name"].split("(")[0], int(r["TotalDurationNs"]) / 1e6, r["Calls"]))
             say("  k_meth_* together %.3f ms beside k_bam_gather's %.2f ms (the event passes read the fixed fields, the CIGAR and, at cytosines only, bases and qualities)"
                 % (total_ns(lambda n: "k_meth_" in n) / 1e6, g / 1e6))
+            if args.mbias:
+                mb, cnt = total_ns(lambda n: "k_meth_mbias" in n), total_ns(lambda n: "k_meth_events<false" in n)
+                say("  k_meth_mbias %.3f ms beside the counting pass k_meth_events<false, ..> %.3f ms (the same walk; the tally adds one LDS or global add per call)" % (mb / 1e6, cnt / 1e6))
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as o:
         o.write("\n".join(lines) + "\n")
