@@ -323,7 +323,6 @@ __device__ unsigned long long g_bgzf_prof[8];
 #endif
 
 // ---- BGZF: one workgroup deflates one block of <= 0xff00 input bytes --------------------------------------------------------------
-#define BGZF_IN       0xff00                // input bytes per block (bgzf.h BGZF_BLOCK_SIZE)
 #define BGZF_SLOT     65536                 // bytes of a block's slot in the scratch output (a stored block fits: 0xff00 + 5 + 26)
 #define BGZF_THREADS  256
 #define BGZF_SEG      256                   // input bytes parsed by one thread

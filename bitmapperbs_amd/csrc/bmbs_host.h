@@ -1,6 +1,8 @@
 // bitmapperbs_amd/csrc/bmbs_host.h -- host-side state of the library (lanes, buffers, the public handle) and the functions its translation
-// units share: bmbs_api.hip (mapping kernels, the stage and mapping entry points) and bmbs_textpath.hip (the two ends of the file path:
-// FASTQ text / BGZF in, SAM text / BAM out).  Round 5 split them: one 3 000-line file had rebuilt ~85 kernels for a one-line change.
+// units share: bmbs_api.hip (mapping kernels, the stage and mapping entry points), bmbs_textpath.hip (the two ends of the file path:
+// FASTQ text / BGZF in, SAM text / BAM out, with the sort and the deflater the text calls run) and bmbs_records.hip (the stages behind
+// the sorted BAM, on records that are on the device or come from the host: bmbs_bam_sort, its .bai pieces, duplicate signatures and
+// marks, methylation calls).  Round 5 split the first two: one 3 000-line file had rebuilt ~85 kernels for a one-line change.
 #ifndef BMBS_HOST_H
 #define BMBS_HOST_H
 #include "../../include/bmbs.h"
@@ -143,6 +145,9 @@ struct Occ3Shared {
     ~Occ3Shared() { if (occ3 || c3) { (void)hipSetDevice(dev); if (occ3) (void)hipFree(occ3); if (c3) (void)hipFree(c3); } }
 };
 
+// records the host handed over (bmbs_records.hip: stage_records): the bytes as uploaded, the entries' lengths, their exclusive scan
+struct RecIn { DevBuf in, len, off; };
+
 // One lane = one stream with its own work buffers, counters and HIP-event profile: what a whole context was in round 2.  A context
 // owns BMBS_LANES (default three, device_lanes) of them on one attached index and deals the chunks of a call to them, so that the issue-bound kernels (DP, Myers,
 // row preparation) of one chunk run beside the memory-bound seeding kernels of another without a second context or host thread.
@@ -198,40 +203,88 @@ struct Lane {
     // bmbs_map_*_text: newline index built on the device, SAM text written on the device
     DevBuf tx_tilecnt, tx_tileoff, tx_nl[2], tx_rec[2], tx_info, sam_len, sam_off, sam_out, chrom_chars, chrom_off;
     DevBuf bam_raw, bam_slots, bam_slot_len, bam_off, stats_snap;      // --bam: record stream, deflate scratch, BGZF slots
-    // coordinate sort of BAM records (k_bamsort.hip): keys / record numbers before and behind the pair sort, the sorted records' lengths and
-    // offsets, rocPRIM's scratch, the records of bmbs_bam_sort as uploaded and their lengths, the sorted record stream; bs_n = records of the
-    // last BMBS_TEXT_BAM_SORTED call (bmbs_text_sorted_index reads bs_key2 / bs_slen), -1: none
-    DevBuf bs_key, bs_key2, bs_idx, bs_idx2, bs_slen, bs_soff, bs_tmp, bs_in, bs_len, bs_off, bs_sorted;
-    int64_t bs_n = -1;
-    // .bai pieces of the last bmbs_bam_sort call that returned BGZF blocks (k_bai.hip, bmbs_bam_sort_index): bai_n = its records (-1: none,
-    // or bs_sorted / bs_soff / bam_off have been written since), bai_bytes / bai_z = its uncompressed / compressed size, bai_ref_max = its
-    // largest refID.  bai_a: per-record and per-reference work arrays, bai_b: the chunks and window candidates, bai_out: the three result
-    // arrays (at bai_at), kept (bai_done, bai_cnt = chunks, windows, references, records without a reference) for the call that follows a size query
+    // ---- the record stages behind the sorted BAM (bmbs_records.hip).  Each group: what a call left on the device for the calls that
+    // fetch it, beside the buffers it lives in; `ends` (below the struct) is the one place that says which call takes it away again.
+    // coordinate sort (k_bamsort.hip): keys / record numbers before and behind the pair sort, the sorted records' lengths and offsets, the
+    // sorted record stream; rocPRIM's scratch (pair_sort: every stage's)
+    DevBuf bs_key, bs_key2, bs_idx, bs_idx2, bs_slen, bs_soff, bs_sorted, bs_tmp;
+    // the last BMBS_TEXT_BAM_SORTED call.  n = its records (bmbs_text_sorted_index reads bs_key2 / bs_slen; -1: none); lines = its output
+    // lines, pairs if `pe` (-1: none, or bam_raw / sam_off / sam_len / bs_idx2 have been written since: what bmbs_text_sorted_dup and
+    // bmbs_text_sorted_clip read); sigs_done: dp_sig / dp_tmpl hold its signatures (computed when asked for, kept for the call that follows
+    // a size query)
+    struct SortedText {
+        int64_t n = -1, lines = -1;
+        bool pe = false, sigs_done = false;
+        void holds(int64_t records, int64_t output_lines, bool pairs) { n = records; lines = output_lines; pe = pairs; sigs_done = false; }
+    } st;
+    // the last bmbs_bam_sort call.  Its records as uploaded, with their lengths and offsets, stay in `in` for bmbs_bam_sort_methyl: n of
+    // them, `bytes` in all (-1: none).  If it returned BGZF blocks, bmbs_bam_sort_index makes the .bai pieces (k_bai.hip) from bs_sorted /
+    // bs_soff / bam_off: bai_n = its records (-1: none, or one of the three has been written since), bai_bytes / bai_z = its uncompressed /
+    // compressed size, bai_ref_max = its largest refID.  bai_a: per-record and per-reference work arrays, bai_b: the chunks and window
+    // candidates, bai_out: the three result arrays (at bai_at), kept (bai_done, bai_cnt = chunks, windows, references, records without a
+    // reference) for the call that follows a size query
+    struct SortCall {
+        RecIn in;
+        int64_t n = -1, bai_n = -1;
+        int64_t bai_cnt[4] = {0, 0, 0, 0};
+        u64 bytes = 0, bai_bytes = 0, bai_z = 0, bai_at[3] = {0, 0, 0};
+        u32 bai_ref_max = 0;
+        bool bai_done = false;
+    } sc;
     DevBuf bai_a, bai_b, bai_out;
-    int64_t bai_n = -1;
-    u64 bai_bytes = 0, bai_z = 0, bai_cnt[4] = {0, 0, 0, 0}, bai_at[3] = {0, 0, 0};
-    u32 bai_ref_max = 0;
-    bool bai_done = false;
-    // duplicate marking (k_markdup.hip): the records of bmbs_bam_dup_sigs as uploaded with their lengths and offsets, the signatures, keys /
-    // entry numbers before and behind a pair sort, the marks, the templates of a sorted text call's records.  dup_n2 = output lines of the
-    // last BMBS_TEXT_BAM_SORTED call (-1: none, or bam_raw / sam_off / sam_len / bs_idx2 have been written since), dup_pe: they are pairs;
-    // dup_done: dp_sig / dp_tmpl hold that call's signatures (bmbs_text_sorted_dup: computed when asked for, kept for the call that
-    // follows a size query)
-    DevBuf dp_in, dp_len, dp_off, dp_sig, dp_key, dp_key2, dp_idx, dp_idx2, dp_dup, dp_tmpl;
-    int64_t dup_n2 = -1;
-    bool dup_pe = false, dup_done = false;
-    // methylation counts (k_methyl.hip): the records of bmbs_bam_methyl as uploaded with their lengths, offsets and clips; events per record
-    // and their scan; the (key, value) events before and behind the pair sort; the reduction's work arrays; the sites of earlier slices of
-    // records as pairs (mt_slice: where each slice's lie); the result (bmbs_methyl_sites: mt_sites of them, -1: none); the clips of a sorted
-    // text call.  ms_n = records of the last bmbs_bam_sort call, still in bs_in / bs_off / bs_len (-1: none, as for bai_n).
-    // mt_mbias: the M-bias table of the last call (bmbs_methyl_mbias) if mt_has_mbias (mt_mbias_zero: a call without records, the table
-    // is all zero and not on the device); mt_cus: the device's compute units (0: not asked yet)
-    DevBuf mt_in, mt_len, mt_off, mt_clip, mt_cnt, mt_eoff, mt_ev, mt_work, mt_acc, mt_site, mt_cl2, mt_mbias;
+    // duplicate marking (k_markdup.hip): the records of bmbs_bam_dup_sigs as uploaded, the signatures, keys / entry numbers before and
+    // behind a pair sort, the marks, the templates of a sorted text call's records
+    RecIn dp_in;
+    DevBuf dp_sig, dp_key, dp_key2, dp_idx, dp_idx2, dp_dup, dp_tmpl;
+    // methylation counts (k_methyl.hip): the records of bmbs_bam_methyl as uploaded and their clips; events per record and their scan; the
+    // (key, value) events before and behind the pair sort; the reduction's work arrays; the sites of earlier slices of records as pairs
+    // (mt_slice: where each slice's lie); the sites; the clips of a sorted text call; the M-bias table; mt_cus: the device's compute units
+    // (0: not asked yet)
+    RecIn mt_in;
+    DevBuf mt_clip, mt_cnt, mt_eoff, mt_ev, mt_work, mt_acc, mt_site, mt_cl2, mt_mbias;
     std::vector<std::pair<u64, u64>> mt_slice;
-    int64_t ms_n = -1, mt_sites = -1;
-    bool mt_has_mbias = false, mt_mbias_zero = false;
     int mt_cus = 0;
-    u64 ms_bytes = 0;
+    // the last methyl call: `sites` of them in mt_site (bmbs_methyl_sites; -1: none); has_mbias: it made the M-bias table
+    // (bmbs_methyl_mbias) -- in mt_mbias, or (mbias_zero) a call without records: the table is all zero and not on the device
+    struct MethylCall {
+        int64_t sites = -1;
+        bool has_mbias = false, mbias_zero = false;
+    } mc;
+    // What is about to be rewritten or begun -> the results that end with it.  A result that stayed would hand another call's bytes to
+    // its fetch without any error; tests/test_record_residency.py runs every pair of calls against every fetch.
+    enum Ends {
+        SORTED_TEXT_CALL,   // a BMBS_TEXT_BAM_SORTED call begins, whatever becomes of it
+        TEXT_LINES,         // sam_len / sam_off / bam_raw: every text call's output lines
+        SORT_BUFFERS,       // bs_sorted / bs_soff / bs_idx2: bam_sort_device
+        BGZF_BLOCKS,        // bam_off: bgzf_deflate
+        BAM_SORT_CALL,      // a bmbs_bam_sort call begins, whatever becomes of it
+        SORT_KEYS,          // bs_key2 / bs_slen, by bmbs_bam_sort (its argument checks have passed)
+        DUP_SIGS,           // dp_sig: bmbs_bam_dup_sigs, bmbs_dup_select
+        METHYL_CALL         // a methyl call begins, whatever becomes of it
+    };
+    void ends(Ends what)
+    {
+        switch (what) {
+        // bmbs_text_sorted_index / _dup / _clip describe the LAST sorted text call; and bmbs_bam_sort_methyl the last sort of either
+        // kind, as bmbs_bam_sort_index does
+        case SORTED_TEXT_CALL: st.n = -1; st.lines = -1; sc.n = -1; break;
+        // what bmbs_text_sorted_dup / bmbs_text_sorted_clip would read
+        case TEXT_LINES: st.lines = -1; break;
+        // bs_sorted / bs_soff: what bmbs_bam_sort_index would read; bs_idx2: what bmbs_text_sorted_dup / bmbs_text_sorted_clip would;
+        // bmbs_bam_sort_methyl reads the LAST bmbs_bam_sort call's records, as bmbs_bam_sort_index does
+        case SORT_BUFFERS: sc.bai_n = -1; st.lines = -1; sc.n = -1; break;
+        // what bmbs_bam_sort_index would read
+        case BGZF_BLOCKS: sc.bai_n = -1; break;
+        // bmbs_bam_sort_index describes the LAST call, and so does bmbs_bam_sort_methyl
+        case BAM_SORT_CALL: sc.bai_n = -1; sc.n = -1; break;
+        // the sort's buffers are those of the text calls' sorted index
+        case SORT_KEYS: st.n = -1; break;
+        // what bmbs_text_sorted_dup keeps behind a size query: it computes again (bam_raw is still there)
+        case DUP_SIGS: st.sigs_done = false; break;
+        // bmbs_methyl_sites / bmbs_methyl_mbias describe the LAST methyl call
+        case METHYL_CALL: mc.sites = -1; mc.has_mbias = mc.mbias_zero = false; break;
+        }
+    }
     DevBuf z_comp, z_off, z_text, z_err, z_nl, z_comp2, z_off2, z_err2;         // bmbs_inflate_bgzf; (…2: mate 2 of bmbs_text_open_bgzf)
     struct OpenText { bool valid = false, pe = false; u64 bytes1 = 0, bytes2 = 0; int64_t n = 0; } open_text;      // between bmbs_text_open_bgzf and bmbs_text_map_open
     u32* h_info = nullptr;                              // page-locked: 8 info words + 4 totals of the text path
@@ -303,4 +356,13 @@ inline int fin(bmbs_ctx* X, Lane* c, int rc) { if (rc && X && c) X->err = c->err
 #define ON_LANE0(call) Lane* c = lane0(X); if (!c) return BMBS_EINVAL; { const int rs_ = settle_all(X); if (rs_) return rs_; } X->used_lanes = 1; return fin(X, c, call)
 extern std::mutex g_h2d_mu[16], g_d2h_mu[16];     // one copy per direction and device at a time (bmbs_textpath.hip)
 void textpath_device_init(Lane* c);               // bmbs_textpath.hip: the constants its kernels read (CRC-32 powers)
+// bmbs_textpath.hip, what the record stages run of it: the coordinate sort of a record stream on the device, its BGZF blocks, a download
+#define BGZF_IN 0xff00                            // input bytes per BGZF block (bgzf.h BGZF_BLOCK_SIZE): the deflater's, and the .bai's virtual offsets
+int bam_sort_device(Lane* c, const char* raw, const u64* off, const u32* len, u64 n, u64 total, bool skip_empty, u64* n_records);
+int bgzf_deflate(Lane* c, const char* raw, const u64* total_ptr, u64 raw_total, u64* ztotal);
+int bgzf_collect(Lane* c, u64 raw_total, u64 ztotal);
+int download_locked(Lane* c, char* dst, const char* src, u64 bytes, hipStream_t after, double* copy_s);
+// ... and the one call the other way: bam_sort_device's pair sort is bmbs_records.hip's, where every pair sort of the library is, so that
+// rocPRIM's kernels are compiled into one object.  The two units need each other: a sorted text call runs code of both
+int bam_pair_sort(Lane* c, u64* ka, u64* kb, u32* va, u32* vb, u64 n, unsigned end_bit);
 #endif

@@ -1,20 +1,15 @@
 // bitmapperbs_amd/csrc/bmbs_textpath.hip -- the two ends of the file path, their kernels and their entry points (a translation unit of its
 // own since round 5): FASTQ text -> line index -> read rows (bmbs_map_*_fastq, bmbs_map_*_text), BGZF blocks inflated on the device
-// (bmbs_inflate_bgzf, bmbs_text_open_bgzf / bmbs_text_map_open), records -> SAM text or BAM records in BGZF blocks.  The mapping in
-// between is bmbs_api.hip's (lane_enqueue / lane_settle).  Kernels: bmbs_text.hip, bmbs_bam.hip, bmbs_inflate.hip, k_bamsort.hip (the
-// coordinate sort of BAM records: BMBS_TEXT_BAM_SORTED, bmbs_bam_sort), k_bai.hip (the .bai pieces of a sorted call: bmbs_bam_sort_index),
-// k_markdup.hip (duplicate marking: bmbs_bam_dup_sigs, bmbs_text_sorted_dup, bmbs_dup_select), k_methyl.hip (methylation counts per
-// cytosine, read-end trimming, M-bias table: bmbs_bam_methyl[_opts], bmbs_bam_sort_methyl[_opts], bmbs_methyl_sites, bmbs_methyl_mbias,
-// bmbs_text_sorted_clip).
+// (bmbs_inflate_bgzf, bmbs_text_open_bgzf / bmbs_text_map_open), records -> SAM text or BAM records in BGZF blocks, or (BMBS_TEXT_BAM_SORTED)
+// the BAM records in coordinate order.  The mapping in between is bmbs_api.hip's (lane_enqueue / lane_settle).  Kernels: bmbs_text.hip,
+// bmbs_bam.hip, bmbs_inflate.hip, k_bamsort.hip.  The sort, the deflater and the download (bam_sort_device, bgzf_deflate, bgzf_collect,
+// download_locked) also serve the stages behind the sorted BAM, which are bmbs_records.hip's.
 #include "bmbs_host.h"
 #define DEVI __device__ __forceinline__
 #include "bmbs_text.hip"
 #include "bmbs_bam.hip"
 #include "bmbs_inflate.hip"
 #include "k_bamsort.hip"
-#include "k_bai.hip"
-#include "k_markdup.hip"
-#include "k_methyl.hip"
 
 // the constants the kernels of this file read: x^(2^n) mod P of CRC-32 for the BGZF blocks' CRCs (bmbs_bytes.h: crc_x8n); per device
 void textpath_device_init(Lane* c)
@@ -177,7 +172,6 @@ std::mutex g_d2h_mu[16];
 // copy waited on the stream for its kernel or was queued once the kernel had ended (tools/e2e_quick.sh, same box, alternating runs).
 // *copy_s = seconds the copy held the link.
 int d2h_chunked(Lane* c, char* dst, const char* src, u64 bytes, hipStream_t st);
-extern std::mutex g_d2h_mu[16];
 int download_locked(Lane* c, char* dst, const char* src, u64 bytes, hipStream_t after, double* copy_s)
 {
     hipStream_t ds = c->down_stream ? c->down_stream : c->stream;
@@ -210,10 +204,10 @@ int lane_map_text(Lane* c, bool pe, const char* text1, u64 bytes1, const char* t
     if (sam_bytes) *sam_bytes = 0;
     if (n_lines_out) *n_lines_out = 0;
     if ((flags_in & BMBS_TEXT_BAM_SORTED) && !(flags_in & BMBS_TEXT_BAM)) { c->err = "text call: BMBS_TEXT_BAM_SORTED is only valid together with BMBS_TEXT_BAM"; return BMBS_EINVAL; }
-    if (flags_in & BMBS_TEXT_BAM_SORTED) { c->bs_n = -1; c->dup_n2 = -1; c->ms_n = -1; }
+    if (flags_in & BMBS_TEXT_BAM_SORTED) c->ends(Lane::SORTED_TEXT_CALL);
     if (!c->attached) { c->err = "no index attached"; return BMBS_ESTATE; }
     if (c->n_refs != c->ix.n_chrom) { c->err = "bmbs_sam_refs has not been given the index's reference names"; return BMBS_ESTATE; }
-    if (n_records <= 0) { if (flags_in & BMBS_TEXT_BAM_SORTED) { c->bs_n = 0; c->dup_n2 = 0; c->dup_pe = pe; c->dup_done = false; } return BMBS_OK; }
+    if (n_records <= 0) { if (flags_in & BMBS_TEXT_BAM_SORTED) c->st.holds(0, 0, pe); return BMBS_OK; }
     if (!text1 || (pe && !text2) || !sam) { c->err = "text call: NULL buffer"; return BMBS_EINVAL; }
     if (bytes1 >= (1ull << 32) || bytes2 >= (1ull << 32)) { c->err = "a text window has to be smaller than 4 GiB (32-bit offsets)"; return BMBS_EINVAL; }
     HIPCHK(c, hipSetDevice(c->dev));
@@ -284,10 +278,10 @@ static TxwPlan txw_plan(bool pe, u64 text_bytes, u64 n_lines, int hb)
 // ---- a record stream on the device -> BGZF blocks of BGZF_IN input bytes (the last one shorter), deflated by one workgroup each into
 // the slots; total_ptr = the stream's size in device memory (what k_bgzf_block reads); *ztotal = the compressed bytes.  bgzf_collect
 // then puts the blocks one behind the other into c->sam_out.
-static int bgzf_deflate(Lane* c, const char* raw, const u64* total_ptr, u64 raw_total, u64* ztotal)
+int bgzf_deflate(Lane* c, const char* raw, const u64* total_ptr, u64 raw_total, u64* ztotal)
 {
     const u64 nb = (raw_total + BGZF_IN - 1) / BGZF_IN;
-    c->bai_n = -1;                                        // (bam_off is rewritten: what bmbs_bam_sort_index would read)
+    c->ends(Lane::BGZF_BLOCKS);
     ENS(c, c->bam_slots, nb * (u64)BGZF_SLOT);
     ENS(c, c->bam_slot_len, nb * 4 + 64); ENS(c, c->bam_off, (nb + 1) * 8 + 64);
     const size_t lds = (size_t)BGZF_THREADS * BGZF_PSTRIDE * 4;                      // the block's bytes (padded segments)
@@ -304,7 +298,7 @@ static int bgzf_deflate(Lane* c, const char* raw, const u64* total_ptr, u64 raw_
     *ztotal = *reinterpret_cast<const u64*>(c->h_info + 26);
     return BMBS_OK;
 }
-static int bgzf_collect(Lane* c, u64 raw_total, u64 ztotal)
+int bgzf_collect(Lane* c, u64 raw_total, u64 ztotal)
 {
     const u64 nb = (raw_total + BGZF_IN - 1) / BGZF_IN;
     ENS(c, c->sam_out, ztotal + 64);
@@ -319,12 +313,10 @@ static int bgzf_collect(Lane* c, u64 raw_total, u64 ztotal)
 // c->bs_key2 / c->bs_slen their keys and lengths in that order, totals[23] their size.  skip_empty: entries of length 0 are output
 // lines that print nothing, not records (they end up behind the records); *n_records = the others.
 // BMBS_BSG_TINY=1 (test aid): no piece fits the gather kernel's image -- every workgroup takes the plain path.
-static int bam_sort_device(Lane* c, const char* raw, const u64* off, const u32* len, u64 n, u64 total, bool skip_empty, u64* n_records)
+int bam_sort_device(Lane* c, const char* raw, const u64* off, const u32* len, u64 n, u64 total, bool skip_empty, u64* n_records)
 {
     static const bool tiny = getenv("BMBS_BSG_TINY") != nullptr;
-    c->bai_n = -1;                                        // (bs_sorted / bs_soff are rewritten: what bmbs_bam_sort_index would read)
-    c->dup_n2 = -1;                                       // (bs_idx2 is rewritten: what bmbs_text_sorted_dup / bmbs_text_sorted_clip would read)
-    c->ms_n = -1;                                         // (bmbs_bam_sort_methyl reads the LAST bmbs_bam_sort call's records, as bmbs_bam_sort_index does)
+    c->ends(Lane::SORT_BUFFERS);
     ENS(c, c->bs_key, n * 8 + 64); ENS(c, c->bs_key2, n * 8 + 64); ENS(c, c->bs_idx, n * 4 + 64); ENS(c, c->bs_idx2, n * 4 + 64);
     ENS(c, c->bs_slen, n * 4 + 64); ENS(c, c->bs_soff, (n + 1) * 8 + 64); ENS(c, c->bs_sorted, total + 256);
     u32* const info = c->tx_info.as<u32>() + 8;
@@ -339,22 +331,13 @@ static int bam_sort_device(Lane* c, const char* raw, const u64* off, const u32* 
         return BMBS_EINVAL;
     }
     if (n_records) *n_records = n - c->h_info[10];
-    c->bai_ref_max = c->h_info[9];
+    c->sc.bai_ref_max = c->h_info[9];
     // the key bits that can be set: 33 of position and strand, and those of the largest reference index (-1 is all ones: it stays last
     // under any number of low bits, because no other index has them all set)
     int ref_bits = 1;
     while (ref_bits < 32 && ((u64)c->h_info[9] + 1) >> ref_bits) ref_bits++;
     const unsigned end_bit = (unsigned)(33 + ref_bits);
-    size_t tmp_bytes = 0;
-    if (rocprim::radix_sort_pairs(nullptr, tmp_bytes, c->bs_key.as<u64>(), c->bs_key2.as<u64>(), c->bs_idx.as<u32>(), c->bs_idx2.as<u32>(), (size_t)n, 0u, end_bit, c->stream) != hipSuccess) {
-        c->err = "bam sort: radix_sort_pairs (size query) failed"; return BMBS_ENODEV;
-    }
-    ENS(c, c->bs_tmp, tmp_bytes + 64);
-    prof_begin(c, "bam_pair_sort");
-    if (rocprim::radix_sort_pairs(c->bs_tmp.p, tmp_bytes, c->bs_key.as<u64>(), c->bs_key2.as<u64>(), c->bs_idx.as<u32>(), c->bs_idx2.as<u32>(), (size_t)n, 0u, end_bit, c->stream) != hipSuccess) {
-        c->err = "bam sort: radix_sort_pairs failed"; return BMBS_ENODEV;
-    }
-    prof_end(c);
+    { const int rc = bam_pair_sort(c, c->bs_key.as<u64>(), c->bs_key2.as<u64>(), c->bs_idx.as<u32>(), c->bs_idx2.as<u32>(), n, end_bit); if (rc) return rc; }
     hipLaunchKernelGGL(k_bam_slen, dim3(nblk(n, 256)), dim3(256), 0, c->stream, len, c->bs_idx2.as<u32>(), (long)n, c->bs_slen.as<u32>());
     const int rc = scan_u32(c, c->bs_slen.as<u32>(), n, c->bs_soff.as<u64>(), 23);
     if (rc) return rc;
@@ -374,7 +357,7 @@ int lane_text_finish(Lane* c, bool pe, u64 bytes1, u64 bytes2, int64_t n_records
                      int64_t* n_lines_out, double t_start, double t_uploaded)
 {
     const u64 n = (u64)n_records, n2 = pe ? 2 * n : n;
-    c->dup_n2 = -1;                                       // (sam_len / sam_off / bam_raw are rewritten: what bmbs_text_sorted_dup would read)
+    c->ends(Lane::TEXT_LINES);
     static const bool trace = getenv("BMBS_TEXT_TRACE") != nullptr;
     auto wall = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; };
     double tp[8] = {t_start, 0, 0, 0, 0, 0, 0, t_uploaded}, t_uplock = t_start, t_dnlock = 0, t_dnstart = 0;
@@ -465,7 +448,7 @@ int lane_text_finish(Lane* c, bool pe, u64 bytes1, u64 bytes2, int64_t n_records
         const u64 raw_total = *reinterpret_cast<const u64*>(c->h_info + 24);
         if (n_lines_out) *n_lines_out = (int64_t)n2;
         if (c->h_info[3]) { c->err = "output line " + std::to_string(c->h_info[3] - 1) + " of this batch has a read name of more than 254 characters: BAM cannot hold it"; return BMBS_EINVAL; }
-        if (!raw_total) { if (flags_in & BMBS_TEXT_BAM_SORTED) { c->bs_n = 0; c->dup_n2 = (int64_t)n2; c->dup_pe = pe; c->dup_done = false; } return BMBS_OK; }
+        if (!raw_total) { if (flags_in & BMBS_TEXT_BAM_SORTED) c->st.holds(0, (int64_t)n2, pe); return BMBS_OK; }
         ENS(c, c->bam_raw, raw_total + 256);
         const TxwPlan tw = txw_plan(pe, bytes1 + bytes2, n2, (36 + 4 * std::max(max_ops, 1) + 8 + 15) & ~15);
         if (!tw.lpb) { c->err = "text call: CIGARs too long"; return BMBS_EINVAL; }
@@ -480,8 +463,7 @@ int lane_text_finish(Lane* c, bool pe, u64 bytes1, u64 bytes2, int64_t n_records
             u64 n_rec = 0;
             rc = bam_sort_device(c, c->bam_raw.as<char>(), c->sam_off.as<u64>(), c->sam_len.as<u32>(), n2, raw_total, true, &n_rec);
             if (rc) return rc;
-            c->bs_n = (int64_t)n_rec;
-            c->dup_n2 = (int64_t)n2; c->dup_pe = pe; c->dup_done = false;         // (bmbs_text_sorted_dup: computed when asked for)
+            c->st.holds((int64_t)n_rec, (int64_t)n2, pe);                         // (bmbs_text_sorted_dup: computed when asked for)
             if (trace) { HIPCHK(c, hipStreamSynchronize(c->stream)); tp[5] = wall(); }
             double cs = 0;
             rc = download_locked(c, sam, c->bs_sorted.as<char>(), raw_total, c->stream, &cs);
@@ -682,7 +664,7 @@ int lane_text_map_open(Lane* c, int32_t flags_in, char* sam, u64 sam_cap, u64* s
     if (sam_bytes) *sam_bytes = 0;
     if (n_lines_out) *n_lines_out = 0;
     if ((flags_in & BMBS_TEXT_BAM_SORTED) && !(flags_in & BMBS_TEXT_BAM)) { c->err = "text call: BMBS_TEXT_BAM_SORTED is only valid together with BMBS_TEXT_BAM"; return BMBS_EINVAL; }
-    if (flags_in & BMBS_TEXT_BAM_SORTED) { c->bs_n = -1; c->dup_n2 = -1; c->ms_n = -1; }
+    if (flags_in & BMBS_TEXT_BAM_SORTED) c->ends(Lane::SORTED_TEXT_CALL);
     if (!c->open_text.valid) { c->err = "text map: no open batch (bmbs_text_open_bgzf first)"; return BMBS_ESTATE; }
     if (c->n_refs != c->ix.n_chrom) { c->err = "bmbs_sam_refs has not been given the index's reference names"; return BMBS_ESTATE; }
     if (!sam) { c->err = "text call: NULL buffer"; return BMBS_EINVAL; }
@@ -818,688 +800,6 @@ extern "C" int bmbs_text_times(bmbs_ctx* X, double out[4])
     return BMBS_OK;
 }
 
-
-// ---- coordinate sort (k_bamsort.hip): the index of the last sorted text call, and the sort of records the host holds ----------------------
-static int lane_text_sorted_index(Lane* c, uint64_t* key, uint32_t* len, int64_t cap, int64_t* n)
-{
-    if (!n) { c->err = "sorted index: NULL argument"; return BMBS_EINVAL; }
-    *n = 0;
-    if (c->bs_n < 0) { c->err = "sorted index: the context's last text call was not a BMBS_TEXT_BAM_SORTED call that returned records"; return BMBS_ESTATE; }
-    *n = c->bs_n;
-    if (c->bs_n > cap) { c->err = "sorted index: the arrays are too small (n tells what is needed)"; return BMBS_ENOMEM; }
-    if (!c->bs_n) return BMBS_OK;
-    if (!key || !len) { c->err = "sorted index: NULL argument"; return BMBS_EINVAL; }
-    HIPCHK(c, hipSetDevice(c->dev));
-    hipStream_t ds = c->down_stream ? c->down_stream : c->stream;
-    HIPCHK(c, hipMemcpyAsync(key, c->bs_key2.p, (size_t)c->bs_n * 8, hipMemcpyDeviceToHost, ds));
-    HIPCHK(c, hipMemcpyAsync(len, c->bs_slen.p, (size_t)c->bs_n * 4, hipMemcpyDeviceToHost, ds));
-    HIPCHK(c, hipStreamSynchronize(ds));
-    return BMBS_OK;
-}
-
-static int lane_bam_sort(Lane* c, const char* records, uint64_t bytes, const uint32_t* len, int64_t n_in, int32_t flags, char* out, uint64_t out_cap, uint64_t* out_bytes)
-{
-    if (out_bytes) *out_bytes = 0;
-    c->bai_n = -1;                                        // bmbs_bam_sort_index describes the LAST call
-    c->ms_n = -1;                                         // ... and so does bmbs_bam_sort_methyl
-    if (n_in < 0 || n_in >= (1ll << 31) || (flags & ~BMBS_BAMSORT_RAW)) { c->err = "bam sort: bad argument"; return BMBS_EINVAL; }
-    if (n_in && (!records || !len)) { c->err = "bam sort: NULL buffer"; return BMBS_EINVAL; }
-    const u64 n = (u64)n_in;
-    u64 sum = 0;
-    for (u64 i = 0; i < n; i++) {
-        if (len[i] < 36) { c->err = "bam sort: the length given for record " + std::to_string(i) + " is below the 36 bytes every BAM record has"; return BMBS_EINVAL; }
-        sum += len[i];
-    }
-    if (sum != bytes) { c->err = "bam sort: the record lengths add up to " + std::to_string(sum) + " bytes, not to the " + std::to_string(bytes) + " given"; return BMBS_EINVAL; }
-    if (!n) return BMBS_OK;
-    const bool rawout = (flags & BMBS_BAMSORT_RAW) != 0;
-    if (rawout) {
-        if (out_bytes) *out_bytes = bytes;
-        if (bytes > out_cap) { c->err = "bam sort: the output buffer is too small (out_bytes tells what is needed)"; return BMBS_ENOMEM; }
-    }
-    if (!out) { c->err = "bam sort: NULL buffer"; return BMBS_EINVAL; }
-    HIPCHK(c, hipSetDevice(c->dev));
-    c->bs_n = -1;                                         // (the sort's buffers are those of the text calls' sorted index)
-    ENS(c, c->bs_in, bytes + 256); ENS(c, c->bs_len, n * 4 + 64); ENS(c, c->bs_off, (n + 1) * 8 + 64);
-    {
-        std::lock_guard<std::mutex> up(g_h2d_mu[c->dev & 15]);
-        hipStream_t us = c->up_stream ? c->up_stream : c->stream;
-        const u64 piece = 128ull << 20;
-        for (u64 o = 0; o < bytes; o += piece) HIPCHK(c, hipMemcpyAsync(c->bs_in.as<char>() + o, records + o, std::min(piece, bytes - o), hipMemcpyHostToDevice, us));
-        HIPCHK(c, hipMemcpyAsync(c->bs_len.p, len, n * 4, hipMemcpyHostToDevice, us));
-        HIPCHK(c, hipStreamSynchronize(us));
-    }
-    int rc = scan_u32(c, c->bs_len.as<u32>(), n, c->bs_off.as<u64>(), 24);
-    if (rc) return rc;
-    rc = bam_sort_device(c, c->bs_in.as<char>(), c->bs_off.as<u64>(), c->bs_len.as<u32>(), n, bytes, false, nullptr);
-    if (rc) return rc;
-    if (rawout) {
-        rc = download_locked(c, out, c->bs_sorted.as<char>(), bytes, c->stream, nullptr);
-        if (!rc) { c->ms_n = (int64_t)n; c->ms_bytes = bytes; }
-        return rc;
-    }
-    u64 ztotal = 0;
-    rc = bgzf_deflate(c, c->bs_sorted.as<char>(), c->totals.as<u64>() + 23, bytes, &ztotal);
-    if (rc) return rc;
-    if (out_bytes) *out_bytes = ztotal;
-    if (ztotal > out_cap) { c->err = "bam sort: the output buffer is too small (out_bytes tells what is needed)"; return BMBS_ENOMEM; }
-    rc = bgzf_collect(c, bytes, ztotal);
-    if (rc) return rc;
-    rc = download_locked(c, out, c->sam_out.as<char>(), ztotal, c->stream, nullptr);
-    if (rc) return rc;
-    c->bai_n = (int64_t)n; c->bai_bytes = bytes; c->bai_z = ztotal; c->bai_done = false;      // (bmbs_bam_sort_index: computed when asked for)
-    c->ms_n = (int64_t)n; c->ms_bytes = bytes;                                                // (bmbs_bam_sort_methyl: bs_in / bs_off / bs_len stay as they are)
-    return BMBS_OK;
-}
-
-// ---- the .bai pieces of that call (k_bai.hip) from bs_sorted / bs_soff / bam_off -> c->bai_out, counts in c->bai_cnt ------------------------
-static int bai_compute(Lane* c)
-{
-    const u64 n = (u64)c->bai_n, total = c->bai_bytes, nb = (total + BGZF_IN - 1) / BGZF_IN, nw = (n + 63) / 64;
-    const u64 R = (u64)c->bai_ref_max + 1;
-    if (R > (1ull << 24)) { c->err = "bam sort index: reference index " + std::to_string(c->bai_ref_max) + " is beyond the 2^24 sequences this call keeps counts for"; return BMBS_EINVAL; }
-    u64 at = 0;
-    auto take = [&](u64 bytes) { const u64 a = at; at += (bytes + 255) & ~255ull; return a; };
-    const u64 o_rb = take(n * 8), o_rw = take(n * 4), o_wc = take(n * 4), o_woff = take((n + 1) * 8), o_wave = take(nw * 4), o_hoff = take((nw + 1) * 8),
-              o_cnt = take(R * 8), o_has = take(R * 4), o_first = take(R * 4), o_last = take(R * 4), o_rlist = take(R * 4);
-    ENS(c, c->bai_a, at + 64);
-    char* const A = c->bai_a.as<char>();
-    u64* const rb = reinterpret_cast<u64*>(A + o_rb); u64* const woff = reinterpret_cast<u64*>(A + o_woff); u64* const hoff = reinterpret_cast<u64*>(A + o_hoff);
-    u32* const rw = reinterpret_cast<u32*>(A + o_rw); u32* const wc = reinterpret_cast<u32*>(A + o_wc); u32* const wave = reinterpret_cast<u32*>(A + o_wave);
-    u32* const cnt = reinterpret_cast<u32*>(A + o_cnt); u32* const has = reinterpret_cast<u32*>(A + o_has); u32* const first = reinterpret_cast<u32*>(A + o_first);
-    u32* const last = reinterpret_cast<u32*>(A + o_last); u32* const rlist = reinterpret_cast<u32*>(A + o_rlist);
-    u32* const info = c->tx_info.as<u32>() + 8;
-    u64* const tot = c->totals.as<u64>();
-    HIPCHK(c, hipMemsetAsync(info, 0, 32, c->stream));
-    HIPCHK(c, hipMemsetAsync(cnt, 0, o_first - o_cnt, c->stream));                          // cnt and has
-    const BaiVoff v = {c->bs_soff.as<u64>(), c->bam_off.as<u64>(), total, nb};
-    hipLaunchKernelGGL(k_bai_records, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->bs_sorted.as<char>(), c->bs_soff.as<u64>(), (long)n, (u32)R, rb, rw, cnt, info);
-    hipLaunchKernelGGL(k_bai_heads, dim3(nblk(n, 256)), dim3(256), 0, c->stream, rb, rw, (long)n, (u32)R, wave, wc, has, first, last);
-    int rc = scan_u32(c, wave, nw, hoff, 25);
-    if (rc) return rc;
-    rc = scan_u32(c, wc, n, woff, 26);
-    if (rc) return rc;
-    rc = scan_u32(c, has, R, nullptr, 27, rlist);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->h_info, info, 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 16, tot + 25, 24, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->h_info[1]) { c->err = "bam sort index: the read name and CIGAR of record " + std::to_string(~c->h_info[1]) + " (in sorted order) do not fit its length"; return BMBS_EINVAL; }
-    if (c->h_info[0]) {
-        c->err = "bam sort index: record " + std::to_string(~c->h_info[0]) + " (in sorted order) ends behind position 2^29: a BAI index cannot hold it (CSI is not written)";
-        return BMBS_EINVAL;
-    }
-    const u64 nnc = c->h_info[2];
-    const u64 m = reinterpret_cast<const u64*>(c->h_info + 16)[0], T = reinterpret_cast<const u64*>(c->h_info + 16)[1], n_ref = reinterpret_cast<const u64*>(c->h_info + 16)[2];
-    const u64 mr = m - (nnc ? 1 : 0);                    // (the first record without a reference only ends the last run)
-    at = 0;
-    const u64 o_hj = take((m + 1) * 4), o_ckey = take(m * 8), o_ckey2 = take(m * 8), o_cidx = take(m * 4), o_cidx2 = take(m * 4), o_be = take(m * 16),
-              o_wkey = take(T * 8), o_wkey2 = take(T * 8), o_wval = take(T * 4), o_wval2 = take(T * 4), o_wflag = take(T * 4), o_wlist = take(T * 4);
-    ENS(c, c->bai_b, at + 64);
-    char* const B = c->bai_b.as<char>();
-    u32* const hj = reinterpret_cast<u32*>(B + o_hj); u64* const ckey = reinterpret_cast<u64*>(B + o_ckey); u64* const ckey2 = reinterpret_cast<u64*>(B + o_ckey2);
-    u32* const cidx = reinterpret_cast<u32*>(B + o_cidx); u32* const cidx2 = reinterpret_cast<u32*>(B + o_cidx2); u64* const be = reinterpret_cast<u64*>(B + o_be);
-    u64* const wkey = reinterpret_cast<u64*>(B + o_wkey); u64* const wkey2 = reinterpret_cast<u64*>(B + o_wkey2); u32* const wval = reinterpret_cast<u32*>(B + o_wval);
-    u32* const wval2 = reinterpret_cast<u32*>(B + o_wval2); u32* const wflag = reinterpret_cast<u32*>(B + o_wflag); u32* const wlist = reinterpret_cast<u32*>(B + o_wlist);
-    at = 0;
-    c->bai_at[0] = take(mr * sizeof(bmbs_bai_chunk)); c->bai_at[1] = take(T * sizeof(bmbs_bai_win)); c->bai_at[2] = take(n_ref * sizeof(bmbs_bai_ref));
-    ENS(c, c->bai_out, at + 64);
-    char* const O = c->bai_out.as<char>();
-    // the key bits that can be set: those of the largest reference index above the bin's 16 / the window's 15 (as in bam_sort_device)
-    int ref_bits = 1;
-    while (ref_bits < 32 && R >> ref_bits) ref_bits++;
-    hipLaunchKernelGGL(k_bai_emit, dim3(nblk(n, 256)), dim3(256), 0, c->stream, rb, rw, (long)n, hoff, woff, hj, wkey, wval);
-    if (mr) {
-        hipLaunchKernelGGL(k_bai_chunks, dim3(nblk(m, 256)), dim3(256), 0, c->stream, hj, (long)m, (long)n, rb, v, ckey, cidx, be);
-        size_t tmp = 0;
-        if (rocprim::radix_sort_pairs(nullptr, tmp, ckey, ckey2, cidx, cidx2, (size_t)mr, 0u, (unsigned)(16 + ref_bits), c->stream) != hipSuccess) { c->err = "bam sort index: radix_sort_pairs (size query) failed"; return BMBS_ENODEV; }
-        ENS(c, c->bs_tmp, tmp + 64);
-        if (rocprim::radix_sort_pairs(c->bs_tmp.p, tmp, ckey, ckey2, cidx, cidx2, (size_t)mr, 0u, (unsigned)(16 + ref_bits), c->stream) != hipSuccess) { c->err = "bam sort index: radix_sort_pairs failed"; return BMBS_ENODEV; }
-        hipLaunchKernelGGL(k_bai_chunk_out, dim3(nblk(mr, 256)), dim3(256), 0, c->stream, ckey2, cidx2, be, (long)mr, reinterpret_cast<bmbs_bai_chunk*>(O + c->bai_at[0]));
-    }
-    u64 n_win = 0;
-    if (T) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));        // (bs_tmp may be replaced: the chunk sort has to be through with it)
-        size_t tmp = 0;
-        if (rocprim::radix_sort_pairs(nullptr, tmp, wkey, wkey2, wval, wval2, (size_t)T, 0u, (unsigned)(15 + ref_bits), c->stream) != hipSuccess) { c->err = "bam sort index: radix_sort_pairs (size query) failed"; return BMBS_ENODEV; }
-        ENS(c, c->bs_tmp, tmp + 64);
-        if (rocprim::radix_sort_pairs(c->bs_tmp.p, tmp, wkey, wkey2, wval, wval2, (size_t)T, 0u, (unsigned)(15 + ref_bits), c->stream) != hipSuccess) { c->err = "bam sort index: radix_sort_pairs failed"; return BMBS_ENODEV; }
-        hipLaunchKernelGGL(k_bai_win_flag, dim3(nblk(T, 256)), dim3(256), 0, c->stream, wkey2, (long)T, wflag);
-        rc = scan_u32(c, wflag, T, nullptr, 28, wlist);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_bai_win_out, dim3(nblk(T, 256)), dim3(256), 0, c->stream, wlist, tot + 28, wkey2, wval2, v, reinterpret_cast<bmbs_bai_win*>(O + c->bai_at[1]));
-        HIPCHK(c, hipMemcpyAsync(c->h_info + 16, tot + 28, 8, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (n_ref) hipLaunchKernelGGL(k_bai_ref_out, dim3(nblk(n_ref, 256)), dim3(256), 0, c->stream, rlist, (long)n_ref, first, last, cnt, v, reinterpret_cast<bmbs_bai_ref*>(O + c->bai_at[2]));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    if (T) n_win = reinterpret_cast<const u64*>(c->h_info + 16)[0];
-    c->bai_cnt[0] = mr; c->bai_cnt[1] = n_win; c->bai_cnt[2] = n_ref; c->bai_cnt[3] = nnc;
-    c->bai_done = true;
-    return BMBS_OK;
-}
-
-static int lane_bam_sort_index(Lane* c, bmbs_bai_chunk* chunk, int64_t chunk_cap, int64_t* n_chunk, bmbs_bai_win* win, int64_t win_cap, int64_t* n_win,
-                               bmbs_bai_ref* ref, int64_t ref_cap, int64_t* n_ref, uint64_t* n_no_coor)
-{
-    if (!n_chunk || !n_win || !n_ref || !n_no_coor) { c->err = "bam sort index: NULL argument"; return BMBS_EINVAL; }
-    *n_chunk = *n_win = *n_ref = 0; *n_no_coor = 0;
-    if (c->bai_n < 0) {
-        c->err = "bam sort index: the context's last bmbs_bam_sort call returned no BGZF blocks (none yet, BMBS_BAMSORT_RAW, no records, or it failed), or another call has used its buffers since";
-        return BMBS_ESTATE;
-    }
-    HIPCHK(c, hipSetDevice(c->dev));
-    if (!c->bai_done) { const int rc = bai_compute(c); if (rc) return rc; }
-    *n_chunk = (int64_t)c->bai_cnt[0]; *n_win = (int64_t)c->bai_cnt[1]; *n_ref = (int64_t)c->bai_cnt[2]; *n_no_coor = c->bai_cnt[3];
-    if (*n_chunk > chunk_cap || *n_win > win_cap || *n_ref > ref_cap) { c->err = "bam sort index: an array is too small (n_chunk, n_win and n_ref tell what is needed)"; return BMBS_ENOMEM; }
-    if ((*n_chunk && !chunk) || (*n_win && !win) || (*n_ref && !ref)) { c->err = "bam sort index: NULL argument"; return BMBS_EINVAL; }
-    const char* const O = c->bai_out.as<char>();
-    if (*n_chunk) HIPCHK(c, hipMemcpyAsync(chunk, O + c->bai_at[0], (size_t)*n_chunk * sizeof(bmbs_bai_chunk), hipMemcpyDeviceToHost, c->stream));
-    if (*n_win) HIPCHK(c, hipMemcpyAsync(win, O + c->bai_at[1], (size_t)*n_win * sizeof(bmbs_bai_win), hipMemcpyDeviceToHost, c->stream));
-    if (*n_ref) HIPCHK(c, hipMemcpyAsync(ref, O + c->bai_at[2], (size_t)*n_ref * sizeof(bmbs_bai_ref), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return BMBS_OK;
-}
-
-// ---- duplicate marking (k_markdup.hip) -----------------------------------------------------------------------------------------------------
-// the signatures of n_tmpl templates -> c->dp_sig; entry i = len[i] bytes at raw + off[i] (raw is padded by 16 bytes and more)
-static int dup_sig_device(Lane* c, const char* raw, const u64* off, const u32* len, bool paired, u64 n_tmpl)
-{
-    ENS(c, c->dp_sig, n_tmpl * sizeof(bmbs_dup_sig) + 64);
-    u32* const info = c->tx_info.as<u32>() + 8;
-    HIPCHK(c, hipMemsetAsync(info, 0, 32, c->stream));
-    prof_begin(c, "k_dup_sig");
-    hipLaunchKernelGGL(k_dup_sig, dim3(nblk(n_tmpl * DUP_GROUP, 256)), dim3(256), 0, c->stream, raw, off, len, paired ? 1 : 0, (long)n_tmpl, c->dp_sig.as<bmbs_dup_sig>(), info);
-    prof_end(c);
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 8, info, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    if (c->h_info[8]) {
-        c->err = "dup sigs: the length given for record " + std::to_string(~c->h_info[8]) + " is not its block_size + 4 (or is below the 36 bytes every BAM record has)";
-        return BMBS_EINVAL;
-    }
-    if (c->h_info[9]) { c->err = "dup sigs: the read name, CIGAR, sequence and qualities of record " + std::to_string(~c->h_info[9]) + " do not fit its length"; return BMBS_EINVAL; }
-    return BMBS_OK;
-}
-
-static int lane_bam_dup_sigs(Lane* c, const char* records, uint64_t bytes, const uint32_t* len, int64_t n_in, int32_t paired, bmbs_dup_sig* sig, int64_t sig_cap,
-                             int64_t* n_sig)
-{
-    if (!n_sig) { c->err = "dup sigs: NULL argument"; return BMBS_EINVAL; }
-    *n_sig = 0;
-    if (n_in < 0 || n_in >= (1ll << 31)) { c->err = "dup sigs: bad argument"; return BMBS_EINVAL; }
-    if (paired && (n_in & 1)) { c->err = "dup sigs: an odd number of entries (" + std::to_string(n_in) + ") cannot be pairs"; return BMBS_EINVAL; }
-    if (n_in && !len) { c->err = "dup sigs: NULL buffer"; return BMBS_EINVAL; }
-    const u64 n = (u64)n_in;
-    u64 sum = 0;
-    for (u64 i = 0; i < n; i++) {
-        if (len[i] && len[i] < 36) { c->err = "dup sigs: the length given for record " + std::to_string(i) + " is below the 36 bytes every BAM record has"; return BMBS_EINVAL; }
-        sum += len[i];
-    }
-    if (sum != bytes) { c->err = "dup sigs: the record lengths add up to " + std::to_string(sum) + " bytes, not to the " + std::to_string(bytes) + " given"; return BMBS_EINVAL; }
-    const u64 nt = paired ? n / 2 : n;
-    *n_sig = (int64_t)nt;
-    if ((int64_t)nt > sig_cap) { c->err = "dup sigs: the array is too small (n_sig tells what is needed)"; return BMBS_ENOMEM; }
-    if (!nt) return BMBS_OK;
-    if (!sig || (bytes && !records)) { c->err = "dup sigs: NULL buffer"; return BMBS_EINVAL; }
-    HIPCHK(c, hipSetDevice(c->dev));
-    c->dup_done = false;                                  // (dp_sig is rewritten: what bmbs_text_sorted_dup keeps behind a size query)
-    ENS(c, c->dp_in, bytes + 256); ENS(c, c->dp_len, n * 4 + 64); ENS(c, c->dp_off, (n + 1) * 8 + 64);
-    {
-        std::lock_guard<std::mutex> up(g_h2d_mu[c->dev & 15]);
-        hipStream_t us = c->up_stream ? c->up_stream : c->stream;
-        const u64 piece = 128ull << 20;
-        for (u64 o = 0; o < bytes; o += piece) HIPCHK(c, hipMemcpyAsync(c->dp_in.as<char>() + o, records + o, std::min(piece, bytes - o), hipMemcpyHostToDevice, us));
-        HIPCHK(c, hipMemcpyAsync(c->dp_len.p, len, n * 4, hipMemcpyHostToDevice, us));
-        HIPCHK(c, hipStreamSynchronize(us));
-    }
-    int rc = scan_u32(c, c->dp_len.as<u32>(), n, c->dp_off.as<u64>(), 29);
-    if (rc) return rc;
-    rc = dup_sig_device(c, c->dp_in.as<char>(), c->dp_off.as<u64>(), c->dp_len.as<u32>(), paired != 0, nt);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(sig, c->dp_sig.p, nt * sizeof(bmbs_dup_sig), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return BMBS_OK;
-}
-
-static int lane_text_sorted_dup(Lane* c, bmbs_dup_sig* sig, int64_t sig_cap, int64_t* n_sig, uint32_t* tmpl, int64_t cap, int64_t* n)
-{
-    if (!n_sig || !n) { c->err = "sorted dup: NULL argument"; return BMBS_EINVAL; }
-    *n_sig = *n = 0;
-    if (c->dup_n2 < 0 || c->bs_n < 0) {
-        c->err = "sorted dup: the context's last text call was not a BMBS_TEXT_BAM_SORTED call that returned records, or another call has used its buffers since";
-        return BMBS_ESTATE;
-    }
-    const u64 nt = (u64)(c->dup_n2 >> (c->dup_pe ? 1 : 0)), nr = (u64)c->bs_n;
-    *n_sig = (int64_t)nt; *n = (int64_t)nr;
-    if ((int64_t)nt > sig_cap || (int64_t)nr > cap) { c->err = "sorted dup: an array is too small (n_sig and n tell what is needed)"; return BMBS_ENOMEM; }
-    if (!nt) return BMBS_OK;
-    if (!sig || (nr && !tmpl)) { c->err = "sorted dup: NULL argument"; return BMBS_EINVAL; }
-    HIPCHK(c, hipSetDevice(c->dev));
-    if (!c->dup_done) {
-        const int rc = dup_sig_device(c, c->bam_raw.as<char>(), c->sam_off.as<u64>(), c->sam_len.as<u32>(), c->dup_pe, nt);
-        if (rc) return rc;
-        if (nr) {
-            ENS(c, c->dp_tmpl, nr * 4 + 64);
-            hipLaunchKernelGGL(k_dup_tmpl, dim3(nblk(nr, 256)), dim3(256), 0, c->stream, c->bs_idx2.as<u32>(), (long)nr, c->dup_pe ? 1 : 0, c->dp_tmpl.as<u32>());
-        }
-        c->dup_done = true;
-    }
-    HIPCHK(c, hipMemcpyAsync(sig, c->dp_sig.p, nt * sizeof(bmbs_dup_sig), hipMemcpyDeviceToHost, c->stream));
-    if (nr) HIPCHK(c, hipMemcpyAsync(tmpl, c->dp_tmpl.p, nr * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return BMBS_OK;
-}
-
-static int lane_dup_select(Lane* c, const bmbs_dup_sig* sig, int64_t n_in, uint8_t* dup, int64_t* n_dup)
-{
-    if (n_dup) *n_dup = 0;
-    if (n_in < 0 || n_in >= (1ll << 31)) { c->err = "dup select: bad argument"; return BMBS_EINVAL; }
-    if (!n_in) return BMBS_OK;
-    if (!sig || !dup) { c->err = "dup select: NULL buffer"; return BMBS_EINVAL; }
-    const u64 n = (u64)n_in;
-    HIPCHK(c, hipSetDevice(c->dev));
-    c->dup_done = false;                                  // (dp_sig is rewritten)
-    ENS(c, c->dp_sig, n * sizeof(bmbs_dup_sig) + 64); ENS(c, c->dp_key, n * 8 + 64); ENS(c, c->dp_key2, n * 8 + 64);
-    ENS(c, c->dp_idx, n * 4 + 64); ENS(c, c->dp_idx2, n * 4 + 64); ENS(c, c->dp_dup, n + 64);
-    {
-        std::lock_guard<std::mutex> up(g_h2d_mu[c->dev & 15]);
-        hipStream_t us = c->up_stream ? c->up_stream : c->stream;
-        HIPCHK(c, hipMemcpyAsync(c->dp_sig.p, sig, n * sizeof(bmbs_dup_sig), hipMemcpyHostToDevice, us));
-        HIPCHK(c, hipStreamSynchronize(us));
-    }
-    const bmbs_dup_sig* const ds = c->dp_sig.as<bmbs_dup_sig>();
-    u64* const ka = c->dp_key.as<u64>(); u64* const kb = c->dp_key2.as<u64>();
-    u32* const ia = c->dp_idx.as<u32>(); u32* const ib = c->dp_idx2.as<u32>();
-    u32* const info = c->tx_info.as<u32>() + 8;           // three 64-bit ORs and the count of duplicates
-    HIPCHK(c, hipMemsetAsync(info, 0, 32, c->stream));
-    hipLaunchKernelGGL(k_dup_bits, dim3(nblk(n, 256)), dim3(256), 0, c->stream, ds, (long)n, reinterpret_cast<unsigned long long*>(info));
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 8, info, 24, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    // each pass over the key bits that can be set only
-    unsigned end_bit[3];
-    size_t tmp_bytes = 0;
-    for (int p = 0; p < 3; p++) {
-        u64 bits; memcpy(&bits, c->h_info + 8 + 2 * p, 8);
-        end_bit[p] = 1;
-        while (end_bit[p] < 64 && bits >> end_bit[p]) end_bit[p]++;
-        size_t t = 0;
-        if (rocprim::radix_sort_pairs(nullptr, t, ka, kb, ia, ib, (size_t)n, 0u, end_bit[p], c->stream) != hipSuccess) { c->err = "dup select: radix_sort_pairs (size query) failed"; return BMBS_ENODEV; }
-        tmp_bytes = std::max(tmp_bytes, t);
-    }
-    ENS(c, c->bs_tmp, tmp_bytes + 64);
-    // (key, entry) pairs from the least significant field up; the entry numbers go back and forth between ia and ib
-    prof_begin(c, "dup_pair_sorts");
-    for (int p = 0; p < 3; p++) {
-        u32* const in = p == 1 ? ib : ia; u32* const out = p == 1 ? ia : ib;
-        hipLaunchKernelGGL(k_dup_keys, dim3(nblk(n, 256)), dim3(256), 0, c->stream, ds, p ? in : nullptr, (long)n, p, ka, in);
-        size_t t = tmp_bytes;
-        if (rocprim::radix_sort_pairs(c->bs_tmp.p, t, ka, kb, in, out, (size_t)n, 0u, end_bit[p], c->stream) != hipSuccess) { c->err = "dup select: radix_sort_pairs failed"; return BMBS_ENODEV; }
-    }
-    prof_end(c);
-    prof_begin(c, "k_dup_heads");
-    hipLaunchKernelGGL(k_dup_heads, dim3(nblk(n, 256)), dim3(256), 0, c->stream, ds, ib, (long)n, c->dp_dup.as<uint8_t>(), info + 6);
-    prof_end(c);
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 14, info + 6, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dup, c->dp_dup.p, n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    if (n_dup) *n_dup = (int64_t)c->h_info[14];
-    return BMBS_OK;
-}
-
-extern "C" int bmbs_bam_dup_sigs(bmbs_ctx* X, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, int32_t paired, bmbs_dup_sig* sig, int64_t sig_cap,
-                                 int64_t* n_sig)
-{ ON_LANE0(lane_bam_dup_sigs(c, records, bytes, len, n, paired, sig, sig_cap, n_sig)); }
-extern "C" int bmbs_text_sorted_dup(bmbs_ctx* X, bmbs_dup_sig* sig, int64_t sig_cap, int64_t* n_sig, uint32_t* tmpl, int64_t cap, int64_t* n)
-{ ON_LANE0(lane_text_sorted_dup(c, sig, sig_cap, n_sig, tmpl, cap, n)); }
-extern "C" int bmbs_dup_select(bmbs_ctx* X, const bmbs_dup_sig* sig, int64_t n, uint8_t* dup, int64_t* n_dup) { ON_LANE0(lane_dup_select(c, sig, n, dup, n_dup)); }
-
-// ---- methylation counts per cytosine (k_methyl.hip) -----------------------------------------------------------------------------------------
-// n (key, value) pairs in ka / va (kb / vb: as large, the sort's other side) -> one entry per distinct key with the values' halves added
-// up: bmbs_methyl_site at `site`, or (key, value) pairs at okey / oval; *n_out = their number
-static int meth_reduce(Lane* c, u64* ka, u64* va, u64* kb, u64* vb, u64 n, int pos_bits, int key_bits, bmbs_methyl_site* site, u64* okey, u64* oval, u64* n_out)
-{
-    *n_out = 0;
-    if (!n) return BMBS_OK;
-    const u64 nw = (n + 63) / 64;
-    u64 at = 0;
-    auto take = [&](u64 bytes) { const u64 a = at; at += (bytes + 255) & ~255ull; return a; };
-    const u64 o_wave = take(nw * 4), o_hoff = take((nw + 1) * 8), o_m = take(n * 4), o_u = take(n * 4), o_ms = take((n + 1) * 8), o_us = take((n + 1) * 8), o_hpos = take(n * 4);
-    ENS(c, c->mt_work, at + 64);
-    char* const A = c->mt_work.as<char>();
-    u32* const wave = reinterpret_cast<u32*>(A + o_wave); u64* const hoff = reinterpret_cast<u64*>(A + o_hoff); u32* const m = reinterpret_cast<u32*>(A + o_m);
-    u32* const u = reinterpret_cast<u32*>(A + o_u); u64* const ms = reinterpret_cast<u64*>(A + o_ms); u64* const us = reinterpret_cast<u64*>(A + o_us);
-    u32* const hpos = reinterpret_cast<u32*>(A + o_hpos);
-    size_t tmp = 0;
-    if (rocprim::radix_sort_pairs(nullptr, tmp, ka, kb, va, vb, (size_t)n, 0u, (unsigned)key_bits, c->stream) != hipSuccess) { c->err = "methyl: radix_sort_pairs (size query) failed"; return BMBS_ENODEV; }
-    HIPCHK(c, hipStreamSynchronize(c->stream));           // (bs_tmp may be replaced: an earlier sort has to be through with it)
-    ENS(c, c->bs_tmp, tmp + 64);
-    prof_begin(c, "meth_pair_sort");
-    if (rocprim::radix_sort_pairs(c->bs_tmp.p, tmp, ka, kb, va, vb, (size_t)n, 0u, (unsigned)key_bits, c->stream) != hipSuccess) { c->err = "methyl: radix_sort_pairs failed"; return BMBS_ENODEV; }
-    prof_end(c);
-    prof_begin(c, "k_meth_heads");
-    hipLaunchKernelGGL(k_meth_heads, dim3(nblk(n, 256)), dim3(256), 0, c->stream, kb, vb, (long)n, wave, m, u);
-    prof_end(c);
-    int rc = scan_u32(c, wave, nw, hoff, 30);
-    if (rc) return rc;
-    rc = scan_u32(c, m, n, ms, 31);
-    if (rc) return rc;
-    rc = scan_u32(c, u, n, us, 31);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 28, c->totals.as<u64>() + 30, 8, hipMemcpyDeviceToHost, c->stream));
-    hipLaunchKernelGGL(k_meth_hpos, dim3(nblk(n, 256)), dim3(256), 0, c->stream, kb, (long)n, hoff, hpos);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const u64 nh = *reinterpret_cast<const u64*>(c->h_info + 28);
-    if (nh > n) { c->err = "methyl: more run heads than entries"; return BMBS_ESTATE; }
-    *n_out = nh;
-    prof_begin(c, "k_meth_sites");
-    hipLaunchKernelGGL(k_meth_sites, dim3(nblk(nh, 256)), dim3(256), 0, c->stream, c->ix.gen2p, c->ix.chrom_start, kb, hpos, (long)nh, (long)n, ms, us, pos_bits, site, okey, oval);
-    prof_end(c);
-    return BMBS_OK;
-}
-
-static int methyl_params_as_opts(Lane* c, const bmbs_methyl_params* par, bmbs_methyl_opts* o)
-{
-    *o = bmbs_methyl_opts{1, 10, 5, 0, {0, 0}, {0, 0}};
-    if (!par) return BMBS_OK;
-    if (par->contexts < 1 || par->contexts > 7 || par->min_mapq < 0 || par->min_mapq > 255 || par->min_phred < 0 || par->min_phred > 255 || par->reserved) {
-        c->err = "methyl: bad parameters (contexts 1..7, min_mapq and min_phred 0..255, reserved 0)"; return BMBS_EINVAL;
-    }
-    o->contexts = par->contexts; o->min_mapq = par->min_mapq; o->min_phred = par->min_phred;
-    return BMBS_OK;
-}
-
-// the options of a call: *opts if given (the _opts calls), else the old calls' parameters with no flags and no trim (NULL: the defaults)
-static int methyl_get_opts(Lane* c, const bmbs_methyl_params* par, const bmbs_methyl_opts* opts, bmbs_methyl_opts* out)
-{
-    if (!opts) return methyl_params_as_opts(c, par, out);
-    const bmbs_methyl_opts& o = *out = *opts;
-    bool bad = o.contexts < 1 || o.contexts > 7 || o.min_mapq < 0 || o.min_mapq > 255 || o.min_phred < 0 || o.min_phred > 255 || (o.flags & ~BMBS_METHYL_MBIAS);
-    for (int m = 0; m < 2; m++) bad = bad || o.ignore_5p[m] < 0 || o.ignore_5p[m] > 65535 || o.ignore_3p[m] < 0 || o.ignore_3p[m] > 65535;
-    if (bad) { c->err = "methyl: bad parameters (contexts 1..7, min_mapq and min_phred 0..255, flags BMBS_METHYL_MBIAS or 0, ignore values 0..65535)"; return BMBS_EINVAL; }
-    return BMBS_OK;
-}
-
-// the records at raw / off / len (device; off = the exclusive scan of len), their clips (device, or NULL) -> c->mt_site, c->mt_sites;
-// with BMBS_METHYL_MBIAS the M-bias table of all n records -> c->mt_mbias too (once, whatever the slices).  Options: methyl_get_opts
-static int methyl_device(Lane* c, const char* raw, const u64* off, const u32* len, const u32* clip, u64 n, const bmbs_methyl_params* par_in, const bmbs_methyl_opts* opts,
-                         int64_t* n_site)
-{
-    // BMBS_METHYL_EVENTS (test aid): the events a slice of records may hold
-    static const u64 slice_cap = [] { const char* e = getenv("BMBS_METHYL_EVENTS"); const long long v = e ? atoll(e) : 0; return v > 0 ? (u64)v : (u64)1 << 26; }();
-    bmbs_methyl_opts pp;
-    if (int rc = methyl_get_opts(c, par_in, opts, &pp)) return rc;
-    c->mt_sites = -1;
-    MethPar par;
-    par.contexts = (u32)pp.contexts; par.min_mapq = (u32)pp.min_mapq; par.min_phred = (u32)pp.min_phred; par.n_chrom = c->ix.n_chrom;
-    for (int m = 0; m < 2; m++) { par.ig5[m] = (u32)pp.ignore_5p[m]; par.ig3[m] = (u32)pp.ignore_3p[m]; }
-    const bool trim = par.ig5[0] || par.ig5[1] || par.ig3[0] || par.ig3[1];
-    const bool mbias = (pp.flags & BMBS_METHYL_MBIAS) != 0;
-    int pos_bits = 1, ref_bits = 1;
-    while (pos_bits < 40 && c->ix.G >> pos_bits) pos_bits++;
-    while (ref_bits < 24 && (u64)c->ix.n_chrom >> ref_bits) ref_bits++;
-    par.pos_bits = pos_bits;
-    ENS(c, c->mt_cnt, n * 4 + 64); ENS(c, c->mt_eoff, (n + 1) * 8 + 64);
-    u32* const info = c->tx_info.as<u32>() + 8;
-    HIPCHK(c, hipMemsetAsync(info, 0, 32, c->stream));
-    const unsigned grid = nblk(n * METH_GROUP, 256);
-    // (without a trim: the kernels as they were before there was one)
-    const auto k_count = trim ? k_meth_events<false, true> : k_meth_events<false, false>;
-    const auto k_emit = trim ? k_meth_events<true, true> : k_meth_events<true, false>;
-    prof_begin(c, "k_meth_count");
-    hipLaunchKernelGGL(k_count, dim3(grid), dim3(256), 0, c->stream, c->ix.gen2p, c->ix.chrom_start, raw, off, len, clip, 0l,
-                       (long)n, par, c->mt_cnt.as<u32>(), (const u64*)nullptr, (u64*)nullptr, (u64*)nullptr, info);
-    prof_end(c);
-    int rc = scan_u32(c, c->mt_cnt.as<u32>(), n, c->mt_eoff.as<u64>(), 30);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 8, info, 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 28, c->totals.as<u64>() + 30, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    if (c->h_info[8]) { c->err = "methyl: the length given for record " + std::to_string(~c->h_info[8]) + " is not its block_size + 4 (or is below the 36 bytes every BAM record has)"; return BMBS_EINVAL; }
-    if (c->h_info[9]) { c->err = "methyl: the read name, CIGAR, sequence and qualities of record " + std::to_string(~c->h_info[9]) + " do not fit its length"; return BMBS_EINVAL; }
-    if (c->h_info[10]) { c->err = "methyl: the refID of record " + std::to_string(~c->h_info[10]) + " is beyond the " + std::to_string(c->ix.n_chrom) + " sequences of the index"; return BMBS_EINVAL; }
-    if (c->h_info[11]) { c->err = "methyl: the reference span of record " + std::to_string(~c->h_info[11]) + " runs off its sequence"; return BMBS_EINVAL; }
-    if (mbias) {
-        // 6 blocks per CU, each with its own tally in LDS (k_methyl.hip): the 6 waves per SIMD its registers allow, and 144 of the CU's 160
-        // KiB of LDS -- the walk waits on memory most of its time, so resident waves are what it runs on.  The count pass above has
-        // found nothing to refuse
-        if (!c->mt_cus) { int cus = 0; HIPCHK(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->dev)); c->mt_cus = cus > 0 ? cus : 1; }
-        ENS(c, c->mt_mbias, METH_MBIAS_ROWS * BMBS_MBIAS_CYCLES * 8 + 64);
-        HIPCHK(c, hipMemsetAsync(c->mt_mbias.p, 0, METH_MBIAS_ROWS * BMBS_MBIAS_CYCLES * 8, c->stream));
-        const unsigned mgrid = (unsigned)std::min<u64>((u64)c->mt_cus * 6, nblk(n * METH_GROUP, 256));
-        prof_begin(c, "k_meth_mbias");
-        hipLaunchKernelGGL(k_meth_mbias, dim3(mgrid), dim3(256), 0, c->stream, c->ix.gen2p, c->ix.chrom_start, raw, off, len, clip, (long)n, par,
-                           c->mt_mbias.as<unsigned long long>());
-        prof_end(c);
-    }
-    const u64 n_ev = *reinterpret_cast<const u64*>(c->h_info + 28);
-    const u64* const eoff = c->mt_eoff.as<u64>();
-    u64 n_acc = 0, n_sites = 0;
-    bool sliced = false;
-    for (u64 start = 0; start < n && n_ev;) {
-        // a slice of records [start, end) with at most slice_cap events (a record with more is a slice of its own)
-        u64 end = n, e0 = 0, e1 = n_ev;
-        if (n_ev > slice_cap) {
-            sliced = true;
-            hipLaunchKernelGGL(k_meth_cut, dim3(1), dim3(64), 0, c->stream, eoff, (long)start, (long)n, slice_cap, reinterpret_cast<u64*>(info));
-            HIPCHK(c, hipMemcpyAsync(c->h_info + 8, info, 8, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipMemcpyAsync(c->h_info + 10, eoff + start, 8, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            end = *reinterpret_cast<const u64*>(c->h_info + 8); e0 = *reinterpret_cast<const u64*>(c->h_info + 10);
-            if (end <= start || end > n) { c->err = "methyl: bad slice"; return BMBS_ESTATE; }
-            HIPCHK(c, hipMemcpyAsync(c->h_info + 10, eoff + end, 8, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            e1 = *reinterpret_cast<const u64*>(c->h_info + 10);
-        }
-        const u64 ne = e1 - e0;
-        if (ne >= (1ull << 32)) { c->err = "methyl: a record with 2^32 events and more"; return BMBS_EINVAL; }
-        if (ne) {
-            const u64 q = (ne * 8 + 255) & ~255ull;
-            ENS(c, c->mt_ev, 4 * q + 64);
-            char* const E = c->mt_ev.as<char>();
-            u64* const ka = reinterpret_cast<u64*>(E); u64* const kb = reinterpret_cast<u64*>(E + q); u64* const va = reinterpret_cast<u64*>(E + 2 * q); u64* const vb = reinterpret_cast<u64*>(E + 3 * q);
-            prof_begin(c, "k_meth_emit");
-            hipLaunchKernelGGL(k_emit, dim3(nblk((end - start) * METH_GROUP, 256)), dim3(256), 0, c->stream, c->ix.gen2p,
-                               c->ix.chrom_start, raw, off, len, clip, (long)start, (long)(end - start), par, (u32*)nullptr, eoff + start, ka, va, info + 4);
-            prof_end(c);
-            u64 got = 0;
-            if (!sliced) {
-                ENS(c, c->mt_site, ne * sizeof(bmbs_methyl_site) + 64);
-                rc = meth_reduce(c, ka, va, kb, vb, ne, pos_bits, pos_bits + ref_bits, c->mt_site.as<bmbs_methyl_site>(), nullptr, nullptr, &got);
-                if (rc) return rc;
-                n_sites = got;
-            } else {
-                // the slice's sites as pairs behind those of the slices before (the buffer grows: what it holds is copied over)
-                if (c->mt_acc.cap < (n_acc + ne) * 16 + 64) {
-                    DevBuf grown;
-                    ENS(c, grown, (n_acc + ne) * 16 * 2 + 64);
-                    if (n_acc) HIPCHK(c, hipMemcpyAsync(grown.p, c->mt_acc.p, n_acc * 16, hipMemcpyDeviceToDevice, c->stream));
-                    HIPCHK(c, hipStreamSynchronize(c->stream));
-                    release(c->mt_acc); c->mt_acc = grown;
-                }
-                // (pairs interleaved as key, value would need another kernel: keys in the first half of each slice's piece, values behind)
-                ENS(c, c->mt_site, ne * 16 + 64);
-                u64* const sk = c->mt_site.as<u64>(); u64* const sv = sk + ne;
-                rc = meth_reduce(c, ka, va, kb, vb, ne, pos_bits, pos_bits + ref_bits, nullptr, sk, sv, &got);
-                if (rc) return rc;
-                HIPCHK(c, hipMemcpyAsync(c->mt_acc.as<u64>() + 2 * n_acc, sk, got * 8, hipMemcpyDeviceToDevice, c->stream));
-                HIPCHK(c, hipMemcpyAsync(c->mt_acc.as<u64>() + 2 * n_acc + got, sv, got * 8, hipMemcpyDeviceToDevice, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                c->mt_slice.push_back({n_acc, got});
-                n_acc += got;
-            }
-        }
-        start = end;
-    }
-    if (sliced) {
-        // the slices' sites, one more reduction: keys and values gathered into the two sides of the event buffer
-        const u64 q = (n_acc * 8 + 255) & ~255ull;
-        ENS(c, c->mt_ev, 4 * q + 64);
-        char* const E = c->mt_ev.as<char>();
-        u64* const ka = reinterpret_cast<u64*>(E); u64* const kb = reinterpret_cast<u64*>(E + q); u64* const va = reinterpret_cast<u64*>(E + 2 * q); u64* const vb = reinterpret_cast<u64*>(E + 3 * q);
-        for (const auto& s : c->mt_slice) {
-            HIPCHK(c, hipMemcpyAsync(ka + s.first, c->mt_acc.as<u64>() + 2 * s.first, s.second * 8, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(va + s.first, c->mt_acc.as<u64>() + 2 * s.first + s.second, s.second * 8, hipMemcpyDeviceToDevice, c->stream));
-        }
-        c->mt_slice.clear();
-        ENS(c, c->mt_site, n_acc * sizeof(bmbs_methyl_site) + 64);
-        rc = meth_reduce(c, ka, va, kb, vb, n_acc, pos_bits, pos_bits + ref_bits, c->mt_site.as<bmbs_methyl_site>(), nullptr, nullptr, &n_sites);
-        if (rc) return rc;
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    c->mt_sites = (int64_t)n_sites;
-    c->mt_has_mbias = mbias;
-    if (n_site) *n_site = (int64_t)n_sites;
-    return BMBS_OK;
-}
-
-static int lane_bam_methyl(Lane* c, const char* records, uint64_t bytes, const uint32_t* len, int64_t n_in, const uint32_t* clip, const bmbs_methyl_params* par,
-                           const bmbs_methyl_opts* opts, int64_t* n_site)
-{
-    if (n_site) *n_site = 0;
-    c->mt_sites = -1; c->mt_has_mbias = c->mt_mbias_zero = false;
-    c->mt_slice.clear();
-    if (!c->attached) { c->err = "methyl: no index attached"; return BMBS_ESTATE; }
-    if (n_in < 0 || n_in >= (1ll << 31)) { c->err = "methyl: bad argument"; return BMBS_EINVAL; }
-    if (n_in && !len) { c->err = "methyl: NULL buffer"; return BMBS_EINVAL; }
-    const u64 n = (u64)n_in;
-    u64 sum = 0;
-    for (u64 i = 0; i < n; i++) {
-        if (len[i] && len[i] < 36) { c->err = "methyl: the length given for record " + std::to_string(i) + " is below the 36 bytes every BAM record has"; return BMBS_EINVAL; }
-        sum += len[i];
-    }
-    if (sum != bytes) { c->err = "methyl: the record lengths add up to " + std::to_string(sum) + " bytes, not to the " + std::to_string(bytes) + " given"; return BMBS_EINVAL; }
-    if (!n) {
-        // (no record: no device work; an _opts call still has its options checked, and its table is all zero)
-        bmbs_methyl_opts pp;
-        if (opts) { if (int rc = methyl_get_opts(c, par, opts, &pp)) return rc; c->mt_has_mbias = c->mt_mbias_zero = (pp.flags & BMBS_METHYL_MBIAS) != 0; }
-        c->mt_sites = 0;
-        return BMBS_OK;
-    }
-    if (bytes && !records) { c->err = "methyl: NULL buffer"; return BMBS_EINVAL; }
-    HIPCHK(c, hipSetDevice(c->dev));
-    ENS(c, c->mt_in, bytes + 256); ENS(c, c->mt_len, n * 4 + 64); ENS(c, c->mt_off, (n + 1) * 8 + 64);
-    if (clip) ENS(c, c->mt_clip, n * 4 + 64);
-    {
-        std::lock_guard<std::mutex> up(g_h2d_mu[c->dev & 15]);
-        hipStream_t us = c->up_stream ? c->up_stream : c->stream;
-        const u64 piece = 128ull << 20;
-        for (u64 o = 0; o < bytes; o += piece) HIPCHK(c, hipMemcpyAsync(c->mt_in.as<char>() + o, records + o, std::min(piece, bytes - o), hipMemcpyHostToDevice, us));
-        HIPCHK(c, hipMemcpyAsync(c->mt_len.p, len, n * 4, hipMemcpyHostToDevice, us));
-        if (clip) HIPCHK(c, hipMemcpyAsync(c->mt_clip.p, clip, n * 4, hipMemcpyHostToDevice, us));
-        HIPCHK(c, hipStreamSynchronize(us));
-    }
-    const int rc = scan_u32(c, c->mt_len.as<u32>(), n, c->mt_off.as<u64>(), 29);
-    if (rc) return rc;
-    return methyl_device(c, c->mt_in.as<char>(), c->mt_off.as<u64>(), c->mt_len.as<u32>(), clip ? c->mt_clip.as<u32>() : nullptr, n, par, opts, n_site);
-}
-
-static int lane_bam_sort_methyl(Lane* c, const uint32_t* clip, const bmbs_methyl_params* par, const bmbs_methyl_opts* opts, int64_t* n_site)
-{
-    if (n_site) *n_site = 0;
-    c->mt_sites = -1; c->mt_has_mbias = c->mt_mbias_zero = false;
-    c->mt_slice.clear();
-    if (!c->attached) { c->err = "sort methyl: no index attached"; return BMBS_ESTATE; }
-    if (c->ms_n < 0) {
-        c->err = "sort methyl: no bmbs_bam_sort call's records are resident (none yet, no records, or it failed), or another call has used its buffers since";
-        return BMBS_ESTATE;
-    }
-    const u64 n = (u64)c->ms_n;
-    HIPCHK(c, hipSetDevice(c->dev));
-    if (clip) {
-        ENS(c, c->mt_clip, n * 4 + 64);
-        std::lock_guard<std::mutex> up(g_h2d_mu[c->dev & 15]);
-        hipStream_t us = c->up_stream ? c->up_stream : c->stream;
-        HIPCHK(c, hipMemcpyAsync(c->mt_clip.p, clip, n * 4, hipMemcpyHostToDevice, us));
-        HIPCHK(c, hipStreamSynchronize(us));
-    }
-    return methyl_device(c, c->bs_in.as<char>(), c->bs_off.as<u64>(), c->bs_len.as<u32>(), clip ? c->mt_clip.as<u32>() : nullptr, n, par, opts, n_site);
-}
-
-static int lane_methyl_sites(Lane* c, bmbs_methyl_site* site, int64_t cap, int64_t* n)
-{
-    if (!n) { c->err = "methyl sites: NULL argument"; return BMBS_EINVAL; }
-    *n = 0;
-    if (c->mt_sites < 0) { c->err = "methyl sites: the context's last bmbs_bam_methyl / bmbs_bam_sort_methyl call left no result"; return BMBS_ESTATE; }
-    *n = c->mt_sites;
-    if (c->mt_sites > cap) { c->err = "methyl sites: the array is too small (n tells what is needed)"; return BMBS_ENOMEM; }
-    if (!c->mt_sites) return BMBS_OK;
-    if (!site) { c->err = "methyl sites: NULL argument"; return BMBS_EINVAL; }
-    HIPCHK(c, hipSetDevice(c->dev));
-    hipStream_t ds = c->down_stream ? c->down_stream : c->stream;
-    HIPCHK(c, hipMemcpyAsync(site, c->mt_site.p, (size_t)c->mt_sites * sizeof(bmbs_methyl_site), hipMemcpyDeviceToHost, ds));
-    HIPCHK(c, hipStreamSynchronize(ds));
-    return BMBS_OK;
-}
-
-static int lane_methyl_mbias(Lane* c, uint64_t* table, int64_t cap, int64_t* n)
-{
-    if (!n) { c->err = "methyl mbias: NULL argument"; return BMBS_EINVAL; }
-    *n = 0;
-    if (c->mt_sites < 0 || !c->mt_has_mbias) {
-        c->err = "methyl mbias: the context's last bmbs_bam_methyl_opts / bmbs_bam_sort_methyl_opts call left no table (none yet, it failed, or BMBS_METHYL_MBIAS was not set)";
-        return BMBS_ESTATE;
-    }
-    const int64_t entries = (int64_t)METH_MBIAS_ROWS * BMBS_MBIAS_CYCLES;
-    *n = entries;
-    if (entries > cap) { c->err = "methyl mbias: the array is too small (n tells what is needed)"; return BMBS_ENOMEM; }
-    if (!table) { c->err = "methyl mbias: NULL argument"; return BMBS_EINVAL; }
-    if (c->mt_mbias_zero) { memset(table, 0, (size_t)entries * 8); return BMBS_OK; }
-    HIPCHK(c, hipSetDevice(c->dev));
-    hipStream_t ds = c->down_stream ? c->down_stream : c->stream;
-    HIPCHK(c, hipMemcpyAsync(table, c->mt_mbias.p, (size_t)entries * 8, hipMemcpyDeviceToHost, ds));
-    HIPCHK(c, hipStreamSynchronize(ds));
-    return BMBS_OK;
-}
-
-static int lane_text_sorted_clip(Lane* c, uint32_t* clip, int64_t cap, int64_t* n)
-{
-    if (!n) { c->err = "sorted clip: NULL argument"; return BMBS_EINVAL; }
-    *n = 0;
-    if (c->dup_n2 < 0 || c->bs_n < 0) {
-        c->err = "sorted clip: the context's last text call was not a BMBS_TEXT_BAM_SORTED call that returned records, or another call has used its buffers since";
-        return BMBS_ESTATE;
-    }
-    const u64 nr = (u64)c->bs_n;
-    *n = (int64_t)nr;
-    if ((int64_t)nr > cap) { c->err = "sorted clip: the array is too small (n tells what is needed)"; return BMBS_ENOMEM; }
-    if (!nr) return BMBS_OK;
-    if (!clip) { c->err = "sorted clip: NULL argument"; return BMBS_EINVAL; }
-    HIPCHK(c, hipSetDevice(c->dev));
-    ENS(c, c->mt_cl2, nr * 4 + 64);
-    u32* const info = c->tx_info.as<u32>() + 8;
-    HIPCHK(c, hipMemsetAsync(info, 0, 32, c->stream));
-    prof_begin(c, "k_meth_clip");
-    hipLaunchKernelGGL(k_meth_clip, dim3(nblk(nr, 256)), dim3(256), 0, c->stream, c->bam_raw.as<char>(), c->sam_off.as<u64>(), c->sam_len.as<u32>(), c->bs_idx2.as<u32>(), (long)nr,
-                       c->dup_pe ? 1 : 0, c->mt_cl2.as<u32>(), info);
-    prof_end(c);
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 8, info, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(clip, c->mt_cl2.p, nr * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    if (c->h_info[8]) { c->err = "sorted clip: the overlap of record " + std::to_string(~c->h_info[8]) + " (in sorted order) with its mate does not fit 16 bits"; return BMBS_EINVAL; }
-    return BMBS_OK;
-}
-
-extern "C" int bmbs_bam_methyl(bmbs_ctx* X, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, const uint32_t* clip, const bmbs_methyl_params* par, int64_t* n_site)
-{ ON_LANE0(lane_bam_methyl(c, records, bytes, len, n, clip, par, nullptr, n_site)); }
-extern "C" int bmbs_bam_sort_methyl(bmbs_ctx* X, const uint32_t* clip, const bmbs_methyl_params* par, int64_t* n_site) { ON_LANE0(lane_bam_sort_methyl(c, clip, par, nullptr, n_site)); }
-extern "C" int bmbs_bam_methyl_opts(bmbs_ctx* X, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, const uint32_t* clip, const bmbs_methyl_opts* opts, int64_t* n_site)
-{ ON_LANE0(lane_bam_methyl(c, records, bytes, len, n, clip, nullptr, opts, n_site)); }
-extern "C" int bmbs_bam_sort_methyl_opts(bmbs_ctx* X, const uint32_t* clip, const bmbs_methyl_opts* opts, int64_t* n_site) { ON_LANE0(lane_bam_sort_methyl(c, clip, nullptr, opts, n_site)); }
-extern "C" int bmbs_methyl_mbias(bmbs_ctx* X, uint64_t* table, int64_t cap, int64_t* n) { ON_LANE0(lane_methyl_mbias(c, table, cap, n)); }
-extern "C" int bmbs_methyl_sites(bmbs_ctx* X, bmbs_methyl_site* site, int64_t cap, int64_t* n) { ON_LANE0(lane_methyl_sites(c, site, cap, n)); }
-extern "C" int bmbs_text_sorted_clip(bmbs_ctx* X, uint32_t* clip, int64_t cap, int64_t* n) { ON_LANE0(lane_text_sorted_clip(c, clip, cap, n)); }
-
-extern "C" int bmbs_text_sorted_index(bmbs_ctx* X, uint64_t* key, uint32_t* len, int64_t cap, int64_t* n) { ON_LANE0(lane_text_sorted_index(c, key, len, cap, n)); }
-extern "C" int bmbs_bam_sort(bmbs_ctx* X, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, int32_t flags, char* out, uint64_t out_cap, uint64_t* out_bytes)
-{ ON_LANE0(lane_bam_sort(c, records, bytes, len, n, flags, out, out_cap, out_bytes)); }
-extern "C" int bmbs_bam_sort_index(bmbs_ctx* X, bmbs_bai_chunk* chunk, int64_t chunk_cap, int64_t* n_chunk, bmbs_bai_win* win, int64_t win_cap, int64_t* n_win,
-                                   bmbs_bai_ref* ref, int64_t ref_cap, int64_t* n_ref, uint64_t* n_no_coor)
-{ ON_LANE0(lane_bam_sort_index(c, chunk, chunk_cap, n_chunk, win, win_cap, n_win, ref, ref_cap, n_ref, n_no_coor)); }
 
 extern "C" int bmbs_sam_refs(bmbs_ctx* X, const char* const* names, int32_t n_names) { ON_LANE0(lane_sam_refs(c, names, n_names)); }
 extern "C" int bmbs_map_se_text(bmbs_ctx* X, const char* text, uint64_t text_bytes, int64_t n_records, int32_t flags, char* sam, uint64_t sam_cap,
