@@ -64,9 +64,9 @@ void prof_collect(Lane* c, int slot)
     c->acc_calls++;
 }
 
-// exclusive scan u32[n] -> u64[n+1], total left in c->totals[slot]; n_dev: a device-side count that bounds n (see k_scan_partial)
+// exclusive scan u32[n] -> u64[n+1], total left in the lane's word `slot` (bmbs_words.h); n_dev: a device-side count that bounds n (see k_scan_partial)
 // Two launches (tile sums, offsets) by default; BMBS_SCAN_CHAIN=1: one (k_scan_chain).
-int scan_u32(Lane* c, const u32* in, u64 n, u64* out, int slot, u32* list, int nz, const u64* n_dev)
+int scan_u32(Lane* c, const u32* in, u64 n, u64* out, Tot slot, u32* list, int nz, const u64* n_dev)
 {
     const u64 per = (u64)SCAN_BLOCK * SCAN_ITEMS;
     const u64 nb = n ? (n + per - 1) / per : 1;
@@ -74,7 +74,7 @@ int scan_u32(Lane* c, const u32* in, u64 n, u64* out, int slot, u32* list, int n
         ENS(c, c->scan_tmp, (nb + 1) * 8);
         u64* bs = c->scan_tmp.as<u64>();
         hipLaunchKernelGGL(k_scan_partial, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, c->stream, in, n, bs, nz, n_dev);
-        hipLaunchKernelGGL(k_scan_final, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, c->stream, in, n, bs, out, list, nz, n_dev, c->totals.as<u64>() + slot);
+        hipLaunchKernelGGL(k_scan_final, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, c->stream, in, n, bs, out, list, nz, n_dev, tot_at(c, slot));
         return BMBS_OK;
     }
     // status words: zeroed when the buffer is (re)allocated and when the epoch wraps, so no word of an earlier scan carries this scan's epoch
@@ -85,7 +85,7 @@ int scan_u32(Lane* c, const u32* in, u64 n, u64* out, int slot, u32* list, int n
         if (hipMemsetAsync(c->scan_tmp.p, 0, c->scan_tmp.cap, c->stream) != hipSuccess) { c->err = "hipMemsetAsync failed"; return BMBS_ESTATE; }
         c->scan_epoch = 1;
     }
-    hipLaunchKernelGGL(k_scan_chain, dim3((unsigned)nt), dim3(SCAN_BLOCK), 0, c->stream, in, n, out, list, nz, n_dev, c->totals.as<u64>() + slot,
+    hipLaunchKernelGGL(k_scan_chain, dim3((unsigned)nt), dim3(SCAN_BLOCK), 0, c->stream, in, n, out, list, nz, n_dev, tot_at(c, slot),
                        c->scan_ticket.as<unsigned int>(), c->scan_ticket_base, c->scan_tmp.as<u64>(), c->scan_epoch);
     c->scan_ticket_base += (u32)nt;
     return BMBS_OK;
@@ -255,7 +255,7 @@ void launch_sw(Lane* c, const char* d_seq, const char* d_qual, const char* d_qua
     auto kern = gm.len ? k_align_sw<KB, false> : gm.k == KB ? k_align_sw<KB, true, true> : k_align_sw<KB, true, false>;
     for (u64 base = 0; base < n_jobs; base += slots)
         hipLaunchKernelGGL(kern, dim3((unsigned)(slots / 64)), dim3(64), lds, c->stream, c->ix, c->sp, c->pen_lut.as<int>(), d_seq,
-                           d_qual, d_qual2, gm, stride, c->totals.as<u64>() + 2, c->sw_job.as<u32>(), jobs, rev_from, c->trace.as<u64>(),
+                           d_qual, d_qual2, gm, stride, tot_at(c, TOT_SW), c->sw_job.as<u32>(), jobs, rev_from, c->trace.as<u64>(),
                            slots, base, d_cigar_pool, max_ops, c->a_start.as<int>(), c->a_end.as<int>(), c->a_nm.as<u32>(),
                            c->a_score.as<int>(), c->a_nops.as<int>(), prw);
 }
@@ -269,7 +269,7 @@ void launch_sw2(Lane* c, const char* d_seq, const char* d_qual, const char* d_qu
     auto kern = !prw.base ? k_align_sw2<KB, false, false> : gm.k == KB ? k_align_sw2<KB, true, true> : k_align_sw2<KB, false, true>;
     for (u64 base = 0; base < n_jobs; base += 2 * slots)
         hipLaunchKernelGGL(kern, dim3((unsigned)(slots / 64)), dim3(64), sw_window_lds(gm, 2), c->stream, c->ix, c->sp, c->pen_lut.as<int>(), d_seq,
-                           d_qual, d_qual2, gm, stride, c->totals.as<u64>() + 2, c->sw_job.as<u32>(), jobs, rev_from, c->trace.as<u64>(),
+                           d_qual, d_qual2, gm, stride, tot_at(c, TOT_SW), c->sw_job.as<u32>(), jobs, rev_from, c->trace.as<u64>(),
                            slots, base, d_cigar_pool, max_ops, c->a_start.as<int>(), c->a_end.as<int>(), c->a_nm.as<u32>(),
                            c->a_score.as<int>(), c->a_nops.as<int>(), prw);
 }
@@ -341,18 +341,18 @@ int run_align(Lane* c, const char* d_seq, const char* d_qual, const char* d_qual
                            c->a_score.as<int>(), c->a_nops.as<int>(), c->need_sw.as<u32>(), cnt);
     prof_end(c);
     prof_begin(c, "scan_sw");
-    int rc = scan_u32(c, c->need_sw.as<u32>(), n_jobs, c->sw_off.as<u64>(), 2, c->sw_job.as<u32>(), 0, n_jobs_dev);
+    int rc = scan_u32(c, c->need_sw.as<u32>(), n_jobs, c->sw_off.as<u64>(), TOT_SW, c->sw_job.as<u32>(), 0, n_jobs_dev);
     if (rc) return rc;
     prof_end(c);
     if (n_jobs_dev && reg_form && sw_bound < n_jobs)
-        hipLaunchKernelGGL(k_guard_count, dim3(1), dim3(1), 0, c->stream, c->totals.as<u64>() + 2, sw_bound, c->flags.as<u32>(), BMBS_FLAG_SW);
+        hipLaunchKernelGGL(k_guard_count, dim3(1), dim3(1), 0, c->stream, tot_at(c, TOT_SW), sw_bound, c->flags.as<u32>(), BMBS_FLAG_SW);
     prof_begin(c, "k_align_sw");
     if (!reg_form) {
         // one alignment per 16 / 32 / 64 lanes (band of 2k+1 cells), trace + CIGAR in LDS
         const size_t words = (size_t)sww_lds_words(L, k);
 #define SWW_LAUNCH(LANES)                                                                                                             \
         hipLaunchKernelGGL((k_align_sw_wave<LANES>), dim3(nblk(n_jobs, 64 / LANES)), dim3(64), words * 4 * (64 / LANES), c->stream, c->ix, \
-                           c->sp, c->pen_lut.as<int>(), d_seq, d_qual, d_qual2, gm, stride, c->totals.as<u64>() + 2, c->sw_job.as<u32>(),   \
+                           c->sp, c->pen_lut.as<int>(), d_seq, d_qual, d_qual2, gm, stride, tot_at(c, TOT_SW), c->sw_job.as<u32>(),   \
                            jobs, rev_from, d_cigar_pool, max_ops, c->a_start.as<int>(), c->a_end.as<int>(), c->a_nm.as<u32>(),          \
                            c->a_score.as<int>(), c->a_nops.as<int>(), pr)
         if (k <= 7) SWW_LAUNCH(16);
@@ -503,16 +503,16 @@ int launch_seeding(Lane* c, const char* d_seq, const ReadGeom& gm, int stride, u
                            c->prm.seed_len, pe_mode, st, sc, cnt);
     prof_end(c);
     prof_begin(c, "list_second");
-    int rc = scan_u32(c, sc.flag_c, n, sc.off_c, 3, sc.list_c);          // scan + list in one pass
+    int rc = scan_u32(c, sc.flag_c, n, sc.off_c, TOT_SEED_SECOND, sc.list_c);          // scan + list in one pass
     if (rc) return rc;
     prof_end(c);
     prof_begin(c, "k_seed_second");
-    if (packed && kg) hipLaunchKernelGGL((k_seed_second<true, true>), dim3(chunks_min), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, c->totals.as<u64>() + 3, target_waves, pe_mode, st, sc, cnt);
-    else if (packed) hipLaunchKernelGGL(k_seed_second<true>, dim3(chunks_min), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, c->totals.as<u64>() + 3, target_waves, pe_mode, st, sc, cnt);
-    else hipLaunchKernelGGL(k_seed_second<false>, dim3(chunks_min), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, c->totals.as<u64>() + 3, target_waves, pe_mode, st, sc, cnt);
+    if (packed && kg) hipLaunchKernelGGL((k_seed_second<true, true>), dim3(chunks_min), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, tot_at(c, TOT_SEED_SECOND), target_waves, pe_mode, st, sc, cnt);
+    else if (packed) hipLaunchKernelGGL(k_seed_second<true>, dim3(chunks_min), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, tot_at(c, TOT_SEED_SECOND), target_waves, pe_mode, st, sc, cnt);
+    else hipLaunchKernelGGL(k_seed_second<false>, dim3(chunks_min), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, tot_at(c, TOT_SEED_SECOND), target_waves, pe_mode, st, sc, cnt);
     prof_end(c);
     prof_begin(c, "list_extra");
-    rc = scan_u32(c, sc.flag_d, n, sc.off_d, 4, sc.list_d);
+    rc = scan_u32(c, sc.flag_d, n, sc.off_d, TOT_SEED_EXTRA, sc.list_d);
     if (rc) return rc;
     prof_end(c);
     prof_begin(c, "k_seed_extra");
@@ -527,19 +527,19 @@ int launch_seeding(Lane* c, const char* d_seq, const ReadGeom& gm, int stride, u
         // packed rows: the lane's row in its LDS slot (4.6 KB per wave at 150 bases: no occupancy lost); rows too long for 16 KB: from global memory
         const size_t plds = (size_t)64 * (pr.pwords + 1) * 8;
         if (packed && plds <= 16 * 1024 && kg)
-            hipLaunchKernelGGL((k_seed_extra<false, true, true, true>), dim3(chunks_min), dim3(64), plds, c->stream, c->ix, d_seq, pr, gm, stride, c->totals.as<u64>() + 4,
+            hipLaunchKernelGGL((k_seed_extra<false, true, true, true>), dim3(chunks_min), dim3(64), plds, c->stream, c->ix, d_seq, pr, gm, stride, tot_at(c, TOT_SEED_EXTRA),
                                target_waves, c->prm.seed_len, pe_mode, st, sc, cnt);
         else if (packed && plds <= 16 * 1024)
-            hipLaunchKernelGGL((k_seed_extra<false, true, true>), dim3(chunks_min), dim3(64), plds, c->stream, c->ix, d_seq, pr, gm, stride, c->totals.as<u64>() + 4,
+            hipLaunchKernelGGL((k_seed_extra<false, true, true>), dim3(chunks_min), dim3(64), plds, c->stream, c->ix, d_seq, pr, gm, stride, tot_at(c, TOT_SEED_EXTRA),
                                target_waves, c->prm.seed_len, pe_mode, st, sc, cnt);
         else if (packed)
-            hipLaunchKernelGGL((k_seed_extra<false, true>), dim3(chunks_min), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, c->totals.as<u64>() + 4,
+            hipLaunchKernelGGL((k_seed_extra<false, true>), dim3(chunks_min), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, tot_at(c, TOT_SEED_EXTRA),
                                target_waves, c->prm.seed_len, pe_mode, st, sc, cnt);
         else if (rows_in_lds)
-            hipLaunchKernelGGL((k_seed_extra<true, false>), dim3(chunks_min), dim3(64), lds, c->stream, c->ix, d_seq, pr, gm, stride, c->totals.as<u64>() + 4,
+            hipLaunchKernelGGL((k_seed_extra<true, false>), dim3(chunks_min), dim3(64), lds, c->stream, c->ix, d_seq, pr, gm, stride, tot_at(c, TOT_SEED_EXTRA),
                                target_waves, c->prm.seed_len, pe_mode, st, sc, cnt);
         else
-            hipLaunchKernelGGL((k_seed_extra<false, false>), dim3(chunks_min), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, c->totals.as<u64>() + 4,
+            hipLaunchKernelGGL((k_seed_extra<false, false>), dim3(chunks_min), dim3(64), 0, c->stream, c->ix, d_seq, pr, gm, stride, tot_at(c, TOT_SEED_EXTRA),
                                target_waves, c->prm.seed_len, pe_mode, st, sc, cnt);
     }
     prof_end(c);
@@ -551,15 +551,15 @@ int cand_total(Lane* c, const ReadState& st, u64 n, bool exact, u64* tot_out)
 {
     if (exact) {
         u64 tot = 0;
-        HIPCHK(c, hipMemcpyAsync(&tot, c->totals.as<u64>(), 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&tot, tot_at(c, TOT_CAND), sizeof tot, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         *tot_out = tot;
         return BMBS_OK;
     }
     const u64 cap = cap_from(c->lr_cand, n, n, c->kn.cap_scale);
-    hipLaunchKernelGGL(k_guard_cand, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->totals.as<u64>(), cap, c->flags.as<u32>(), (long)n, st.verdict,
+    hipLaunchKernelGGL(k_guard_cand, dim3(nblk(n, 256)), dim3(256), 0, c->stream, tot_at(c, TOT_CAND), cap, c->flags.as<u32>(), (long)n, st.verdict,
                        st.n_cand, st.cand_off);
-    hipLaunchKernelGGL(k_guard_done, dim3(1), dim3(1), 0, c->stream, c->totals.as<u64>(), c->flags.as<u32>(), BMBS_FLAG_CAND);
+    hipLaunchKernelGGL(k_guard_done, dim3(1), dim3(1), 0, c->stream, tot_at(c, TOT_CAND), c->flags.as<u32>(), BMBS_FLAG_CAND);
     *tot_out = cap;
     return BMBS_OK;
 }
@@ -571,7 +571,7 @@ int run_seed_stages(Lane* c, const char* d_seq, const ReadGeom& gm, int stride, 
     int rc = launch_seeding(c, d_seq, gm, stride, n, pe_mode, prepacked);
     if (rc) return rc;
     prof_begin(c, "scan_cand");
-    rc = scan_u32(c, st.n_cand, n, st.cand_off, 0);
+    rc = scan_u32(c, st.n_cand, n, st.cand_off, TOT_CAND);
     if (rc) return rc;
     prof_end(c);
     u64 tot = 0;
@@ -587,7 +587,7 @@ int run_seed_stages(Lane* c, const char* d_seq, const ReadGeom& gm, int stride, 
     // the reads that have candidates, compacted (the scan's list mode on n_cand != 0), so that the vote kernel's waves are dense
     HIPCHK(c, hipMemsetAsync(c->long_flag.p, 0, n * 4, c->stream));
     HIPCHK(c, hipMemsetAsync(st.n_votes, 0, n * 4, c->stream));
-    rc = scan_u32(c, st.n_cand, n, c->long_off.as<u64>(), 10, c->vote_list.as<u32>(), 1);
+    rc = scan_u32(c, st.n_cand, n, c->long_off.as<u64>(), TOT_VOTE_READS, c->vote_list.as<u32>(), 1);
     if (rc) return rc;
     // long reads (up to 25 seeds): lists of 17..32 candidates are the rule, not the repeat case -- they get a kernel of their
     // own (k_vote_mid); its flag and list live in the seeding work-list buffers, free by now
@@ -597,37 +597,37 @@ int run_seed_stages(Lane* c, const char* d_seq, const ReadGeom& gm, int stride, 
     u32* mid_flag = use_mid ? c->sd_flag_c.as<u32>() : nullptr;
     if (use_mid) HIPCHK(c, hipMemsetAsync(mid_flag, 0, n * 4, c->stream));
     hipLaunchKernelGGL(k_vote_fused, dim3(nblk(n, 64)), dim3(64), 0, c->stream, c->ix, (long)n, gm, st, c->cand.as<u64>(),
-                       c->votes.as<bmbs_vote>(), c->slot_read.as<u32>(), c->long_flag.as<u32>(), c->totals.as<u64>() + 10,
+                       c->votes.as<bmbs_vote>(), c->slot_read.as<u32>(), c->long_flag.as<u32>(), tot_at(c, TOT_VOTE_READS),
                        c->vote_list.as<u32>(), mid_flag);
     prof_end(c);
     if (use_mid) {
         prof_begin(c, "k_vote_mid");
-        rc = scan_u32(c, mid_flag, n, c->long_off.as<u64>(), 11, c->sd_list_c.as<u32>());
+        rc = scan_u32(c, mid_flag, n, c->long_off.as<u64>(), TOT_MID, c->sd_list_c.as<u32>());
         if (rc) return rc;
-        hipLaunchKernelGGL(k_vote_mid, dim3(nblk(n, 64)), dim3(64), 0, c->stream, c->ix, gm, st, c->totals.as<u64>() + 11, c->sd_list_c.as<u32>(),
+        hipLaunchKernelGGL(k_vote_mid, dim3(nblk(n, 64)), dim3(64), 0, c->stream, c->ix, gm, st, tot_at(c, TOT_MID), c->sd_list_c.as<u32>(),
                            c->cand.as<u64>(), c->votes.as<bmbs_vote>(), c->slot_read.as<u32>(), c->counters.as<unsigned long long>());
         prof_end(c);
     }
     // reads with more than 16 candidates (repeats): one block per read
     prof_begin(c, "k_vote_long");
-    rc = scan_u32(c, c->long_flag.as<u32>(), n, c->long_off.as<u64>(), 9, c->long_list.as<u32>());
+    rc = scan_u32(c, c->long_flag.as<u32>(), n, c->long_off.as<u64>(), TOT_LONG, c->long_list.as<u32>());
     if (rc) return rc;
-    // the wave form (lists of up to 256 candidates) walks the list and hands the longer ones to a list of their own (slot 13)
+    // the wave form (lists of up to 256 candidates) walks the list and hands the longer ones to a list of their own (TOT_BIG)
     ENS(c, c->big_list, n * 4 + 64);
-    unsigned long long* big_count = c->totals.as<unsigned long long>() + 13;
+    unsigned long long* big_count = c->totals.as<unsigned long long>() + TOT_BIG;
     HIPCHK(c, hipMemsetAsync(big_count, 0, 8, c->stream));
-    hipLaunchKernelGGL((k_vote_long<VM_CAP, VM_BLOCK, VOTE_REG>), dim3(32768), dim3(VM_BLOCK), 0, c->stream, c->ix, gm, st, c->totals.as<u64>() + 9,
+    hipLaunchKernelGGL((k_vote_long<VM_CAP, VM_BLOCK, VOTE_REG>), dim3(32768), dim3(VM_BLOCK), 0, c->stream, c->ix, gm, st, tot_at(c, TOT_LONG),
                        c->long_list.as<u32>(), c->cand.as<u64>(), c->votes.as<bmbs_vote>(), c->slot_read.as<u32>(), c->big_list.as<u32>(), big_count, c->counters.as<unsigned long long>());
     prof_end(c);
     prof_begin(c, "k_vote_big");
     // the handed-over lists in two size classes (as k_vote_pe_long): the <= 1024-key form needs 14 KB of LDS instead of 57 KB, so five
     // times as many reads are in flight -- the vote order (std::sort's permutation, one partition pass after the other) is a
     // chain of barriers, not work
-    hipLaunchKernelGGL((k_vote_long<1024, 128, VM_CAP>), dim3(8192), dim3(128), 0, c->stream, c->ix, gm, st, c->totals.as<u64>() + 13,
+    hipLaunchKernelGGL((k_vote_long<1024, 128, VM_CAP>), dim3(8192), dim3(128), 0, c->stream, c->ix, gm, st, tot_at(c, TOT_BIG),
                        c->big_list.as<u32>(), c->cand.as<u64>(), c->votes.as<bmbs_vote>(), c->slot_read.as<u32>(), (u32*)nullptr, (unsigned long long*)nullptr, c->counters.as<unsigned long long>());
-    hipLaunchKernelGGL((k_vote_long<2048, 256, 1024>), dim3(4096), dim3(256), 0, c->stream, c->ix, gm, st, c->totals.as<u64>() + 13,
+    hipLaunchKernelGGL((k_vote_long<2048, 256, 1024>), dim3(4096), dim3(256), 0, c->stream, c->ix, gm, st, tot_at(c, TOT_BIG),
                        c->big_list.as<u32>(), c->cand.as<u64>(), c->votes.as<bmbs_vote>(), c->slot_read.as<u32>(), (u32*)nullptr, (unsigned long long*)nullptr, c->counters.as<unsigned long long>());
-    hipLaunchKernelGGL((k_vote_long<VL_CAP, VL_BLOCK, 2048>), dim3(2048), dim3(VL_BLOCK), 0, c->stream, c->ix, gm, st, c->totals.as<u64>() + 13,
+    hipLaunchKernelGGL((k_vote_long<VL_CAP, VL_BLOCK, 2048>), dim3(2048), dim3(VL_BLOCK), 0, c->stream, c->ix, gm, st, tot_at(c, TOT_BIG),
                        c->big_list.as<u32>(), c->cand.as<u64>(), c->votes.as<bmbs_vote>(), c->slot_read.as<u32>(), (u32*)nullptr, (unsigned long long*)nullptr, c->counters.as<unsigned long long>());
     prof_end(c);
     return BMBS_OK;
@@ -679,17 +679,17 @@ Lane* lane_create(int device_id, const bmbs_params& prm, const Knobs& kn, bool f
     }
     const size_t shard_bytes = BMBS_SHARDS * BMBS_SHARD_WORDS * 8;
     if (ensure(c, c->pen_lut, sizeof(lut)) || ensure(c, c->stats, shard_bytes) || ensure(c, c->call_stats, shard_bytes) || ensure(c, c->counters, shard_bytes) ||
-        ensure(c, c->totals, 32 * 8) || ensure(c, c->flags, BMBS_FLAG_WORDS * 4) || ensure(c, c->tx_info, 64) ||
-        hipHostMalloc((void**)&c->h_info, 128, hipHostMallocPortable) != hipSuccess ||
-        hipHostMalloc((void**)&c->h_tot, 8 * 20 * 8, hipHostMallocPortable) != hipSuccess) { lane_destroy(c); return nullptr; }
-    memset(c->h_tot, 0, 8 * 20 * 8);
+        ensure(c, c->totals, TOT_WORDS * sizeof(u64)) || ensure(c, c->flags, BMBS_FLAG_WORDS * sizeof(u32)) || ensure(c, c->tx_info, TXI_WORDS * sizeof(u32)) ||
+        hipHostMalloc((void**)&c->h_info, sizeof(HostInfo), hipHostMallocPortable) != hipSuccess ||
+        hipHostMalloc((void**)&c->h_tot, BMBS_SLOTS * sizeof(CallWords), hipHostMallocPortable) != hipSuccess) { lane_destroy(c); return nullptr; }
+    memset(c->h_tot, 0, BMBS_SLOTS * sizeof(CallWords));
     (void)hipMemcpy(c->pen_lut.p, lut, sizeof(lut), hipMemcpyHostToDevice);
     (void)hipMemset(c->stats.p, 0, shard_bytes);
     (void)hipMemset(c->call_stats.p, 0, shard_bytes);
     (void)hipMemset(c->counters.p, 0, shard_bytes);
     textpath_device_init(c);
-    (void)hipMemset(c->totals.p, 0, 32 * 8);
-    (void)hipMemset(c->flags.p, 0, BMBS_FLAG_WORDS * 4);
+    (void)hipMemset(c->totals.p, 0, TOT_WORDS * sizeof(u64));
+    (void)hipMemset(c->flags.p, 0, BMBS_FLAG_WORDS * sizeof(u32));
     // diagnostic: per-wave timeline of the kernels that call wavelog_begin/_end (one context at a time; tools/wavelog.py)
     if (first)
     if (const char* wl = getenv("BMBS_WAVELOG")) {
@@ -948,21 +948,19 @@ int call_begin(Lane* c, int slot)
 {
     c->cur_slot = slot; c->prof_used[slot] = 0;
     HIPCHK(c, hipMemsetAsync(c->counters.p, 0, BMBS_SHARDS * BMBS_SHARD_WORDS * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->flags.p, 0, BMBS_FLAG_WORDS * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->totals.p, 0, 16 * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->flags.p, 0, BMBS_FLAG_WORDS * sizeof(u32), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->totals.p, 0, TOT_CALL_WORDS * sizeof(u64), c->stream));
     return BMBS_OK;
 }
-#define BMBS_SLOTS 8                // calls a lane may have in flight: one set of page-locked words each
-#define BMBS_SLOT_WORDS 20          // 16 totals + the flag words
 int call_end(Lane* c, int slot)
 {
-    u64* h = c->h_tot + (size_t)slot * BMBS_SLOT_WORDS;
+    CallWords* h = c->h_tot + slot;
     const int words = BMBS_SHARDS * BMBS_SHARD_WORDS;
     hipLaunchKernelGGL(k_stats_commit, dim3(nblk(words, 256)), dim3(256), 0, c->stream, c->flags.as<u32>(), c->call_stats.as<unsigned long long>(),
                        c->stats.as<unsigned long long>(), words);
-    hipLaunchKernelGGL(k_call_chain_counts, dim3(1), dim3(64), 0, c->stream, c->counters.as<unsigned long long>(), c->totals.as<u64>());
-    HIPCHK(c, hipMemcpyAsync(h, c->totals.p, 16 * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h + 16, c->flags.p, BMBS_FLAG_WORDS * 4, hipMemcpyDeviceToHost, c->stream));
+    hipLaunchKernelGGL(k_call_chain_counts, dim3(1), dim3(64), 0, c->stream, c->counters.as<unsigned long long>(), c->totals.as<u64>());      // (the array: TOT_CHAIN_*)
+    HIPCHK(c, hipMemcpyAsync(h->tot, c->totals.p, sizeof h->tot, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h->flags, c->flags.p, sizeof h->flags, hipMemcpyDeviceToHost, c->stream));
     return BMBS_OK;
 }
 
@@ -1034,21 +1032,21 @@ int align_jobs(Lane* c, const Pending& P, const ReadGeom& gm, const ReadState& s
                u32 rev_from, int max_ops)
 {
     prof_begin(c, "scan_jobs");
-    int rc = scan_u32(c, st.job_flag, reads, st.job_off, 1);
+    int rc = scan_u32(c, st.job_flag, reads, st.job_off, TOT_JOBS);
     if (rc) return rc;
     prof_end(c);
     u64 n_jobs = reads, sw_bound = ~0ull;
     const u64* n_jobs_dev = nullptr;
     if (P.exact) {
-        HIPCHK(c, hipMemcpyAsync(&n_jobs, c->totals.as<u64>() + 1, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&n_jobs, tot_at(c, TOT_JOBS), sizeof n_jobs, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if ((u64)P.cigar_cap < n_jobs * (u64)max_ops) { c->err = "cigar pool too small (it takes bmbs_max_cigar_ops() slots per read)"; return BMBS_ENOMEM; }
     } else {
-        n_jobs_dev = c->totals.as<u64>() + 1;
+        n_jobs_dev = tot_at(c, TOT_JOBS);
         sw_bound = cap_from(c->lr_sw, reads, c->kn.cap_scale < 1.0 ? 64 : 16384, c->kn.cap_scale);
         if ((u64)P.cigar_cap < reads * (u64)max_ops) {
             hipLaunchKernelGGL(k_guard_jobs, dim3(nblk(reads, 256)), dim3(256), 0, c->stream, n_jobs_dev, (u64)max_ops, (u64)P.cigar_cap, c->flags.as<u32>(), (long)reads, st.job_flag);
-            hipLaunchKernelGGL(k_guard_done, dim3(1), dim3(1), 0, c->stream, c->totals.as<u64>() + 1, c->flags.as<u32>(), BMBS_FLAG_CIGAR);
+            hipLaunchKernelGGL(k_guard_done, dim3(1), dim3(1), 0, c->stream, tot_at(c, TOT_JOBS), c->flags.as<u32>(), BMBS_FLAG_CIGAR);
         }
     }
     c->last_n_jobs = n_jobs;
@@ -1076,15 +1074,15 @@ int se_filter_reduce(Lane* c, const ReadGeom& gm, const ReadState& st, const cha
         ENS(c, c->votes_dense, t1 * sizeof(bmbs_vote)); ENS(c, c->dense_read, t1 * 4);
     }
     prof_begin(c, "vote_compact");
-    int rc = scan_u32(c, st.n_votes, n, c->vote_off.as<u64>(), 5);
+    int rc = scan_u32(c, st.n_votes, n, c->vote_off.as<u64>(), TOT_VOTES);
     if (rc) return rc;
     if (tot)
-        hipLaunchKernelGGL(k_vote_compact, dim3(nblk(tot, 256)), dim3(256), 0, c->stream, tot, exact ? (const u64*)nullptr : c->totals.as<u64>(), st,
+        hipLaunchKernelGGL(k_vote_compact, dim3(nblk(tot, 256)), dim3(256), 0, c->stream, tot, exact ? (const u64*)nullptr : tot_at(c, TOT_CAND), st,
                            c->vote_off.as<u64>(), c->slot_read.as<u32>(), c->votes.as<bmbs_vote>(), c->votes_dense.as<bmbs_vote>(), c->dense_read.as<u32>());
     prof_end(c);
     if (tot) {
         prof_begin(c, "k_filter");
-        hipLaunchKernelGGL(k_filter, dim3(nblk(tot, 256)), dim3(256), 0, c->stream, c->ix, d_seq, packed_rows(c, gm), gm, stride, c->totals.as<u64>() + 5,
+        hipLaunchKernelGGL(k_filter, dim3(nblk(tot, 256)), dim3(256), 0, c->stream, c->ix, d_seq, packed_rows(c, gm), gm, stride, tot_at(c, TOT_VOTES),
                            c->dense_read.as<u32>(), c->votes_dense.as<bmbs_vote>(), c->ferr.as<u32>(), c->fend.as<int>(), c->counters.as<unsigned long long>());
         prof_end(c);
     }
@@ -1093,7 +1091,7 @@ int se_filter_reduce(Lane* c, const ReadGeom& gm, const ReadState& st, const cha
     HIPCHK(c, hipMemsetAsync(st.job_flag, 0, n * 4, c->stream));
     HIPCHK(c, hipMemsetAsync(st.red_status, 0, n, c->stream));
     hipLaunchKernelGGL(k_reduce, dim3(nblk(n, 256)), dim3(256), 0, c->stream, (long)n, c->prm.ambiguous_out, st, c->vote_off.as<u64>(),
-                       c->votes_dense.as<bmbs_vote>(), c->ferr.as<u32>(), c->fend.as<int>(), c->totals.as<u64>() + 10, c->vote_list.as<u32>());
+                       c->votes_dense.as<bmbs_vote>(), c->ferr.as<u32>(), c->fend.as<int>(), tot_at(c, TOT_VOTE_READS), c->vote_list.as<u32>());
     prof_end(c);
     return BMBS_OK;
 }
@@ -1205,7 +1203,7 @@ int PeCall::seed()
     int rc = launch_seeding(c, seq_all, gm, stride, n2, 1, prepacked);
     if (rc) return rc;
     prof_begin(c, "scan_cand");
-    rc = scan_u32(c, st.n_cand, n2, st.cand_off, 0);
+    rc = scan_u32(c, st.n_cand, n2, st.cand_off, TOT_CAND);
     if (rc) return rc;
     prof_end(c);
     rc = cand_total(c, st, n2, exact, &tot);
@@ -1240,32 +1238,32 @@ int PeCall::votes()
     prof_end(c);
     if (use_mid) {
         prof_begin(c, "k_vote_pe_mid");
-        int rc = scan_u32(c, mid_flag, n2, c->long_off.as<u64>(), 11, c->pe_mid_list.as<u32>());
+        int rc = scan_u32(c, mid_flag, n2, c->long_off.as<u64>(), TOT_MID, c->pe_mid_list.as<u32>());
         if (rc) return rc;
-        hipLaunchKernelGGL(k_vote_pe_mid, dim3(nblk(n2, 64)), dim3(64), 0, c->stream, c->ix, gm, st, ps, c->totals.as<u64>() + 11, c->pe_mid_list.as<u32>(), A, cnt);
+        hipLaunchKernelGGL(k_vote_pe_mid, dim3(nblk(n2, 64)), dim3(64), 0, c->stream, c->ix, gm, st, ps, tot_at(c, TOT_MID), c->pe_mid_list.as<u32>(), A, cnt);
         prof_end(c);
     }
     prof_begin(c, "k_vote_pe_long");
     // fast mode: located sites without a partner on the mate's finished list are dropped before the sort (k_pe_fast.hip; --sensitive
     // uses the lists differently, Schema.cpp:19953-21459).  BMBS_PREFILTER=0: off (A/B runs, tests)
     const int prefilter = (!c->prm.sensitive && c->kn.prefilter) ? 1 : 0;
-    int rc = scan_u32(c, c->long_flag.as<u32>(), n2, c->long_off.as<u64>(), 9, c->long_list.as<u32>());
+    int rc = scan_u32(c, c->long_flag.as<u32>(), n2, c->long_off.as<u64>(), TOT_LONG, c->long_list.as<u32>());
     if (rc) return rc;
     ENS(c, c->big_list, n2 * 4 + 64);
-    unsigned long long* big_count = c->totals.as<unsigned long long>() + 13;
+    unsigned long long* big_count = c->totals.as<unsigned long long>() + TOT_BIG;
     HIPCHK(c, hipMemsetAsync(big_count, 0, 8, c->stream));
     hipLaunchKernelGGL((k_vote_pe_long<VM_CAP, VM_BLOCK, VOTE_REG>), dim3(32768), dim3(VM_BLOCK), 0, c->stream, c->ix, gm, st, ps,
-                       c->totals.as<u64>() + 9, c->long_list.as<u32>(), A, c->big_list.as<u32>(), big_count, c->cand.as<u64>(), cnt, (long)n, pi, prefilter, c->long_flag.as<u32>());
+                       tot_at(c, TOT_LONG), c->long_list.as<u32>(), A, c->big_list.as<u32>(), big_count, c->cand.as<u64>(), cnt, (long)n, pi, prefilter, c->long_flag.as<u32>());
     prof_end(c);
     prof_begin(c, "k_vote_pe_big");
     // the handed-over lists in two size classes: up to 1024 candidates (10 KB of LDS per block: twice the blocks per CU of the
     // 4096-key form; on the GRCh38-like genome 88 % of the handed-over lists), and the rest
     hipLaunchKernelGGL((k_vote_pe_long<1024, 128, VM_CAP>), dim3(8192), dim3(128), 0, c->stream, c->ix, gm, st, ps,
-                       c->totals.as<u64>() + 13, c->big_list.as<u32>(), A, (u32*)nullptr, (unsigned long long*)nullptr, c->cand.as<u64>(), cnt, (long)n, pi, prefilter, c->long_flag.as<u32>());
+                       tot_at(c, TOT_BIG), c->big_list.as<u32>(), A, (u32*)nullptr, (unsigned long long*)nullptr, c->cand.as<u64>(), cnt, (long)n, pi, prefilter, c->long_flag.as<u32>());
     hipLaunchKernelGGL((k_vote_pe_long<2048, 256, 1024>), dim3(4096), dim3(256), 0, c->stream, c->ix, gm, st, ps,
-                       c->totals.as<u64>() + 13, c->big_list.as<u32>(), A, (u32*)nullptr, (unsigned long long*)nullptr, c->cand.as<u64>(), cnt, (long)n, pi, prefilter, c->long_flag.as<u32>());
+                       tot_at(c, TOT_BIG), c->big_list.as<u32>(), A, (u32*)nullptr, (unsigned long long*)nullptr, c->cand.as<u64>(), cnt, (long)n, pi, prefilter, c->long_flag.as<u32>());
     hipLaunchKernelGGL((k_vote_pe_long<VL_CAP, VL_BLOCK, 2048>), dim3(2048), dim3(VL_BLOCK), 0, c->stream, c->ix, gm, st, ps,
-                       c->totals.as<u64>() + 13, c->big_list.as<u32>(), A, (u32*)nullptr, (unsigned long long*)nullptr, c->cand.as<u64>(), cnt, (long)n, pi, prefilter, c->long_flag.as<u32>());
+                       tot_at(c, TOT_BIG), c->big_list.as<u32>(), A, (u32*)nullptr, (unsigned long long*)nullptr, c->cand.as<u64>(), cnt, (long)n, pi, prefilter, c->long_flag.as<u32>());
     prof_end(c);
     return BMBS_OK;
 }
@@ -1279,12 +1277,12 @@ int PeCall::verify_round(int round, u64 cap, const char* name_f, const char* nam
         u32* wcnt = c->sd_flag_c.as<u32>();
         u64* woff = c->sd_off_c.as<u64>();
         hipLaunchKernelGGL(k_pe_count, dim3(nblk(n2, 256)), dim3(256), 0, c->stream, (long)n, (long)n2, round, ps, wcnt);
-        int rc = scan_u32(c, wcnt, n2, woff, 6);
+        int rc = scan_u32(c, wcnt, n2, woff, TOT_PE_WORK);
         if (rc) return rc;
         hipLaunchKernelGGL(k_pe_worklist, dim3(nblk(n2, 256)), dim3(256), 0, c->stream, (long)n2, wcnt, woff, c->dense_read.as<u32>(),
                            c->ferr.as<u32>());
         hipLaunchKernelGGL(k_filter_pe, dim3(nblk(cap, 256)), dim3(256), 0, c->stream, c->ix, seq_all, packed_rows(c, gm), gm, stride, st, ps, A, B,
-                           c->totals.as<u64>() + 6, c->dense_read.as<u32>(), c->ferr.as<u32>(), c->counters.as<unsigned long long>());
+                           tot_at(c, TOT_PE_WORK), c->dense_read.as<u32>(), c->ferr.as<u32>(), c->counters.as<unsigned long long>());
         prof_end(c);
     }
     prof_begin(c, name_c);
@@ -1305,9 +1303,9 @@ int PeCall::verify_fast()
     hipLaunchKernelGGL(k_pe_filter_pairs, dim3(nblk(n, 64)), dim3(64), 0, c->stream, (long)n, gm, pi, st, ps, A, B, pef_flag,
                        c->counters.as<unsigned long long>());
     if (pef_flag) {
-        int rc = scan_u32(c, pef_flag, n, c->long_off.as<u64>(), 12, c->long_list.as<u32>());
+        int rc = scan_u32(c, pef_flag, n, c->long_off.as<u64>(), TOT_PEF_LONG, c->long_list.as<u32>());
         if (rc) return rc;
-        hipLaunchKernelGGL(k_pe_filter_pairs_long, dim3((unsigned)std::min<u64>(n, 65536)), dim3(64), 0, c->stream, (long)n, gm, pi, st, ps, c->totals.as<u64>() + 12,
+        hipLaunchKernelGGL(k_pe_filter_pairs_long, dim3((unsigned)std::min<u64>(n, 65536)), dim3(64), 0, c->stream, (long)n, gm, pi, st, ps, tot_at(c, TOT_PEF_LONG),
                            c->long_list.as<u32>(), A, B);
     }
     prof_end(c);
@@ -1337,9 +1335,9 @@ int PeCall::verify_sensitive()
     u32* rflag = c->pe_rflag.as<u32>();
     u32* rlist = c->pe_rlist.as<u32>();
     u32* rcnt = c->pe_rcnt.as<u32>();
-    u64* n_reseed = c->totals.as<u64>() + 7;
+    u64* n_reseed = tot_at(c, TOT_RESEED);
     hipLaunchKernelGGL(k_pes_reseed_flag, dim3(nblk(n, 256)), dim3(256), 0, c->stream, (long)n, ps, rflag);
-    rc = scan_u32(c, rflag, n, c->pe_rscan.as<u64>(), 7, rlist);
+    rc = scan_u32(c, rflag, n, c->pe_rscan.as<u64>(), TOT_RESEED, rlist);
     if (rc) return rc;
     HIPCHK(c, hipMemsetAsync(rcnt, 0, n * 4, c->stream));
     {
@@ -1348,18 +1346,18 @@ int PeCall::verify_sensitive()
         hipLaunchKernelGGL((kg ? k_pes_reseed<true, true> : prs.base ? k_pes_reseed<true> : k_pes_reseed<false>), dim3(nblk(n, 64)), dim3(64), 0, c->stream, c->ix, seq_all, prs, gm, stride,
                            (long)n, n_reseed, rlist, st, ps, rcnt, cnt);
     }
-    rc = scan_u32(c, rcnt, n, c->pe_ritem_off.as<u64>(), 8);
+    rc = scan_u32(c, rcnt, n, c->pe_ritem_off.as<u64>(), TOT_RCAND);
     if (rc) return rc;
     prof_end(c);
-    u64 rt[2] = {0, 0};          // pairs to re-seed, their candidates: counts (exact) or capacities with a guard
+    u64 rt[2] = {0, 0};          // pairs to re-seed, their candidates (TOT_RESEED, TOT_RCAND): counts (exact) or capacities with a guard
     if (exact) {
-        HIPCHK(c, hipMemcpyAsync(rt, c->totals.as<u64>() + 7, 16, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(rt, tot_at(c, TOT_RESEED), sizeof rt, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     } else {
         rt[0] = n; rt[1] = cap_from(c->lr_rcand, n2, c->kn.cap_scale < 1.0 ? 64 : 65536, c->kn.cap_scale);
-        hipLaunchKernelGGL(k_guard_rcand, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->totals.as<u64>() + 8, rt[1], c->flags.as<u32>(), (long)n, rcnt,
+        hipLaunchKernelGGL(k_guard_rcand, dim3(nblk(n, 256)), dim3(256), 0, c->stream, tot_at(c, TOT_RCAND), rt[1], c->flags.as<u32>(), (long)n, rcnt,
                            c->pe_ritem_off.as<u64>());
-        hipLaunchKernelGGL(k_guard_done, dim3(1), dim3(1), 0, c->stream, c->totals.as<u64>() + 8, c->flags.as<u32>(), BMBS_FLAG_RCAND);
+        hipLaunchKernelGGL(k_guard_done, dim3(1), dim3(1), 0, c->stream, tot_at(c, TOT_RCAND), c->flags.as<u32>(), BMBS_FLAG_RCAND);
     }
     c->last_reseeded = rt[0]; c->last_reseed_cand = rt[1];
     if (!rt[0]) return BMBS_OK;
@@ -1368,19 +1366,19 @@ int PeCall::verify_sensitive()
     ENS(c, c->dense_read, rtot * 4); ENS(c, c->ferr, rtot * 4);
     ps.R = c->pe_R.as<PeCand>();
     prof_begin(c, "k_pes_vote");
-    // mates with more than PESV_LONG candidates are flagged, listed (slot 14) and sorted by a block each
+    // mates with more than PESV_LONG candidates are flagged, listed (TOT_PESV_LONG) and sorted by a block each
     u32* pv_flag = c->long_flag.as<u32>();                                  // n2 words: free again after the vote stage
     hipLaunchKernelGGL(k_pes_vote, dim3(nblk(rt[0], 64)), dim3(64), 0, c->stream, c->ix, (long)n, gm, pi, n_reseed, rlist,
                        c->pe_ritem_off.as<u64>(), st, ps, c->pe_rcand.as<u64>(), A, B, pv_flag, cnt);
-    rc = scan_u32(c, pv_flag, rt[0], c->long_off.as<u64>(), 14, c->long_list.as<u32>(), 0, n_reseed);
+    rc = scan_u32(c, pv_flag, rt[0], c->long_off.as<u64>(), TOT_PESV_LONG, c->long_list.as<u32>(), 0, n_reseed);
     if (rc) return rc;
-    hipLaunchKernelGGL((k_pes_vote_long<1024, 128, PESV_LONG>), dim3(8192), dim3(128), 0, c->stream, c->ix, (long)n, gm, pi, c->totals.as<u64>() + 14,
+    hipLaunchKernelGGL((k_pes_vote_long<1024, 128, PESV_LONG>), dim3(8192), dim3(128), 0, c->stream, c->ix, (long)n, gm, pi, tot_at(c, TOT_PESV_LONG),
                        c->long_list.as<u32>(), rlist, c->pe_ritem_off.as<u64>(), st, ps, c->pe_rcand.as<u64>(), A, B);
     // (three size classes, as the vote kernels: a re-seeded mate of 1 025 .. 2 048 candidates in the 4 096-key form held 41 KB of
     // LDS -- three lists per CU; r6)
-    hipLaunchKernelGGL((k_pes_vote_long<2048, 256, 1024>), dim3(4096), dim3(256), 0, c->stream, c->ix, (long)n, gm, pi, c->totals.as<u64>() + 14,
+    hipLaunchKernelGGL((k_pes_vote_long<2048, 256, 1024>), dim3(4096), dim3(256), 0, c->stream, c->ix, (long)n, gm, pi, tot_at(c, TOT_PESV_LONG),
                        c->long_list.as<u32>(), rlist, c->pe_ritem_off.as<u64>(), st, ps, c->pe_rcand.as<u64>(), A, B);
-    hipLaunchKernelGGL((k_pes_vote_long<VL_CAP, VL_BLOCK, 2048>), dim3(2048), dim3(VL_BLOCK), 0, c->stream, c->ix, (long)n, gm, pi, c->totals.as<u64>() + 14,
+    hipLaunchKernelGGL((k_pes_vote_long<VL_CAP, VL_BLOCK, 2048>), dim3(2048), dim3(VL_BLOCK), 0, c->stream, c->ix, (long)n, gm, pi, tot_at(c, TOT_PESV_LONG),
                        c->long_list.as<u32>(), rlist, c->pe_ritem_off.as<u64>(), st, ps, c->pe_rcand.as<u64>(), A, B);
     prof_end(c);
     return verify_round(3, rt[1], "k_filter_pe_r3", "k_pe_compact_r3");
@@ -1434,19 +1432,19 @@ int lane_settle(Lane* c)
         Pending P = c->inflight.front();
         c->inflight.pop_front();
         for (int attempt = 0; attempt < 2; attempt++) {
-            const u64* t = c->h_tot + (size_t)P.slot * BMBS_SLOT_WORDS;
-            const u32* f = reinterpret_cast<const u32*>(t + 16);
+            const u64* t = c->h_tot[P.slot].tot;
+            const u32* f = c->h_tot[P.slot].flags;
             if (f[BMBS_FLAG_CIGAR]) { c->err = "cigar pool too small (it takes bmbs_max_cigar_ops() slots per read)"; rc_all = BMBS_ENOMEM; break; }
             if (!(f[BMBS_FLAG_CAND] | f[BMBS_FLAG_SW] | f[BMBS_FLAG_RCAND])) {
                 const double nr = (double)(P.pe ? 2 * P.n : P.n);
                 if (nr > 0) {
-                    c->lr_cand = std::max(c->lr_cand, std::max(1e-9, (double)t[0] / nr));
-                    c->lr_sw = std::max(c->lr_sw, (double)t[2] / nr);
-                    c->lr_rcand = std::max(c->lr_rcand, (double)t[8] / nr);
-                    c->lr_long = ((double)t[9] + (double)t[11]) / nr;             // reads whose candidate lists went to the mid / long kernels
-                    if (t[14]) { c->lr_chain = (double)t[15] / (double)t[14]; occ3_want(c, true); }      // (the table is built here, behind the call that showed the chains)
+                    c->lr_cand = std::max(c->lr_cand, std::max(1e-9, (double)t[TOT_CAND] / nr));
+                    c->lr_sw = std::max(c->lr_sw, (double)t[TOT_SW] / nr);
+                    c->lr_rcand = std::max(c->lr_rcand, (double)t[TOT_RCAND] / nr);
+                    c->lr_long = ((double)t[TOT_LONG] + (double)t[TOT_MID]) / nr;             // reads whose candidate lists went to the mid / long kernels
+                    if (t[TOT_CHAIN_LOOKUPS]) { c->lr_chain = (double)t[TOT_CHAIN_EXT] / (double)t[TOT_CHAIN_LOOKUPS]; occ3_want(c, true); }      // (the table is built here, behind the call that showed the chains)
                 }
-                c->last_total_cand = t[0]; c->last_n_jobs = t[1];
+                c->last_total_cand = t[TOT_CAND]; c->last_n_jobs = t[TOT_JOBS];
                 prof_collect(c, P.slot);
                 break;
             }

@@ -3,6 +3,7 @@
 #define BMBS_DEV_H
 #include <stdint.h>
 #include <hip/hip_runtime.h>
+#include "bmbs_words.h"          // the slots of the lanes' count and info words
 
 typedef uint64_t u64; typedef uint32_t u32; typedef uint16_t u16; typedef uint8_t u8;
 

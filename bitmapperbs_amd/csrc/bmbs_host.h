@@ -287,7 +287,7 @@ struct Lane {
     }
     DevBuf z_comp, z_off, z_text, z_err, z_nl, z_comp2, z_off2, z_err2;         // bmbs_inflate_bgzf; (…2: mate 2 of bmbs_text_open_bgzf)
     struct OpenText { bool valid = false, pe = false; u64 bytes1 = 0, bytes2 = 0; int64_t n = 0; } open_text;      // between bmbs_text_open_bgzf and bmbs_text_map_open
-    u32* h_info = nullptr;                              // page-locked: 8 info words + 4 totals of the text path
+    HostInfo* h_info = nullptr;                         // page-locked: what the text calls and the record stages read back (bmbs_words.h)
     int n_refs = 0, max_ref_len = 0;
     // paired-end workspace
     DevBuf sd_sp0, sd_hits0, sd_ml0, sd_tm, sd_seed_id, sd_clen, sd_first_ml, sd_flag_c, sd_flag_d, sd_off_c, sd_off_d, sd_list_c, sd_list_d;
@@ -297,8 +297,8 @@ struct Lane {
     DevBuf stats, call_stats, flags, counters, long_flag, long_off, long_list;     // long_*: reads whose candidate lists go to k_vote_long
     // HIP-event profile: one set of event pairs per call in flight (slot); lane_settle reads a settled call's set into `last`
     // (bmbs_profile_last) and adds it to `acc` (bmbs_profile_total: sums since the last reset, read without forcing a wait per call)
-    std::vector<Prof> profset[8];
-    int prof_used[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    std::vector<Prof> profset[BMBS_SLOTS];
+    int prof_used[BMBS_SLOTS] = {};
     int cur_slot = 0;
     struct ProfSum { const char* name; double ms; };
     std::vector<ProfSum> last, acc;
@@ -310,7 +310,7 @@ struct Lane {
     // ---- launches without host round trips: what the stages of earlier calls needed, per read (0: nothing known yet -> the
     // first call of a lane waits for its counts); the pinned words the device leaves its counts and guard flags in; the call in flight
     double lr_cand = 0, lr_sw = 0, lr_rcand = 0, lr_long = 0;
-    u64* h_tot = nullptr;                      // page-locked: per call in flight, totals[16] followed by the flag words (call_end)
+    CallWords* h_tot = nullptr;                // page-locked: BMBS_SLOTS of them, one per call in flight (call_end writes, lane_settle reads)
     std::deque<Pending> inflight;
     int next_slot = 0;
     u64 n_retries = 0;
@@ -344,7 +344,11 @@ void release(DevBuf& b);
 inline unsigned nblk(u64 n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
 void prof_begin(Lane* c, const char* name);
 void prof_end(Lane* c);
-int scan_u32(Lane* c, const u32* in, u64 n, u64* out, int slot, u32* list = nullptr, int nz = 0, const u64* n_dev = nullptr);
+// the lane's words by name (bmbs_words.h): a total, the two halves of tx_info
+inline u64* tot_at(Lane* c, Tot t) { return c->totals.as<u64>() + t; }
+inline u32* line_info(Lane* c) { return c->tx_info.as<u32>() + TXI_LINE; }
+inline u32* stage_info(Lane* c) { return c->tx_info.as<u32>() + TXI_STAGE; }
+int scan_u32(Lane* c, const u32* in, u64 n, u64* out, Tot slot, u32* list = nullptr, int nz = 0, const u64* n_dev = nullptr);
 int threshold_k(const bmbs_params& P, int L);
 int cigar_ops_bound(const bmbs_params& P, int L, int k);
 int lane_settle(Lane* c);

@@ -21,8 +21,14 @@
 #define DEVI __device__ __forceinline__
 
 #define SHARD(p) ((p) + (size_t)(blockIdx.x & (BMBS_SHARDS - 1)) * BMBS_SHARD_WORDS)
-// event counter words beyond the seeding ones (bmbs_counters_all): what the list kernels handled, for the per-kernel byte terms of the
-// bench line.  (-DBMBS_UTIL builds overload words 8..13 with lane-utilisation probes.)
+// event counter words (bmbs_counters_all).  The seeding ones (flush_counters, k_seed.hip; per-kernel copies from word 16 on):
+#define CNT_LOOKUPS    0      // 16-mer lookups          (k_call_chain_counts sums words CNT_LOOKUPS and CNT_EXT, which follow each other)
+#define CNT_EXT        1      // backward extensions
+#define CNT_SA         2      // suffix-array reads
+#define CNT_UNGAPPED   5      // un-gapped checks
+#define CNT_JUMP       8      // three-letter steps taken (each also counts three in CNT_EXT)
+// ... and beyond them what the list kernels handled, for the per-kernel byte terms of the bench line.  (-DBMBS_UTIL builds overload
+// words 8..13 with lane-utilisation probes.)
 #define CNT_CAND_MID   9      // candidates located by k_vote_mid / k_vote_pe_mid (lists of 17..32)
 #define CNT_CAND_LONG 10      // ... by the wave form of k_vote_long / k_vote_pe_long (33..256)
 #define CNT_CAND_BIG  11      // ... by their block forms (beyond 256)

@@ -39,8 +39,8 @@ static int records_check(Lane* c, const char* what, const char* records, uint64_
 }
 
 // checked entries -> r: the bytes (padded: the kernels read whole words) and the lengths go up under the device's upload lock, the bytes
-// in pieces (bmbs_textpath.hip: d2h_chunked), r.off = the exclusive scan of the lengths (scan slot `slot`); clip, if given, -> *clip_dst
-static int records_stage(Lane* c, RecIn& r, const char* records, u64 bytes, const uint32_t* len, u64 n, int slot, const uint32_t* clip = nullptr, DevBuf* clip_dst = nullptr)
+// in pieces (bmbs_textpath.hip: d2h_chunked), r.off = the exclusive scan of the lengths (its total: the word `slot`); clip, if given, -> *clip_dst
+static int records_stage(Lane* c, RecIn& r, const char* records, u64 bytes, const uint32_t* len, u64 n, Tot slot, const uint32_t* clip = nullptr, DevBuf* clip_dst = nullptr)
 {
     ENS(c, r.in, bytes + 256); ENS(c, r.len, n * 4 + 64); ENS(c, r.off, (n + 1) * 8 + 64);
     if (clip) ENS(c, *clip_dst, n * 4 + 64);
@@ -151,7 +151,7 @@ static int lane_bam_sort(Lane* c, const char* records, uint64_t bytes, const uin
     HIPCHK(c, hipSetDevice(c->dev));
     c->ends(Lane::SORT_KEYS);
     RecIn& r = c->sc.in;
-    int rc = records_stage(c, r, records, bytes, len, n, 24);
+    int rc = records_stage(c, r, records, bytes, len, n, TOT_SORT_IN);
     if (rc) return rc;
     if ((rc = bam_sort_device(c, r.in.as<char>(), r.off.as<u64>(), r.len.as<u32>(), n, bytes, false, nullptr))) return rc;
     if (rawout) {
@@ -160,7 +160,7 @@ static int lane_bam_sort(Lane* c, const char* records, uint64_t bytes, const uin
         return rc;
     }
     u64 ztotal = 0;
-    if ((rc = bgzf_deflate(c, c->bs_sorted.as<char>(), c->totals.as<u64>() + 23, bytes, &ztotal))) return rc;
+    if ((rc = bgzf_deflate(c, c->bs_sorted.as<char>(), tot_at(c, TOT_SORTED_BYTES), bytes, &ztotal))) return rc;
     if (out_bytes) *out_bytes = ztotal;
     if (ztotal > out_cap) { c->err = "bam sort: the output buffer is too small (out_bytes tells what is needed)"; return BMBS_ENOMEM; }
     if ((rc = bgzf_collect(c, bytes, ztotal))) return rc;
@@ -182,27 +182,27 @@ static int bai_compute(Lane* c)
     u64* const rb = A.get<u64>(); u32* const rw = A.get<u32>(); u32* const wc = A.get<u32>(); u64* const woff = A.get<u64>(); u32* const wave = A.get<u32>();
     u64* const hoff = A.get<u64>(); u32* const cnt = A.get<u32>(); u32* const has = A.get<u32>(); u32* const first = A.get<u32>(); u32* const last = A.get<u32>();
     u32* const rlist = A.get<u32>();
-    u32* const info = c->tx_info.as<u32>() + 8;
-    u64* const tot = c->totals.as<u64>();
-    HIPCHK(c, hipMemsetAsync(info, 0, 32, c->stream));
+    u32* const info = stage_info(c);
+    HostInfo* const hi = c->h_info;
+    HIPCHK(c, hipMemsetAsync(info, 0, TXI_HALF_WORDS * sizeof(u32), c->stream));
     HIPCHK(c, hipMemsetAsync(cnt, 0, (size_t)(reinterpret_cast<char*>(first) - reinterpret_cast<char*>(cnt)), c->stream));      // cnt and has: one behind the other
     const BaiVoff v = {c->bs_soff.as<u64>(), c->bam_off.as<u64>(), total, nb};
     hipLaunchKernelGGL(k_bai_records, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->bs_sorted.as<char>(), c->bs_soff.as<u64>(), (long)n, (u32)R, rb, rw, cnt, info);
     hipLaunchKernelGGL(k_bai_heads, dim3(nblk(n, 256)), dim3(256), 0, c->stream, rb, rw, (long)n, (u32)R, wave, wc, has, first, last);
-    int rc = scan_u32(c, wave, nw, hoff, 25);
+    int rc = scan_u32(c, wave, nw, hoff, TOT_BAI_HEADS);
     if (rc) return rc;
-    if ((rc = scan_u32(c, wc, n, woff, 26))) return rc;
-    if ((rc = scan_u32(c, has, R, nullptr, 27, rlist))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->h_info, info, 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 16, tot + 25, 24, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = scan_u32(c, wc, n, woff, TOT_BAI_WINS))) return rc;
+    if ((rc = scan_u32(c, has, R, nullptr, TOT_BAI_REFS, rlist))) return rc;
+    HIPCHK(c, hipMemcpyAsync(hi->stage, info, sizeof hi->stage, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hi->bai, tot_at(c, TOT_BAI_HEADS), sizeof hi->bai, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->h_info[1]) { c->err = "bam sort index: the read name and CIGAR of record " + std::to_string(~c->h_info[1]) + " (in sorted order) do not fit its length"; return BMBS_EINVAL; }
-    if (c->h_info[0]) {
-        c->err = "bam sort index: record " + std::to_string(~c->h_info[0]) + " (in sorted order) ends behind position 2^29: a BAI index cannot hold it (CSI is not written)";
+    if (hi->stage[1]) { c->err = "bam sort index: the read name and CIGAR of record " + std::to_string(~hi->stage[1]) + " (in sorted order) do not fit its length"; return BMBS_EINVAL; }
+    if (hi->stage[0]) {
+        c->err = "bam sort index: record " + std::to_string(~hi->stage[0]) + " (in sorted order) ends behind position 2^29: a BAI index cannot hold it (CSI is not written)";
         return BMBS_EINVAL;
     }
-    const u64 nnc = c->h_info[2];
-    const u64 m = reinterpret_cast<const u64*>(c->h_info + 16)[0], T = reinterpret_cast<const u64*>(c->h_info + 16)[1], n_ref = reinterpret_cast<const u64*>(c->h_info + 16)[2];
+    const u64 nnc = hi->stage[2];
+    const u64 m = hi->bai[0], T = hi->bai[1], n_ref = hi->bai[2];
     const u64 mr = m - (nnc ? 1 : 0);                    // (the first record without a reference only ends the last run)
     Carve B;
     if ((rc = B.make(c, c->bai_b, {(m + 1) * 4, m * 8, m * 8, m * 4, m * 4, m * 16, T * 8, T * 8, T * 4, T * 4, T * 4, T * 4}))) return rc;
@@ -226,14 +226,14 @@ static int bai_compute(Lane* c)
     if (T) {
         if ((rc = pair_sort(c, "bam sort index", wkey, wkey2, wval, wval2, T, (unsigned)(15 + ref_bits), nullptr, true))) return rc;      // (the chunk sort)
         hipLaunchKernelGGL(k_bai_win_flag, dim3(nblk(T, 256)), dim3(256), 0, c->stream, wkey2, (long)T, wflag);
-        if ((rc = scan_u32(c, wflag, T, nullptr, 28, wlist))) return rc;
-        hipLaunchKernelGGL(k_bai_win_out, dim3(nblk(T, 256)), dim3(256), 0, c->stream, wlist, tot + 28, wkey2, wval2, v, o_win);
-        HIPCHK(c, hipMemcpyAsync(c->h_info + 16, tot + 28, 8, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = scan_u32(c, wflag, T, nullptr, TOT_BAI_NWIN, wlist))) return rc;
+        hipLaunchKernelGGL(k_bai_win_out, dim3(nblk(T, 256)), dim3(256), 0, c->stream, wlist, tot_at(c, TOT_BAI_NWIN), wkey2, wval2, v, o_win);
+        HIPCHK(c, hipMemcpyAsync(&hi->bai_nwin, tot_at(c, TOT_BAI_NWIN), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     }
     if (n_ref) hipLaunchKernelGGL(k_bai_ref_out, dim3(nblk(n_ref, 256)), dim3(256), 0, c->stream, rlist, (long)n_ref, first, last, cnt, v, o_ref);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
-    if (T) n_win = reinterpret_cast<const u64*>(c->h_info + 16)[0];
+    if (T) n_win = hi->bai_nwin;
     s.bai_cnt[0] = (int64_t)mr; s.bai_cnt[1] = (int64_t)n_win; s.bai_cnt[2] = (int64_t)n_ref; s.bai_cnt[3] = (int64_t)nnc;
     s.bai_done = true;
     return BMBS_OK;
@@ -264,19 +264,20 @@ static int lane_bam_sort_index(Lane* c, bmbs_bai_chunk* chunk, int64_t chunk_cap
 static int dup_sig_device(Lane* c, const char* raw, const u64* off, const u32* len, bool paired, u64 n_tmpl)
 {
     ENS(c, c->dp_sig, n_tmpl * sizeof(bmbs_dup_sig) + 64);
-    u32* const info = c->tx_info.as<u32>() + 8;
-    HIPCHK(c, hipMemsetAsync(info, 0, 32, c->stream));
+    u32* const info = stage_info(c);
+    HIPCHK(c, hipMemsetAsync(info, 0, TXI_HALF_WORDS * sizeof(u32), c->stream));
     prof_begin(c, "k_dup_sig");
     hipLaunchKernelGGL(k_dup_sig, dim3(nblk(n_tmpl * DUP_GROUP, 256)), dim3(256), 0, c->stream, raw, off, len, paired ? 1 : 0, (long)n_tmpl, c->dp_sig.as<bmbs_dup_sig>(), info);
     prof_end(c);
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 8, info, 8, hipMemcpyDeviceToHost, c->stream));
+    const u32* const got = c->h_info->stage;
+    HIPCHK(c, hipMemcpyAsync(c->h_info->stage, info, 2 * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
-    if (c->h_info[8]) {
-        c->err = "dup sigs: the length given for record " + std::to_string(~c->h_info[8]) + " is not its block_size + 4 (or is below the 36 bytes every BAM record has)";
+    if (got[0]) {
+        c->err = "dup sigs: the length given for record " + std::to_string(~got[0]) + " is not its block_size + 4 (or is below the 36 bytes every BAM record has)";
         return BMBS_EINVAL;
     }
-    if (c->h_info[9]) { c->err = "dup sigs: the read name, CIGAR, sequence and qualities of record " + std::to_string(~c->h_info[9]) + " do not fit its length"; return BMBS_EINVAL; }
+    if (got[1]) { c->err = "dup sigs: the read name, CIGAR, sequence and qualities of record " + std::to_string(~got[1]) + " do not fit its length"; return BMBS_EINVAL; }
     return BMBS_OK;
 }
 
@@ -294,7 +295,7 @@ static int lane_bam_dup_sigs(Lane* c, const char* records, uint64_t bytes, const
     HIPCHK(c, hipSetDevice(c->dev));
     c->ends(Lane::DUP_SIGS);
     RecIn& r = c->dp_in;
-    int rc = records_stage(c, r, records, bytes, len, n, 29);
+    int rc = records_stage(c, r, records, bytes, len, n, TOT_RECS_IN);
     if (rc) return rc;
     if ((rc = dup_sig_device(c, r.in.as<char>(), r.off.as<u64>(), r.len.as<u32>(), paired != 0, nt))) return rc;
     HIPCHK(c, hipMemcpyAsync(sig, c->dp_sig.p, nt * sizeof(bmbs_dup_sig), hipMemcpyDeviceToHost, c->stream));
@@ -346,16 +347,16 @@ static int lane_dup_select(Lane* c, const bmbs_dup_sig* sig, int64_t n_in, uint8
     const bmbs_dup_sig* const ds = c->dp_sig.as<bmbs_dup_sig>();
     u64* const ka = c->dp_key.as<u64>(); u64* const kb = c->dp_key2.as<u64>();
     u32* const ia = c->dp_idx.as<u32>(); u32* const ib = c->dp_idx2.as<u32>();
-    u32* const info = c->tx_info.as<u32>() + 8;           // three 64-bit ORs and the count of duplicates
-    HIPCHK(c, hipMemsetAsync(info, 0, 32, c->stream));
+    u32* const info = stage_info(c);                      // three 64-bit ORs and the count of duplicates (TXI_DUP_COUNT)
+    HIPCHK(c, hipMemsetAsync(info, 0, TXI_HALF_WORDS * sizeof(u32), c->stream));
     hipLaunchKernelGGL(k_dup_bits, dim3(nblk(n, 256)), dim3(256), 0, c->stream, ds, (long)n, reinterpret_cast<unsigned long long*>(info));
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 8, info, 24, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_info->dup_bits, info, sizeof c->h_info->dup_bits, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     // each pass over the key bits that can be set only
     unsigned end_bit[3];
     size_t tmp_bytes = 0;
     for (int p = 0; p < 3; p++) {
-        u64 bits; memcpy(&bits, c->h_info + 8 + 2 * p, 8);
+        const u64 bits = c->h_info->dup_bits[p];
         end_bit[p] = 1;
         while (end_bit[p] < 64 && bits >> end_bit[p]) end_bit[p]++;
         size_t t = 0;
@@ -372,13 +373,13 @@ static int lane_dup_select(Lane* c, const bmbs_dup_sig* sig, int64_t n_in, uint8
     }
     prof_end(c);
     prof_begin(c, "k_dup_heads");
-    hipLaunchKernelGGL(k_dup_heads, dim3(nblk(n, 256)), dim3(256), 0, c->stream, ds, ib, (long)n, c->dp_dup.as<uint8_t>(), info + 6);
+    hipLaunchKernelGGL(k_dup_heads, dim3(nblk(n, 256)), dim3(256), 0, c->stream, ds, ib, (long)n, c->dp_dup.as<uint8_t>(), info + TXI_DUP_COUNT);
     prof_end(c);
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 14, info + 6, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&c->h_info->stage[TXI_DUP_COUNT], info + TXI_DUP_COUNT, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(dup, c->dp_dup.p, n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
-    if (n_dup) *n_dup = (int64_t)c->h_info[14];
+    if (n_dup) *n_dup = (int64_t)c->h_info->stage[TXI_DUP_COUNT];
     return BMBS_OK;
 }
 
@@ -400,13 +401,13 @@ static int meth_reduce(Lane* c, const MethEv& e, u64 n, int pos_bits, int key_bi
     prof_begin(c, "k_meth_heads");
     hipLaunchKernelGGL(k_meth_heads, dim3(nblk(n, 256)), dim3(256), 0, c->stream, e.kb, e.vb, (long)n, wave, m, u);
     prof_end(c);
-    if ((rc = scan_u32(c, wave, nw, hoff, 30))) return rc;
-    if ((rc = scan_u32(c, m, n, ms, 31))) return rc;
-    if ((rc = scan_u32(c, u, n, us, 31))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 28, c->totals.as<u64>() + 30, 8, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = scan_u32(c, wave, nw, hoff, TOT_METH_HEADS))) return rc;
+    if ((rc = scan_u32(c, m, n, ms, TOT_METH_M))) return rc;
+    if ((rc = scan_u32(c, u, n, us, TOT_METH_U))) return rc;
+    HIPCHK(c, hipMemcpyAsync(&c->h_info->meth_heads, tot_at(c, TOT_METH_HEADS), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     hipLaunchKernelGGL(k_meth_hpos, dim3(nblk(n, 256)), dim3(256), 0, c->stream, e.kb, (long)n, hoff, hpos);
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    const u64 nh = *reinterpret_cast<const u64*>(c->h_info + 28);
+    const u64 nh = c->h_info->meth_heads;
     if (nh > n) { c->err = "methyl: more run heads than entries"; return BMBS_ESTATE; }
     *n_out = nh;
     prof_begin(c, "k_meth_sites");
@@ -448,16 +449,16 @@ static int methyl_get_opts(Lane* c, const bmbs_methyl_params* par, const bmbs_me
 // a slice of records [start, *end) with at most `cap` events (a record with more is a slice of its own), events [*e0, *e1) of eoff
 static int meth_slice(Lane* c, const u64* eoff, u64 start, u64 n, u64 cap, u64* end, u64* e0, u64* e1)
 {
-    u32* const info = c->tx_info.as<u32>() + 8;
+    u32* const info = stage_info(c);
     hipLaunchKernelGGL(k_meth_cut, dim3(1), dim3(64), 0, c->stream, eoff, (long)start, (long)n, cap, reinterpret_cast<u64*>(info));
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 8, info, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 10, eoff + start, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&c->h_info->meth_cut, info, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&c->h_info->meth_eoff, eoff + start, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    *end = *reinterpret_cast<const u64*>(c->h_info + 8); *e0 = *reinterpret_cast<const u64*>(c->h_info + 10);
+    *end = c->h_info->meth_cut; *e0 = c->h_info->meth_eoff;
     if (*end <= start || *end > n) { c->err = "methyl: bad slice"; return BMBS_ESTATE; }
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 10, eoff + *end, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&c->h_info->meth_eoff, eoff + *end, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    *e1 = *reinterpret_cast<const u64*>(c->h_info + 10);
+    *e1 = c->h_info->meth_eoff;
     return BMBS_OK;
 }
 
@@ -481,8 +482,8 @@ static int methyl_device(Lane* c, const char* raw, const u64* off, const u32* le
     while (ref_bits < 24 && (u64)c->ix.n_chrom >> ref_bits) ref_bits++;
     par.pos_bits = pos_bits;
     ENS(c, c->mt_cnt, n * 4 + 64); ENS(c, c->mt_eoff, (n + 1) * 8 + 64);
-    u32* const info = c->tx_info.as<u32>() + 8;
-    HIPCHK(c, hipMemsetAsync(info, 0, 32, c->stream));
+    u32* const info = stage_info(c);
+    HIPCHK(c, hipMemsetAsync(info, 0, TXI_HALF_WORDS * sizeof(u32), c->stream));
     const unsigned grid = nblk(n * METH_GROUP, 256);
     // (without a trim: the kernels as they were before there was one)
     const auto k_count = trim ? k_meth_events<false, true> : k_meth_events<false, false>;
@@ -491,16 +492,17 @@ static int methyl_device(Lane* c, const char* raw, const u64* off, const u32* le
     hipLaunchKernelGGL(k_count, dim3(grid), dim3(256), 0, c->stream, c->ix.gen2p, c->ix.chrom_start, raw, off, len, clip, 0l,
                        (long)n, par, c->mt_cnt.as<u32>(), (const u64*)nullptr, (u64*)nullptr, (u64*)nullptr, info);
     prof_end(c);
-    int rc = scan_u32(c, c->mt_cnt.as<u32>(), n, c->mt_eoff.as<u64>(), 30);
+    int rc = scan_u32(c, c->mt_cnt.as<u32>(), n, c->mt_eoff.as<u64>(), TOT_METH_EVENTS);
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 8, info, 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 28, c->totals.as<u64>() + 30, 8, hipMemcpyDeviceToHost, c->stream));
+    const u32* const got = c->h_info->stage;
+    HIPCHK(c, hipMemcpyAsync(c->h_info->stage, info, 4 * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&c->h_info->meth_events, tot_at(c, TOT_METH_EVENTS), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
-    if (c->h_info[8]) { c->err = "methyl: the length given for record " + std::to_string(~c->h_info[8]) + " is not its block_size + 4 (or is below the 36 bytes every BAM record has)"; return BMBS_EINVAL; }
-    if (c->h_info[9]) { c->err = "methyl: the read name, CIGAR, sequence and qualities of record " + std::to_string(~c->h_info[9]) + " do not fit its length"; return BMBS_EINVAL; }
-    if (c->h_info[10]) { c->err = "methyl: the refID of record " + std::to_string(~c->h_info[10]) + " is beyond the " + std::to_string(c->ix.n_chrom) + " sequences of the index"; return BMBS_EINVAL; }
-    if (c->h_info[11]) { c->err = "methyl: the reference span of record " + std::to_string(~c->h_info[11]) + " runs off its sequence"; return BMBS_EINVAL; }
+    if (got[0]) { c->err = "methyl: the length given for record " + std::to_string(~got[0]) + " is not its block_size + 4 (or is below the 36 bytes every BAM record has)"; return BMBS_EINVAL; }
+    if (got[1]) { c->err = "methyl: the read name, CIGAR, sequence and qualities of record " + std::to_string(~got[1]) + " do not fit its length"; return BMBS_EINVAL; }
+    if (got[2]) { c->err = "methyl: the refID of record " + std::to_string(~got[2]) + " is beyond the " + std::to_string(c->ix.n_chrom) + " sequences of the index"; return BMBS_EINVAL; }
+    if (got[3]) { c->err = "methyl: the reference span of record " + std::to_string(~got[3]) + " runs off its sequence"; return BMBS_EINVAL; }
     if (mbias) {
         // 6 blocks per CU, each with its own tally in LDS (k_methyl.hip): the 6 waves per SIMD its registers allow, and 144 of the CU's 160
         // KiB of LDS -- the walk waits on memory most of its time, so resident waves are what it runs on.  The count pass above has
@@ -514,7 +516,7 @@ static int methyl_device(Lane* c, const char* raw, const u64* off, const u32* le
                            c->mt_mbias.as<unsigned long long>());
         prof_end(c);
     }
-    const u64 n_ev = *reinterpret_cast<const u64*>(c->h_info + 28);
+    const u64 n_ev = c->h_info->meth_events;
     const u64* const eoff = c->mt_eoff.as<u64>();
     u64 n_acc = 0, n_sites = 0;
     bool sliced = false;
@@ -531,7 +533,7 @@ static int methyl_device(Lane* c, const char* raw, const u64* off, const u32* le
             if ((rc = meth_events(c, ne, e))) return rc;
             prof_begin(c, "k_meth_emit");
             hipLaunchKernelGGL(k_emit, dim3(nblk((end - start) * METH_GROUP, 256)), dim3(256), 0, c->stream, c->ix.gen2p,
-                               c->ix.chrom_start, raw, off, len, clip, (long)start, (long)(end - start), par, (u32*)nullptr, eoff + start, e.ka, e.va, info + 4);
+                               c->ix.chrom_start, raw, off, len, clip, (long)start, (long)(end - start), par, (u32*)nullptr, eoff + start, e.ka, e.va, info + TXI_METH_EMIT);
             prof_end(c);
             u64 got = 0;
             if (!sliced) {
@@ -598,7 +600,7 @@ static int lane_bam_methyl(Lane* c, const char* records, uint64_t bytes, const u
     if (bytes && !records) { c->err = "methyl: NULL buffer"; return BMBS_EINVAL; }
     HIPCHK(c, hipSetDevice(c->dev));
     RecIn& r = c->mt_in;
-    if (int rc = records_stage(c, r, records, bytes, len, n, 29, clip, &c->mt_clip)) return rc;
+    if (int rc = records_stage(c, r, records, bytes, len, n, TOT_RECS_IN, clip, &c->mt_clip)) return rc;
     return methyl_device(c, r.in.as<char>(), r.off.as<u64>(), r.len.as<u32>(), clip ? c->mt_clip.as<u32>() : nullptr, n, par, opts, n_site);
 }
 
@@ -662,17 +664,17 @@ static int lane_text_sorted_clip(Lane* c, uint32_t* clip, int64_t cap, int64_t* 
     if (!nr) return BMBS_OK;
     HIPCHK(c, hipSetDevice(c->dev));
     ENS(c, c->mt_cl2, nr * 4 + 64);
-    u32* const info = c->tx_info.as<u32>() + 8;
-    HIPCHK(c, hipMemsetAsync(info, 0, 32, c->stream));
+    u32* const info = stage_info(c);
+    HIPCHK(c, hipMemsetAsync(info, 0, TXI_HALF_WORDS * sizeof(u32), c->stream));
     prof_begin(c, "k_meth_clip");
     hipLaunchKernelGGL(k_meth_clip, dim3(nblk(nr, 256)), dim3(256), 0, c->stream, c->bam_raw.as<char>(), c->sam_off.as<u64>(), c->sam_len.as<u32>(), c->bs_idx2.as<u32>(), (long)nr,
                        t.pe ? 1 : 0, c->mt_cl2.as<u32>(), info);
     prof_end(c);
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 8, info, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_info->stage, info, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(clip, c->mt_cl2.p, nr * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
-    if (c->h_info[8]) { c->err = "sorted clip: the overlap of record " + std::to_string(~c->h_info[8]) + " (in sorted order) with its mate does not fit 16 bits"; return BMBS_EINVAL; }
+    if (c->h_info->stage[0]) { c->err = "sorted clip: the overlap of record " + std::to_string(~c->h_info->stage[0]) + " (in sorted order) with its mate does not fit 16 bits"; return BMBS_EINVAL; }
     return BMBS_OK;
 }
 

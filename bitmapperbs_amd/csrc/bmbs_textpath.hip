@@ -138,7 +138,7 @@ static int lane_map_pe_fastq(Lane* c, const bmbs_fastq_view* mate1, const bmbs_f
 
 // ------------------------------------------------------------------------------------------------
 // FASTQ text in, SAM text out (bmbs_text.hip): the host reads and writes files, everything between is on the device
-// newline index of one text window (already on the device): positions of its first 4 * n_cap newlines; the totals slot 16 + f gets
+// newline index of one text window (already on the device): positions of its first 4 * n_cap newlines; the word TOT_LINES_1 (file 2: _2) gets
 // the number of lines found
 int text_index(Lane* c, DevBuf& dtext, u64 bytes, u64 n_cap, int f)
 {
@@ -146,7 +146,7 @@ int text_index(Lane* c, DevBuf& dtext, u64 bytes, u64 n_cap, int f)
     ENS(c, c->tx_tilecnt, tiles * 4 + 64); ENS(c, c->tx_tileoff, (tiles + 1) * 8 + 64);
     ENS(c, c->tx_nl[f], (4 * n_cap + 8) * 4);
     hipLaunchKernelGGL(k_fq_count, dim3((unsigned)tiles), dim3(FQ_TILE_THREADS), 0, c->stream, dtext.as<char>(), bytes, c->tx_tilecnt.as<u32>());
-    int rc = scan_u32(c, c->tx_tilecnt.as<u32>(), tiles, c->tx_tileoff.as<u64>(), 16 + f);
+    int rc = scan_u32(c, c->tx_tilecnt.as<u32>(), tiles, c->tx_tileoff.as<u64>(), tot_file(TOT_LINES_1, f));
     if (rc) return rc;
     hipLaunchKernelGGL(k_fq_lines, dim3((unsigned)tiles), dim3(FQ_TILE_THREADS), 0, c->stream, dtext.as<char>(), bytes, c->tx_tileoff.as<u64>(), 4 * n_cap, c->tx_nl[f].as<u32>());
     return BMBS_OK;
@@ -217,7 +217,7 @@ int lane_map_text(Lane* c, bool pe, const char* text1, u64 bytes1, const char* t
     static const bool trace = getenv("BMBS_TEXT_TRACE") != nullptr;       // diagnostic: host-side phase times of every text call
     auto wall = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; };
     const double t_start = wall();
-    HIPCHK(c, hipMemsetAsync(c->tx_info.p, 0, 64, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->tx_info.p, 0, TXI_WORDS * sizeof(u32), c->stream));
     int rc;
     ENS(c, c->fq_text1, bytes1 + 64);
     if (pe) ENS(c, c->fq_text2, bytes2 + 64);
@@ -291,11 +291,11 @@ int bgzf_deflate(Lane* c, const char* raw, const u64* total_ptr, u64 raw_total, 
     prof_begin(c, "k_bgzf_block");
     hipLaunchKernelGGL(k_bgzf_block, dim3((unsigned)nb), dim3(BGZF_THREADS), lds, c->stream, raw, total_ptr, c->bam_slots.as<char>(), c->bam_slot_len.as<u32>());
     prof_end(c);
-    const int rc = scan_u32(c, c->bam_slot_len.as<u32>(), nb, c->bam_off.as<u64>(), 20);
+    const int rc = scan_u32(c, c->bam_slot_len.as<u32>(), nb, c->bam_off.as<u64>(), TOT_BGZF_BYTES);
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 26, c->totals.as<u64>() + 20, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&c->h_info->z_bytes, tot_at(c, TOT_BGZF_BYTES), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    *ztotal = *reinterpret_cast<const u64*>(c->h_info + 26);
+    *ztotal = c->h_info->z_bytes;
     return BMBS_OK;
 }
 int bgzf_collect(Lane* c, u64 raw_total, u64 ztotal)
@@ -310,7 +310,7 @@ int bgzf_collect(Lane* c, u64 raw_total, u64 ztotal)
 
 // ---- coordinate sort of a record stream on the device (k_bamsort.hip): n entries, entry i = len[i] bytes at raw + off[i] (off: the
 // exclusive scan of len, `total` bytes in all; raw is padded by 16 bytes and more) -> c->bs_sorted: the records stably sorted by key,
-// c->bs_key2 / c->bs_slen their keys and lengths in that order, totals[23] their size.  skip_empty: entries of length 0 are output
+// c->bs_key2 / c->bs_slen their keys and lengths in that order, the word TOT_SORTED_BYTES their size.  skip_empty: entries of length 0 are output
 // lines that print nothing, not records (they end up behind the records); *n_records = the others.
 // BMBS_BSG_TINY=1 (test aid): no piece fits the gather kernel's image -- every workgroup takes the plain path.
 int bam_sort_device(Lane* c, const char* raw, const u64* off, const u32* len, u64 n, u64 total, bool skip_empty, u64* n_records)
@@ -319,27 +319,28 @@ int bam_sort_device(Lane* c, const char* raw, const u64* off, const u32* len, u6
     c->ends(Lane::SORT_BUFFERS);
     ENS(c, c->bs_key, n * 8 + 64); ENS(c, c->bs_key2, n * 8 + 64); ENS(c, c->bs_idx, n * 4 + 64); ENS(c, c->bs_idx2, n * 4 + 64);
     ENS(c, c->bs_slen, n * 4 + 64); ENS(c, c->bs_soff, (n + 1) * 8 + 64); ENS(c, c->bs_sorted, total + 256);
-    u32* const info = c->tx_info.as<u32>() + 8;
-    HIPCHK(c, hipMemsetAsync(info, 0, 16, c->stream));
+    u32* const info = stage_info(c);
+    const u32* const got = c->h_info->stage;             // k_bam_keys' words: a bad record, the largest refID, entries of length 0
+    HIPCHK(c, hipMemsetAsync(info, 0, 4 * sizeof(u32), c->stream));
     prof_begin(c, "k_bam_keys");
     hipLaunchKernelGGL(k_bam_keys, dim3(nblk(n, 256)), dim3(256), 0, c->stream, raw, off, len, (long)n, skip_empty ? 1 : 0, c->bs_key.as<u64>(), c->bs_idx.as<u32>(), info);
     prof_end(c);
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 8, info, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_info->stage, info, 4 * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->h_info[8]) {
-        c->err = "bam sort: the length given for record " + std::to_string(~c->h_info[8]) + " is not its block_size + 4 (or is below the 36 bytes every BAM record has)";
+    if (got[0]) {
+        c->err = "bam sort: the length given for record " + std::to_string(~got[0]) + " is not its block_size + 4 (or is below the 36 bytes every BAM record has)";
         return BMBS_EINVAL;
     }
-    if (n_records) *n_records = n - c->h_info[10];
-    c->sc.bai_ref_max = c->h_info[9];
+    if (n_records) *n_records = n - got[2];
+    c->sc.bai_ref_max = got[1];
     // the key bits that can be set: 33 of position and strand, and those of the largest reference index (-1 is all ones: it stays last
     // under any number of low bits, because no other index has them all set)
     int ref_bits = 1;
-    while (ref_bits < 32 && ((u64)c->h_info[9] + 1) >> ref_bits) ref_bits++;
+    while (ref_bits < 32 && ((u64)got[1] + 1) >> ref_bits) ref_bits++;
     const unsigned end_bit = (unsigned)(33 + ref_bits);
     { const int rc = bam_pair_sort(c, c->bs_key.as<u64>(), c->bs_key2.as<u64>(), c->bs_idx.as<u32>(), c->bs_idx2.as<u32>(), n, end_bit); if (rc) return rc; }
     hipLaunchKernelGGL(k_bam_slen, dim3(nblk(n, 256)), dim3(256), 0, c->stream, len, c->bs_idx2.as<u32>(), (long)n, c->bs_slen.as<u32>());
-    const int rc = scan_u32(c, c->bs_slen.as<u32>(), n, c->bs_soff.as<u64>(), 23);
+    const int rc = scan_u32(c, c->bs_slen.as<u32>(), n, c->bs_soff.as<u64>(), TOT_SORTED_BYTES);
     if (rc) return rc;
     // records per workgroup: three quarters of the image at the stream's mean record size
     const u64 mean = total / std::max<u64>(n, 1) + 1;
@@ -366,24 +367,24 @@ int lane_text_finish(Lane* c, bool pe, u64 bytes1, u64 bytes2, int64_t n_records
     if (rc) return rc;
     if (pe) { rc = fq_rec_setup(c, n, 1, rec[1]); if (rc) return rc; }
     // records can only be cut out once the host knows that every one of them is complete: the line counts first
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 16, c->totals.as<u64>() + 16, 16, hipMemcpyDeviceToHost, c->stream));
+    const u64* const lines = c->h_info->lines;
+    HIPCHK(c, hipMemcpyAsync(c->h_info->lines, tot_at(c, TOT_LINES_1), sizeof c->h_info->lines, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     tp[1] = wall();
-    const u64* lines = reinterpret_cast<const u64*>(c->h_info + 16);
     if (lines[0] < 4 * n || (pe && lines[1] < 4 * n)) { c->err = "text call: a window holds fewer than 4 lines per record"; return BMBS_EINVAL; }
-    hipLaunchKernelGGL(k_fq_records, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->tx_nl[0].as<u32>(), (long)n, rec[0], c->tx_info.as<u32>());
-    if (pe) hipLaunchKernelGGL(k_fq_records, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->tx_nl[1].as<u32>(), (long)n, rec[1], c->tx_info.as<u32>() + 4);
-    HIPCHK(c, hipMemcpyAsync(c->h_info, c->tx_info.p, 32, hipMemcpyDeviceToHost, c->stream));
+    hipLaunchKernelGGL(k_fq_records, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->tx_nl[0].as<u32>(), (long)n, rec[0], line_info(c));
+    if (pe) hipLaunchKernelGGL(k_fq_records, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->tx_nl[1].as<u32>(), (long)n, rec[1], line_info(c) + TXI_FQ_WORDS);
+    HIPCHK(c, hipMemcpyAsync(c->h_info->line, line_info(c), sizeof c->h_info->line, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     tp[2] = wall();
-    const u32* inf = c->h_info;
+    const u32* const inf = c->h_info->line; const u32* const inf2 = inf + TXI_FQ_WORDS;      // k_fq_records' words of file 1, of file 2
     for (int f = 0; f < (pe ? 2 : 1); f++)
-        if (inf[4 * f + 2]) {
-            c->err = "record " + std::to_string(inf[4 * f + 2] - 1) + " of this batch has an empty or longer-than-" + std::to_string(BMBS_MAX_READ) + "-character sequence line: not supported (the reference's own buffers end there)";
+        if (inf[TXI_FQ_WORDS * f + 2]) {
+            c->err = "record " + std::to_string(inf[TXI_FQ_WORDS * f + 2] - 1) + " of this batch has an empty or longer-than-" + std::to_string(BMBS_MAX_READ) + "-character sequence line: not supported (the reference's own buffers end there)";
             return BMBS_EINVAL;
         }
     int maxL = (int)inf[0], minL = (int)~inf[1];
-    if (pe) { maxL = std::max(maxL, (int)inf[4]); minL = std::min(minL, (int)~inf[5]); }
+    if (pe) { maxL = std::max(maxL, (int)inf2[0]); minL = std::min(minL, (int)~inf2[1]); }
     const bool uniform = minL == maxL;
     const int ds = (maxL + 15) / 16 * 16;
     const int max_ops = cigar_ops_bound(c->prm, maxL, threshold_k(c->prm, maxL));
@@ -437,17 +438,17 @@ int lane_text_finish(Lane* c, bool pe, u64 bytes1, u64 bytes2, int64_t n_records
     if (flags_in & BMBS_TEXT_BAM) {
         // ---- records -> BAM records -> BGZF blocks, all on the device (bmbs_bam.hip)
         prof_begin(c, "k_bam_len");
-        hipLaunchKernelGGL(k_bam_len, dim3(nblk(n2, 256)), dim3(256), 0, c->stream, in, (long)n2, c->sam_len.as<u32>(), c->tx_info.as<u32>());
-        rc = scan_u32(c, c->sam_len.as<u32>(), n2, c->sam_off.as<u64>(), 19);
+        hipLaunchKernelGGL(k_bam_len, dim3(nblk(n2, 256)), dim3(256), 0, c->stream, in, (long)n2, c->sam_len.as<u32>(), line_info(c));
+        rc = scan_u32(c, c->sam_len.as<u32>(), n2, c->sam_off.as<u64>(), TOT_BAM_BYTES);
         if (rc) return rc;
         prof_end(c);
-        HIPCHK(c, hipMemcpyAsync(c->h_info + 24, c->totals.as<u64>() + 19, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->h_info, c->tx_info.p, 32, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&c->h_info->out_bytes, tot_at(c, TOT_BAM_BYTES), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->h_info->line, line_info(c), sizeof c->h_info->line, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         tp[4] = wall();
-        const u64 raw_total = *reinterpret_cast<const u64*>(c->h_info + 24);
+        const u64 raw_total = c->h_info->out_bytes;
         if (n_lines_out) *n_lines_out = (int64_t)n2;
-        if (c->h_info[3]) { c->err = "output line " + std::to_string(c->h_info[3] - 1) + " of this batch has a read name of more than 254 characters: BAM cannot hold it"; return BMBS_EINVAL; }
+        if (inf[3]) { c->err = "output line " + std::to_string(inf[3] - 1) + " of this batch has a read name of more than 254 characters: BAM cannot hold it"; return BMBS_EINVAL; }
         if (!raw_total) { if (flags_in & BMBS_TEXT_BAM_SORTED) c->st.holds(0, (int64_t)n2, pe); return BMBS_OK; }
         ENS(c, c->bam_raw, raw_total + 256);
         const TxwPlan tw = txw_plan(pe, bytes1 + bytes2, n2, (36 + 4 * std::max(max_ops, 1) + 8 + 15) & ~15);
@@ -478,7 +479,7 @@ int lane_text_finish(Lane* c, bool pe, u64 bytes1, u64 bytes2, int64_t n_records
             return BMBS_OK;
         }
         u64 ztotal = 0;
-        rc = bgzf_deflate(c, c->bam_raw.as<char>(), c->totals.as<u64>() + 19, raw_total, &ztotal);
+        rc = bgzf_deflate(c, c->bam_raw.as<char>(), tot_at(c, TOT_BAM_BYTES), raw_total, &ztotal);
         if (rc) return rc;
         if (sam_bytes) *sam_bytes = ztotal;
         if (ztotal > sam_cap) return too_small("text call: the BAM buffer is too small (sam_bytes tells what this batch needs)");
@@ -501,13 +502,13 @@ int lane_text_finish(Lane* c, bool pe, u64 bytes1, u64 bytes2, int64_t n_records
     }
     prof_begin(c, "k_sam_len");
     hipLaunchKernelGGL(k_sam_len, dim3(nblk(n2, 256)), dim3(256), 0, c->stream, in, (long)n2, c->sam_len.as<u32>());
-    rc = scan_u32(c, c->sam_len.as<u32>(), n2, c->sam_off.as<u64>(), 18);
+    rc = scan_u32(c, c->sam_len.as<u32>(), n2, c->sam_off.as<u64>(), TOT_SAM_BYTES);
     if (rc) return rc;
     prof_end(c);
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 24, c->totals.as<u64>() + 18, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&c->h_info->out_bytes, tot_at(c, TOT_SAM_BYTES), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     tp[4] = wall();
-    const u64 total = *reinterpret_cast<const u64*>(c->h_info + 24);
+    const u64 total = c->h_info->out_bytes;
     if (sam_bytes) *sam_bytes = total;
     if (n_lines_out) *n_lines_out = (int64_t)n2;
     if (total > sam_cap) return too_small("text call: the SAM buffer is too small (sam_bytes tells what this batch needs)");
@@ -546,20 +547,19 @@ static int lane_text_open_finish(Lane* c, bool pe, DevBuf* const* texts, u64* by
     int rc = text_index(c, c->fq_text1, bytes[0], n_cap, 0);
     if (rc) return rc;
     if (pe) { rc = text_index(c, c->fq_text2, bytes[1], n_cap, 1); if (rc) return rc; }
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 16, c->totals.as<u64>() + 16, 16, hipMemcpyDeviceToHost, c->stream));
+    const u64* const lines = c->h_info->lines;
+    HIPCHK(c, hipMemcpyAsync(c->h_info->lines, tot_at(c, TOT_LINES_1), sizeof c->h_info->lines, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     tp[2] = wall();
-    const u64* lines = reinterpret_cast<const u64*>(c->h_info + 16);
     u64 n = lines[0] / 4;
     if (pe) n = std::min(n, lines[1] / 4);
     n = std::min(n, n_cap);
     // the text behind the n records: handed back for the next window
     u64 cut[2] = {0, 0};
     if (n) {
-        HIPCHK(c, hipMemcpyAsync(c->h_info + 20, c->tx_nl[0].as<u32>() + (4 * n - 1), 4, hipMemcpyDeviceToHost, c->stream));
-        if (pe) HIPCHK(c, hipMemcpyAsync(c->h_info + 21, c->tx_nl[1].as<u32>() + (4 * n - 1), 4, hipMemcpyDeviceToHost, c->stream));
+        for (int f = 0; f < (pe ? 2 : 1); f++) HIPCHK(c, hipMemcpyAsync(&c->h_info->last_nl[f], c->tx_nl[f].as<u32>() + (4 * n - 1), sizeof(u32), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        cut[0] = (u64)c->h_info[20] + 1; if (pe) cut[1] = (u64)c->h_info[21] + 1;
+        for (int f = 0; f < (pe ? 2 : 1); f++) cut[f] = (u64)c->h_info->last_nl[f] + 1;
     }
     hipStream_t ds = c->kn.copy_streams && c->down_stream ? c->down_stream : c->stream;
     char* tails[2] = {tail1, tail2}; uint64_t* tb[2] = {tail1_bytes, tail2_bytes};
@@ -601,7 +601,7 @@ int lane_text_open_bgzf(Lane* c, const bmbs_ztext* z1, const bmbs_ztext* z2, int
     static const bool trace = getenv("BMBS_TEXT_TRACE") != nullptr;
     auto wall = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; };
     double tp[6] = {wall(), 0, 0, 0, 0, 0};
-    HIPCHK(c, hipMemsetAsync(c->tx_info.p, 0, 64, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->tx_info.p, 0, TXI_WORDS * sizeof(u32), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     // each file on a stream of its own: upload, inflate (one wave per block: a launch of one file's blocks leaves most of the chip's
     // wave slots empty, so the two files' launches run side by side), last line
@@ -634,12 +634,12 @@ int lane_text_open_bgzf(Lane* c, const bmbs_ztext* z1, const bmbs_ztext* z2, int
         }
         if (last[f] && bytes[f]) {
             // an unterminated last line counts as a line (the reader's rule): the newline is added here, on the device
-            hipLaunchKernelGGL(k_close_last_line, dim3(1), dim3(1), 0, fs[f], A[f].text->as<char>(), bytes[f], c->totals.as<u64>() + 21 + f);
-        } else HIPCHK(c, hipMemsetAsync(c->totals.as<u64>() + 21 + f, 0, 8, fs[f]));
+            hipLaunchKernelGGL(k_close_last_line, dim3(1), dim3(1), 0, fs[f], A[f].text->as<char>(), bytes[f], tot_at(c, tot_file(TOT_NL_ADDED_1, f)));
+        } else HIPCHK(c, hipMemsetAsync(tot_at(c, tot_file(TOT_NL_ADDED_1, f)), 0, sizeof(u64), fs[f]));
     }
     if (pe && fs[1] != c->stream) HIPCHK(c, hipStreamSynchronize(fs[1]));
     // whether a newline was added has to be known before the lines are indexed
-    HIPCHK(c, hipMemcpyAsync(c->h_info + 28, c->totals.as<u64>() + 21, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_info->nl_added, tot_at(c, TOT_NL_ADDED_1), sizeof c->h_info->nl_added, hipMemcpyDeviceToHost, c->stream));
     std::vector<u32> err[2];
     for (int f = 0; f < (pe ? 2 : 1); f++) {
         const u64 nb = (u64)std::max<int64_t>(0, A[f].z->n_blocks);
@@ -651,7 +651,7 @@ int lane_text_open_bgzf(Lane* c, const bmbs_ztext* z1, const bmbs_ztext* z2, int
         for (size_t i = 0; i < err[f].size(); i++)
             if (err[f][i]) { c->err = "corrupt BGZF block in the .gz input (file " + std::to_string(f + 1) + ", block " + std::to_string(i) + " of this window, code " + std::to_string(err[f][i]) + ")"; return BMBS_EINVAL; }
     tp[1] = wall();
-    const u64* added = reinterpret_cast<const u64*>(c->h_info + 28);
+    const u64* const added = c->h_info->nl_added;
     bytes[0] += added[0]; if (pe) bytes[1] += added[1];
     DevBuf* texts[2] = {&c->fq_text1, &c->fq_text2};
     return lane_text_open_finish(c, pe, texts, bytes, max_records, n_records, tail1, tail_cap, tail1_bytes, tail2, tail2_bytes, tp, trace ? "bgzf" : nullptr,

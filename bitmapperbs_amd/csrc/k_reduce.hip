@@ -106,12 +106,8 @@ k_reduce(long n, int ambiguous_out, ReadState st, const u64* __restrict__ vote_o
 // guards compare the real count with that capacity right after the scan that produced it.  On overflow the guard raises a
 // flag and takes the work away from every later kernel (nothing is written out of bounds); the host sees the flag when it next
 // synchronises and runs the batch again with exact sizes.  The statistics of a call are added to the context's counters by
-// k_stats_commit only when no flag is up, so a repeated batch counts once.
-#define BMBS_FLAG_CAND   0   // candidate slots > capacity
-#define BMBS_FLAG_SW     1   // DP jobs > capacity of the launches issued
-#define BMBS_FLAG_RCAND  2   // --sensitive: re-seeded candidates > capacity
-#define BMBS_FLAG_CIGAR  3   // the caller's CIGAR pool is too small for the jobs of this batch (an error, not a retry)
-#define BMBS_FLAG_WORDS  8
+// k_stats_commit only when no flag is up, so a repeated batch counts once.  (The flag words, BMBS_FLAG_*: bmbs_words.h -- the host
+// reads them too.)
 __global__ void __launch_bounds__(256)
 k_guard_cand(u64* __restrict__ total, u64 cap, u32* __restrict__ flags, long n, u8* __restrict__ verdict, u32* __restrict__ n_cand,
              u64* __restrict__ cand_off)
@@ -154,15 +150,15 @@ k_stats_commit(const u32* __restrict__ flags, unsigned long long* __restrict__ c
     if (!again && v) stats[i] += v;
 }
 
-// 16-mer lookups and extensions of this call (summed over the counter shards) -> totals[14], [15]: the host learns from them
+// 16-mer lookups and extensions of this call (summed over the counter shards) -> totals[TOT_CHAIN_LOOKUPS], [TOT_CHAIN_EXT]: the host learns from them
 // whether the reads of this input walk the index in long chains (three-letter steps pay off) or not
 __global__ void k_call_chain_counts(const unsigned long long* __restrict__ counters, u64* __restrict__ totals)
 {
-    const int j = threadIdx.x;                  // 0: lookups, 1: extensions
+    const int j = threadIdx.x;                  // 0: lookups (CNT_LOOKUPS), 1: extensions (CNT_EXT)
     if (j >= 2) return;
     u64 t = 0;
     for (int sdx = 0; sdx < BMBS_SHARDS; sdx++) t += counters[sdx * BMBS_SHARD_WORDS + j];
-    totals[14 + j] = t;
+    totals[TOT_CHAIN_LOOKUPS + j] = t;
 }
 
 // job arrays shared by the fused path and bmbs_align_batch

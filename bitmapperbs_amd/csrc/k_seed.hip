@@ -422,7 +422,7 @@ DEVI long seed_chunk(long total, int target_waves)
 }
 
 struct LaneCounters { u32 n_hash, n_ext, n_sa, n_ung, n_jump; };      // n_jump: three-letter steps taken (each also counts three in n_ext)
-// totals in counters[0,1,2,5]; per-kernel copies in counters[16 + 4*kid ..] (kid 0 first, 1 second, 2 extra)
+// totals in counters[CNT_LOOKUPS, CNT_EXT, CNT_SA, CNT_UNGAPPED] and [CNT_JUMP]; per-kernel copies in counters[16 + 4*kid ..] (kid 0 first, 1 second, 2 extra)
 DEVI void flush_counters(unsigned long long* counters, const LaneCounters& c, int kid)
 {
     // 64-thread blocks: one wave; reduce with shuffles, one atomic per wave and counter
@@ -430,12 +430,12 @@ DEVI void flush_counters(unsigned long long* counters, const LaneCounters& c, in
     for (int o = 32; o > 0; o >>= 1) { a += __shfl_down(a, o); b += __shfl_down(b, o); d += __shfl_down(d, o); e += __shfl_down(e, o); j += __shfl_down(j, o); }
     if ((threadIdx.x & 63) == 0 && counters) {
         counters = SHARD(counters);
-        if (j) atomicAdd(&counters[8], (unsigned long long)j);
+        if (j) atomicAdd(&counters[CNT_JUMP], (unsigned long long)j);
         unsigned long long* k = counters + 16 + 4 * kid;
-        if (a) { atomicAdd(&counters[0], (unsigned long long)a); atomicAdd(&k[0], (unsigned long long)a); }
-        if (b) { atomicAdd(&counters[1], (unsigned long long)b); atomicAdd(&k[1], (unsigned long long)b); }
-        if (d) { atomicAdd(&counters[2], (unsigned long long)d); atomicAdd(&k[2], (unsigned long long)d); }
-        if (e) { atomicAdd(&counters[5], (unsigned long long)e); atomicAdd(&k[3], (unsigned long long)e); }
+        if (a) { atomicAdd(&counters[CNT_LOOKUPS], (unsigned long long)a); atomicAdd(&k[0], (unsigned long long)a); }
+        if (b) { atomicAdd(&counters[CNT_EXT], (unsigned long long)b); atomicAdd(&k[1], (unsigned long long)b); }
+        if (d) { atomicAdd(&counters[CNT_SA], (unsigned long long)d); atomicAdd(&k[2], (unsigned long long)d); }
+        if (e) { atomicAdd(&counters[CNT_UNGAPPED], (unsigned long long)e); atomicAdd(&k[3], (unsigned long long)e); }
     }
 }
 
