@@ -39,6 +39,7 @@ struct seed_res { u64 hits, sp, ep, match_len; };
 struct vote_t { u64 site, vote; unsigned err; u64 end_site; };      // seed_votes, Schema.h:169-176
 struct fq_rec { std::string name, seq, rseq, qual; };
 void window_at(const orc_index* ix, u64 site, u64 len, char* out);
+void window_rest(const orc_index* ix, u64 loc, u64 off, u64 len, char* out);
 int  mismatch_penalty(const orc_params* P, int Q);
 seed_res count_terminate(const orc_index* ix, const char* pat, u64 length, orc_counters* C);
 seed_res count_fixed(const orc_index* ix, const char* pat, u64 length, orc_counters* C);

@@ -41,6 +41,14 @@ void window_at(const orc_index* ix, u64 site, u64 len, char* out)
     if (site < ix->G) window_fwd(ix, site, len, out);
     else window_rc(ix, site - ix->G, len, out);
 }
+// the rest of a read behind its located first seed (try_process_unique_mismatch_end_to_end*, Schema.cpp:15194-15206, 15695): the strand
+// is the one the HIT's first base lies on.  A hit on the forward side whose rest reaches beyond the forward text gets
+// get_actuall_genome's all-zero window, not the reverse strand's text that follows it in the doubled coordinates.
+void window_rest(const orc_index* ix, u64 loc, u64 off, u64 len, char* out)
+{
+    if (loc < ix->G) window_fwd(ix, loc + off, len, out);
+    else window_rc(ix, loc + off - ix->G, len, out);
+}
 extern "C" void orc_window(const orc_index* ix, uint64_t site, int len, char* out) { window_at(ix, site, len, out); }
 
 // ------------------------------------------------------------------------------------------------
@@ -523,7 +531,7 @@ static void map_one_se(const orc_index* ix, const orc_params* P, const read_t& r
             if (match_length != (u64)L) {
                 int need = L - (int)match_length;
                 win.assign(need + 8, 0);
-                window_at(ix, loc + match_length, need, win.data());
+                window_rest(ix, loc, match_length, need, win.data());
                 if (C) C->n_ungapped++;
                 int read_i = (int)match_length;
                 for (int i = 0; i < need; i++) {

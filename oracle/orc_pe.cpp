@@ -46,7 +46,7 @@ int get_candidates(const orc_index* ix, const orc_params* P, const char* read, i
             if (match_length != (u64)L) {
                 int need = L - (int)match_length;
                 win.assign(need + 8, 0);
-                window_at(ix, loc + match_length, need, win.data());
+                window_rest(ix, loc, match_length, need, win.data());
                 int read_i = (int)match_length;
                 for (int i = 0; i < need; i++) {
                     if (read[read_i] != win[i] && !(read[read_i] == 'T' && win[i] == 'C')) {
@@ -288,7 +288,7 @@ void first_seed(const orc_index* ix, const orc_params* P, mate_t& m, orc_counter
             if (match_length != (u64)L) {
                 int need = L - (int)match_length;
                 win.assign(need + 8, 0);
-                window_at(ix, loc + match_length, need, win.data());
+                window_rest(ix, loc, match_length, need, win.data());
                 int read_i = (int)match_length;
                 for (int i = 0; i < need; i++) {
                     if (read[read_i] != win[i] && !(read[read_i] == 'T' && win[i] == 'C')) { error++; if (error == 1) match_length = read_i; else break; }

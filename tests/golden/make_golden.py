@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Regenerates the golden fixtures in this directory by RUNNING THE REAL REFERENCE here.
 
-  python tests/golden/make_golden.py [--psascan /path/to/psascan] [--only small|big]
+  python tests/golden/make_golden.py [--psascan /path/to/psascan] [--only small|big|ends]
 
 Needs oracle/_ref/bitmapperBS (oracle/build_ref.sh; /root/reference present) and, for the index pins, the reference's external
 suffix sorter oracle/_ref/psascan (oracle/build_psascan.sh; used by default when it is there).  Fixtures are data only:
@@ -22,6 +22,9 @@ Genome and reads are NOT stored: they are regenerated from their seeds (numpy PC
 recorded here; of the reference's SAM the fixture keeps every column except QNAME / SEQ / QUAL (derivable from the inputs) plus
 the sha256 of the complete SAM body, which is what the tests compare the product's complete SAM text with.  The big index is
 written by the REFERENCE's own `--index` (psascan) and its file hashes are recorded as a second pin of our builders.
+
+The ENDS family (ends.json / ends_*): reads and pairs at and across chromosome ends, from tests/ends.py; `--only ends` writes these
+files and no other.
 """
 import argparse, gzip, hashlib, json, os, shutil, subprocess, sys, tempfile
 import numpy as np
@@ -162,13 +165,72 @@ def big_family(ref, psascan):
     json.dump(meta, open(os.path.join(HERE, "big_family.json"), "w"), indent=1)
     shutil.rmtree(wd)
 
+# The ENDS family (ends_*): reads and pairs at and across chromosome ends (tests/ends.py), on a genome of 30 sequences down to 80
+# bases.  Genome and FASTQ files are stored; every run keeps the reference's SAM (or BAM) and mapstats.
+ENDS = {
+    "se": dict(kind="se", args=[]),
+    "se_ua": dict(kind="se", args=["--unmapped_out", "--ambiguous_out"]),
+    "se_trim": dict(kind="se", trim=[21], args=["--ambiguous_out"]),
+    "se_bam": dict(kind="se", bam=True, args=["--bam", "--unmapped_out", "--ambiguous_out"]),
+    "pe": dict(kind="pe", args=[]),
+    "pe_sens": dict(kind="pe", args=["--sensitive"]),
+    "pe_ua": dict(kind="pe", args=["--unmapped_out", "--ambiguous_out"]),
+    "pe_minmax": dict(kind="pe", args=["--min", "200", "--max", "300"]),
+    "pe_trim": dict(kind="pe", trim=[22, 23], args=["--unmapped_out"]),
+    "pe_bam": dict(kind="pe", bam=True, args=["--bam", "--unmapped_out"]),
+}
+
+def ends_family(ref):
+    import ends
+    from common import trim_fastq
+    wd = tempfile.mkdtemp(prefix="golden_ends_")
+    names, chroms = ends.genome()                      # without plant (ii): see tests/ends.py
+    fa = os.path.join(wd, "genome.fa")
+    ends.write_fasta(fa, names, chroms)
+    orc.load().orc_index_build(fa.encode(), fa.encode())
+    os.symlink(ref, os.path.join(wd, "bitmapperBS"))
+    fq = os.path.join(wd, "se.fq"); f1 = os.path.join(wd, "pe_1.fq"); f2 = os.path.join(wd, "pe_2.fq")
+    ends.write_fastq(fq, ends.se_reads(chroms))
+    m1, m2, _ = ends.pe_reads(chroms)
+    ends.write_fastq(f1, m1); ends.write_fastq(f2, m2)
+    for src, dst in ((fa, "ends_genome.fa.gz"), (fq, "ends_se.fq.gz"), (f1, "ends_pe_1.fq.gz"), (f2, "ends_pe_2.fq.gz")):
+        with open(src, "rb") as f, gzip.GzipFile(os.path.join(HERE, dst), "wb", mtime=0) as g: g.write(f.read())
+    for name, v in ENDS.items():
+        out = os.path.join(wd, name + ".out")
+        files = [fq] if v["kind"] == "se" else [f1, f2]
+        if v.get("trim"):
+            for i, f_ in enumerate(files):
+                trim_fastq(f_, f_[:-3] + "_trim.fq", v["trim"][i])
+            files = [f_[:-3] + "_trim.fq" for f_ in files]
+        # names relative to the working directory: the command line goes into the BAM header, and the file is to come out bit for bit
+        files = [os.path.basename(f_) for f_ in files]
+        inp = ["--seq", files[0]] if v["kind"] == "se" else ["--seq1", files[0], "--seq2", files[1]]
+        p = subprocess.run(["./bitmapperBS", "--search", "genome.fa"] + inp + ["-t", "1", "-o", os.path.basename(out)] + v["args"],
+                           capture_output=True, text=True, cwd=wd)
+        assert p.returncode == 0, p.stderr
+        stats = "".join(l for l in p.stderr.splitlines(True) if l.startswith("No. of") or l.startswith("Mismatch"))
+        open(os.path.join(HERE, "ends_%s.ref.stats" % name), "w").write(stats)
+        if v.get("bam"):
+            shutil.copy(out, os.path.join(HERE, "ends_%s.ref.bam" % name))
+            print("ENDS", name, "bam bytes", os.path.getsize(out), stats.splitlines()[1])
+            continue
+        body = "".join(l for l in open(out) if not l.startswith("@PG"))
+        with gzip.GzipFile(os.path.join(HERE, "ends_%s.ref.sam.gz" % name), "wb", mtime=0) as g: g.write(body.encode())
+        print("ENDS", name, "lines", body.count("\n"), stats.splitlines()[1], stats.splitlines()[2])
+    json.dump(ENDS, open(os.path.join(HERE, "ends.json"), "w"), indent=1)
+    shutil.rmtree(wd)
+
 def main():
-    ap = argparse.ArgumentParser(); ap.add_argument("--psascan"); ap.add_argument("--only", choices=["small", "big"])
+    ap = argparse.ArgumentParser(); ap.add_argument("--psascan"); ap.add_argument("--only", choices=["small", "big", "ends"])
     a = ap.parse_args()
     ref = os.path.join(ROOT, "oracle", "_ref", "bitmapperBS")
     assert os.path.exists(ref), "build the reference first: oracle/build_ref.sh"
     if not a.psascan and os.path.exists(os.path.join(ROOT, "oracle", "_ref", "psascan")):
         a.psascan = os.path.join(ROOT, "oracle", "_ref", "psascan")
+    if a.only in (None, "ends"):
+        ends_family(ref)
+        if a.only == "ends":
+            return
     if a.only != "small":
         big_family(ref, a.psascan)
         if a.only == "big":

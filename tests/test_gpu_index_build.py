@@ -35,6 +35,21 @@ def test_device_builder_matches_reference_index_hashes(tmp_path):
     assert sha_file(fa + ".index.bs.index.sa", 8) == ref["index.bs.index.sa[:-8]"]
 
 
+def test_three_builders_agree_on_the_genome_of_short_sequences(tmp_path):
+    """tests/ends.py: 30 sequences, twenty of 400 bases and four of 80 (shorter than a read, shorter than a 128-base block of any
+    layout), the joins planted with copies of each other: host builder == device builder == the oracle's builder, all six files"""
+    import ends
+    import orc
+    names, chroms = ends.genome(plant_ii=True)
+    fa_d = _both(tmp_path, lambda p: ends.write_fasta(p, names, chroms))
+    fa_o = str(tmp_path / "o" / "genome.fa")
+    os.makedirs(os.path.dirname(fa_o))
+    ends.write_fasta(fa_o, names, chroms)
+    assert orc.load().orc_index_build(fa_o.encode(), fa_o.encode()) == 0
+    for s in SUFFIXES:
+        assert open(fa_d + "." + s, "rb").read() == open(fa_o + "." + s, "rb").read(), s
+
+
 @pytest.mark.parametrize("case", ["repeats", "tandem", "odd_sizes", "lowercase_N"])
 def test_device_builder_equals_host_builder(tmp_path, case):
     """repeat-rich texts drive the prefix doubling through many rounds (ties far beyond the 32-symbol radix key); sizes that

@@ -262,3 +262,49 @@ def test_oracle_cli_equals_reference_on_random_files_and_options(tmp_path):
         t = fz.draw(rng)
         bad, lines = fz.run_trial(t, env, str(tmp_path))
         assert not bad, (t, bad[:2])
+
+
+# ---- reads and pairs at and across chromosome ends (tests/ends.py; the reference's own output: make_golden.py --only ends) ------------
+def ends_runs():
+    import json
+    return json.load(open(os.path.join(GOLD, "ends.json")))
+
+
+def ends_inputs(v, tmp_path):
+    """FASTQ arguments of an `ends_*` run, built from the committed read sets"""
+    from common import trim_fastq
+    files = [str(tmp_path / "se.fq")] if v["kind"] == "se" else [str(tmp_path / "pe_1.fq"), str(tmp_path / "pe_2.fq")]
+    for i, f in enumerate(files):
+        gunzip_to(os.path.join(GOLD, "ends_" + os.path.basename(f) + ".gz"), f)
+        if v.get("trim"):
+            trim_fastq(f, f[:-3] + "_trim.fq", v["trim"][i]); files[i] = f[:-3] + "_trim.fq"
+    return ["--seq", files[0]] if v["kind"] == "se" else ["--seq1", files[0], "--seq2", files[1]]
+
+
+@pytest.fixture(scope="module")
+def ends_index(tmp_path_factory, oracle):
+    wd = tmp_path_factory.mktemp("ends")
+    fa = str(wd / "genome.fa")
+    gunzip_to(os.path.join(GOLD, "ends_genome.fa.gz"), fa)
+    assert oracle.orc_index_build(fa.encode(), fa.encode()) == 0
+    return fa
+
+
+@pytest.mark.parametrize("name", sorted(ends_runs()))
+def test_oracle_cli_reproduces_reference_at_chromosome_ends(name, ends_index, tmp_path):
+    """off-end rejection on every exit path, pairs whose mates lie on two chromosomes, TLEN at --min/--max: the oracle's SAM and
+    mapstats equal the reference's; its --bam runs are compared record by record (the oracle writes SAM only)"""
+    v = ends_runs()[name]
+    out = str(tmp_path / "o.sam")
+    q = subprocess.run([os.path.join(ROOT, "oracle", "bmbs_oracle"), "search", ends_index] + ends_inputs(v, tmp_path) + ["-o", out] +
+                       [a for a in v["args"] if a != "--bam"], capture_output=True, text=True)
+    assert q.returncode == 0, q.stderr
+    if v.get("bam"):
+        from common import bam_payload, sam_to_bam_records
+        refs = [l.split("\t")[1][3:] for l in open(out) if l.startswith("@SQ")]
+        assert sam_to_bam_records(open(out, "rb").read(), refs) == bam_payload(os.path.join(GOLD, "ends_%s.ref.bam" % name))[1]
+    else:
+        mine = "".join(l for l in open(out) if not l.startswith("@PG"))
+        assert mine == gzip.open(os.path.join(GOLD, "ends_%s.ref.sam.gz" % name), "rt").read()
+    stats = "".join(l + "\n" for l in q.stderr.splitlines() if l.startswith("No. of") or l.startswith("Mismatch"))
+    assert stats == open(os.path.join(GOLD, "ends_%s.ref.stats" % name)).read()
