@@ -1144,6 +1144,7 @@ struct PeCall {
     int seed();
     int votes();
     int verify_round(int round, u64 cap, const char* name_f, const char* name_c);
+    int verify_round_pairs(int round, u64 cap, const u32* cnt, const char* name_f, const char* name_c);
     int verify_fast();
     int verify_sensitive();
 };
@@ -1291,9 +1292,38 @@ int PeCall::verify_round(int round, u64 cap, const char* name_f, const char* nam
     return BMBS_OK;
 }
 
+// The same round in fast mode (BMBS_PE_ROUNDS=1), where a round verifies at most one mate of a pair: cnt holds per PAIR the entries of
+// the mate scheduled in `round`, left there by the kernel before the round (k_pe_filter_pairs[_long], k_pe_prune); a scan over the n
+// pairs whose second launch writes the work list itself (k_scan_expand -- always the two-launch form), Myers, compaction with one lane
+// per pair.  The same candidates as verify_round's list, in the order of the pairs
+int PeCall::verify_round_pairs(int round, u64 cap, const u32* cnt, const char* name_f, const char* name_c)
+{
+    if (cap) {
+        prof_begin(c, name_f);
+        const u64 per = (u64)SCAN_BLOCK * SCAN_ITEMS;
+        const u64 nb = n ? (n + per - 1) / per : 1;
+        // (under BMBS_SCAN_CHAIN=1 scan_tmp holds the chained scans' status words: tile sums never carry a live epoch, fresh memory might)
+        { int rc = ensure(c, c->scan_tmp, (nb + 1) * 8, c->kn.scan_chain != 0); if (rc) return rc; }
+        u64* bs = c->scan_tmp.as<u64>();
+        hipLaunchKernelGGL(k_scan_partial, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, c->stream, cnt, n, bs, 0, (const u64*)nullptr);
+        hipLaunchKernelGGL(k_scan_expand, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, c->stream, cnt, n, bs, ps.vround, round,
+                           c->dense_read.as<u32>(), c->ferr.as<u32>(), tot_at(c, TOT_PE_WORK));
+        hipLaunchKernelGGL(k_filter_pe, dim3(nblk(cap, 256)), dim3(256), 0, c->stream, c->ix, seq_all, packed_rows(c, gm), gm, stride, st, ps, A, B,
+                           tot_at(c, TOT_PE_WORK), c->dense_read.as<u32>(), c->ferr.as<u32>(), c->counters.as<unsigned long long>());
+        prof_end(c);
+    }
+    prof_begin(c, name_c);
+    hipLaunchKernelGGL(k_pe_compact_pair, dim3(nblk(n, 64)), dim3(64), 0, c->stream, (long)n, gm, round, st, ps, A, B);
+    prof_end(c);
+    return BMBS_OK;
+}
+
 // fast mode: the lists cut down to sites with a partner on the mate's list, verified in two rounds
 int PeCall::verify_fast()
 {
+    // BMBS_PE_ROUNDS=1: the rounds' per-pair counts, written by the kernels before them into a buffer the seeding stage is done with
+    // (n2 words; round 1 has read its counts when k_pe_prune writes round 2's).  0: the rounds count for themselves (verify_round)
+    u32* rcnt = c->kn.pe_rounds ? c->sd_flag_c.as<u32>() : nullptr;
     prof_begin(c, "k_pe_filter_pairs");
     // pairs with long candidate lists (repeats) are left to a second kernel, one wave per pair -- on repeat-rich input only (the last
     // call left more than 0.5 % of its reads to the long-list vote kernels): flag array, scan and the extra launch cost 0.3 ms per
@@ -1301,20 +1331,20 @@ int PeCall::verify_fast()
     u32* pef_flag = (c->kn.pef_long == 2 || (c->kn.pef_long == 1 && c->lr_long > 0.005)) ? c->long_flag.as<u32>() : nullptr;
     if (pef_flag) HIPCHK(c, hipMemsetAsync(pef_flag, 0, n * 4, c->stream));
     hipLaunchKernelGGL(k_pe_filter_pairs, dim3(nblk(n, 64)), dim3(64), 0, c->stream, (long)n, gm, pi, st, ps, A, B, pef_flag,
-                       c->counters.as<unsigned long long>());
+                       c->counters.as<unsigned long long>(), rcnt);
     if (pef_flag) {
         int rc = scan_u32(c, pef_flag, n, c->long_off.as<u64>(), TOT_PEF_LONG, c->long_list.as<u32>());
         if (rc) return rc;
         hipLaunchKernelGGL(k_pe_filter_pairs_long, dim3((unsigned)std::min<u64>(n, 65536)), dim3(64), 0, c->stream, (long)n, gm, pi, st, ps, tot_at(c, TOT_PEF_LONG),
-                           c->long_list.as<u32>(), A, B);
+                           c->long_list.as<u32>(), A, B, rcnt);
     }
     prof_end(c);
-    int rc = verify_round(1, tot, "k_filter_pe_r1", "k_pe_compact_r1");
+    int rc = rcnt ? verify_round_pairs(1, tot, rcnt, "k_filter_pe_r1", "k_pe_compact_r1") : verify_round(1, tot, "k_filter_pe_r1", "k_pe_compact_r1");
     if (rc) return rc;
     prof_begin(c, "k_pe_prune");
-    hipLaunchKernelGGL(k_pe_prune, dim3(nblk(n, 64)), dim3(64), 0, c->stream, (long)n, gm, pi, st, ps, A, B);
+    hipLaunchKernelGGL(k_pe_prune, dim3(nblk(n, 64)), dim3(64), 0, c->stream, (long)n, gm, pi, st, ps, A, B, rcnt);
     prof_end(c);
-    return verify_round(2, tot, "k_filter_pe_r2", "k_pe_compact_r2");
+    return rcnt ? verify_round_pairs(2, tot, rcnt, "k_filter_pe_r2", "k_pe_compact_r2") : verify_round(2, tot, "k_filter_pe_r2", "k_pe_compact_r2");
 }
 
 // --sensitive (Map_Pair_Seq_end_to_end): first mate verified in full, second mate filtered by it, rescue by re-seeding (a third round)

@@ -60,7 +60,7 @@ struct Prof { const char* name; hipEvent_t a, b; bool used; };
 // GPU suite runs each one in single-end and paired-end mode (test_ab_switches_give_identical_records); DESIGN.md section 3 lists them.
 //   forms:      BMBS_LEGACY=1 (the round-1 ASCII-row seeding engine and byte-wise mate preparation, as a whole), BMBS_SW=reg2|reg|wave,
 //               BMBS_KGRAM=0|1|2, BMBS_T20=0, BMBS_TDEPTH=20|21|h32|h33 (ternary outcome table of that depth | balanced one of that many index bits), BMBS_WIDE=1 (+ BMBS_SUPER_SHIFT), BMBS_LANES=n, BMBS_EXACT=1, BMBS_SEED_WAVES=n,
-//               BMBS_SEED_STAGE=0|1, BMBS_VOTE_DENSE=0|1
+//               BMBS_SEED_STAGE=0|1, BMBS_VOTE_DENSE=0|1, BMBS_PE_ROUNDS=0|1
 //   test aids:  BMBS_CAP_SCALE, BMBS_SPLIT_MIN, BMBS_CHUNK, BMBS_PEF_LONG=2 (make small inputs reach the paths large ones take)
 struct Knobs {
     int sw_form = 0;            // BMBS_SW: 0 default (reg2 from k = 5), 1 reg, 2 reg2, 3 wave
@@ -81,6 +81,10 @@ struct Knobs {
     int pef_long = 1;           // BMBS_PEF_LONG: 1 long lists of k_pe_filter_pairs get a wave when the input is repeat-rich, 2 always (tests)
     int vote_dense = 1;         // BMBS_VOTE_DENSE: 1 (default) the paired-end vote stage compacts the reads that have lists onto dense lanes inside each block
                                 // (k_vote_pe_dense); 0 one lane per read (k_vote_pe_fused, the round-3 form; A/B runs, tests)
+    int pe_rounds = 1;          // BMBS_PE_ROUNDS: 1 (default) the two verification rounds of paired-end fast mode take their per-PAIR counts from the kernel
+                                // before them (k_pe_filter_pairs[_long], k_pe_prune), the scan's second launch writes the work list itself (k_scan_expand: no
+                                // offsets stored, no k_pe_count, no k_pe_worklist) and the compaction runs one lane per pair; 0 the round-3 form over 2n reads
+                                // (A/B runs, tests).  --sensitive is not touched.  (These scans keep the two-launch form under BMBS_SCAN_CHAIN=1 as well.)
     int kgram = 1;              // BMBS_KGRAM: 0 no trigram table, 1 (default) its kernels are used once a context has seen reads that walk the index in long chains, 2 always
     int seed_stage = 1;         // BMBS_SEED_STAGE: 1 (default) k_seed_first writes its chunk's results coalesced out of LDS, k_seed_decide_p keeps back
                                 // the exit-A record nobody reads (except under --sensitive); 0 both store lane by lane (the round-6 forms)
@@ -108,6 +112,7 @@ struct Knobs {
         if ((e = getenv("BMBS_PEF_LONG"))) pef_long = atoi(e);
         if ((e = getenv("BMBS_PREFILTER"))) prefilter = atoi(e);
         if ((e = getenv("BMBS_VOTE_DENSE"))) vote_dense = atoi(e);
+        if ((e = getenv("BMBS_PE_ROUNDS"))) pe_rounds = atoi(e) == 0 ? 0 : 1;
         if ((e = getenv("BMBS_UP_TURNS"))) up_turns = atoi(e);
         if ((e = getenv("BMBS_SCAN_CHAIN"))) scan_chain = atoi(e);
         if ((e = getenv("BMBS_SEED_STAGE"))) seed_stage = atoi(e) == 0 ? 0 : 1;

@@ -26,7 +26,7 @@ enum Tot : int {
     TOT_SEED_SECOND = 3,     // reads on k_seed_second's list       list_second                    k_seed_second
     TOT_SEED_EXTRA = 4,      // reads on k_seed_extra's list        list_extra                     k_seed_extra
     TOT_VOTES = 5,           // single end: votes to verify         vote_compact                   k_filter
-    TOT_PE_WORK = 6,         // paired end: the work list of one    verify_round                   k_filter_pe of that round (each round writes it anew)
+    TOT_PE_WORK = 6,         // paired end: the work list of one    verify_round[_pairs]           k_filter_pe of that round (each round writes it anew)
                              // verification round
     TOT_RESEED = 7,          // --sensitive: pairs to re-seed       k_pes_reseed's scan            k_pes_reseed, k_pes_vote; verify_sensitive (exact: with TOT_RCAND, one copy)
     TOT_RCAND = 8,           // --sensitive: their candidates       the scan behind k_pes_reseed   k_guard_rcand / _done; verify_sensitive (exact); lane_settle (lr_rcand)

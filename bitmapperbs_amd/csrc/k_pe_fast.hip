@@ -564,21 +564,28 @@ DEVI PeCand* pe_list(const PeState& ps, const ReadState& st, PeCand* A, PeCand* 
 
 // filter_pairs (Schema.cpp:16052-16180) + the driver's choice of what to verify (19050-19290)
 // what follows the two filtered lists (Schema.cpp:19050-19290): who is verified in which round
-DEVI void pe_filter_decide(const PeState& ps, long p, long r1, long r2, int occ1, int occ2, long la, long lb)
+// cnt1 (may be null; BMBS_PE_ROUNDS=1): the pair's entries on round 1's work list -- the length of the list of the mate that gets
+// vround 1 -- are left in cnt1[p]; a pair that dies here keeps the 0 k_pe_filter_pairs wrote
+DEVI void pe_filter_decide(const PeState& ps, long p, long r1, long r2, int occ1, int occ2, long la, long lb, u32* __restrict__ cnt1)
 {
     ps.cur[r1] = 1; ps.cur[r2] = 1;
     ps.len[r1] = (u32)la; ps.len[r2] = (u32)lb;
     if (la == 0 || lb == 0) { ps.dead[p] = 1; return; }
+    bool first1;                                    // mate 1 is the one verified in round 1
     if (occ1 == -1 && occ2 == -1) {
         ps.both[p] = 1;
-        if (la <= lb) { ps.vround[r1] = 1; ps.vround[r2] = 2; } else { ps.vround[r2] = 1; ps.vround[r1] = 2; }
+        first1 = la <= lb;
+        if (first1) { ps.vround[r1] = 1; ps.vround[r2] = 2; } else { ps.vround[r2] = 1; ps.vround[r1] = 2; }
     } else if (occ1 != -1) {
         if (la < occ1) ps.occ[r1] = (int)la;
         ps.vround[r2] = 1;
+        first1 = false;
     } else {
         if (lb < occ2) ps.occ[r2] = (int)lb;
         ps.vround[r1] = 1;
+        first1 = true;
     }
+    if (cnt1) cnt1[p] = (u32)(first1 ? la : lb);
 }
 // the reference's merge loop itself, one lane
 DEVI void pe_filter_serial(const PeCand* a, long na, const PeCand* b, long nb, long long maxd, long long mind, PeCand* ra, PeCand* rb, long& la_out, long& lb_out)
@@ -607,7 +614,7 @@ DEVI void pe_filter_serial(const PeCand* a, long na, const PeCand* b, long nb, l
 #define PEF_LONG 24       // pairs whose two lists hold more candidates than this go to k_pe_filter_pairs_long (one wave per pair)
 __global__ void __launch_bounds__(64)
 k_pe_filter_pairs(long n, ReadGeom gm, PeIns pi, ReadState st, PeState ps, PeCand* __restrict__ A, PeCand* __restrict__ B, u32* __restrict__ long_flag,
-                  unsigned long long* __restrict__ counters)
+                  unsigned long long* __restrict__ counters, u32* __restrict__ cnt1)
 {
     const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long r1 = p, r2 = p + n;
@@ -615,6 +622,7 @@ k_pe_filter_pairs(long n, ReadGeom gm, PeIns pi, ReadState st, PeState ps, PeCan
     if (p < n) {
         occ1 = ps.occ[r1]; occ2 = ps.occ[r2];
         ps.dead[p] = 0; ps.both[p] = 0; ps.npair[p] = 0; ps.sbd[p] = 0;
+        if (cnt1) cnt1[p] = 0;                      // settled, dead or left to k_pe_filter_pairs_long: nothing for round 1 (pe_filter_decide writes the others)
     }
     const bool runs = p < n && !(occ1 > 0 && occ2 > 0) && occ1 != 0 && occ2 != 0;       // filter_pairs is reached (Schema.cpp:19084-19110)
     const long na = runs ? (long)ps.len[r1] : 0, nb = runs ? (long)ps.len[r2] : 0;
@@ -629,7 +637,7 @@ k_pe_filter_pairs(long n, ReadGeom gm, PeIns pi, ReadState st, PeState ps, PeCan
     if (long_flag && na + nb > PEF_LONG) { long_flag[p] = 1; return; }
     long la, lb;
     pe_filter_serial(A + st.cand_off[r1], na, A + st.cand_off[r2], nb, maxd, mind, B + st.cand_off[r1], B + st.cand_off[r2], la, lb);
-    pe_filter_decide(ps, p, r1, r2, occ1, occ2, la, lb);
+    pe_filter_decide(ps, p, r1, r2, occ1, occ2, la, lb, cnt1);
 }
 
 // One wave per pair with long lists.  With mind <= 0 (the default --min 0 makes it negative) a pair of sites hits iff they lie
@@ -666,7 +674,7 @@ DEVI long pe_filter_side(const PeCand* x, long nx, const PeCand* y, long ny, u64
 }
 __global__ void __launch_bounds__(64)
 k_pe_filter_pairs_long(long n, ReadGeom gm, PeIns pi, ReadState st, PeState ps, const u64* __restrict__ count_ptr, const u32* __restrict__ list,
-                       PeCand* __restrict__ A, PeCand* __restrict__ B)
+                       PeCand* __restrict__ A, PeCand* __restrict__ B, u32* __restrict__ cnt1)
 {
     const long total = (long)*count_ptr;
     for (long item = blockIdx.x; item < total; item += gridDim.x) {
@@ -691,7 +699,7 @@ k_pe_filter_pairs_long(long n, ReadGeom gm, PeIns pi, ReadState st, PeState ps, 
             if ((threadIdx.x & 63) == 0) pe_filter_serial(a, na, b, nb, maxd, mind, ra, rb, la, lb);
             la = __shfl((int)la, 0, 64); lb = __shfl((int)lb, 0, 64);
         }
-        if ((threadIdx.x & 63) == 0) pe_filter_decide(ps, p, r1, r2, occ1, occ2, la, lb);
+        if ((threadIdx.x & 63) == 0) pe_filter_decide(ps, p, r1, r2, occ1, occ2, la, lb, cnt1);
     }
 }
 
@@ -733,13 +741,10 @@ k_filter_pe(DevIndex ix, const char* __restrict__ seq, PackedRows pr, ReadGeom g
 // the PE compaction (Schema.cpp:7480-7690): keep err <= k whose site+end differs from the previous candidate's
 // A lane walks its read's list; a list of more than 64 entries (a read inside a repeat family: hundreds to thousands) is walked by
 // the whole wave afterwards, 64 entries a step -- one such lane used to hold its wave for the length of its list.
-__global__ void __launch_bounds__(64)
-k_pe_compact(long n, long n2, ReadGeom gm, int round, ReadState st, PeState ps, PeCand* __restrict__ A, PeCand* __restrict__ B)
+// (the wave's lanes each bring a read r of their own, act: it has a list to compact; every lane of the wave must call)
+DEVI void pe_compact_lists(long r, bool act, const ReadGeom& gm, const ReadState& st, const PeState& ps, PeCand* __restrict__ A, PeCand* __restrict__ B)
 {
-    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63;
-    bool act = r < n2 && ps.vround[r] == round;
-    if (act) { const long p = r < n ? r : r - n; if (ps.dead[p]) act = false; }
     const long m = act ? (long)ps.len[r] : 0;
     const bool coop = m > 64;
     if (act && !coop) {
@@ -781,6 +786,29 @@ k_pe_compact(long n, long n2, ReadGeom gm, int round, ReadState st, PeState ps, 
         if (lane == src) ps.occ[rr] = occ;
     }
 }
+// one lane per read: every read scheduled in `round` whose pair is alive (--sensitive, and fast mode under BMBS_PE_ROUNDS=0)
+__global__ void __launch_bounds__(64)
+k_pe_compact(long n, long n2, ReadGeom gm, int round, ReadState st, PeState ps, PeCand* __restrict__ A, PeCand* __restrict__ B)
+{
+    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    bool act = r < n2 && ps.vround[r] == round;
+    if (act) { const long p = r < n ? r : r - n; if (ps.dead[p]) act = false; }
+    pe_compact_lists(r, act, gm, st, ps, A, B);
+}
+// fast mode: at most one mate of a pair is scheduled in a round, so one lane per PAIR takes that mate (the same reads as above, half
+// the lanes; mate 2's round byte is looked at only where mate 1's says no)
+__global__ void __launch_bounds__(64)
+k_pe_compact_pair(long n, ReadGeom gm, int round, ReadState st, PeState ps, PeCand* __restrict__ A, PeCand* __restrict__ B)
+{
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    long r = p;
+    bool act = false;
+    if (p < n && !ps.dead[p]) {
+        if (ps.vround[p] == round) act = true;
+        else if (ps.vround[p + n] == round) { r = p + n; act = true; }
+    }
+    pe_compact_lists(r, act, gm, st, ps, A, B);
+}
 
 // after round 1 of a both-unverified pair: filter_pairs_single_side (Schema.cpp:16186-16270)
 // The reference's merge loop, one lane per pair -- and, for a pair whose two lists hold more than 64 entries, by the whole wave:
@@ -788,7 +816,7 @@ k_pe_compact(long n, long n2, ReadGeom gm, int round, ReadState st, PeState ps, 
 // it (it drops b[j] only when the current a[i] is more than maxd above it, and then so is every later one; it leaves the scan of
 // a[i] only at a b[j] more than maxd above a[i], and then so is every later one), so every b[j] is decided by one binary search in a.
 __global__ void __launch_bounds__(64)
-k_pe_prune(long n, ReadGeom gm, PeIns pi, ReadState st, PeState ps, PeCand* __restrict__ A, PeCand* __restrict__ B)
+k_pe_prune(long n, ReadGeom gm, PeIns pi, ReadState st, PeState ps, PeCand* __restrict__ A, PeCand* __restrict__ B, u32* __restrict__ cnt2)
 {
     const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63;
@@ -822,7 +850,8 @@ k_pe_prune(long n, ReadGeom gm, PeIns pi, ReadState st, PeState ps, PeCand* __re
         return len2;
     };
     const bool coop = act && nb + occ_s > 64 && mind <= 0 && maxd >= 0;
-    if (act && !coop) ps.len[ro] = (u32)serial(pe_list(ps, st, A, B, rs), occ_s, pe_list(ps, st, A, B, ro), nb, maxd, mind);
+    u32 left = 0;                                   // what round 2 verifies of this lane's pair: the pruned list of a live `both` pair
+    if (act && !coop) { left = (u32)serial(pe_list(ps, st, A, B, rs), occ_s, pe_list(ps, st, A, B, ro), nb, maxd, mind); ps.len[ro] = left; }
     unsigned long long todo = __ballot(coop);
     while (todo) {
         const int src = __ffsll((long long)todo) - 1;
@@ -836,7 +865,7 @@ k_pe_prune(long n, ReadGeom gm, PeIns pi, ReadState st, PeState ps, PeCand* __re
         PeCand* b = pe_list(ps, st, A, B, ro2);
         // sites that wrapped below zero (the last ones of an ascending list) make the distances negative: the loop itself decides
         if ((a[na - 1].site >> 63) || (nbb && (b[nbb - 1].site >> 63))) {
-            if (lane == src) ps.len[ro2] = (u32)serial(a, na, b, nbb, mxd, mnd);
+            if (lane == src) { left = (u32)serial(a, na, b, nbb, mxd, mnd); ps.len[ro2] = left; }
             continue;
         }
         long len2 = 0;
@@ -853,6 +882,8 @@ k_pe_prune(long n, ReadGeom gm, PeIns pi, ReadState st, PeState ps, PeCand* __re
             if (keep) b[len2 + __popcll(kb & ((1ull << lane) - 1))] = e;
             len2 += __popcll(kb);
         }
-        if (lane == src) ps.len[ro2] = (u32)len2;
+        if (lane == src) { left = (u32)len2; ps.len[ro2] = left; }
     }
+    // BMBS_PE_ROUNDS=1: the pair's entries on round 2's work list, (both[p] && !dead[p]) ? len[ro] : 0 after the updates above
+    if (cnt2 && p < n) cnt2[p] = left;
 }

@@ -50,14 +50,10 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan_partial(const u32* in, u64 
     (void)block_scan_incl(s, sh, total);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
 }
-// list != nullptr: `in` holds 0/1 flags and the positions of the ones are written, in order, to list[]; the offsets
-// themselves are not stored (the work lists of the seeding stages need nothing else)
-__global__ void __launch_bounds__(SCAN_BLOCK) k_scan_final(const u32* in, u64 n, const u64* __restrict__ block_sums, u64* out, u32* list, int nz, const u64* __restrict__ n_dev, u64* total)
+// The head of the second launch: the thread's eight values into x, the sum of everything before them returned (what the tiles before
+// this one hold -- 256 threads over blockIdx.x sums -- plus what the threads before this one hold); the last tile leaves the total
+DEVI u64 scan_final_run(const u32* in, u64 n, const u64* __restrict__ block_sums, int nz, u64 base, u32 x[SCAN_ITEMS], u64* sh, u64* total)
 {
-    __shared__ u64 sh[SCAN_BLOCK / 64];
-    if (n_dev) { const u64 nd = *n_dev; if (nd < n) n = nd; }
-    const u64 base = (u64)blockIdx.x * SCAN_BLOCK * SCAN_ITEMS + (u64)threadIdx.x * SCAN_ITEMS;
-    u32 x[SCAN_ITEMS];
     scan_load8(in, base, n, x);
     if (nz) {
 #pragma unroll
@@ -66,7 +62,6 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan_final(const u32* in, u64 n,
     u64 s = 0;
 #pragma unroll
     for (int j = 0; j < SCAN_ITEMS; j++) s += x[j];
-    // what the tiles before this one hold: 256 threads over blockIdx.x sums
     u64 before = 0;
     for (u32 i = threadIdx.x; i < blockIdx.x; i += SCAN_BLOCK) before += block_sums[i];
     u64 prefix;
@@ -74,7 +69,17 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan_final(const u32* in, u64 n,
     u64 tot;
     const u64 incl = block_scan_incl(s, sh, tot);
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *total = prefix + tot;
-    u64 run = incl - s + prefix;
+    return incl - s + prefix;
+}
+// list != nullptr: `in` holds 0/1 flags and the positions of the ones are written, in order, to list[]; the offsets
+// themselves are not stored (the work lists of the seeding stages need nothing else)
+__global__ void __launch_bounds__(SCAN_BLOCK) k_scan_final(const u32* in, u64 n, const u64* __restrict__ block_sums, u64* out, u32* list, int nz, const u64* __restrict__ n_dev, u64* total)
+{
+    __shared__ u64 sh[SCAN_BLOCK / 64];
+    if (n_dev) { const u64 nd = *n_dev; if (nd < n) n = nd; }
+    const u64 base = (u64)blockIdx.x * SCAN_BLOCK * SCAN_ITEMS + (u64)threadIdx.x * SCAN_ITEMS;
+    u32 x[SCAN_ITEMS];
+    u64 run = scan_final_run(in, n, block_sums, nz, base, x, sh, total);
     if (list) {
 #pragma unroll
         for (int j = 0; j < SCAN_ITEMS; j++) if (base + j < n && x[j]) { list[run] = (u32)(base + j); run += x[j]; }
@@ -93,6 +98,27 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan_final(const u32* in, u64 n,
     }
     if (base <= n && n < base + SCAN_ITEMS) out[n] = run;                   // the thread that owns position n writes the total
     if (n % ((u64)SCAN_BLOCK * SCAN_ITEMS) == 0 && n && base + SCAN_ITEMS == n) out[n] = run;
+}
+// Expand mode (the work lists of the paired-end verification rounds, fast mode): `in` holds one count per PAIR, and instead of the
+// offsets the work list itself is written -- for a pair p with a count m the m entries (read, 0) .. (read, m - 1) from work_r / work_i
+// [its offset] on, where read is the pair's mate scheduled in `round`: p if vround[p] == round, else p + n.  vround is read for pairs
+// with a count only.  The list is in the order of the pairs; nothing but the total is left behind.
+__global__ void __launch_bounds__(SCAN_BLOCK) k_scan_expand(const u32* in, u64 n, const u64* __restrict__ block_sums, const u8* __restrict__ vround, int round,
+                                                            u32* __restrict__ work_r, u32* __restrict__ work_i, u64* total)
+{
+    __shared__ u64 sh[SCAN_BLOCK / 64];
+    const u64 base = (u64)blockIdx.x * SCAN_BLOCK * SCAN_ITEMS + (u64)threadIdx.x * SCAN_ITEMS;
+    u32 x[SCAN_ITEMS];
+    u64 run = scan_final_run(in, n, block_sums, 0, base, x, sh, total);
+#pragma unroll
+    for (int j = 0; j < SCAN_ITEMS; j++) {
+        const u32 m = x[j];                                     // (scan_load8 gives 0 beyond n)
+        if (!m) continue;
+        const u64 p = base + j;
+        const u32 r = (u32)(vround[p] == round ? p : p + n);
+        for (u32 i = 0; i < m; i++) { work_r[run + i] = r; work_i[run + i] = i; }
+        run += m;
+    }
 }
 // ------------------------------------------------------------------------------------------------
 // The same scan in ONE launch (a chained scan with look-back): a block takes its tile from a ticket (so every tile before it is

@@ -1,6 +1,7 @@
 // tools/scan_kbench.hip -- the two scans of k_scan.hip alone: the chained one-launch form against the two-launch form and a host prefix
 // sum, over sizes around the tile edges and the mapping path's sizes, many scans back to back on one status buffer (the epoch is what
-// keeps an earlier scan's words apart).
+// keeps an earlier scan's words apart).  And the two-launch form's expand mode (k_scan_expand: per-pair counts -> the (read, index) work
+// list of a paired-end verification round) against a host expansion, over the same sizes.
 // build (here):  hipcc -O3 -std=c++17 --offload-arch=gfx950 -o tools/scan_kbench tools/scan_kbench.hip
 // run (GPU box): timeout 120 ./tools/scan_kbench
 #include <hip/hip_runtime.h>
@@ -65,6 +66,54 @@ int main()
             if (k != tot) ok = false;
             if (!ok) { printf("chain list DIFFERS n=%llu\n", n); bad++; }
         }
+    }
+    // expand mode: counts per pair (two in three none, most of the others a few, one in 64 of those up to 299), the round byte of
+    // mate 1 decides which mate's number is written; the list against a host expansion, the slot behind its end untouched
+    {
+        std::vector<u32> hcnt(N); std::vector<u8> hvr(N);
+        u64 cap = 0;
+        for (u64 i = 0; i < N; i++) {
+            hcnt[i] = (rnd() % 3 == 0) ? ((rnd() % 64 == 0) ? (u32)(rnd() % 300) : 1u + (u32)(rnd() % 4)) : 0u;
+            hvr[i] = (u8)(rnd() % 3);
+            cap += hcnt[i];
+        }
+        u32 *d_cnt, *d_wr, *d_wi; u8* d_vr;
+        CK(hipMalloc(&d_cnt, N * 4)); CK(hipMemcpy(d_cnt, hcnt.data(), N * 4, hipMemcpyHostToDevice));
+        CK(hipMalloc(&d_vr, N)); CK(hipMemcpy(d_vr, hvr.data(), N, hipMemcpyHostToDevice));
+        CK(hipMalloc(&d_wr, (cap + 1) * 4)); CK(hipMalloc(&d_wi, (cap + 1) * 4));
+        std::vector<u32> wr(cap + 1), wi(cap + 1);
+        for (u64 n : sizes) for (int round = 1; round <= 2; round++) {
+            if (n * 2 > 0xffffffffull) continue;
+            const u64 nb = n ? (n + per - 1) / per : 1;
+            u64 want = 0;
+            for (u64 i = 0; i < n; i++) want += hcnt[i];
+            CK(hipMemset(d_wr, 0xee, (want + 1) * 4)); CK(hipMemset(d_wi, 0xee, (want + 1) * 4));
+            hipLaunchKernelGGL(k_scan_partial, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, 0, d_cnt, n, d_bs, 0, (const u64*)nullptr);
+            hipLaunchKernelGGL(k_scan_expand, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, 0, d_cnt, n, d_bs, d_vr, round, d_wr, d_wi, d_total + 1);
+            u64 tot; CK(hipMemcpy(&tot, d_total + 1, 8, hipMemcpyDeviceToHost));
+            CK(hipMemcpy(wr.data(), d_wr, (want + 1) * 4, hipMemcpyDeviceToHost)); CK(hipMemcpy(wi.data(), d_wi, (want + 1) * 4, hipMemcpyDeviceToHost));
+            bool ok = tot == want && wr[want] == 0xeeeeeeeeu && wi[want] == 0xeeeeeeeeu;
+            u64 k = 0;
+            for (u64 i = 0; i < n && ok; i++) {
+                const u32 r = (u32)(hvr[i] == round ? i : i + n);
+                for (u32 j = 0; j < hcnt[i]; j++, k++) if (wr[k] != r || wi[k] != j) { ok = false; break; }
+            }
+            if (!ok) { printf("expand DIFFERS n=%llu round=%d\n", n, round); bad++; }
+        }
+        // the expand pair against count-free offsets of the same length (what the round-3 form stored on top of the list)
+        hipEvent_t a, b; CK(hipEventCreate(&a)); CK(hipEventCreate(&b));
+        for (u64 n : {(u64)2500000, (u64)10000000}) {
+            const u64 nb = (n + per - 1) / per;
+            float t;
+            for (int i = 0; i < 23; i++) {
+                if (i == 3) CK(hipEventRecord(a));
+                hipLaunchKernelGGL(k_scan_partial, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, 0, d_cnt, n, d_bs, 0, (const u64*)nullptr);
+                hipLaunchKernelGGL(k_scan_expand, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, 0, d_cnt, n, d_bs, d_vr, 1, d_wr, d_wi, d_total + 1);
+            }
+            CK(hipEventRecord(b)); CK(hipEventSynchronize(b)); CK(hipEventElapsedTime(&t, a, b));
+            printf("n=%9llu: expand (two launches, list written) %.1f us per scan\n", n, t * 50);
+        }
+        CK(hipFree(d_cnt)); CK(hipFree(d_vr)); CK(hipFree(d_wr)); CK(hipFree(d_wi));
     }
     // timing at the mapping path's sizes
     hipEvent_t a, b; CK(hipEventCreate(&a)); CK(hipEventCreate(&b));
