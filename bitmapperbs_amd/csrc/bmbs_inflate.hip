@@ -10,7 +10,9 @@
 //   by their lanes, matches copied by the whole wave; the block's CRC-32 and ISIZE are checked against its trailer (segments
 //   combined with x^(8n) mod P as in bmbs_bam.hip).
 // Everything zlib's inflate refuses is refused (err[block] != 0): over-subscribed / incomplete codes, missing end-of-block code,
-// reserved block type, distance too far back, stored-length check, output longer than the trailer says, CRC mismatch.
+// reserved block type, distance too far back, stored-length check, output longer than the trailer says, CRC mismatch, and deflate data
+// whose final block does not end in the last byte in front of the trailer (zlib reads CRC-32 and ISIZE from where the data ends: a
+// stream that runs on into the trailer's bytes, or stops short of them, has another trailer there).
 #ifndef BMBS_INFLATE_HIP
 #define BMBS_INFLATE_HIP
 #include "bmbs_bytes.h"
@@ -213,6 +215,7 @@ DEVI void inf_wave(const u8* z, const u8* zend, u32 start_bit, u8* out, u32 isiz
     u32 fenced = 0;                                       // every byte of the text below this offset is visible to every lane
     S last_byte = (S)0;                                   // the symbol at n_out - 1 (wave-uniform)
     bool last = false;
+    u32 end_byte = 0;                                     // the byte offset behind the block read last (wave-uniform)
     while (!status && !last) {
         // ---- block header (lane 0 reads, the wave follows)
         u32 btype = 0;
@@ -235,6 +238,7 @@ DEVI void inf_wave(const u8* z, const u8* zend, u32 start_bit, u8* out, u32 isiz
             n_out += len;
             if (len) last_byte = (S)z[at + len - 1];
             if (lane == 0) in.init(z + at + len, zend);
+            end_byte = (u32)(at + len);
             continue;
         }
         // ---- the two codes
@@ -545,9 +549,11 @@ DEVI void inf_wave(const u8* z, const u8* zend, u32 start_bit, u8* out, u32 isiz
             }
             INF_T(7);
         }
+        end_byte = (bp + 7) >> 3;
         // the next block header is read by lane 0 from bp
         if (lane == 0) { in.init(z + (bp >> 3), zend); in.refill(); in.drop((int)(bp & 7u)); }
     }
+    if (!status && end_byte != (u32)(zend - z)) status = 10;         // the final block ends inside the trailer, or short of it
     status_r = status; n_out_r = n_out;
 #ifdef INF_PROFILE
     prof[15] = clock64() - t_begin;

@@ -608,7 +608,8 @@ private:
         k.redo.reset(new OutBuf<u8>);
         if (!k.redo->reserve(opt_.span * 5)) { k.st = ST_ERROR; k.why = "out of memory"; return; }
         memcpy(k.redo->mem, window_.data(), WIN);
-        k.ends.clear();
+        // (k.ends, the member ends the task's own decode met, stay until the outcome is known: where the decode from the known boundary
+        // lands on the task's start they follow the ones met here; otherwise they are replaced)
         std::unique_ptr<Tables> dyn(new Tables);
         // up to the task's own start when that lies ahead (its symbols then follow), else to the boundary behind the next cut
         const bool join = k.found && k.st != ST_ERROR && k.start_bit > known_bit_ && k.start_bit < stop;

@@ -123,9 +123,17 @@ def inflate(data, pos=0, trace=True):
     ll_lens, d_lens, header_bits (from BFINAL to the last code length); for btype 1 and 2 tokens, a list of ("lit", byte) and
     ("match", length, distance, length symbol, distance symbol), the end-of-block symbol not included; for btype 0 `stored_len`; `bits`,
     the size of the whole block.
-    trace=False keeps no token lists."""
-    br = _Bits(data, pos)
+    trace=False keeps no token lists.  A DeflateError carries the bytes that were read before it as its `partial`."""
     out = bytearray()
+    try:
+        return _inflate(data, pos, trace, out)
+    except DeflateError as e:
+        e.partial = bytes(out)
+        raise
+
+
+def _inflate(data, pos, trace, out):
+    br = _Bits(data, pos)
     blocks = []
     while True:
         bit0 = br.bit_pos()

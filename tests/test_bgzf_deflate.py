@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import deflate_spec as ds
+from deflate_writer import BitWriter as _BitWriter, hand_built as _hand_built
 
 BLK = 0xff00                                  # input bytes of a BGZF block
 HDR = 36                                      # block_size word + the 32-byte core of a BAM record
@@ -302,37 +303,6 @@ def test_spec_inflater_reads_the_deep_trees_zlib_writes():
         out, blocks, end = ds.inflate(z)
         assert out == data and end == len(z)
         assert max(max(b["ll_lens"]) for b in blocks if b["btype"] == 2) == 15
-
-
-class _BitWriter:
-    def __init__(self):
-        self.v = 0
-        self.n = 0
-
-    def put(self, value, bits):
-        self.v |= value << self.n
-        self.n += bits
-
-    def code(self, code, bits):                             # a Huffman code: most significant bit first
-        for i in range(bits - 1, -1, -1):
-            self.put((code >> i) & 1, 1)
-
-    def bytes(self):
-        return self.v.to_bytes((self.n + 7) // 8, "little")
-
-
-def _hand_built(ll, dist, body):
-    """a dynamic block whose code-length code gives the lengths 0, 1, 2 and 3 two bits each: ll / dist = the code lengths to declare,
-    body(w) writes what follows the header"""
-    w = _BitWriter()
-    w.put(1, 1); w.put(2, 2); w.put(len(ll) - 257, 5); w.put(len(dist) - 1, 5); w.put(19 - 4, 4)
-    cl = {0: 2, 1: 2, 2: 2, 3: 2}
-    for s in ds.CL_ORDER:
-        w.put(cl.get(s, 0), 3)
-    for l in list(ll) + list(dist):
-        w.code(l, 2)                                        # (four codes of two bits: the canonical code of symbol s is s)
-    body(w)
-    return w.bytes()
 
 
 def _both(z):
