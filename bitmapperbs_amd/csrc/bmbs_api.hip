@@ -13,7 +13,7 @@ int ensure(Lane* c, DevBuf& b, size_t bytes, bool zero)
     if (bytes == 0) bytes = 16;
     if (b.cap >= bytes) return BMBS_OK;
     size_t want = bytes + bytes / 8 + 256;
-    if (c->kn.arena && want <= ((size_t)256 << 20)) {              // larger ones keep a hipMalloc of their own (freed when they grow)
+    if (want <= ((size_t)256 << 20)) {              // larger ones keep a hipMalloc of their own (freed when they grow)
         // an arena buffer leaves its old region behind when it grows: growing by half bounds what a stream of slowly rising needs strands
         if (b.cap) want = std::min<size_t>(std::max(want, b.cap + b.cap / 2), (size_t)256 << 20);
         void* p = c->arena.alloc(want);
@@ -1633,7 +1633,7 @@ int dispatch_host(bmbs_ctx* X, bool pe, const HostIn& in, int32_t L, int32_t str
             for (auto& a : c->acc) if (!strcmp(a.name, "k_qual_expand")) { a.ms += t; found = true; break; }
             if (!found) c->acc.push_back({"k_qual_expand", (double)t});
         }
-        const bool cs = c->kn.copy_streams && c->up_stream && c->down_stream && c->ev_up && c->ev_k;
+        const bool cs = c->up_stream && c->down_stream && c->ev_up && c->ev_k;
         hipStream_t dsn = cs ? c->down_stream : c->stream;
         if (c->n_retries != retries0)               // the chunk was issued again with exact sizes: the records copied behind the first attempt are stale
             HIPCHK(c, hipMemcpyAsync(results + o.off * rpu, c->out_res.p, (u64)o.m * rpu * 32, hipMemcpyDeviceToHost, dsn));
@@ -1658,7 +1658,7 @@ int dispatch_host(bmbs_ctx* X, bool pe, const HostIn& in, int32_t L, int32_t str
             ENS(c, c->cig_pool, pool * 4);
             int ds = 0;
             const size_t ro = (size_t)off * (size_t)stride;
-            const bool cs = c->kn.copy_streams && c->up_stream && c->down_stream && c->ev_up && c->ev_k;
+            const bool cs = c->up_stream && c->down_stream && c->ev_up && c->ev_k;
             hipStream_t us = cs ? c->up_stream : c->stream, dsn = cs ? c->down_stream : c->stream;
             int r1 = BMBS_OK;
             // One upload at a time per device (the text calls' rule, bmbs_textpath.hip): four lanes that upload side by side share the
@@ -2251,7 +2251,6 @@ extern "C" int bmbs_reserve(bmbs_ctx* X, uint64_t bytes_per_lane)
 {
     if (!X) return BMBS_EINVAL;
     for (Lane* c : X->lanes) {
-        if (!c->kn.arena) continue;
         HIPCHK(c, hipSetDevice(c->dev));
         size_t have = 0;
         for (const auto& sl : c->arena.slabs) have += sl.cap - sl.used;
@@ -2276,7 +2275,7 @@ extern "C" int bmbs_host_prefault(bmbs_ctx* X, void* p, uint64_t bytes, int32_t 
     DevBuf tmp;
     void* d = nullptr;
     if (hipMalloc(&d, piece) != hipSuccess) return BMBS_ENOMEM;
-    hipStream_t st = c->down_stream ? c->down_stream : c->stream;
+    hipStream_t st = down_stream_of(c);
     hipError_t e = hipSuccess;
     for (u64 o = 0; o < bytes && e == hipSuccess; o += piece) {
         const u64 m = std::min(piece, bytes - o);

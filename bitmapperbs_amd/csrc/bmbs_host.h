@@ -89,7 +89,6 @@ struct Knobs {
     int seed_stage = 1;         // BMBS_SEED_STAGE: 1 (default) k_seed_first writes its chunk's results coalesced out of LDS, k_seed_decide_p keeps back
                                 // the exit-A record nobody reads (except under --sensitive); 0 both store lane by lane (the round-6 forms)
     double cap_scale = 1.0;     // BMBS_CAP_SCALE: scales the learned capacities (tests: a small value forces the repeat-with-exact-sizes path)
-    static const bool copy_streams = true, copy_lock = true, arena = true;     // (measured in round 3; the alternatives are gone)
     void read()
     {
         auto is = [](const char* e, const char* v) { return e && !strcmp(e, v); };
@@ -321,6 +320,11 @@ struct Lane {
     u64 n_retries = 0;
 };
 
+
+// the streams a lane's copies from and to host buffers go on: its copy streams, or its kernel stream where lane_copy_streams could not
+// create them (it ignores the result)
+inline hipStream_t up_stream_of(const Lane* c) { return c->up_stream ? c->up_stream : c->stream; }
+inline hipStream_t down_stream_of(const Lane* c) { return c->down_stream ? c->down_stream : c->stream; }
 
 // the public handle: parameters + the lanes (lane 0 owns the index unless the context shares another one's)
 struct bmbs_ctx {

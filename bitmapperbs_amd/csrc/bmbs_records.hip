@@ -46,7 +46,7 @@ static int records_stage(Lane* c, RecIn& r, const char* records, u64 bytes, cons
     if (clip) ENS(c, *clip_dst, n * 4 + 64);
     {
         std::lock_guard<std::mutex> up(g_h2d_mu[c->dev & 15]);
-        hipStream_t us = c->up_stream ? c->up_stream : c->stream;
+        hipStream_t us = up_stream_of(c);
         const u64 piece = 128ull << 20;
         for (u64 o = 0; o < bytes; o += piece) HIPCHK(c, hipMemcpyAsync(r.in.as<char>() + o, records + o, std::min(piece, bytes - o), hipMemcpyHostToDevice, us));
         HIPCHK(c, hipMemcpyAsync(r.len.p, len, n * 4, hipMemcpyHostToDevice, us));
@@ -127,7 +127,7 @@ static int lane_text_sorted_index(Lane* c, uint64_t* key, uint32_t* len, int64_t
                              "the arrays are too small (n tells what is needed)")) return rc;
     if (!c->st.n) return BMBS_OK;
     HIPCHK(c, hipSetDevice(c->dev));
-    hipStream_t ds = c->down_stream ? c->down_stream : c->stream;
+    hipStream_t ds = down_stream_of(c);
     HIPCHK(c, hipMemcpyAsync(key, c->bs_key2.p, (size_t)c->st.n * 8, hipMemcpyDeviceToHost, ds));
     HIPCHK(c, hipMemcpyAsync(len, c->bs_slen.p, (size_t)c->st.n * 4, hipMemcpyDeviceToHost, ds));
     HIPCHK(c, hipStreamSynchronize(ds));
@@ -340,7 +340,7 @@ static int lane_dup_select(Lane* c, const bmbs_dup_sig* sig, int64_t n_in, uint8
     ENS(c, c->dp_idx, n * 4 + 64); ENS(c, c->dp_idx2, n * 4 + 64); ENS(c, c->dp_dup, n + 64);
     {
         std::lock_guard<std::mutex> up(g_h2d_mu[c->dev & 15]);
-        hipStream_t us = c->up_stream ? c->up_stream : c->stream;
+        hipStream_t us = up_stream_of(c);
         HIPCHK(c, hipMemcpyAsync(c->dp_sig.p, sig, n * sizeof(bmbs_dup_sig), hipMemcpyHostToDevice, us));
         HIPCHK(c, hipStreamSynchronize(us));
     }
@@ -619,7 +619,7 @@ static int lane_bam_sort_methyl(Lane* c, const uint32_t* clip, const bmbs_methyl
     if (clip) {
         ENS(c, c->mt_clip, n * 4 + 64);
         std::lock_guard<std::mutex> up(g_h2d_mu[c->dev & 15]);
-        hipStream_t us = c->up_stream ? c->up_stream : c->stream;
+        hipStream_t us = up_stream_of(c);
         HIPCHK(c, hipMemcpyAsync(c->mt_clip.p, clip, n * 4, hipMemcpyHostToDevice, us));
         HIPCHK(c, hipStreamSynchronize(us));
     }
@@ -634,7 +634,7 @@ static int lane_methyl_sites(Lane* c, bmbs_methyl_site* site, int64_t cap, int64
                              "the array is too small (n tells what is needed)")) return rc;
     if (!c->mc.sites) return BMBS_OK;
     HIPCHK(c, hipSetDevice(c->dev));
-    hipStream_t ds = c->down_stream ? c->down_stream : c->stream;
+    hipStream_t ds = down_stream_of(c);
     HIPCHK(c, hipMemcpyAsync(site, c->mt_site.p, (size_t)c->mc.sites * sizeof(bmbs_methyl_site), hipMemcpyDeviceToHost, ds));
     HIPCHK(c, hipStreamSynchronize(ds));
     return BMBS_OK;
@@ -648,7 +648,7 @@ static int lane_methyl_mbias(Lane* c, uint64_t* table, int64_t cap, int64_t* n)
                              "the array is too small (n tells what is needed)")) return rc;
     if (c->mc.mbias_zero) { memset(table, 0, (size_t)entries * 8); return BMBS_OK; }
     HIPCHK(c, hipSetDevice(c->dev));
-    hipStream_t ds = c->down_stream ? c->down_stream : c->stream;
+    hipStream_t ds = down_stream_of(c);
     HIPCHK(c, hipMemcpyAsync(table, c->mt_mbias.p, (size_t)entries * 8, hipMemcpyDeviceToHost, ds));
     HIPCHK(c, hipStreamSynchronize(ds));
     return BMBS_OK;

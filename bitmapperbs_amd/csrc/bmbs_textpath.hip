@@ -23,9 +23,16 @@ void textpath_device_init(Lane* c)
     (void)hipMemcpyToSymbol(HIP_SYMBOL(c_x2n), x2n, sizeof x2n);
 }
 
+// ---- one clock for the host-side phase times of this file (bmbs_text_times; BMBS_TEXT_TRACE=1, a diagnostic: a line per call on stderr)
+static double wall() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
+static bool text_trace() { static const bool on = getenv("BMBS_TEXT_TRACE") != nullptr; return on; }
+// a call's phase marks, each taken when its phase has ended (an open call: uploaded = inflated, delivered = tails); down_wait: what of the download was not the copy
+struct TextClock { double start = 0, uploaded = 0, lines = 0, records = 0, mapped = 0, sized = 0, written = 0, delivered = 0, down_wait = 0; };
+
 // ------------------------------------------------------------------------------------------------
 // FASTQ text in (the host only finds the line starts; the rows are cut out of the text on the device)
-struct FqDev { const char* text; const u32* seq_off; const u32* qual_off; const u16* seq_len; const u16* qual_len; };
+// what the row stage reads of one FASTQ text on the device: the text, and where each record's sequence and quality lines are
+struct FqSrc { const char* text; const u32* seq_off; const u32* qual_off; const u16* seq_len; const u16* qual_len; };
 
 int fastq_check(Lane* c, const bmbs_fastq_view* v, int64_t n, int L_max)
 {
@@ -42,7 +49,7 @@ int fastq_check(Lane* c, const bmbs_fastq_view* v, int64_t n, int L_max)
     return BMBS_OK;
 }
 // text + index arrays of one file to the device; idx_at = byte offset of this file's arrays inside c->fq_idx
-int fastq_upload(Lane* c, DevBuf& dtext, const bmbs_fastq_view* v, u64 n, u64 idx_at, FqDev& out)
+int fastq_upload(Lane* c, DevBuf& dtext, const bmbs_fastq_view* v, u64 n, u64 idx_at, FqSrc& out)
 {
     ENS(c, dtext, v->text_bytes + 64);
     HIPCHK(c, hipMemcpyAsync(dtext.p, v->text, v->text_bytes, hipMemcpyHostToDevice, c->stream));
@@ -56,74 +63,56 @@ int fastq_upload(Lane* c, DevBuf& dtext, const bmbs_fastq_view* v, u64 n, u64 id
     return BMBS_OK;
 }
 
-static int lane_map_se_fastq(Lane* c, const bmbs_fastq_view* reads, int64_t n_reads, int32_t L_max, int32_t uniform, int32_t pbat,
-                                 bmbs_result* results, uint32_t* cigar_pool, int64_t cigar_cap, int64_t* n_cigar_used)
+// The row stage: n records (pairs: src[1] is mate 2's text) of at most L bases -> the lane's read rows (k_fastq_rows), and in P the
+// call that maps them into out_res / cig_pool.  Sizes the lane's row, quality, length, result and CIGAR buffers.  pbat (single end):
+// every read reverse-complemented, its qualities mirrored; uniform: the caller knows that every read has L bases
+static int fastq_rows(Lane* c, bool pe, const FqSrc* src, u64 n, int L, int pbat, bool uniform, Pending& P)
 {
-    if (!c) return BMBS_EINVAL;
-    HIPCHK(c, hipSetDevice(c->dev));
-    if (n_cigar_used) *n_cigar_used = 0;
-    if (n_reads <= 0) return BMBS_OK;
-    if (L_max <= 0 || L_max > BMBS_MAX_READ) { c->err = "bad read geometry"; return BMBS_EINVAL; }
-    { const int r0 = fastq_check(c, reads, n_reads, L_max); if (r0) return r0; }
-    const u64 n = (u64)n_reads;
-    const int ds = (L_max + 15) / 16 * 16;
-    const int k = threshold_k(c->prm, L_max);
-    const u64 pool = n * (u64)cigar_ops_bound(c->prm, L_max, k);
-    ENS(c, c->out_res, n * 32); ENS(c, c->cig_pool, pool * 4);
-    ENS(c, c->in_seq, n * (u64)ds + 64); ENS(c, c->in_qual, n * (u64)ds + 64); ENS(c, c->in_len, n * 2 + 16);
-    ENS(c, c->fq_idx, n * 12 + 64);
-    FqDev f;
-    { const int r1 = fastq_upload(c, c->fq_text1, reads, n, 0, f); if (r1) return r1; }
-    hipLaunchKernelGGL(k_fastq_rows, dim3(nblk(n * (u64)(ds / 16), 256)), dim3(256), 0, c->stream, f.text, f.seq_off, f.qual_off, f.seq_len,
-                       f.qual_len, (long)n, ds, pbat ? 1 : 0, pbat ? 1 : 0, c->in_seq.as<char>(), c->in_qual.as<char>(), c->in_len.as<u16>());
-    Pending P;
-    P.pe = false; P.L = L_max; P.stride = ds; P.n = n_reads;
-    P.a[0] = (uint64_t)c->in_seq.p; P.a[1] = (uint64_t)c->in_qual.p; P.d_len = uniform ? nullptr : c->in_len.as<u16>();
+    const u64 n2 = pe ? 2 * n : n;
+    const int ds = (L + 15) / 16 * 16;
+    const u64 pool = n2 * (u64)cigar_ops_bound(c->prm, L, threshold_k(c->prm, L));
+    DevBuf& rows = pe ? c->pe_seq : c->in_seq;
+    ENS(c, c->out_res, n2 * 32); ENS(c, c->cig_pool, pool * 4); ENS(c, c->in_len, n2 * 2 + 16);
+    ENS(c, rows, n2 * (u64)ds + 64); ENS(c, c->in_qual, n * (u64)ds + 64);
+    if (pe) ENS(c, c->in_qual2, n * (u64)ds + 64);
+    // pairs: rows 0..n-1 = mate 1 as read, rows n..2n-1 = mate 2 reverse-complemented; the qualities stay in FASTQ order (qual_row)
+    char* const seq = rows.as<char>();
+    char* const seq2 = seq + n * (u64)ds;
+    const unsigned g = nblk(n * (u64)(ds / 16), 256);
+    hipLaunchKernelGGL(k_fastq_rows, dim3(g), dim3(256), 0, c->stream, src[0].text, src[0].seq_off, src[0].qual_off, src[0].seq_len, src[0].qual_len, (long)n, ds,
+                       pbat, pbat, seq, c->in_qual.as<char>(), c->in_len.as<u16>());
+    if (pe)
+        hipLaunchKernelGGL(k_fastq_rows, dim3(g), dim3(256), 0, c->stream, src[1].text, src[1].seq_off, src[1].qual_off, src[1].seq_len, src[1].qual_len, (long)n, ds,
+                           1, 0, seq2, c->in_qual2.as<char>(), c->in_len.as<u16>() + n);
+    P = Pending();
+    P.pe = pe; P.L = L; P.stride = ds; P.n = (int64_t)n; P.prepared = pe;
+    P.a[0] = (uint64_t)seq; P.a[1] = (uint64_t)c->in_qual.p;
+    if (pe) { P.a[2] = (uint64_t)seq2; P.a[3] = (uint64_t)c->in_qual2.p; }
+    P.d_len = uniform ? nullptr : c->in_len.as<u16>();
     P.d_results = (uint64_t)c->out_res.p; P.d_cigar_pool = (uint64_t)c->cig_pool.p; P.cigar_cap = (int64_t)pool;
-    int rc = lane_enqueue(c, P, true);
-    if (rc) return rc;
-    rc = lane_settle(c);                         // counts (and, rarely, the repeat with exact sizes) before anything is copied back
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(results, c->out_res.p, n * 32, hipMemcpyDeviceToHost, c->stream));
-    const u64 used = c->last_n_jobs * (u64)c->last_max_ops;
-    if (used > (u64)cigar_cap) { c->err = "host cigar pool too small"; (void)hipStreamSynchronize(c->stream); return BMBS_ENOMEM; }
-    if (used) HIPCHK(c, hipMemcpyAsync(cigar_pool, c->cig_pool.p, used * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (n_cigar_used) *n_cigar_used = (int64_t)used;
     return BMBS_OK;
 }
 
-static int lane_map_pe_fastq(Lane* c, const bmbs_fastq_view* mate1, const bmbs_fastq_view* mate2, int64_t n_pairs, int32_t L_max,
-                                 int32_t uniform, bmbs_result* results, uint32_t* cigar_pool, int64_t cigar_cap, int64_t* n_cigar_used)
+// bmbs_map_se_fastq / bmbs_map_pe_fastq: check, upload, row stage, mapping, records and CIGAR words back to the host
+static int lane_map_fastq(Lane* c, bool pe, const bmbs_fastq_view* const* views, int64_t n_in, int32_t L_max, int32_t uniform, int32_t pbat,
+                          bmbs_result* results, uint32_t* cigar_pool, int64_t cigar_cap, int64_t* n_cigar_used)
 {
     if (!c) return BMBS_EINVAL;
     HIPCHK(c, hipSetDevice(c->dev));
     if (n_cigar_used) *n_cigar_used = 0;
-    if (n_pairs <= 0) return BMBS_OK;
+    if (n_in <= 0) return BMBS_OK;
     if (L_max <= 0 || L_max > BMBS_MAX_READ) { c->err = "bad read geometry"; return BMBS_EINVAL; }
-    { int r0 = fastq_check(c, mate1, n_pairs, L_max); if (r0) return r0; r0 = fastq_check(c, mate2, n_pairs, L_max); if (r0) return r0; }
-    const u64 n = (u64)n_pairs, n2 = 2 * n;
-    const int ds = (L_max + 15) / 16 * 16;
-    const int k = threshold_k(c->prm, L_max);
-    const u64 pool = n2 * (u64)cigar_ops_bound(c->prm, L_max, k);
-    ENS(c, c->out_res, n2 * 32); ENS(c, c->cig_pool, pool * 4);
-    ENS(c, c->pe_seq, n2 * (u64)ds + 64); ENS(c, c->in_qual, n * (u64)ds + 64); ENS(c, c->in_qual2, n * (u64)ds + 64); ENS(c, c->in_len, n2 * 2 + 16);
-    ENS(c, c->fq_idx, n2 * 12 + 128);
-    FqDev f1, f2;
-    { int r1 = fastq_upload(c, c->fq_text1, mate1, n, 0, f1); if (r1) return r1; r1 = fastq_upload(c, c->fq_text2, mate2, n, (n * 12 + 63) & ~63ull, f2); if (r1) return r1; }
-    // rows 0..n-1 = mate 1 as read, rows n..2n-1 = mate 2 reverse-complemented; the qualities stay in FASTQ order (qual_row)
-    char* seq_all = c->pe_seq.as<char>();
-    const unsigned g = nblk(n * (u64)(ds / 16), 256);
-    hipLaunchKernelGGL(k_fastq_rows, dim3(g), dim3(256), 0, c->stream, f1.text, f1.seq_off, f1.qual_off, f1.seq_len, f1.qual_len, (long)n, ds, 0, 0,
-                       seq_all, c->in_qual.as<char>(), c->in_len.as<u16>());
-    hipLaunchKernelGGL(k_fastq_rows, dim3(g), dim3(256), 0, c->stream, f2.text, f2.seq_off, f2.qual_off, f2.seq_len, f2.qual_len, (long)n, ds, 1, 0,
-                       seq_all + n * (u64)ds, c->in_qual2.as<char>(), c->in_len.as<u16>() + n);
+    const int nf = pe ? 2 : 1;
+    for (int f = 0; f < nf; f++) { const int r0 = fastq_check(c, views[f], n_in, L_max); if (r0) return r0; }
+    const u64 n = (u64)n_in, n2 = (u64)nf * n;
+    ENS(c, c->fq_idx, n2 * 12 + 64 * (u64)nf);
+    FqSrc src[2] = {};
+    DevBuf* const text[2] = {&c->fq_text1, &c->fq_text2};
+    for (int f = 0; f < nf; f++) { const int r1 = fastq_upload(c, *text[f], views[f], n, f ? (n * 12 + 63) & ~63ull : 0, src[f]); if (r1) return r1; }
     Pending P;
-    P.pe = true; P.L = L_max; P.stride = ds; P.n = n_pairs; P.prepared = true;
-    P.a[0] = (uint64_t)seq_all; P.a[1] = (uint64_t)c->in_qual.p; P.a[2] = (uint64_t)(seq_all + n * (u64)ds); P.a[3] = (uint64_t)c->in_qual2.p;
-    P.d_len = uniform ? nullptr : c->in_len.as<u16>();
-    P.d_results = (uint64_t)c->out_res.p; P.d_cigar_pool = (uint64_t)c->cig_pool.p; P.cigar_cap = (int64_t)pool;
-    int rc = lane_enqueue(c, P, true);
+    int rc = fastq_rows(c, pe, src, n, L_max, !pe && pbat ? 1 : 0, uniform != 0, P);
+    if (rc) return rc;
+    rc = lane_enqueue(c, P, true);
     if (rc) return rc;
     rc = lane_settle(c);                         // counts (and, rarely, the repeat with exact sizes) before anything is copied back
     if (rc) return rc;
@@ -161,6 +150,14 @@ int fq_rec_setup(Lane* c, u64 n, int f, FqRec& rec)
     rec.seq_len = reinterpret_cast<u16*>(b + 3 * n4); rec.qual_len = reinterpret_cast<u16*>(b + 3 * n4 + n2); rec.name_len = reinterpret_cast<u16*>(b + 3 * n4 + 2 * n2);
     return BMBS_OK;
 }
+// D2H in pieces: one 2 GiB device-to-host copy ran at a quarter of the link rate on the MI355X boxes (tools/pcie_probe)
+int d2h_chunked(Lane* c, char* dst, const char* src, u64 bytes, hipStream_t st)
+{
+    const u64 piece = 128ull << 20;
+    for (u64 o = 0; o < bytes; o += piece) HIPCHK(c, hipMemcpyAsync(dst + o, src + o, std::min(piece, bytes - o), hipMemcpyDeviceToHost, st));
+    return BMBS_OK;
+}
+
 // One upload and one download at a time per device, whatever the number of contexts: concurrent copies in one direction share the
 // link badly (tools/pcie_probe: 48 GB/s each way with one stream per direction, 33 with three), and a context's copies are long
 // enough (hundreds of MB) to fill the link on their own.  Held from the first copy of a phase until the wait that ends it.
@@ -171,86 +168,17 @@ std::mutex g_d2h_mu[16];
 // copies queued back to back without the host in between: 320 M reads to /dev/null took 3.3-3.8 s instead of 2.9-3.05 s, whether the
 // copy waited on the stream for its kernel or was queued once the kernel had ended (tools/e2e_quick.sh, same box, alternating runs).
 // *copy_s = seconds the copy held the link.
-int d2h_chunked(Lane* c, char* dst, const char* src, u64 bytes, hipStream_t st);
 int download_locked(Lane* c, char* dst, const char* src, u64 bytes, hipStream_t after, double* copy_s)
 {
-    hipStream_t ds = c->down_stream ? c->down_stream : c->stream;
+    hipStream_t ds = down_stream_of(c);
     HIPCHK(c, hipStreamSynchronize(after));                  // the bytes are complete before the link is claimed
     std::lock_guard<std::mutex> down(g_d2h_mu[c->dev & 15]);
-    timespec t0, t1; clock_gettime(CLOCK_MONOTONIC, &t0);
+    const double t0 = wall();
     const int rc = d2h_chunked(c, dst, src, bytes, ds);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(ds));
-    clock_gettime(CLOCK_MONOTONIC, &t1);
-    if (copy_s) *copy_s = (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec);
+    if (copy_s) *copy_s = wall() - t0;
     return BMBS_OK;
-}
-
-// D2H in pieces: one 2 GiB device-to-host copy ran at a quarter of the link rate on the MI355X boxes (tools/pcie_probe)
-int d2h_chunked(Lane* c, char* dst, const char* src, u64 bytes, hipStream_t st)
-{
-    const u64 piece = 128ull << 20;
-    for (u64 o = 0; o < bytes; o += piece) HIPCHK(c, hipMemcpyAsync(dst + o, src + o, std::min(piece, bytes - o), hipMemcpyDeviceToHost, st));
-    return BMBS_OK;
-}
-
-int lane_text_finish(Lane* c, bool pe, u64 bytes1, u64 bytes2, int64_t n_records, int32_t flags_in, char* sam, u64 sam_cap, u64* sam_bytes,
-                     int64_t* n_lines_out, double t_start, double t_uploaded);
-
-int lane_map_text(Lane* c, bool pe, const char* text1, u64 bytes1, const char* text2, u64 bytes2, int64_t n_records, int32_t flags_in, char* sam,
-                  u64 sam_cap, u64* sam_bytes, int64_t* n_lines_out)
-{
-    if (!c) return BMBS_EINVAL;
-    if (sam_bytes) *sam_bytes = 0;
-    if (n_lines_out) *n_lines_out = 0;
-    if ((flags_in & BMBS_TEXT_BAM_SORTED) && !(flags_in & BMBS_TEXT_BAM)) { c->err = "text call: BMBS_TEXT_BAM_SORTED is only valid together with BMBS_TEXT_BAM"; return BMBS_EINVAL; }
-    if (flags_in & BMBS_TEXT_BAM_SORTED) c->ends(Lane::SORTED_TEXT_CALL);
-    if (!c->attached) { c->err = "no index attached"; return BMBS_ESTATE; }
-    if (c->n_refs != c->ix.n_chrom) { c->err = "bmbs_sam_refs has not been given the index's reference names"; return BMBS_ESTATE; }
-    if (n_records <= 0) { if (flags_in & BMBS_TEXT_BAM_SORTED) c->st.holds(0, 0, pe); return BMBS_OK; }
-    if (!text1 || (pe && !text2) || !sam) { c->err = "text call: NULL buffer"; return BMBS_EINVAL; }
-    if (bytes1 >= (1ull << 32) || bytes2 >= (1ull << 32)) { c->err = "a text window has to be smaller than 4 GiB (32-bit offsets)"; return BMBS_EINVAL; }
-    HIPCHK(c, hipSetDevice(c->dev));
-    { const int rs = lane_settle(c); if (rs) return rs; }
-    c->open_text.valid = false;
-    const u64 n = (u64)n_records;
-    static const bool trace = getenv("BMBS_TEXT_TRACE") != nullptr;       // diagnostic: host-side phase times of every text call
-    auto wall = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; };
-    const double t_start = wall();
-    HIPCHK(c, hipMemsetAsync(c->tx_info.p, 0, TXI_WORDS * sizeof(u32), c->stream));
-    int rc;
-    ENS(c, c->fq_text1, bytes1 + 64);
-    if (pe) ENS(c, c->fq_text2, bytes2 + 64);
-    {
-        // the link is claimed for the copies alone: the kernels behind them may have to queue behind other contexts' kernels
-        std::unique_lock<std::mutex> up(g_h2d_mu[c->dev & 15], std::defer_lock);
-        if (c->kn.copy_lock) up.lock();
-        const double t_up0 = wall();
-        // on a stream of their own that never carries a kernel (the lane has nothing in flight here: the previous call ended with a wait)
-        hipStream_t us = c->kn.copy_streams && c->up_stream ? c->up_stream : c->stream;
-        HIPCHK(c, hipMemcpyAsync(c->fq_text1.p, text1, bytes1, hipMemcpyHostToDevice, us));
-        if (pe) HIPCHK(c, hipMemcpyAsync(c->fq_text2.p, text2, bytes2, hipMemcpyHostToDevice, us));
-        if (c->kn.copy_lock || us != c->stream) { HIPCHK(c, hipStreamSynchronize(us)); c->link_up_s += wall() - t_up0; }
-    }
-    const double t_uploaded = trace ? wall() : 0;
-    // diagnostic (tools/e2e_trace.sh): BMBS_TEXT_COPY_ONLY=1 moves the bytes of a batch over the link and runs nothing in between
-    static const bool copy_only = getenv("BMBS_TEXT_COPY_ONLY") != nullptr;
-    if (copy_only) {
-        const u64 total = std::min<u64>(sam_cap, (bytes1 + bytes2) * 115 / 100);
-        ENS(c, c->sam_out, total + 64);
-        std::unique_lock<std::mutex> down(g_d2h_mu[c->dev & 15], std::defer_lock);
-        if (c->kn.copy_lock) down.lock();
-        rc = d2h_chunked(c, sam, c->sam_out.as<char>(), total, c->stream);
-        if (rc) return rc;
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (sam_bytes) *sam_bytes = 0;
-        if (trace) fprintf(stderr, "[text] copy only: upload %.2f download %.2f ms\n", (t_uploaded - t_start) * 1e3, (wall() - t_uploaded) * 1e3);
-        return BMBS_OK;
-    }
-    rc = text_index(c, c->fq_text1, bytes1, n, 0);
-    if (rc) return rc;
-    if (pe) { rc = text_index(c, c->fq_text2, bytes2, n, 1); if (rc) return rc; }
-    return lane_text_finish(c, pe, bytes1, bytes2, n_records, flags_in, sam, sam_cap, sam_bytes, n_lines_out, t_start, t_uploaded);
 }
 
 // k_line_write's launch shape: lines per workgroup and the LDS it gets for the image of its piece of the output and for the staged
@@ -352,197 +280,264 @@ int bam_sort_device(Lane* c, const char* raw, const u64* off, const u32* len, u6
     return BMBS_OK;
 }
 
-// the text window(s) are on the device (fq_text1 / fq_text2) and their newline positions are being indexed (text_index): record fields,
-// rows, mapping, SAM text or BAM blocks, download
-int lane_text_finish(Lane* c, bool pe, u64 bytes1, u64 bytes2, int64_t n_records, int32_t flags_in, char* sam, u64 sam_cap, u64* sam_bytes,
-                     int64_t* n_lines_out, double t_start, double t_uploaded)
-{
-    const u64 n = (u64)n_records, n2 = pe ? 2 * n : n;
-    c->ends(Lane::TEXT_LINES);
-    static const bool trace = getenv("BMBS_TEXT_TRACE") != nullptr;
-    auto wall = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; };
-    double tp[8] = {t_start, 0, 0, 0, 0, 0, 0, t_uploaded}, t_uplock = t_start, t_dnlock = 0, t_dnstart = 0;
-    FqRec rec[2] = {};
-    int rc = fq_rec_setup(c, n, 0, rec[0]);
-    if (rc) return rc;
-    if (pe) { rc = fq_rec_setup(c, n, 1, rec[1]); if (rc) return rc; }
-    // records can only be cut out once the host knows that every one of them is complete: the line counts first
-    const u64* const lines = c->h_info->lines;
-    HIPCHK(c, hipMemcpyAsync(c->h_info->lines, tot_at(c, TOT_LINES_1), sizeof c->h_info->lines, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    tp[1] = wall();
-    if (lines[0] < 4 * n || (pe && lines[1] < 4 * n)) { c->err = "text call: a window holds fewer than 4 lines per record"; return BMBS_EINVAL; }
-    hipLaunchKernelGGL(k_fq_records, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->tx_nl[0].as<u32>(), (long)n, rec[0], line_info(c));
-    if (pe) hipLaunchKernelGGL(k_fq_records, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->tx_nl[1].as<u32>(), (long)n, rec[1], line_info(c) + TXI_FQ_WORDS);
-    HIPCHK(c, hipMemcpyAsync(c->h_info->line, line_info(c), sizeof c->h_info->line, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    tp[2] = wall();
-    const u32* const inf = c->h_info->line; const u32* const inf2 = inf + TXI_FQ_WORDS;      // k_fq_records' words of file 1, of file 2
-    for (int f = 0; f < (pe ? 2 : 1); f++)
-        if (inf[TXI_FQ_WORDS * f + 2]) {
-            c->err = "record " + std::to_string(inf[TXI_FQ_WORDS * f + 2] - 1) + " of this batch has an empty or longer-than-" + std::to_string(BMBS_MAX_READ) + "-character sequence line: not supported (the reference's own buffers end there)";
-            return BMBS_EINVAL;
-        }
-    int maxL = (int)inf[0], minL = (int)~inf[1];
-    if (pe) { maxL = std::max(maxL, (int)inf2[0]); minL = std::min(minL, (int)~inf2[1]); }
-    const bool uniform = minL == maxL;
-    const int ds = (maxL + 15) / 16 * 16;
-    const int max_ops = cigar_ops_bound(c->prm, maxL, threshold_k(c->prm, maxL));
-    const u64 pool = n2 * (u64)max_ops;
-    ENS(c, c->out_res, n2 * 32); ENS(c, c->cig_pool, pool * 4); ENS(c, c->in_len, n2 * 2 + 16);
-    Pending P;
-    P.pe = pe; P.L = maxL; P.stride = ds; P.n = n_records;
-    const int pbat = (flags_in & BMBS_TEXT_PBAT) && !pe ? 1 : 0;
-    if (!pe) {
-        ENS(c, c->in_seq, n * (u64)ds + 64); ENS(c, c->in_qual, n * (u64)ds + 64);
-        hipLaunchKernelGGL(k_fastq_rows, dim3(nblk(n * (u64)(ds / 16), 256)), dim3(256), 0, c->stream, c->fq_text1.as<char>(), rec[0].seq_off, rec[0].qual_off,
-                           rec[0].seq_len, rec[0].qual_len, (long)n, ds, pbat, pbat, c->in_seq.as<char>(), c->in_qual.as<char>(), c->in_len.as<u16>());
-        P.a[0] = (uint64_t)c->in_seq.p; P.a[1] = (uint64_t)c->in_qual.p;
-    } else {
-        ENS(c, c->pe_seq, n2 * (u64)ds + 64); ENS(c, c->in_qual, n * (u64)ds + 64); ENS(c, c->in_qual2, n * (u64)ds + 64);
-        char* seq_all = c->pe_seq.as<char>();
-        const unsigned g = nblk(n * (u64)(ds / 16), 256);
-        hipLaunchKernelGGL(k_fastq_rows, dim3(g), dim3(256), 0, c->stream, c->fq_text1.as<char>(), rec[0].seq_off, rec[0].qual_off, rec[0].seq_len, rec[0].qual_len,
-                           (long)n, ds, 0, 0, seq_all, c->in_qual.as<char>(), c->in_len.as<u16>());
-        hipLaunchKernelGGL(k_fastq_rows, dim3(g), dim3(256), 0, c->stream, c->fq_text2.as<char>(), rec[1].seq_off, rec[1].qual_off, rec[1].seq_len, rec[1].qual_len,
-                           (long)n, ds, 1, 0, seq_all + n * (u64)ds, c->in_qual2.as<char>(), c->in_len.as<u16>() + n);
-        P.a[0] = (uint64_t)seq_all; P.a[1] = (uint64_t)c->in_qual.p; P.a[2] = (uint64_t)(seq_all + n * (u64)ds); P.a[3] = (uint64_t)c->in_qual2.p;
-        P.prepared = true;
+// ---- a text call behind its upload, stage by stage (lane_text_finish runs them): the text window(s) are on the device (fq_text1 /
+// fq_text2) and their newline positions are being indexed (text_index).  The caller's arguments and the clock; rec: the records' fields
+// (records); max_ops, in: the CIGAR bound of the batch and what the length and write kernels read (map)
+static const size_t STATS_BYTES = BMBS_SHARDS * BMBS_SHARD_WORDS * 8;
+struct TextCall {
+    Lane* c; bool pe; u64 in_bytes, n, n2; int32_t flags; char* sam; u64 sam_cap; u64* sam_bytes; int64_t* n_lines_out; TextClock t;
+    FqRec rec[2]; int max_ops; SamIn in;
+    // the fields of every record (k_fq_records) -> the longest and the shortest sequence line
+    int records(int* maxL, int* minL)
+    {
+        for (int f = 0; f < (pe ? 2 : 1); f++) { const int rc = fq_rec_setup(c, n, f, rec[f]); if (rc) return rc; }
+        // records can only be cut out once the host knows that every one of them is complete: the line counts first
+        const u64* const lines = c->h_info->lines;
+        HIPCHK(c, hipMemcpyAsync(c->h_info->lines, tot_at(c, TOT_LINES_1), sizeof c->h_info->lines, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        t.lines = wall();
+        if (lines[0] < 4 * n || (pe && lines[1] < 4 * n)) { c->err = "text call: a window holds fewer than 4 lines per record"; return BMBS_EINVAL; }
+        for (int f = 0; f < (pe ? 2 : 1); f++)
+            hipLaunchKernelGGL(k_fq_records, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->tx_nl[f].as<u32>(), (long)n, rec[f], line_info(c) + TXI_FQ_WORDS * f);
+        HIPCHK(c, hipMemcpyAsync(c->h_info->line, line_info(c), sizeof c->h_info->line, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        t.records = wall();
+        const u32* const inf = c->h_info->line; const u32* const inf2 = inf + TXI_FQ_WORDS;      // k_fq_records' words of file 1, of file 2
+        for (int f = 0; f < (pe ? 2 : 1); f++)
+            if (inf[TXI_FQ_WORDS * f + 2]) {
+                c->err = "record " + std::to_string(inf[TXI_FQ_WORDS * f + 2] - 1) + " of this batch has an empty or longer-than-" + std::to_string(BMBS_MAX_READ) + "-character sequence line: not supported (the reference's own buffers end there)";
+                return BMBS_EINVAL;
+            }
+        *maxL = (int)inf[0]; *minL = (int)~inf[1];
+        if (pe) { *maxL = std::max(*maxL, (int)inf2[0]); *minL = std::min(*minL, (int)~inf2[1]); }
+        return BMBS_OK;
     }
-    P.d_len = uniform ? nullptr : c->in_len.as<u16>();
-    P.d_results = (uint64_t)c->out_res.p; P.d_cigar_pool = (uint64_t)c->cig_pool.p; P.cigar_cap = (int64_t)pool;
-    // a caller whose output buffer turns out too small repeats the call (BMBS_ENOMEM below): the batch must not be counted twice
-    const size_t stats_bytes = BMBS_SHARDS * BMBS_SHARD_WORDS * 8;
-    ENS(c, c->stats_snap, stats_bytes);
-    HIPCHK(c, hipMemcpyAsync(c->stats_snap.p, c->stats.p, stats_bytes, hipMemcpyDeviceToDevice, c->stream));
-    auto too_small = [&](const char* what) -> int {
-        (void)hipMemcpyAsync(c->stats.p, c->stats_snap.p, stats_bytes, hipMemcpyDeviceToDevice, c->stream);
+    // rows and mapping: the records are in out_res / cig_pool when this returns, and `in` names them for the kernels of every ending
+    int map(int maxL, bool uniform)
+    {
+        max_ops = cigar_ops_bound(c->prm, maxL, threshold_k(c->prm, maxL));
+        const FqSrc src[2] = {{c->fq_text1.as<char>(), rec[0].seq_off, rec[0].qual_off, rec[0].seq_len, rec[0].qual_len},
+                              {c->fq_text2.as<char>(), rec[1].seq_off, rec[1].qual_off, rec[1].seq_len, rec[1].qual_len}};
+        Pending P;
+        int rc = fastq_rows(c, pe, src, n, maxL, (flags & BMBS_TEXT_PBAT) && !pe ? 1 : 0, uniform, P);
+        if (rc) return rc;
+        // a caller whose output buffer turns out too small repeats the call (too_small): the batch must not be counted twice
+        ENS(c, c->stats_snap, STATS_BYTES);
+        HIPCHK(c, hipMemcpyAsync(c->stats_snap.p, c->stats.p, STATS_BYTES, hipMemcpyDeviceToDevice, c->stream));
+        rc = lane_enqueue(c, P, true);
+        if (rc) return rc;
+        rc = lane_settle(c);
+        if (rc) return rc;
+        t.mapped = wall();
+        in.text[0] = src[0].text; in.text[1] = pe ? src[1].text : nullptr;
+        in.rec[0] = rec[0]; in.rec[1] = rec[1];
+        in.res = c->out_res.as<bmbs_result_dev>(); in.cigar = c->cig_pool.as<u32>();
+        in.chrom_chars = c->chrom_chars.as<char>(); in.chrom_off = c->chrom_off.as<u32>();
+        in.n = (long)n;
+        in.flags = (flags & (BMBS_TEXT_PBAT | BMBS_TEXT_UNMAPPED)) | (c->prm.ambiguous_out ? BMBS_TEXT_AMBIG : 0) | (pe ? BMBS_TEXT_PE : 0);
+        return BMBS_OK;
+    }
+    // BMBS_ENOMEM for an output buffer that is too small: the statistics go back to map's snapshot
+    int too_small(const char* what)
+    {
+        (void)hipMemcpyAsync(c->stats.p, c->stats_snap.p, STATS_BYTES, hipMemcpyDeviceToDevice, c->stream);
         (void)hipStreamSynchronize(c->stream);
         c->err = what;
         return BMBS_ENOMEM;
-    };
-    rc = lane_enqueue(c, P, true);
-    if (rc) return rc;
-    rc = lane_settle(c);
-    if (rc) return rc;
-    tp[3] = wall();
-    // ---- records -> SAM text
-    SamIn in;
-    in.text[0] = c->fq_text1.as<char>(); in.text[1] = pe ? c->fq_text2.as<char>() : nullptr;
-    in.rec[0] = rec[0]; in.rec[1] = rec[1];
-    in.res = c->out_res.as<bmbs_result_dev>(); in.cigar = c->cig_pool.as<u32>();
-    in.chrom_chars = c->chrom_chars.as<char>(); in.chrom_off = c->chrom_off.as<u32>();
-    in.n = (long)n;
-    in.flags = (flags_in & (BMBS_TEXT_PBAT | BMBS_TEXT_UNMAPPED)) | (c->prm.ambiguous_out ? BMBS_TEXT_AMBIG : 0) | (pe ? BMBS_TEXT_PE : 0);
-    ENS(c, c->sam_len, n2 * 4 + 64); ENS(c, c->sam_off, (n2 + 1) * 8 + 64);
-    if (flags_in & BMBS_TEXT_BAM) {
-        // ---- records -> BAM records -> BGZF blocks, all on the device (bmbs_bam.hip)
-        prof_begin(c, "k_bam_len");
-        hipLaunchKernelGGL(k_bam_len, dim3(nblk(n2, 256)), dim3(256), 0, c->stream, in, (long)n2, c->sam_len.as<u32>(), line_info(c));
-        rc = scan_u32(c, c->sam_len.as<u32>(), n2, c->sam_off.as<u64>(), TOT_BAM_BYTES);
+    }
+    // lengths -> offsets -> total on the host, for the SAM lines or the BAM records (k_bam_len also leaves a word in h_info->line)
+    template <bool BAM> int sized(u64* total)
+    {
+        const Tot slot = BAM ? TOT_BAM_BYTES : TOT_SAM_BYTES;
+        ENS(c, c->sam_len, n2 * 4 + 64); ENS(c, c->sam_off, (n2 + 1) * 8 + 64);
+        prof_begin(c, BAM ? "k_bam_len" : "k_sam_len");
+        if (BAM) hipLaunchKernelGGL(k_bam_len, dim3(nblk(n2, 256)), dim3(256), 0, c->stream, in, (long)n2, c->sam_len.as<u32>(), line_info(c));
+        else hipLaunchKernelGGL(k_sam_len, dim3(nblk(n2, 256)), dim3(256), 0, c->stream, in, (long)n2, c->sam_len.as<u32>());
+        const int rc = scan_u32(c, c->sam_len.as<u32>(), n2, c->sam_off.as<u64>(), slot);
         if (rc) return rc;
         prof_end(c);
-        HIPCHK(c, hipMemcpyAsync(&c->h_info->out_bytes, tot_at(c, TOT_BAM_BYTES), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->h_info->line, line_info(c), sizeof c->h_info->line, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&c->h_info->out_bytes, tot_at(c, slot), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        if (BAM) HIPCHK(c, hipMemcpyAsync(c->h_info->line, line_info(c), sizeof c->h_info->line, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        tp[4] = wall();
-        const u64 raw_total = c->h_info->out_bytes;
-        if (n_lines_out) *n_lines_out = (int64_t)n2;
-        if (inf[3]) { c->err = "output line " + std::to_string(inf[3] - 1) + " of this batch has a read name of more than 254 characters: BAM cannot hold it"; return BMBS_EINVAL; }
-        if (!raw_total) { if (flags_in & BMBS_TEXT_BAM_SORTED) c->st.holds(0, (int64_t)n2, pe); return BMBS_OK; }
-        ENS(c, c->bam_raw, raw_total + 256);
-        const TxwPlan tw = txw_plan(pe, bytes1 + bytes2, n2, (36 + 4 * std::max(max_ops, 1) + 8 + 15) & ~15);
-        if (!tw.lpb) { c->err = "text call: CIGARs too long"; return BMBS_EINVAL; }
-        prof_begin(c, "k_bam_write");
-        hipLaunchKernelGGL(k_line_write<true>, dim3(nblk(n2, (unsigned)tw.lpb)), dim3(TXW_THREADS), tw.lds, c->stream, in, (long)n2, c->sam_off.as<u64>(), tw.lpb, tw.out_cap, tw.src_cap,
-                           c->bam_raw.as<char>());
+        t.sized = wall();
+        *total = c->h_info->out_bytes;
+        return BMBS_OK;
+    }
+    // the lines into `out`, `total` bytes (k_line_write): hb bounds the computed columns of one line (txw_plan)
+    template <bool BAM> int write(DevBuf& out, u64 total)
+    {
+        const int ops = std::max(max_ops, 1);
+        ENS(c, out, total + (BAM ? 256 : 64));
+        const TxwPlan tw = txw_plan(pe, in_bytes, n2, ((BAM ? 36 + 4 * ops + 8 : c->max_ref_len + 5 * ops + 96) + 15) & ~15);
+        if (!tw.lpb) { c->err = BAM ? "text call: CIGARs too long" : "text call: reference names too long"; return BMBS_EINVAL; }
+        prof_begin(c, BAM ? "k_bam_write" : "k_sam_write");
+        hipLaunchKernelGGL(k_line_write<BAM>, dim3(nblk(n2, (unsigned)tw.lpb)), dim3(TXW_THREADS), tw.lds, c->stream, in, (long)n2, c->sam_off.as<u64>(), tw.lpb, tw.out_cap, tw.src_cap,
+                           out.as<char>());
         prof_end(c);
-        if (flags_in & BMBS_TEXT_BAM_SORTED) {
-            // ---- the uncompressed records in coordinate order (k_bamsort.hip); a driver merges the batches (bmbs_bam_sort)
-            if (sam_bytes) *sam_bytes = raw_total;
-            if (raw_total > sam_cap) return too_small("text call: the BAM buffer is too small (sam_bytes tells what this batch needs)");
-            u64 n_rec = 0;
-            rc = bam_sort_device(c, c->bam_raw.as<char>(), c->sam_off.as<u64>(), c->sam_len.as<u32>(), n2, raw_total, true, &n_rec);
-            if (rc) return rc;
-            c->st.holds((int64_t)n_rec, (int64_t)n2, pe);                         // (bmbs_text_sorted_dup: computed when asked for)
-            if (trace) { HIPCHK(c, hipStreamSynchronize(c->stream)); tp[5] = wall(); }
-            double cs = 0;
-            rc = download_locked(c, sam, c->bs_sorted.as<char>(), raw_total, c->stream, &cs);
-            if (rc) return rc;
-            c->link_down_s += cs;
-            tp[6] = wall();
-            c->text_call_s += tp[6] - tp[0]; c->text_calls++;
-            if (trace)
-                fprintf(stderr, "[text/bam sorted] n=%ld in=%.1fMB records=%.1fMB  upload %.2f lines+records %.2f rows+map %.2f  len+scan %.2f  write+sort %.2f  download %.2f  total %.2f ms\n",
-                        (long)n2, (double)(bytes1 + bytes2) / 1e6, (double)raw_total / 1e6, (tp[7] - tp[0]) * 1e3, (tp[2] - tp[7]) * 1e3, (tp[3] - tp[2]) * 1e3, (tp[4] - tp[3]) * 1e3,
-                        (tp[5] - tp[4]) * 1e3, (tp[6] - tp[5]) * 1e3, (tp[6] - tp[0]) * 1e3);
-            return BMBS_OK;
-        }
+        return BMBS_OK;
+    }
+    // `bytes` at src, which the lane's stream is still writing, go down into the caller's buffer; the call is counted (bmbs_text_times)
+    int deliver(const char* src, u64 bytes)
+    {
+        if (text_trace()) { HIPCHK(c, hipStreamSynchronize(c->stream)); t.written = wall(); }
+        double cs = 0;
+        const double t_dn0 = wall();
+        const int rc = download_locked(c, sam, src, bytes, c->stream, &cs);
+        if (rc) return rc;
+        c->link_down_s += cs;
+        t.delivered = wall();
+        t.down_wait = t.delivered - cs - t_dn0;
+        c->text_call_s += t.delivered - t.start; c->text_calls++;
+        return BMBS_OK;
+    }
+    // ---- records -> BAM records, all on the device (bmbs_bam.hip): the stream in bam_raw, *raw_total its bytes (0: nothing prints)
+    int bam_records(u64* raw_total)
+    {
+        const int rc = sized<true>(raw_total);
+        if (rc) return rc;
+        if (n_lines_out) *n_lines_out = (int64_t)n2;
+        const u32 long_name = c->h_info->line[3];
+        if (long_name) { c->err = "output line " + std::to_string(long_name - 1) + " of this batch has a read name of more than 254 characters: BAM cannot hold it"; return BMBS_EINVAL; }
+        if (!*raw_total) { if (flags & BMBS_TEXT_BAM_SORTED) c->st.holds(0, (int64_t)n2, pe); return BMBS_OK; }
+        return write<true>(c->bam_raw, *raw_total);
+    }
+    // ---- ... -> BGZF blocks
+    int emit_bam(u64 raw_total)
+    {
         u64 ztotal = 0;
-        rc = bgzf_deflate(c, c->bam_raw.as<char>(), tot_at(c, TOT_BAM_BYTES), raw_total, &ztotal);
+        int rc = bgzf_deflate(c, c->bam_raw.as<char>(), tot_at(c, TOT_BAM_BYTES), raw_total, &ztotal);
         if (rc) return rc;
         if (sam_bytes) *sam_bytes = ztotal;
         if (ztotal > sam_cap) return too_small("text call: the BAM buffer is too small (sam_bytes tells what this batch needs)");
         rc = bgzf_collect(c, raw_total, ztotal);
         if (rc) return rc;
-        if (trace) { HIPCHK(c, hipStreamSynchronize(c->stream)); tp[5] = wall(); }
-        {
-            double cs = 0;
-            rc = download_locked(c, sam, c->sam_out.as<char>(), ztotal, c->stream, &cs);
-            if (rc) return rc;
-            c->link_down_s += cs;
-        }
-        tp[6] = wall();
-        c->text_call_s += tp[6] - tp[0]; c->text_calls++;
-        if (trace)
+        rc = deliver(c->sam_out.as<char>(), ztotal);
+        if (!rc && text_trace())
             fprintf(stderr, "[text/bam] n=%ld in=%.1fMB records=%.1fMB out=%.1fMB  upload %.2f lines+records %.2f rows+map %.2f  len+scan %.2f  write+deflate %.2f  download %.2f  total %.2f ms\n",
-                    (long)n2, (double)(bytes1 + bytes2) / 1e6, (double)raw_total / 1e6, (double)ztotal / 1e6, (tp[7] - tp[0]) * 1e3, (tp[2] - tp[7]) * 1e3, (tp[3] - tp[2]) * 1e3, (tp[4] - tp[3]) * 1e3,
-                    (tp[5] - tp[4]) * 1e3, (tp[6] - tp[5]) * 1e3, (tp[6] - tp[0]) * 1e3);
-        return BMBS_OK;
+                    (long)n2, (double)in_bytes / 1e6, (double)raw_total / 1e6, (double)ztotal / 1e6, (t.uploaded - t.start) * 1e3, (t.records - t.uploaded) * 1e3, (t.mapped - t.records) * 1e3, (t.sized - t.mapped) * 1e3,
+                    (t.written - t.sized) * 1e3, (t.delivered - t.written) * 1e3, (t.delivered - t.start) * 1e3);
+        return rc;
     }
-    prof_begin(c, "k_sam_len");
-    hipLaunchKernelGGL(k_sam_len, dim3(nblk(n2, 256)), dim3(256), 0, c->stream, in, (long)n2, c->sam_len.as<u32>());
-    rc = scan_u32(c, c->sam_len.as<u32>(), n2, c->sam_off.as<u64>(), TOT_SAM_BYTES);
-    if (rc) return rc;
-    prof_end(c);
-    HIPCHK(c, hipMemcpyAsync(&c->h_info->out_bytes, tot_at(c, TOT_SAM_BYTES), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    tp[4] = wall();
-    const u64 total = c->h_info->out_bytes;
-    if (sam_bytes) *sam_bytes = total;
-    if (n_lines_out) *n_lines_out = (int64_t)n2;
-    if (total > sam_cap) return too_small("text call: the SAM buffer is too small (sam_bytes tells what this batch needs)");
-    if (!total) return BMBS_OK;
-    ENS(c, c->sam_out, total + 64);
-    const TxwPlan tw = txw_plan(pe, bytes1 + bytes2, n2, (c->max_ref_len + 5 * std::max(max_ops, 1) + 96 + 15) & ~15);
-    if (!tw.lpb) { c->err = "text call: reference names too long"; return BMBS_EINVAL; }
-    prof_begin(c, "k_sam_write");
-    hipLaunchKernelGGL(k_line_write<false>, dim3(nblk(n2, (unsigned)tw.lpb)), dim3(TXW_THREADS), tw.lds, c->stream, in, (long)n2, c->sam_off.as<u64>(), tw.lpb, tw.out_cap, tw.src_cap,
-                       c->sam_out.as<char>());
-    prof_end(c);
-    if (trace) { HIPCHK(c, hipStreamSynchronize(c->stream)); tp[5] = wall(); }
+    // ---- ... -> the uncompressed records in coordinate order (k_bamsort.hip); a driver merges the batches (bmbs_bam_sort)
+    int emit_sorted(u64 raw_total)
     {
-        double cs = 0;
-        t_dnstart = wall();
-        rc = download_locked(c, sam, c->sam_out.as<char>(), total, c->stream, &cs);
+        if (sam_bytes) *sam_bytes = raw_total;
+        if (raw_total > sam_cap) return too_small("text call: the BAM buffer is too small (sam_bytes tells what this batch needs)");
+        u64 n_rec = 0;
+        int rc = bam_sort_device(c, c->bam_raw.as<char>(), c->sam_off.as<u64>(), c->sam_len.as<u32>(), n2, raw_total, true, &n_rec);
         if (rc) return rc;
-        c->link_down_s += cs;
-        t_dnlock = wall() - cs;                       // (trace: what was not the copy was the wait behind other contexts' copies)
+        c->st.holds((int64_t)n_rec, (int64_t)n2, pe);                         // (bmbs_text_sorted_dup: computed when asked for)
+        rc = deliver(c->bs_sorted.as<char>(), raw_total);
+        if (!rc && text_trace())
+            fprintf(stderr, "[text/bam sorted] n=%ld in=%.1fMB records=%.1fMB  upload %.2f lines+records %.2f rows+map %.2f  len+scan %.2f  write+sort %.2f  download %.2f  total %.2f ms\n",
+                    (long)n2, (double)in_bytes / 1e6, (double)raw_total / 1e6, (t.uploaded - t.start) * 1e3, (t.records - t.uploaded) * 1e3, (t.mapped - t.records) * 1e3, (t.sized - t.mapped) * 1e3,
+                    (t.written - t.sized) * 1e3, (t.delivered - t.written) * 1e3, (t.delivered - t.start) * 1e3);
+        return rc;
     }
-    tp[6] = wall();
-    c->text_call_s += tp[6] - tp[0]; c->text_calls++;
-    if (trace)
-        fprintf(stderr, "[text] n=%ld in=%.1fMB out=%.1fMB  (waits for the link: up %.2f, down %.2f)  upload %.2f lines %.2f  records %.2f  rows+map %.2f  len+scan %.2f  write %.2f  download %.2f  total %.2f ms\n",
-                (long)n2, (double)(bytes1 + bytes2) / 1e6, (double)total / 1e6, (t_uplock - tp[0]) * 1e3, (t_dnlock - t_dnstart) * 1e3, (tp[7] - tp[0]) * 1e3, (tp[1] - tp[7]) * 1e3, (tp[2] - tp[1]) * 1e3, (tp[3] - tp[2]) * 1e3,
-                (tp[4] - tp[3]) * 1e3, (tp[5] - tp[4]) * 1e3, (tp[6] - tp[5]) * 1e3, (tp[6] - tp[0]) * 1e3);
+    // ---- records -> SAM text
+    int emit_sam()
+    {
+        u64 total = 0;
+        int rc = sized<false>(&total);
+        if (rc) return rc;
+        if (sam_bytes) *sam_bytes = total;
+        if (n_lines_out) *n_lines_out = (int64_t)n2;
+        if (total > sam_cap) return too_small("text call: the SAM buffer is too small (sam_bytes tells what this batch needs)");
+        if (!total) return BMBS_OK;
+        rc = write<false>(c->sam_out, total);
+        if (rc) return rc;
+        rc = deliver(c->sam_out.as<char>(), total);
+        // ("up", the wait for the upload lock, has never been measured: it prints the 0.00 it always has, and the line keeps its fields)
+        if (!rc && text_trace())
+            fprintf(stderr, "[text] n=%ld in=%.1fMB out=%.1fMB  (waits for the link: up %.2f, down %.2f)  upload %.2f lines %.2f  records %.2f  rows+map %.2f  len+scan %.2f  write %.2f  download %.2f  total %.2f ms\n",
+                    (long)n2, (double)in_bytes / 1e6, (double)total / 1e6, 0.0, t.down_wait * 1e3, (t.uploaded - t.start) * 1e3, (t.lines - t.uploaded) * 1e3, (t.records - t.lines) * 1e3, (t.mapped - t.records) * 1e3,
+                    (t.sized - t.mapped) * 1e3, (t.written - t.sized) * 1e3, (t.delivered - t.written) * 1e3, (t.delivered - t.start) * 1e3);
+        return rc;
+    }
+};
+
+// record fields, rows, mapping, then SAM text, BAM blocks or sorted BAM records, and their download; t0: the caller's start and uploaded marks
+int lane_text_finish(Lane* c, bool pe, u64 bytes1, u64 bytes2, int64_t n_records, int32_t flags_in, char* sam, u64 sam_cap, u64* sam_bytes,
+                     int64_t* n_lines_out, const TextClock& t0)
+{
+    c->ends(Lane::TEXT_LINES);
+    const u64 n = (u64)n_records;
+    TextCall T = {c, pe, bytes1 + bytes2, n, pe ? 2 * n : n, flags_in, sam, sam_cap, sam_bytes, n_lines_out, t0, {}, 0, {}};
+    int maxL = 0, minL = 0;
+    int rc = T.records(&maxL, &minL);
+    if (!rc) rc = T.map(maxL, minL == maxL);
+    if (rc) return rc;
+    if (!(flags_in & BMBS_TEXT_BAM)) return T.emit_sam();
+    u64 raw_total = 0;
+    rc = T.bam_records(&raw_total);
+    if (rc || !raw_total) return rc;
+    return flags_in & BMBS_TEXT_BAM_SORTED ? T.emit_sorted(raw_total) : T.emit_bam(raw_total);
+}
+
+// what lane_map_text and lane_text_map_open begin with: nothing has been written yet; a sorted call needs BMBS_TEXT_BAM, and, whatever
+// becomes of it, ends what the last one left
+static int text_call_begin(Lane* c, int32_t flags_in, u64* sam_bytes, int64_t* n_lines_out)
+{
+    if (sam_bytes) *sam_bytes = 0;
+    if (n_lines_out) *n_lines_out = 0;
+    if ((flags_in & BMBS_TEXT_BAM_SORTED) && !(flags_in & BMBS_TEXT_BAM)) { c->err = "text call: BMBS_TEXT_BAM_SORTED is only valid together with BMBS_TEXT_BAM"; return BMBS_EINVAL; }
+    if (flags_in & BMBS_TEXT_BAM_SORTED) c->ends(Lane::SORTED_TEXT_CALL);
     return BMBS_OK;
 }
 
-// the part of an "open" call behind the inflated text: newline index, whole records, what is left behind them
-static int lane_text_open_finish(Lane* c, bool pe, DevBuf* const* texts, u64* bytes, int64_t max_records, int64_t* n_records, char* tail1, uint64_t tail_cap,
-                                 uint64_t* tail1_bytes, char* tail2, uint64_t* tail2_bytes, double* tp, const char* what, double comp_mb)
+int lane_map_text(Lane* c, bool pe, const char* text1, u64 bytes1, const char* text2, u64 bytes2, int64_t n_records, int32_t flags_in, char* sam,
+                  u64 sam_cap, u64* sam_bytes, int64_t* n_lines_out)
 {
-    auto wall = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; };
+    if (!c) return BMBS_EINVAL;
+    { const int r0 = text_call_begin(c, flags_in, sam_bytes, n_lines_out); if (r0) return r0; }
+    if (!c->attached) { c->err = "no index attached"; return BMBS_ESTATE; }
+    if (c->n_refs != c->ix.n_chrom) { c->err = "bmbs_sam_refs has not been given the index's reference names"; return BMBS_ESTATE; }
+    if (n_records <= 0) { if (flags_in & BMBS_TEXT_BAM_SORTED) c->st.holds(0, 0, pe); return BMBS_OK; }
+    if (!text1 || (pe && !text2) || !sam) { c->err = "text call: NULL buffer"; return BMBS_EINVAL; }
+    if (bytes1 >= (1ull << 32) || bytes2 >= (1ull << 32)) { c->err = "a text window has to be smaller than 4 GiB (32-bit offsets)"; return BMBS_EINVAL; }
+    HIPCHK(c, hipSetDevice(c->dev));
+    { const int rs = lane_settle(c); if (rs) return rs; }
+    c->open_text.valid = false;
+    TextClock t; t.start = wall();
+    HIPCHK(c, hipMemsetAsync(c->tx_info.p, 0, TXI_WORDS * sizeof(u32), c->stream));
+    ENS(c, c->fq_text1, bytes1 + 64);
+    if (pe) ENS(c, c->fq_text2, bytes2 + 64);
+    {
+        // the link is claimed for the copies alone: the kernels behind them may have to queue behind other contexts' kernels
+        std::lock_guard<std::mutex> up(g_h2d_mu[c->dev & 15]);
+        const double t_up0 = wall();
+        // on a stream of their own that never carries a kernel (the lane has nothing in flight here: the previous call ended with a wait)
+        hipStream_t us = up_stream_of(c);
+        HIPCHK(c, hipMemcpyAsync(c->fq_text1.p, text1, bytes1, hipMemcpyHostToDevice, us));
+        if (pe) HIPCHK(c, hipMemcpyAsync(c->fq_text2.p, text2, bytes2, hipMemcpyHostToDevice, us));
+        HIPCHK(c, hipStreamSynchronize(us));
+        c->link_up_s += wall() - t_up0;
+    }
+    t.uploaded = text_trace() ? wall() : 0;
+    // diagnostic (tools/e2e_trace.sh): BMBS_TEXT_COPY_ONLY=1 moves the bytes of a batch over the link and runs nothing in between
+    static const bool copy_only = getenv("BMBS_TEXT_COPY_ONLY") != nullptr;
+    if (copy_only) {
+        const u64 total = std::min<u64>(sam_cap, (bytes1 + bytes2) * 115 / 100);
+        ENS(c, c->sam_out, total + 64);
+        std::lock_guard<std::mutex> down(g_d2h_mu[c->dev & 15]);
+        const int rd = d2h_chunked(c, sam, c->sam_out.as<char>(), total, c->stream);
+        if (rd) return rd;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (sam_bytes) *sam_bytes = 0;
+        if (text_trace()) fprintf(stderr, "[text] copy only: upload %.2f download %.2f ms\n", (t.uploaded - t.start) * 1e3, (wall() - t.uploaded) * 1e3);
+        return BMBS_OK;
+    }
+    int rc = text_index(c, c->fq_text1, bytes1, (u64)n_records, 0);
+    if (rc) return rc;
+    if (pe) { rc = text_index(c, c->fq_text2, bytes2, (u64)n_records, 1); if (rc) return rc; }
+    return lane_text_finish(c, pe, bytes1, bytes2, n_records, flags_in, sam, sam_cap, sam_bytes, n_lines_out, t);
+}
+
+// the part of an "open" call behind the inflated text (bytes[f] of it in fq_text1 / fq_text2): newline index, whole records, what is left behind them
+static int lane_text_open_finish(Lane* c, bool pe, const u64* bytes, int64_t max_records, int64_t* n_records, char* tail1, uint64_t tail_cap,
+                                 uint64_t* tail1_bytes, char* tail2, uint64_t* tail2_bytes, TextClock& t, double comp_mb)
+{
+    DevBuf* const texts[2] = {&c->fq_text1, &c->fq_text2};
     const u64 n_cap = (u64)max_records;
     int rc = text_index(c, c->fq_text1, bytes[0], n_cap, 0);
     if (rc) return rc;
@@ -550,7 +545,7 @@ static int lane_text_open_finish(Lane* c, bool pe, DevBuf* const* texts, u64* by
     const u64* const lines = c->h_info->lines;
     HIPCHK(c, hipMemcpyAsync(c->h_info->lines, tot_at(c, TOT_LINES_1), sizeof c->h_info->lines, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    tp[2] = wall();
+    t.lines = wall();
     u64 n = lines[0] / 4;
     if (pe) n = std::min(n, lines[1] / 4);
     n = std::min(n, n_cap);
@@ -561,7 +556,7 @@ static int lane_text_open_finish(Lane* c, bool pe, DevBuf* const* texts, u64* by
         HIPCHK(c, hipStreamSynchronize(c->stream));
         for (int f = 0; f < (pe ? 2 : 1); f++) cut[f] = (u64)c->h_info->last_nl[f] + 1;
     }
-    hipStream_t ds = c->kn.copy_streams && c->down_stream ? c->down_stream : c->stream;
+    hipStream_t ds = down_stream_of(c);
     char* tails[2] = {tail1, tail2}; uint64_t* tb[2] = {tail1_bytes, tail2_bytes};
     for (int f = 0; f < (pe ? 2 : 1); f++) *tb[f] = bytes[f] - cut[f];                   // (both sizes are known to a caller that has to come back with room)
     for (int f = 0; f < (pe ? 2 : 1); f++)
@@ -569,18 +564,56 @@ static int lane_text_open_finish(Lane* c, bool pe, DevBuf* const* texts, u64* by
     for (int f = 0; f < (pe ? 2 : 1); f++)
         if (*tb[f]) HIPCHK(c, hipMemcpyAsync(tails[f], texts[f]->as<char>() + cut[f], *tb[f], hipMemcpyDeviceToHost, ds));
     HIPCHK(c, hipStreamSynchronize(ds));
-    tp[3] = wall();
-    if (what)
-        fprintf(stderr, "[text open %s] n=%ld comp=%.1fMB text=%.1fMB  upload+inflate %.2f  lines %.2f  tails %.2f (%.2f MB)  total %.2f ms\n", what, (long)n,
-                comp_mb, (double)(bytes[0] + bytes[1]) / 1e6, (tp[1] - tp[0]) * 1e3, (tp[2] - tp[1]) * 1e3, (tp[3] - tp[2]) * 1e3,
-                (double)(*tb[0] + (pe ? *tb[1] : 0)) / 1e6, (tp[3] - tp[0]) * 1e3);
+    t.delivered = wall();
+    if (text_trace())
+        fprintf(stderr, "[text open bgzf] n=%ld comp=%.1fMB text=%.1fMB  upload+inflate %.2f  lines %.2f  tails %.2f (%.2f MB)  total %.2f ms\n", (long)n,
+                comp_mb, (double)(bytes[0] + bytes[1]) / 1e6, (t.uploaded - t.start) * 1e3, (t.lines - t.uploaded) * 1e3, (t.delivered - t.lines) * 1e3,
+                (double)(*tb[0] + (pe ? *tb[1] : 0)) / 1e6, (t.delivered - t.start) * 1e3);
     *n_records = (int64_t)n;
     c->open_text.valid = n > 0; c->open_text.pe = pe; c->open_text.bytes1 = cut[0]; c->open_text.bytes2 = cut[1]; c->open_text.n = (int64_t)n;
     return BMBS_OK;
 }
 
+// ---- BGZF blocks on the device (bmbs_inflate.hip): what bmbs_text_open_bgzf and bmbs_inflate_bgzf check alike
+// every block has room for its header and trailer and inflates to at most 64 KiB, the offsets ascend; `who` begins the message
+static int blk_table_check(Lane* c, const char* who, const uint64_t* blk_off, const uint64_t* out_off, u64 nb)
+{
+    for (u64 i = 0; i < nb; i++)
+        if (blk_off[i + 1] < blk_off[i] + 26 || out_off[i + 1] < out_off[i] || out_off[i + 1] - out_off[i] > 65536) { c->err = std::string(who) + ": malformed block table"; return BMBS_EINVAL; }
+    return BMBS_OK;
+}
+// k_bgzf_inflate's word per block, on the host: the first block that did not inflate is reported; file 1 / 2: the text-open call's
+// input files, 0: the plain inflate call's
+static int blk_errors(Lane* c, const u32* err, u64 nb, int file)
+{
+    for (u64 i = 0; i < nb; i++)
+        if (err[i]) { c->err = "corrupt BGZF block in the .gz input (" + (file ? "file " + std::to_string(file) + ", " : std::string()) + "block " + std::to_string(i) + " of this window, code " + std::to_string(err[i]) + ")"; return BMBS_EINVAL; }
+    return BMBS_OK;
+}
+
 // ---- compressed input that stays on the device: open (assemble + index a window from BGZF blocks) and map (everything after) -------
-struct ZTextArgs { const bmbs_ztext* z; DevBuf* text; DevBuf* comp; DevBuf* off; DevBuf* err; };
+// one input file of an open call: its arguments, the lane's buffers for it, its blocks; bytes = prefix + inflated text
+struct ZTextArgs { const bmbs_ztext* z; DevBuf* text; DevBuf* comp; DevBuf* off; DevBuf* err; u64 nb, bytes; };
+
+// upload, inflate, last line of file f, all on stream s
+static int ztext_inflate(Lane* c, const ZTextArgs& a, int f, int32_t last, hipStream_t s)
+{
+    const bmbs_ztext* z = a.z;
+    const u64 nb = a.nb;
+    if (z->prefix_bytes) HIPCHK(c, hipMemcpyAsync(a.text->p, z->prefix, z->prefix_bytes, hipMemcpyHostToDevice, s));
+    if (nb) {
+        HIPCHK(c, hipMemcpyAsync(a.comp->p, z->comp, z->comp_bytes, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(a.off->p, z->blk_off, (nb + 1) * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(a.off->as<u64>() + (nb + 1), z->out_off, (nb + 1) * 8, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)nb), dim3(64), 0, s, a.comp->as<u8>(), a.off->as<u64>(), a.off->as<u64>() + (nb + 1), (long)nb,
+                           a.text->as<char>() + z->prefix_bytes, a.err->as<u32>());
+    }
+    if (last && a.bytes) {
+        // an unterminated last line counts as a line (the reader's rule): the newline is added here, on the device
+        hipLaunchKernelGGL(k_close_last_line, dim3(1), dim3(1), 0, s, a.text->as<char>(), a.bytes, tot_at(c, tot_file(TOT_NL_ADDED_1, f)));
+    } else HIPCHK(c, hipMemsetAsync(tot_at(c, tot_file(TOT_NL_ADDED_1, f)), 0, sizeof(u64), s));
+    return BMBS_OK;
+}
 
 int lane_text_open_bgzf(Lane* c, const bmbs_ztext* z1, const bmbs_ztext* z2, int64_t max_records, int32_t last1, int32_t last2, int64_t* n_records,
                         char* tail1, uint64_t tail_cap, uint64_t* tail1_bytes, char* tail2, uint64_t* tail2_bytes)
@@ -595,84 +628,57 @@ int lane_text_open_bgzf(Lane* c, const bmbs_ztext* z1, const bmbs_ztext* z2, int
     HIPCHK(c, hipSetDevice(c->dev));
     { const int rs = lane_settle(c); if (rs) return rs; }
     const bool pe = z2 != nullptr;
-    ZTextArgs A[2] = {{z1, &c->fq_text1, &c->z_comp, &c->z_off, &c->z_err}, {z2, &c->fq_text2, &c->z_comp2, &c->z_off2, &c->z_err2}};
+    ZTextArgs A[2] = {{z1, &c->fq_text1, &c->z_comp, &c->z_off, &c->z_err, 0, 0}, {z2, &c->fq_text2, &c->z_comp2, &c->z_off2, &c->z_err2, 0, 0}};
     const int32_t last[2] = {last1, last2};
-    u64 bytes[2] = {0, 0};
-    static const bool trace = getenv("BMBS_TEXT_TRACE") != nullptr;
-    auto wall = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; };
-    double tp[6] = {wall(), 0, 0, 0, 0, 0};
+    TextClock t; t.start = wall();
     HIPCHK(c, hipMemsetAsync(c->tx_info.p, 0, TXI_WORDS * sizeof(u32), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     // each file on a stream of its own: upload, inflate (one wave per block: a launch of one file's blocks leaves most of the chip's
     // wave slots empty, so the two files' launches run side by side), last line
-    hipStream_t fs[2] = {c->stream, c->kn.copy_streams && c->up_stream ? c->up_stream : c->stream};
+    hipStream_t fs[2] = {c->stream, up_stream_of(c)};
     for (int f = 0; f < (pe ? 2 : 1); f++) {
-        const bmbs_ztext* z = A[f].z;
-        const u64 nb = (u64)std::max<int64_t>(0, z->n_blocks);
+        // the file's buffers and block table checked, the lane's buffers sized
+        ZTextArgs& a = A[f];
+        const bmbs_ztext* z = a.z;
+        const u64 nb = a.nb = (u64)std::max<int64_t>(0, z->n_blocks);
         if ((z->prefix_bytes && !z->prefix) || (nb && (!z->comp || !z->blk_off || !z->out_off))) { c->err = "text open: NULL buffer"; return BMBS_EINVAL; }
-        const u64 text = nb ? z->out_off[nb] : 0;
         if (nb && z->blk_off[nb] > z->comp_bytes) { c->err = "text open: block table outside the compressed bytes"; return BMBS_EINVAL; }
-        for (u64 i = 0; i < nb; i++)
-            if (z->blk_off[i + 1] < z->blk_off[i] + 26 || z->out_off[i + 1] < z->out_off[i] || z->out_off[i + 1] - z->out_off[i] > 65536) { c->err = "text open: malformed block table"; return BMBS_EINVAL; }
+        { const int rc = blk_table_check(c, "text open", z->blk_off, z->out_off, nb); if (rc) return rc; }
         // (the text has to be contiguous behind the prefix: the inflate kernel takes any byte offset, and the line kernels read the
         // window from its 16-byte aligned start)
-        bytes[f] = z->prefix_bytes + text;
-        if (bytes[f] + 1 >= (1ull << 32)) { c->err = "a text window has to be smaller than 4 GiB (32-bit offsets)"; return BMBS_EINVAL; }
-        ENS(c, *A[f].text, bytes[f] + 64 + 16);
-        if (nb) { ENS(c, *A[f].comp, z->comp_bytes + 1024); ENS(c, *A[f].off, 2 * (nb + 1) * 8 + 64); ENS(c, *A[f].err, nb * 4 + 64); }
+        a.bytes = z->prefix_bytes + (nb ? z->out_off[nb] : 0);
+        if (a.bytes + 1 >= (1ull << 32)) { c->err = "a text window has to be smaller than 4 GiB (32-bit offsets)"; return BMBS_EINVAL; }
+        ENS(c, *a.text, a.bytes + 64 + 16);
+        if (nb) { ENS(c, *a.comp, z->comp_bytes + 1024); ENS(c, *a.off, 2 * (nb + 1) * 8 + 64); ENS(c, *a.err, nb * 4 + 64); }
     }
-    for (int f = 0; f < (pe ? 2 : 1); f++) {
-        const bmbs_ztext* z = A[f].z;
-        const u64 nb = (u64)std::max<int64_t>(0, z->n_blocks);
-        if (z->prefix_bytes) HIPCHK(c, hipMemcpyAsync(A[f].text->p, z->prefix, z->prefix_bytes, hipMemcpyHostToDevice, fs[f]));
-        if (nb) {
-            HIPCHK(c, hipMemcpyAsync(A[f].comp->p, z->comp, z->comp_bytes, hipMemcpyHostToDevice, fs[f]));
-            HIPCHK(c, hipMemcpyAsync(A[f].off->p, z->blk_off, (nb + 1) * 8, hipMemcpyHostToDevice, fs[f]));
-            HIPCHK(c, hipMemcpyAsync(A[f].off->as<u64>() + (nb + 1), z->out_off, (nb + 1) * 8, hipMemcpyHostToDevice, fs[f]));
-            hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)nb), dim3(64), 0, fs[f], A[f].comp->as<u8>(), A[f].off->as<u64>(), A[f].off->as<u64>() + (nb + 1), (long)nb,
-                               A[f].text->as<char>() + z->prefix_bytes, A[f].err->as<u32>());
-        }
-        if (last[f] && bytes[f]) {
-            // an unterminated last line counts as a line (the reader's rule): the newline is added here, on the device
-            hipLaunchKernelGGL(k_close_last_line, dim3(1), dim3(1), 0, fs[f], A[f].text->as<char>(), bytes[f], tot_at(c, tot_file(TOT_NL_ADDED_1, f)));
-        } else HIPCHK(c, hipMemsetAsync(tot_at(c, tot_file(TOT_NL_ADDED_1, f)), 0, sizeof(u64), fs[f]));
-    }
+    for (int f = 0; f < (pe ? 2 : 1); f++) { const int rc = ztext_inflate(c, A[f], f, last[f], fs[f]); if (rc) return rc; }
     if (pe && fs[1] != c->stream) HIPCHK(c, hipStreamSynchronize(fs[1]));
     // whether a newline was added has to be known before the lines are indexed
     HIPCHK(c, hipMemcpyAsync(c->h_info->nl_added, tot_at(c, TOT_NL_ADDED_1), sizeof c->h_info->nl_added, hipMemcpyDeviceToHost, c->stream));
     std::vector<u32> err[2];
     for (int f = 0; f < (pe ? 2 : 1); f++) {
-        const u64 nb = (u64)std::max<int64_t>(0, A[f].z->n_blocks);
-        err[f].resize(nb);
-        if (nb) HIPCHK(c, hipMemcpyAsync(err[f].data(), A[f].err->p, nb * 4, hipMemcpyDeviceToHost, c->stream));
+        err[f].resize(A[f].nb);
+        if (A[f].nb) HIPCHK(c, hipMemcpyAsync(err[f].data(), A[f].err->p, A[f].nb * 4, hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int f = 0; f < (pe ? 2 : 1); f++)
-        for (size_t i = 0; i < err[f].size(); i++)
-            if (err[f][i]) { c->err = "corrupt BGZF block in the .gz input (file " + std::to_string(f + 1) + ", block " + std::to_string(i) + " of this window, code " + std::to_string(err[f][i]) + ")"; return BMBS_EINVAL; }
-    tp[1] = wall();
+    for (int f = 0; f < (pe ? 2 : 1); f++) { const int rc = blk_errors(c, err[f].data(), err[f].size(), f + 1); if (rc) return rc; }
+    t.uploaded = wall();
     const u64* const added = c->h_info->nl_added;
-    bytes[0] += added[0]; if (pe) bytes[1] += added[1];
-    DevBuf* texts[2] = {&c->fq_text1, &c->fq_text2};
-    return lane_text_open_finish(c, pe, texts, bytes, max_records, n_records, tail1, tail_cap, tail1_bytes, tail2, tail2_bytes, tp, trace ? "bgzf" : nullptr,
-                                 (double)(z1->comp_bytes + (z2 ? z2->comp_bytes : 0)) / 1e6);
+    const u64 bytes[2] = {A[0].bytes + added[0], pe ? A[1].bytes + added[1] : 0};
+    return lane_text_open_finish(c, pe, bytes, max_records, n_records, tail1, tail_cap, tail1_bytes, tail2, tail2_bytes, t, (double)(z1->comp_bytes + (z2 ? z2->comp_bytes : 0)) / 1e6);
 }
 
 int lane_text_map_open(Lane* c, int32_t flags_in, char* sam, u64 sam_cap, u64* sam_bytes, int64_t* n_lines_out)
 {
     if (!c) return BMBS_EINVAL;
-    if (sam_bytes) *sam_bytes = 0;
-    if (n_lines_out) *n_lines_out = 0;
-    if ((flags_in & BMBS_TEXT_BAM_SORTED) && !(flags_in & BMBS_TEXT_BAM)) { c->err = "text call: BMBS_TEXT_BAM_SORTED is only valid together with BMBS_TEXT_BAM"; return BMBS_EINVAL; }
-    if (flags_in & BMBS_TEXT_BAM_SORTED) c->ends(Lane::SORTED_TEXT_CALL);
+    { const int r0 = text_call_begin(c, flags_in, sam_bytes, n_lines_out); if (r0) return r0; }
     if (!c->open_text.valid) { c->err = "text map: no open batch (bmbs_text_open_bgzf first)"; return BMBS_ESTATE; }
     if (c->n_refs != c->ix.n_chrom) { c->err = "bmbs_sam_refs has not been given the index's reference names"; return BMBS_ESTATE; }
     if (!sam) { c->err = "text call: NULL buffer"; return BMBS_EINVAL; }
     HIPCHK(c, hipSetDevice(c->dev));
-    auto wall = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; };
-    const double t0 = wall();
+    TextClock t; t.start = t.uploaded = wall();
     // (an output buffer that turns out too small leaves the batch open: the call can be repeated)
-    const int rc = lane_text_finish(c, c->open_text.pe, c->open_text.bytes1, c->open_text.bytes2, c->open_text.n, flags_in, sam, sam_cap, sam_bytes, n_lines_out, t0, t0);
+    const int rc = lane_text_finish(c, c->open_text.pe, c->open_text.bytes1, c->open_text.bytes2, c->open_text.n, flags_in, sam, sam_cap, sam_bytes, n_lines_out, t);
     if (rc != BMBS_ENOMEM) c->open_text.valid = false;
     return rc;
 }
@@ -707,15 +713,11 @@ static int lane_inflate_bgzf(Lane* c, const void* comp, uint64_t comp_bytes, con
     if (!comp || !blk_off || !out_off || !text) { c->err = "inflate: NULL buffer"; return BMBS_EINVAL; }
     const u64 n = (u64)n_blocks;
     if (blk_off[n] > comp_bytes || out_off[n] > text_bytes) { c->err = "inflate: block table outside the buffers"; return BMBS_EINVAL; }
-    for (u64 i = 0; i < n; i++)
-        if (blk_off[i + 1] < blk_off[i] + 26 || out_off[i + 1] < out_off[i] || out_off[i + 1] - out_off[i] > 65536) { c->err = "inflate: malformed block table"; return BMBS_EINVAL; }
+    { const int r0 = blk_table_check(c, "inflate", blk_off, out_off, n); if (r0) return r0; }
     HIPCHK(c, hipSetDevice(c->dev));
-    static const bool trace = getenv("BMBS_TEXT_TRACE") != nullptr;       // diagnostic: host-side phase times of every call
-    auto wall = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; };
     const double t0 = wall();
     ENS(c, c->z_comp, comp_bytes + 1024); ENS(c, c->z_off, 2 * (n + 1) * 8 + 64); ENS(c, c->z_text, out_off[n] + 64); ENS(c, c->z_err, n * 4 + 64);
-    hipStream_t us = c->kn.copy_streams && c->up_stream ? c->up_stream : c->stream;
-    hipStream_t ds = c->kn.copy_streams && c->down_stream ? c->down_stream : c->stream;
+    hipStream_t us = up_stream_of(c), ds = down_stream_of(c);
     HIPCHK(c, hipMemcpyAsync(c->z_comp.p, comp, comp_bytes, hipMemcpyHostToDevice, us));
     HIPCHK(c, hipMemcpyAsync(c->z_off.p, blk_off, (n + 1) * 8, hipMemcpyHostToDevice, us));
     HIPCHK(c, hipMemcpyAsync(c->z_off.as<u64>() + (n + 1), out_off, (n + 1) * 8, hipMemcpyHostToDevice, us));
@@ -733,14 +735,12 @@ static int lane_inflate_bgzf(Lane* c, const void* comp, uint64_t comp_bytes, con
     std::vector<u32> err(n);
     HIPCHK(c, hipMemcpyAsync(err.data(), c->z_err.p, n * 4, hipMemcpyDeviceToHost, ds));
     if (n_cnt) HIPCHK(c, hipMemcpyAsync(nl_per_64k, c->z_nl.p, n_cnt * 4, hipMemcpyDeviceToHost, ds));
-    int rc = d2h_chunked(c, text, c->z_text.as<char>(), out_off[n], ds);
+    const int rc = d2h_chunked(c, text, c->z_text.as<char>(), out_off[n], ds);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(ds));
-    if (trace) fprintf(stderr, "[inflate] %lu blocks, %.1f MB -> %.1f MB: alloc+upload %.2f  kernel %.2f  download %.2f ms\n", (unsigned long)n, (double)comp_bytes / 1e6, (double)out_off[n] / 1e6,
-                       (t1 - t0) * 1e3, (t2 - t1) * 1e3, (wall() - t2) * 1e3);
-    for (u64 i = 0; i < n; i++)
-        if (err[i]) { c->err = "corrupt BGZF block in the .gz input (block " + std::to_string(i) + " of this window, code " + std::to_string(err[i]) + ")"; return BMBS_EINVAL; }
-    return BMBS_OK;
+    if (text_trace()) fprintf(stderr, "[inflate] %lu blocks, %.1f MB -> %.1f MB: alloc+upload %.2f  kernel %.2f  download %.2f ms\n", (unsigned long)n, (double)comp_bytes / 1e6, (double)out_off[n] / 1e6,
+                              (t1 - t0) * 1e3, (t2 - t1) * 1e3, (wall() - t2) * 1e3);
+    return blk_errors(c, err.data(), n, 0);
 }
 
 extern "C" int bmbs_inflate_bgzf(bmbs_ctx* X, const void* comp, uint64_t comp_bytes, const uint64_t* blk_off, const uint64_t* out_off, int64_t n_blocks,
@@ -800,7 +800,6 @@ extern "C" int bmbs_text_times(bmbs_ctx* X, double out[4])
     return BMBS_OK;
 }
 
-
 extern "C" int bmbs_sam_refs(bmbs_ctx* X, const char* const* names, int32_t n_names) { ON_LANE0(lane_sam_refs(c, names, n_names)); }
 extern "C" int bmbs_map_se_text(bmbs_ctx* X, const char* text, uint64_t text_bytes, int64_t n_records, int32_t flags, char* sam, uint64_t sam_cap,
                                 uint64_t* sam_bytes, int64_t* n_lines)
@@ -815,8 +814,8 @@ extern "C" int bmbs_map_pe_text(bmbs_ctx* X, const char* text1, uint64_t bytes1,
 { ON_LANE0(lane_map_text(c, true, text1, bytes1, text2, bytes2, n_pairs, flags, sam, sam_cap, sam_bytes, n_lines)); }
 extern "C" int bmbs_map_se_fastq(bmbs_ctx* X, const bmbs_fastq_view* reads, int64_t n_reads, int32_t L_max, int32_t uniform, int32_t pbat,
                                  bmbs_result* results, uint32_t* cigar_pool, int64_t cigar_cap, int64_t* n_cigar_used)
-{ ON_LANE0(lane_map_se_fastq(c, reads, n_reads, L_max, uniform, pbat, results, cigar_pool, cigar_cap, n_cigar_used)); }
+{ const bmbs_fastq_view* const v[2] = {reads, nullptr}; ON_LANE0(lane_map_fastq(c, false, v, n_reads, L_max, uniform, pbat, results, cigar_pool, cigar_cap, n_cigar_used)); }
 extern "C" int bmbs_map_pe_fastq(bmbs_ctx* X, const bmbs_fastq_view* mate1, const bmbs_fastq_view* mate2, int64_t n_pairs, int32_t L_max,
                                  int32_t uniform, bmbs_result* results, uint32_t* cigar_pool, int64_t cigar_cap, int64_t* n_cigar_used)
-{ ON_LANE0(lane_map_pe_fastq(c, mate1, mate2, n_pairs, L_max, uniform, results, cigar_pool, cigar_cap, n_cigar_used)); }
+{ const bmbs_fastq_view* const v[2] = {mate1, mate2}; ON_LANE0(lane_map_fastq(c, true, v, n_pairs, L_max, uniform, 0, results, cigar_pool, cigar_cap, n_cigar_used)); }
 
