@@ -32,8 +32,6 @@ int ensure(Lane* c, DevBuf& b, size_t bytes, bool zero)
 }
 void release(DevBuf& b) { if (b.p && !b.arena) (void)hipFree(b.p); b.p = nullptr; b.cap = 0; b.arena = false; }
 
-
-
 void prof_begin(Lane* c, const char* name)
 {
     std::vector<Prof>& set = c->profset[c->cur_slot];
@@ -48,18 +46,22 @@ void prof_begin(Lane* c, const char* name)
     (void)hipEventRecord(p.a, c->stream);
 }
 void prof_end(Lane* c) { (void)hipEventRecord(c->profset[c->cur_slot][(size_t)c->prof_used[c->cur_slot]].b, c->stream); c->prof_used[c->cur_slot]++; }
+// the time between two events of completed work -> the running sums
+float prof_add(Lane* c, const char* name, hipEvent_t a, hipEvent_t b)
+{
+    float t = 0;
+    if (hipEventElapsedTime(&t, a, b) != hipSuccess) t = 0.f;
+    for (auto& s : c->acc) if (s.name == name || !strcmp(s.name, name)) { s.ms += t; return t; }
+    c->acc.push_back({name, (double)t});
+    return t;
+}
 // the events of a call whose stream work has completed -> `last` and the running sums
 void prof_collect(Lane* c, int slot)
 {
     c->last.clear();
     for (int i = 0; i < c->prof_used[slot]; i++) {
         const Prof& p = c->profset[slot][(size_t)i];
-        float t = 0;
-        if (hipEventElapsedTime(&t, p.a, p.b) != hipSuccess) t = 0.f;
-        c->last.push_back({p.name, (double)t});
-        bool found = false;
-        for (auto& a : c->acc) if (a.name == p.name || !strcmp(a.name, p.name)) { a.ms += t; found = true; break; }
-        if (!found) c->acc.push_back({p.name, (double)t});
+        c->last.push_back({p.name, (double)prof_add(c, p.name, p.a, p.b)});
     }
     c->acc_calls++;
 }
@@ -648,7 +650,6 @@ int upload_rows(Lane* c, DevBuf& dst, const char* src, int L, int stride, u64 n,
     return BMBS_OK;
 }
 
-
 // ================================================================================================
 extern "C" void bmbs_default_params(bmbs_params* p)
 {
@@ -766,8 +767,6 @@ void lane_destroy(Lane* c)
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
-
-// the lane a stage entry point runs on; a failing call leaves its message in the context
 
 extern "C" bmbs_ctx* bmbs_create(int device_id, const bmbs_params* params)
 {
@@ -1509,8 +1508,7 @@ int lane_enqueue(Lane* c, Pending P, bool staged)
 // what earlier calls needed per read is shared by the lanes of a context
 void share_needs(bmbs_ctx* X)
 {
-    double a = 0, b = 0, d = 0, g = 0;
-    double ch = 0;
+    double a = 0, b = 0, d = 0, g = 0, ch = 0;
     for (Lane* c : X->lanes) { a = std::max(a, c->lr_cand); b = std::max(b, c->lr_sw); d = std::max(d, c->lr_rcand); g = std::max(g, c->lr_long); ch = std::max(ch, c->lr_chain); }
     for (Lane* c : X->lanes) { c->lr_cand = a; c->lr_sw = b; c->lr_rcand = d; c->lr_long = g; c->lr_chain = ch; }
 }
@@ -1522,9 +1520,6 @@ int settle_all(bmbs_ctx* X)
     return rc_all;
 }
 
-// units per chunk of a call: the whole call on lane 0 when it is small (or the caller's CIGAR pool has no room for every chunk's
-// worst case), otherwise n / lanes (BMBS_CHUNK overrides) so that every lane gets one chunk per call
-// host_copies: the chunks carry their own H2D / D2H copies; smaller ones (n / 8, within 250 k .. 500 k units) leave a shorter tail behind the last upload
 // lanes a device call is dealt to.  Measured on one box, lanes overlapping (round 6; M reads/s at 2 / 3 / 4 lanes): uniform-random genome
 // 1249 / 1211-vs-1201 / 1179 -- the seeding kernels there sit at the gather ceiling and a fourth lane only adds contention --;
 // GRCh38-like pairs 622 / 640 / 646, single-end 412 / 419 / 421, --sensitive 428 / 440 / 450 -- the list kernels wait on their own
@@ -1532,286 +1527,292 @@ int settle_all(bmbs_ctx* X)
 // settled calls had shown, was built and taken out again: a call's chunk boundaries -- and with them the records' cigar_off -- then
 // differed between the first and the second call of a context on the same input.)
 int device_lanes(const bmbs_ctx* X) { return std::min<int>((int)X->lanes.size(), X->kn.lanes); }
-int64_t chunk_units(const bmbs_ctx* X, int64_t n, int64_t cigar_cap, int rpu, int max_ops, bool host_copies = false, int n_lanes = 0)
+// ---- the chunk plan of a mapping call: how its n units (reads, or pairs: rpu records each) are cut into chunks of ch, and the one
+// place that says where chunk k starts, how long it is, which lane takes it and which part of the caller's CIGAR pool is its own
+struct ChunkPlan {
+    bool pe = false, whole = true;               // whole: the call runs as one chunk on lane 0, on the caller's pool as it is
+    int32_t L = 0; int rpu = 1, max_ops = 0, used_lanes = 1;
+    int64_t n = 0, ch = 0, n_chunks = 0, cigar_cap = 0;
+    int64_t off(int64_t k) const { return k * ch; }
+    int64_t units(int64_t k) const { return std::min(ch, n - off(k)); }
+    int lane(int64_t k) const { return (int)(k % used_lanes); }
+    int64_t worst_case(int64_t k) const { return units(k) * rpu * (int64_t)max_ops; }      // CIGAR words if every read of chunk k needs K12
+    u64 cigar_base(int64_t k) const { return whole ? 0 : (u64)off(k) * rpu * (u64)max_ops; }
+    int64_t cigar_room(int64_t k) const { return whole ? cigar_cap : worst_case(k); }       // what of the caller's pool belongs to chunk k
+};
+// host_copies: a host call -- its chunks carry their own H2D / D2H copies and are dealt to every lane of the context, not to device_lanes of them
+ChunkPlan plan_chunks(const bmbs_ctx* X, bool pe, int32_t L, int64_t n, int64_t cigar_cap, bool host_copies)
 {
-    const int64_t nl = host_copies ? (int64_t)X->lanes.size() : (int64_t)(n_lanes > 0 ? n_lanes : device_lanes(X));
-    if (nl < 2 || n < 2 * X->kn.split_min || cigar_cap < n * rpu * (int64_t)max_ops) return n;
-    int64_t ch = X->kn.chunk > 0 ? X->kn.chunk : (n + nl - 1) / nl;
-    // (a call of 2 M pairs: 126 M reads/s in chunks of 500 k, 133-138 in chunks of 250 k -- the first upload and the last chunk's
-    // kernels and download are not hidden behind anything; tools/hostbuf_ab.py)
-    if (host_copies && X->kn.chunk <= 0) ch = std::min<int64_t>(ch, std::min<int64_t>(500000, std::max<int64_t>(250000, n / 8)));
-    if (ch < X->kn.split_min) ch = X->kn.split_min;
-    return ch < n ? ch : n;
+    ChunkPlan p;
+    p.pe = pe; p.L = L; p.rpu = pe ? 2 : 1; p.max_ops = cigar_ops_bound(X->prm, L, threshold_k(X->prm, L)); p.n = p.ch = n; p.cigar_cap = cigar_cap;
+    const int64_t nl = host_copies ? (int64_t)X->lanes.size() : device_lanes(X);
+    // a small call is not cut, and neither is one whose pool has no room for every chunk's worst case
+    if (nl >= 2 && n >= 2 * X->kn.split_min && cigar_cap >= n * p.rpu * (int64_t)p.max_ops) {
+        p.ch = X->kn.chunk > 0 ? X->kn.chunk : (n + nl - 1) / nl;            // one chunk per lane (BMBS_CHUNK overrides)
+        // ... and smaller ones where they carry copies: a shorter tail behind the last upload (a call of 2 M pairs: 126 M reads/s in
+        // chunks of 500 k, 133-138 in chunks of 250 k -- the first upload and the last chunk's kernels and download are not hidden
+        // behind anything; tools/hostbuf_ab.py)
+        if (host_copies && X->kn.chunk <= 0) p.ch = std::min<int64_t>(p.ch, std::min<int64_t>(500000, std::max<int64_t>(250000, n / 8)));
+        p.ch = std::max<int64_t>(p.ch, X->kn.split_min);
+    }
+    p.whole = p.ch >= n;
+    if (p.whole) p.ch = n;
+    p.n_chunks = n > 0 ? (n + p.ch - 1) / p.ch : 0;
+    p.used_lanes = (int)std::min<int64_t>(nl, p.n_chunks);
+    return p;
 }
-
+// chunk k as the launch sequences take it: its rows at a[] (seq 1, qual 1, seq 2, qual 2; `stride` bytes apart), its lengths, where its records and CIGAR words go
+Pending chunk_pending(const ChunkPlan& p, int64_t k, int32_t stride, const uint64_t a[4], const u16* d_len, uint64_t d_results, uint64_t d_cigar_pool, int64_t pool_cap)
+{
+    Pending P;
+    P.pe = p.pe; P.L = p.L; P.stride = stride; P.n = p.units(k); P.d_len = d_len;
+    for (int i = 0; i < (p.pe ? 4 : 2); i++) P.a[i] = a[i];
+    P.d_results = d_results; P.d_cigar_pool = d_cigar_pool; P.cigar_cap = pool_cap; P.cigar_base = (u32)p.cigar_base(k);
+    return P;
+}
 // *_device entry points: the call is cut into chunks dealt to the lanes in turn; nothing waits (bmbs_sync does)
-int dispatch_device(bmbs_ctx* X, bool pe, uint64_t a0, uint64_t a1, uint64_t a2, uint64_t a3, const u16* d_len, int32_t L, int32_t stride, int64_t n,
-                    uint64_t d_results, uint64_t d_cigar_pool, int64_t cigar_cap)
+struct DevIn { uint64_t seq1 = 0, qual1 = 0, seq2 = 0, qual2 = 0; const u16* len = nullptr; };      // len: [n first mates][n second mates]
+int dispatch_device(bmbs_ctx* X, bool pe, const DevIn& in, int32_t L, int32_t stride, int64_t n, uint64_t d_results, uint64_t d_cigar_pool, int64_t cigar_cap)
 {
     if (!X || X->lanes.empty()) return BMBS_EINVAL;
-    Lane* c0 = X->lanes[0];
     if (L <= 0 || L > BMBS_MAX_READ || stride < L || n < 0) { X->err = "bad read geometry"; return BMBS_EINVAL; }
     if (n == 0) return BMBS_OK;
-    const int rpu = pe ? 2 : 1;
-    const int max_ops = cigar_ops_bound(X->prm, L, threshold_k(X->prm, L));
     share_needs(X);
-    const int n_lanes = device_lanes(X);                  // (fixed for the call: a lane that settles meanwhile may learn a new lr_long)
-    const int64_t ch = chunk_units(X, n, cigar_cap, rpu, max_ops, false, n_lanes);
-    int li = 0, used = 0;
-    for (int64_t off = 0; off < n; off += ch) {
-        const int64_t m = std::min(ch, n - off);
-        Lane* c = ch == n ? c0 : X->lanes[(size_t)li];
-        Pending P;
-        P.pe = pe; P.L = L; P.stride = stride; P.n = m;
+    const ChunkPlan p = plan_chunks(X, pe, L, n, cigar_cap, false);        // (fixed for the call, whatever a lane that settles meanwhile learns)
+    for (int64_t k = 0; k < p.n_chunks; k++) {
+        Lane* c = X->lanes[(size_t)p.lane(k)];
+        const int64_t off = p.off(k), m = p.units(k);
         const uint64_t ro = (uint64_t)off * (uint64_t)stride;
-        P.a[0] = a0 + ro; P.a[1] = a1 + ro; P.a[2] = pe ? a2 + ro : 0; P.a[3] = pe ? a3 + ro : 0;
-        P.d_results = d_results + (uint64_t)off * rpu * 32;
-        bool staged = false;
-        P.d_len = d_len;
-        if (d_len && ch != n) {
-            if (!pe) P.d_len = d_len + off;
-            else {
-                // a chunk of pairs wants its lengths as [m first mates][m second mates]: re-laid into the lane's own array
-                HIPCHK(c, hipSetDevice(c->dev));
-                if (!c->inflight.empty()) { const int rs = lane_settle(c); if (rs) { X->err = c->err; return rs; } }
-                ENS(c, c->in_len, (u64)m * 4 + 16);
-                HIPCHK(c, hipMemcpyAsync(c->in_len.as<u16>(), d_len + off, (size_t)m * 2, hipMemcpyDeviceToDevice, c->stream));
-                HIPCHK(c, hipMemcpyAsync(c->in_len.as<u16>() + m, d_len + n + off, (size_t)m * 2, hipMemcpyDeviceToDevice, c->stream));
-                P.d_len = c->in_len.as<u16>();
-                staged = true;
-            }
+        const uint64_t a[4] = {in.seq1 + ro, in.qual1 + ro, in.seq2 + ro, in.qual2 + ro};
+        const u16* len = in.len && !p.whole ? in.len + off : in.len;
+        const bool staged = in.len && !p.whole && pe;
+        if (staged) {
+            // a chunk of pairs wants its lengths as [m first mates][m second mates]: re-laid into the lane's own array
+            HIPCHK(c, hipSetDevice(c->dev));
+            if (!c->inflight.empty()) { const int rs = lane_settle(c); if (rs) { X->err = c->err; return rs; } }
+            ENS(c, c->in_len, (u64)m * 4 + 16);
+            HIPCHK(c, hipMemcpyAsync(c->in_len.as<u16>(), in.len + off, (size_t)m * 2, hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(c->in_len.as<u16>() + m, in.len + n + off, (size_t)m * 2, hipMemcpyDeviceToDevice, c->stream));
+            len = c->in_len.as<u16>();
         }
-        if (ch == n) { P.d_cigar_pool = d_cigar_pool; P.cigar_cap = cigar_cap; P.cigar_base = 0; }
-        else {
-            const uint64_t base = (uint64_t)off * rpu * (uint64_t)max_ops;
-            P.d_cigar_pool = d_cigar_pool + base * 4; P.cigar_cap = m * rpu * (int64_t)max_ops; P.cigar_base = (u32)base;
-        }
+        const Pending P = chunk_pending(p, k, stride, a, len, d_results + (uint64_t)off * p.rpu * 32, d_cigar_pool + p.cigar_base(k) * 4, p.cigar_room(k));
         const int rc = lane_enqueue(c, P, staged);
         if (rc) { X->err = c->err; return rc; }
-        used = std::max(used, (ch == n ? 0 : li) + 1);
-        li = (li + 1) % n_lanes;
     }
-    X->used_lanes = used;
+    X->used_lanes = p.used_lanes;
     return BMBS_OK;
 }
 
-// host entry points: chunk i is uploaded, mapped and read back on lane i % lanes -- its copies run beside the kernels of the
-// chunks on the other lanes (one direction of the link each: 48 GB/s both ways at once on the MI355X boxes, tools/pcie_probe)
-struct HostIn { const char *seq1, *qual1, *seq2, *qual2; const uint16_t *len1, *len2; const uint64_t *rows1 = nullptr, *rows2 = nullptr; int hw = 0;
-                const uint64_t *qrows1 = nullptr, *qrows2 = nullptr; int qw = 0; };      // qw > 0: packed quality classes instead of qual1 / qual2
-int dispatch_host(bmbs_ctx* X, bool pe, const HostIn& in, int32_t L, int32_t stride, int64_t n, bmbs_result* results, uint32_t* cigar_pool, int64_t cigar_cap,
-                  int64_t* n_cigar_used)
+// host entry points: chunk k is uploaded, mapped and read back on lane k % lanes -- its copies run beside the kernels of the
+// chunks on the other lanes (one direction of the link each: 48 GB/s both ways at once on the MI355X boxes, tools/pcie_probe).
+// Per mate: ASCII rows or (hw > 0) packed rows hw words apart, quality bytes or (qw > 0) packed quality classes qw words apart, lengths or none
+struct HostMate { const char *seq = nullptr, *qual = nullptr; const uint16_t* len = nullptr; const uint64_t *rows = nullptr, *qrows = nullptr; };
+struct HostIn { HostMate m[2]; int hw = 0, qw = 0; };
+// a host-buffer call, stage by stage: issue (upload, expand_quals, enqueue) puts chunk k on its lane, finish takes it off again
+struct HostCall {
+    bmbs_ctx* X; const HostIn& in; int32_t stride; bmbs_result* results; uint32_t* cigar_pool; const ChunkPlan p;
+    const int ds = (p.L + 15) / 16 * 16;                                        // stride of the rows on the device: what upload_rows gives them
+    std::vector<int64_t> open = std::vector<int64_t>(X->lanes.size(), -1);      // per lane: the chunk in flight (-1: none)
+    std::atomic<int64_t> extent{0};                                             // words of the caller's CIGAR pool in use
+    int rc = BMBS_OK; std::mutex err_mu; std::atomic<int> stop{0};
+    static hipStream_t up_of(const Lane* c) { return copy_streams(c) ? c->up_stream : c->stream; }
+    static hipStream_t down_of(const Lane* c) { return copy_streams(c) ? c->down_stream : c->stream; }
+    // chunk k of an array of w words per read (packed rows, packed quality classes): it goes over as it is, one block per mate
+    int upload_words(Lane* c, DevBuf& dst, const uint64_t* src, int w, int64_t k)
+    {
+        ENS(c, dst, (u64)p.units(k) * (u64)w * 8 + 64);
+        HIPCHK(c, hipMemcpyAsync(dst.p, src + (size_t)p.off(k) * (size_t)w, (u64)p.units(k) * (u64)w * 8, hipMemcpyHostToDevice, up_of(c)));
+        return BMBS_OK;
+    }
+    int upload_bytes(Lane* c, DevBuf& dst, const char* src, int64_t k)
+    { int to = 0; return upload_rows(c, dst, src + (size_t)p.off(k) * (size_t)stride, p.L, stride, (u64)p.units(k), &to, up_of(c)); }
+    // everything chunk k reads, on the upload stream: rows, qualities, lengths; the kernel stream waits for the last of them
+    int upload(Lane* c, int64_t k)
+    {
+        const HostMate &m1 = in.m[0], &m2 = in.m[1];
+        const u64 um = (u64)p.units(k); int r = BMBS_OK;
+        if (in.hw) { r = upload_words(c, c->pk_in1, m1.rows, in.hw, k); if (!r && p.pe) r = upload_words(c, c->pk_in2, m2.rows, in.hw, k); }
+        else r = upload_bytes(c, c->in_seq, m1.seq, k);
+        if (r) return r;
+        if (in.qw) {                                // (the byte rows expand_quals writes are sized here, with the upload buffers)
+            ENS(c, c->in_qual, um * (u64)ds + 64);
+            r = upload_words(c, c->pq_in1, m1.qrows, in.qw, k);
+            if (!r && p.pe) { ENS(c, c->in_qual2, um * (u64)ds + 64); r = upload_words(c, c->pq_in2, m2.qrows, in.qw, k); }
+        } else r = upload_bytes(c, c->in_qual, m1.qual, k);
+        if (r) return r;
+        if (p.pe && !in.hw) { r = upload_bytes(c, c->in_seq2, m2.seq, k); if (r) return r; }
+        if (p.pe && !in.qw) { r = upload_bytes(c, c->in_qual2, m2.qual, k); if (r) return r; }
+        if (m1.len) {
+            r = upload_lens(c, m1.len + p.off(k), um, 0, um * p.rpu, p.L, up_of(c));
+            if (!r && p.pe) r = upload_lens(c, m2.len + p.off(k), um, um, um * p.rpu, p.L, up_of(c));
+            if (r) return r;
+        }
+        if (copy_streams(c)) { HIPCHK(c, hipEventRecord(c->ev_up, c->up_stream)); HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_up, 0)); }
+        return BMBS_OK;
+    }
+    // packed quality classes -> the byte rows, at the stride upload_rows would have given them: on the kernel stream, in front of the call, so that a
+    // chunk issued again with exact sizes finds them in place.  Its two events stand outside the call's event set: finish adds their time to the running sums
+    int expand_quals(Lane* c, int64_t k)
+    {
+        const int Wq = ds / 16;
+        const u64 words = (u64)p.units(k) * (u64)Wq * (u64)p.rpu;
+        if (!c->ev_qx_a) { HIPCHK(c, hipEventCreate(&c->ev_qx_a)); HIPCHK(c, hipEventCreate(&c->ev_qx_b)); }
+        const QualRep rep = {c->qrep_lo, c->qrep_hi};
+        HIPCHK(c, hipEventRecord(c->ev_qx_a, c->stream));
+        hipLaunchKernelGGL(k_qual_expand, dim3(std::min<unsigned>(nblk(words, 256), 4096u)), dim3(256), 0, c->stream, c->pq_in1.as<u64>(),
+                           p.pe ? c->pq_in2.as<u64>() : (const u64*)nullptr, in.qw, Wq, (long)p.units(k), rep, c->in_qual.as<uint4>(),
+                           p.pe ? c->in_qual2.as<uint4>() : (uint4*)nullptr);
+        HIPCHK(c, hipEventRecord(c->ev_qx_b, c->stream));
+        c->qx_timed = true;
+        return BMBS_OK;
+    }
+    // the call on the lane's staging buffers, and the records' download behind it
+    int enqueue(Lane* c, int64_t k)
+    {
+        const uint64_t a[4] = {(uint64_t)(in.hw ? c->pk_in1.p : c->in_seq.p), (uint64_t)c->in_qual.p, (uint64_t)(in.hw ? c->pk_in2.p : c->in_seq2.p), (uint64_t)c->in_qual2.p};
+        Pending P = chunk_pending(p, k, ds, a, in.m[0].len ? c->in_len.as<u16>() : nullptr, (uint64_t)c->out_res.p, (uint64_t)c->cig_pool.p, p.worst_case(k));
+        P.packed_hw = in.hw;
+        { const int r = lane_enqueue(c, P, true); if (r) return r; }
+        if (copy_streams(c)) { HIPCHK(c, hipEventRecord(c->ev_k, c->stream)); HIPCHK(c, hipStreamWaitEvent(c->down_stream, c->ev_k, 0)); }
+        HIPCHK(c, hipMemcpyAsync(results + p.off(k) * p.rpu, c->out_res.p, (u64)p.units(k) * p.rpu * 32, hipMemcpyDeviceToHost, down_of(c)));
+        return BMBS_OK;
+    }
+    // upload, kernels and the records' download of chunk k on its lane (whose previous chunk has been finished)
+    int issue(Lane* c, int64_t k)
+    {
+        HIPCHK(c, hipSetDevice(c->dev));
+        ENS(c, c->out_res, (u64)p.units(k) * p.rpu * 32);
+        ENS(c, c->cig_pool, (u64)p.worst_case(k) * 4);
+        // One upload at a time per device (the text calls' rule, bmbs_textpath.hip): four lanes that upload side by side share the
+        // link, finish together, compute together and leave the link idle meanwhile -- in turn, each chunk goes up at the full
+        // rate and its kernels run beside the next lane's upload.  The lock is held until this chunk's copies have ended; the
+        // kernels are queued behind them meanwhile.  BMBS_UP_TURNS=0: the round-5 form.  (ONE upload stream shared by the lanes --
+        // copies back to back with no host in between -- measured no better than side-by-side uploads: 172 against 174 / 165 M
+        // reads/s, turns 186 / 192; 2 M pairs per call, profiles/HISTORY.md)
+        std::unique_lock<std::mutex> up_turn(g_h2d_mu[c->dev & 15], std::defer_lock);
+        if (copy_streams(c) && p.used_lanes > 1 && c->kn.up_turns) up_turn.lock();
+        int r = upload(c, k);
+        if (!r && in.qw) r = expand_quals(c, k);
+        if (!r) r = enqueue(c, k);
+        if (r) return r;
+        if (up_turn.owns_lock()) HIPCHK(c, hipEventSynchronize(c->ev_up));          // this chunk is up: the next lane's turn
+        return BMBS_OK;
+    }
+    // the chunk in flight on lane li: its counts, then exactly the CIGAR operations it produced
+    int finish(int li)
+    {
+        const int64_t k = std::exchange(open[(size_t)li], -1);
+        if (k < 0) return BMBS_OK;
+        Lane* c = X->lanes[(size_t)li];
+        const u64 retries0 = c->n_retries;
+        { const int r = lane_settle(c); if (r) return r; }
+        if (c->qx_timed) { c->qx_timed = false; prof_add(c, "k_qual_expand", c->ev_qx_a, c->ev_qx_b); }
+        if (c->n_retries != retries0)               // the chunk was issued again with exact sizes: the records copied behind the first attempt are stale
+            HIPCHK(c, hipMemcpyAsync(results + p.off(k) * p.rpu, c->out_res.p, (u64)p.units(k) * p.rpu * 32, hipMemcpyDeviceToHost, down_of(c)));
+        const u64 used = c->last_n_jobs * (u64)p.max_ops, base = p.cigar_base(k);
+        if (base + used > (u64)p.cigar_cap) { c->err = "host cigar pool too small"; return BMBS_ENOMEM; }
+        if (used) {
+            HIPCHK(c, hipMemcpyAsync(cigar_pool + base, c->cig_pool.p, used * 4, hipMemcpyDeviceToHost, down_of(c)));
+            int64_t seen = extent.load();
+            while ((int64_t)(base + used) > seen && !extent.compare_exchange_weak(seen, (int64_t)(base + used))) {}
+        }
+        HIPCHK(c, hipStreamSynchronize(down_of(c)));
+        return BMBS_OK;
+    }
+    // the chunks of lane li, one behind the other; the first error of the call wins rc and X->err and stops the other lanes
+    void run_lane(int li)
+    {
+        Lane* c = X->lanes[(size_t)li];
+        (void)hipSetDevice(c->dev);
+        int r = BMBS_OK;
+        for (int64_t k = li; k < p.n_chunks && !r && !stop.load(); k += p.used_lanes) {
+            r = finish(li);
+            if (!r) r = issue(c, k);
+            if (!r) open[(size_t)li] = k;
+        }
+        if (!r) r = finish(li);
+        if (r) { stop.store(1); std::lock_guard<std::mutex> l(err_mu); if (!rc) { rc = r; X->err = c->err; } }
+    }
+    // One host thread per lane: a chunk is ~110 kernel launches and a handful of waits, and with all of them issued by one thread the
+    // call was bound by that thread on boxes with slower cores (2 M pairs through bmbs_map_pe_packed: 137 M reads/s where the link
+    // would give 200).  Chunk k goes to lane k % lanes whoever issues it: the results do not depend on the threads.
+    int run()
+    {
+        std::vector<std::thread> th;
+        for (int t = 1; t < p.used_lanes; t++) th.emplace_back(&HostCall::run_lane, this, t);
+        run_lane(0);
+        for (auto& t : th) t.join();
+        if (rc) for (Lane* c : X->lanes) { (void)hipStreamSynchronize(c->stream); if (c->down_stream) (void)hipStreamSynchronize(c->down_stream); c->inflight.clear(); }
+        return rc;
+    }
+};
+int dispatch_host(bmbs_ctx* X, bool pe, const HostIn& in, int32_t L, int32_t stride, int64_t n, bmbs_result* results, uint32_t* pool, int64_t cigar_cap, int64_t* n_cigar_used)
 {
     static_assert(sizeof(bmbs_result) == 32 && sizeof(bmbs_result_dev) == 32, "result record is 32 bytes");
     if (!X || X->lanes.empty()) return BMBS_EINVAL;
     if (n_cigar_used) *n_cigar_used = 0;
     if (n <= 0) return BMBS_OK;
     if (L <= 0 || L > BMBS_MAX_READ || stride < L) { X->err = "bad read geometry"; return BMBS_EINVAL; }
-    const int rpu = pe ? 2 : 1;
-    const int max_ops = cigar_ops_bound(X->prm, L, threshold_k(X->prm, L));
-    const int64_t ch = chunk_units(X, n, cigar_cap, rpu, max_ops, true);
-    const int nl = (int)X->lanes.size();
-    const int64_t n_chunks = (n + ch - 1) / ch;
-    const int used_lanes = ch == n ? 1 : (int)std::min<int64_t>(nl, n_chunks);
     share_needs(X);
-    struct Open { bool on = false; int64_t off = 0, m = 0; };
-    std::vector<Open> open((size_t)nl);
-    std::atomic<int64_t> extent(0);
-    auto finish = [&](int li) -> int {            // the chunk in flight on lane li: counts, then exactly the CIGAR operations it produced
-        Open& o = open[(size_t)li];
-        if (!o.on) return BMBS_OK;
-        o.on = false;
-        Lane* c = X->lanes[(size_t)li];
-        const u64 retries0 = c->n_retries;
-        int rc = lane_settle(c);
-        if (rc) return rc;
-        if (c->qx_timed) {                          // k_qual_expand ran in front of the call (outside its event set): into the running sums by hand
-            c->qx_timed = false;
-            float t = 0;
-            if (hipEventElapsedTime(&t, c->ev_qx_a, c->ev_qx_b) != hipSuccess) t = 0.f;
-            bool found = false;
-            for (auto& a : c->acc) if (!strcmp(a.name, "k_qual_expand")) { a.ms += t; found = true; break; }
-            if (!found) c->acc.push_back({"k_qual_expand", (double)t});
-        }
-        const bool cs = c->up_stream && c->down_stream && c->ev_up && c->ev_k;
-        hipStream_t dsn = cs ? c->down_stream : c->stream;
-        if (c->n_retries != retries0)               // the chunk was issued again with exact sizes: the records copied behind the first attempt are stale
-            HIPCHK(c, hipMemcpyAsync(results + o.off * rpu, c->out_res.p, (u64)o.m * rpu * 32, hipMemcpyDeviceToHost, dsn));
-        const u64 used = c->last_n_jobs * (u64)max_ops;
-        const u64 base = ch == n ? 0 : (u64)o.off * rpu * (u64)max_ops;
-        if (base + used > (u64)cigar_cap) { c->err = "host cigar pool too small"; return BMBS_ENOMEM; }
-        if (used) {
-            HIPCHK(c, hipMemcpyAsync(cigar_pool + base, c->cig_pool.p, used * 4, hipMemcpyDeviceToHost, dsn));
-            int64_t seen = extent.load();
-            while ((int64_t)(base + used) > seen && !extent.compare_exchange_weak(seen, (int64_t)(base + used))) {}
-        }
-        HIPCHK(c, hipStreamSynchronize(dsn));
-        return BMBS_OK;
-    };
-    // upload, kernels and the records' download of chunk [off, off + m) on lane lane_i (its previous chunk has been finished)
-    auto issue = [&](int lane_i, int64_t off, int64_t m) -> int {
-        Lane* c = X->lanes[(size_t)lane_i];
-            HIPCHK(c, hipSetDevice(c->dev));
-            const u64 um = (u64)m;
-            ENS(c, c->out_res, um * rpu * 32);
-            const u64 pool = um * rpu * (u64)max_ops;                     // worst case: every read needs K12
-            ENS(c, c->cig_pool, pool * 4);
-            int ds = 0;
-            const size_t ro = (size_t)off * (size_t)stride;
-            const bool cs = c->up_stream && c->down_stream && c->ev_up && c->ev_k;
-            hipStream_t us = cs ? c->up_stream : c->stream, dsn = cs ? c->down_stream : c->stream;
-            int r1 = BMBS_OK;
-            // One upload at a time per device (the text calls' rule, bmbs_textpath.hip): four lanes that upload side by side share the
-            // link, finish together, compute together and leave the link idle meanwhile -- in turn, each chunk goes up at the full
-            // rate and its kernels run beside the next lane's upload.  The lock is held until this chunk's copies have ended; the
-            // kernels are queued behind them meanwhile.  BMBS_UP_TURNS=0: the round-5 form.  (ONE upload stream shared by the lanes --
-            // copies back to back with no host in between -- measured no better than side-by-side uploads: 172 against 174 / 165 M
-            // reads/s, turns 186 / 192; 2 M pairs per call, profiles/HISTORY.md)
-            std::unique_lock<std::mutex> up_turn(g_h2d_mu[c->dev & 15], std::defer_lock);
-            if (cs && used_lanes > 1 && c->kn.up_turns) up_turn.lock();
-            if (in.hw) {
-                // packed rows: hw words per read go over as they are (one block per mate)
-                const u64 pb = um * (u64)in.hw * 8;
-                ENS(c, c->pk_in1, pb + 64);
-                HIPCHK(c, hipMemcpyAsync(c->pk_in1.p, in.rows1 + (size_t)off * (size_t)in.hw, pb, hipMemcpyHostToDevice, us));
-                if (pe) { ENS(c, c->pk_in2, pb + 64); HIPCHK(c, hipMemcpyAsync(c->pk_in2.p, in.rows2 + (size_t)off * (size_t)in.hw, pb, hipMemcpyHostToDevice, us)); }
-            } else { r1 = upload_rows(c, c->in_seq, in.seq1 + ro, L, stride, um, &ds, us); if (r1) return r1; }
-            if (in.qw) {
-                // packed quality classes: qw words per read go over as they are; k_qual_expand (below) writes the byte rows at the stride
-                // upload_rows would have given them
-                const u64 qb = um * (u64)in.qw * 8;
-                ds = (L + 15) / 16 * 16;
-                ENS(c, c->pq_in1, qb + 64); ENS(c, c->in_qual, um * (u64)ds + 64);
-                HIPCHK(c, hipMemcpyAsync(c->pq_in1.p, in.qrows1 + (size_t)off * (size_t)in.qw, qb, hipMemcpyHostToDevice, us));
-                if (pe) {
-                    ENS(c, c->pq_in2, qb + 64); ENS(c, c->in_qual2, um * (u64)ds + 64);
-                    HIPCHK(c, hipMemcpyAsync(c->pq_in2.p, in.qrows2 + (size_t)off * (size_t)in.qw, qb, hipMemcpyHostToDevice, us));
-                }
-            } else { r1 = upload_rows(c, c->in_qual, in.qual1 + ro, L, stride, um, &ds, us); if (r1) return r1; }
-            if (pe) {
-                if (!in.hw) { r1 = upload_rows(c, c->in_seq2, in.seq2 + ro, L, stride, um, &ds, us); if (r1) return r1; }
-                if (!in.qw) { r1 = upload_rows(c, c->in_qual2, in.qual2 + ro, L, stride, um, &ds, us); if (r1) return r1; }
-            }
-            if (in.len1) {
-                r1 = upload_lens(c, in.len1 + off, um, 0, um * rpu, L, us); if (r1) return r1;
-                if (pe) { r1 = upload_lens(c, in.len2 + off, um, um, um * rpu, L, us); if (r1) return r1; }
-            }
-            if (cs) { HIPCHK(c, hipEventRecord(c->ev_up, us)); HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_up, 0)); }
-            if (in.qw) {
-                // on the kernel stream, in front of the call: a chunk that is issued again with exact sizes finds its byte rows in place
-                const int Wq = ds / 16;
-                const u64 words = um * (u64)Wq * (u64)rpu;
-                if (!c->ev_qx_a) { HIPCHK(c, hipEventCreate(&c->ev_qx_a)); HIPCHK(c, hipEventCreate(&c->ev_qx_b)); }
-                const QualRep rep = {c->qrep_lo, c->qrep_hi};
-                HIPCHK(c, hipEventRecord(c->ev_qx_a, c->stream));
-                hipLaunchKernelGGL(k_qual_expand, dim3(std::min<unsigned>(nblk(words, 256), 4096u)), dim3(256), 0, c->stream, c->pq_in1.as<u64>(),
-                                   pe ? c->pq_in2.as<u64>() : (const u64*)nullptr, in.qw, Wq, (long)m, rep, c->in_qual.as<uint4>(), pe ? c->in_qual2.as<uint4>() : (uint4*)nullptr);
-                HIPCHK(c, hipEventRecord(c->ev_qx_b, c->stream));
-                c->qx_timed = true;
-            }
-            Pending P;
-            P.pe = pe; P.L = L; P.stride = ds; P.n = m;
-            P.a[0] = (uint64_t)c->in_seq.p; P.a[1] = (uint64_t)c->in_qual.p; P.a[2] = pe ? (uint64_t)c->in_seq2.p : 0; P.a[3] = pe ? (uint64_t)c->in_qual2.p : 0;
-            if (in.hw) { P.packed_hw = in.hw; P.a[0] = (uint64_t)c->pk_in1.p; P.a[2] = pe ? (uint64_t)c->pk_in2.p : 0; }
-            P.d_len = in.len1 ? c->in_len.as<u16>() : nullptr;
-            P.d_results = (uint64_t)c->out_res.p; P.d_cigar_pool = (uint64_t)c->cig_pool.p; P.cigar_cap = (int64_t)pool;
-            P.cigar_base = ch == n ? 0u : (u32)((u64)off * rpu * (u64)max_ops);
-            r1 = lane_enqueue(c, P, true);
-            if (r1) return r1;
-            if (cs) { HIPCHK(c, hipEventRecord(c->ev_k, c->stream)); HIPCHK(c, hipStreamWaitEvent(dsn, c->ev_k, 0)); }
-            HIPCHK(c, hipMemcpyAsync(results + off * rpu, c->out_res.p, um * rpu * 32, hipMemcpyDeviceToHost, dsn));
-            if (up_turn.owns_lock()) HIPCHK(c, hipEventSynchronize(c->ev_up));          // this chunk is up: the next lane's turn
-            return BMBS_OK;
-    };
-    // One host thread per lane: a chunk is ~110 kernel launches and a handful of waits, and with all of them issued by one thread the
-    // call was bound by that thread on boxes with slower cores (2 M pairs through bmbs_map_pe_packed: 137 M reads/s where the link
-    // would give 200).  Chunk k goes to lane k % lanes whoever issues it: the results do not depend on the threads.
-    int rc = BMBS_OK;
-    std::mutex err_mu;
-    std::atomic<int> stop(0);
-    auto worker = [&](int lane_i) {
-        Lane* c = X->lanes[(size_t)lane_i];
-        (void)hipSetDevice(c->dev);
-        int r = BMBS_OK;
-        for (int64_t k = lane_i; k < n_chunks && !r && !stop.load(); k += used_lanes) {
-            const int64_t off = k * ch, m = std::min(ch, n - off);
-            r = finish(lane_i);
-            if (!r) r = issue(lane_i, off, m);
-            if (!r) { open[(size_t)lane_i].on = true; open[(size_t)lane_i].off = off; open[(size_t)lane_i].m = m; }
-        }
-        if (!r) r = finish(lane_i);
-        if (r) { stop.store(1); std::lock_guard<std::mutex> l(err_mu); if (!rc) { rc = r; X->err = c->err; } }
-    };
-    if (used_lanes == 1) worker(0);
-    else {
-        std::vector<std::thread> th;
-        for (int t = 1; t < used_lanes; t++) th.emplace_back(worker, t);
-        worker(0);
-        for (auto& t : th) t.join();
-    }
-    if (rc) { for (Lane* c : X->lanes) { (void)hipStreamSynchronize(c->stream); if (c->down_stream) (void)hipStreamSynchronize(c->down_stream); c->inflight.clear(); } return rc; }
-    X->used_lanes = used_lanes;
-    if (n_cigar_used) *n_cigar_used = extent.load();
+    HostCall call{X, in, stride, results, pool, plan_chunks(X, pe, L, n, cigar_cap, true)};
+    { const int rc = call.run(); if (rc) return rc; }
+    X->used_lanes = call.p.used_lanes;
+    if (n_cigar_used) *n_cigar_used = call.extent.load();
     return BMBS_OK;
 }
 
-extern "C" int bmbs_sync(bmbs_ctx* X)
-{
-    if (!X) return BMBS_EINVAL;
-    return settle_all(X);
-}
+extern "C" int bmbs_sync(bmbs_ctx* X) { return X ? settle_all(X) : BMBS_EINVAL; }
 
 extern "C" int bmbs_map_se_device(bmbs_ctx* X, uint64_t d_seq, uint64_t d_qual, int32_t L, int32_t stride,
                                   int64_t n_reads, uint64_t d_results, uint64_t d_cigar_pool, int64_t cigar_cap)
 {
-    return dispatch_device(X, false, d_seq, d_qual, 0, 0, nullptr, L, stride, n_reads, d_results, d_cigar_pool, cigar_cap);
+    DevIn in; in.seq1 = d_seq; in.qual1 = d_qual;
+    return dispatch_device(X, false, in, L, stride, n_reads, d_results, d_cigar_pool, cigar_cap);
 }
 extern "C" int bmbs_map_se_var_device(bmbs_ctx* X, uint64_t d_seq, uint64_t d_qual, uint64_t d_len, int32_t L_max, int32_t stride,
                                       int64_t n_reads, uint64_t d_results, uint64_t d_cigar_pool, int64_t cigar_cap)
 {
     if (X && !d_len) { X->err = "d_len is NULL"; return BMBS_EINVAL; }
-    return dispatch_device(X, false, d_seq, d_qual, 0, 0, reinterpret_cast<const u16*>(d_len), L_max, stride, n_reads, d_results, d_cigar_pool, cigar_cap);
+    DevIn in; in.seq1 = d_seq; in.qual1 = d_qual; in.len = reinterpret_cast<const u16*>(d_len);
+    return dispatch_device(X, false, in, L_max, stride, n_reads, d_results, d_cigar_pool, cigar_cap);
 }
 extern "C" int bmbs_map_se(bmbs_ctx* X, const char* seq, const char* qual, int32_t L, int32_t stride, int64_t n_reads,
                            bmbs_result* results, uint32_t* cigar_pool, int64_t cigar_cap, int64_t* n_cigar_used)
 {
-    const HostIn in = {seq, qual, nullptr, nullptr, nullptr, nullptr};
+    HostIn in; in.m[0].seq = seq; in.m[0].qual = qual;
     return dispatch_host(X, false, in, L, stride, n_reads, results, cigar_pool, cigar_cap, n_cigar_used);
 }
 extern "C" int bmbs_map_se_var(bmbs_ctx* X, const char* seq, const char* qual, const uint16_t* len, int32_t L_max, int32_t stride,
                                int64_t n_reads, bmbs_result* results, uint32_t* cigar_pool, int64_t cigar_cap, int64_t* n_cigar_used)
 {
     if (X && !len) { X->err = "len is NULL"; return BMBS_EINVAL; }
-    const HostIn in = {seq, qual, nullptr, nullptr, len, nullptr};
+    HostIn in; in.m[0].seq = seq; in.m[0].qual = qual; in.m[0].len = len;
     return dispatch_host(X, false, in, L_max, stride, n_reads, results, cigar_pool, cigar_cap, n_cigar_used);
 }
-extern "C" int bmbs_map_pe_device(bmbs_ctx* X, uint64_t d_seq1, uint64_t d_qual1, uint64_t d_seq2, uint64_t d_qual2,
-                                  int32_t L, int32_t stride, int64_t n_pairs, uint64_t d_results, uint64_t d_cigar_pool,
-                                  int64_t cigar_cap)
+extern "C" int bmbs_map_pe_device(bmbs_ctx* X, uint64_t d_seq1, uint64_t d_qual1, uint64_t d_seq2, uint64_t d_qual2, int32_t L, int32_t stride,
+                                  int64_t n_pairs, uint64_t d_results, uint64_t d_cigar_pool, int64_t cigar_cap)
 {
-    return dispatch_device(X, true, d_seq1, d_qual1, d_seq2, d_qual2, nullptr, L, stride, n_pairs, d_results, d_cigar_pool, cigar_cap);
+    DevIn in; in.seq1 = d_seq1; in.qual1 = d_qual1; in.seq2 = d_seq2; in.qual2 = d_qual2;
+    return dispatch_device(X, true, in, L, stride, n_pairs, d_results, d_cigar_pool, cigar_cap);
 }
 extern "C" int bmbs_map_pe_var_device(bmbs_ctx* X, uint64_t d_seq1, uint64_t d_qual1, uint64_t d_seq2, uint64_t d_qual2, uint64_t d_len,
-                                      int32_t L_max, int32_t stride, int64_t n_pairs, uint64_t d_results, uint64_t d_cigar_pool,
-                                      int64_t cigar_cap)
+                                      int32_t L_max, int32_t stride, int64_t n_pairs, uint64_t d_results, uint64_t d_cigar_pool, int64_t cigar_cap)
 {
     if (X && !d_len) { X->err = "d_len is NULL"; return BMBS_EINVAL; }
-    return dispatch_device(X, true, d_seq1, d_qual1, d_seq2, d_qual2, reinterpret_cast<const u16*>(d_len), L_max, stride, n_pairs, d_results,
-                           d_cigar_pool, cigar_cap);
+    DevIn in; in.seq1 = d_seq1; in.qual1 = d_qual1; in.seq2 = d_seq2; in.qual2 = d_qual2; in.len = reinterpret_cast<const u16*>(d_len);
+    return dispatch_device(X, true, in, L_max, stride, n_pairs, d_results, d_cigar_pool, cigar_cap);
 }
-extern "C" int bmbs_map_pe(bmbs_ctx* X, const char* seq1, const char* qual1, const char* seq2, const char* qual2, int32_t L,
-                           int32_t stride, int64_t n_pairs, bmbs_result* results, uint32_t* cigar_pool, int64_t cigar_cap,
-                           int64_t* n_cigar_used)
+extern "C" int bmbs_map_pe(bmbs_ctx* X, const char* seq1, const char* qual1, const char* seq2, const char* qual2, int32_t L, int32_t stride,
+                           int64_t n_pairs, bmbs_result* results, uint32_t* cigar_pool, int64_t cigar_cap, int64_t* n_cigar_used)
 {
-    const HostIn in = {seq1, qual1, seq2, qual2, nullptr, nullptr};
+    HostIn in; in.m[0].seq = seq1; in.m[0].qual = qual1; in.m[1].seq = seq2; in.m[1].qual = qual2;
     return dispatch_host(X, true, in, L, stride, n_pairs, results, cigar_pool, cigar_cap, n_cigar_used);
 }
-extern "C" int bmbs_map_pe_var(bmbs_ctx* X, const char* seq1, const char* qual1, const char* seq2, const char* qual2,
-                               const uint16_t* len1, const uint16_t* len2, int32_t L_max, int32_t stride, int64_t n_pairs,
-                               bmbs_result* results, uint32_t* cigar_pool, int64_t cigar_cap, int64_t* n_cigar_used)
+extern "C" int bmbs_map_pe_var(bmbs_ctx* X, const char* seq1, const char* qual1, const char* seq2, const char* qual2, const uint16_t* len1, const uint16_t* len2,
+                               int32_t L_max, int32_t stride, int64_t n_pairs, bmbs_result* results, uint32_t* cigar_pool, int64_t cigar_cap, int64_t* n_cigar_used)
 {
     if (X && (!len1 || !len2)) { X->err = "len1 / len2 is NULL"; return BMBS_EINVAL; }
-    const HostIn in = {seq1, qual1, seq2, qual2, len1, len2};
+    HostIn in; in.m[0].seq = seq1; in.m[0].qual = qual1; in.m[0].len = len1; in.m[1].seq = seq2; in.m[1].qual = qual2; in.m[1].len = len2;
     return dispatch_host(X, true, in, L_max, stride, n_pairs, results, cigar_pool, cigar_cap, n_cigar_used);
 }
 
@@ -1820,8 +1821,7 @@ extern "C" int bmbs_map_se_packed(bmbs_ctx* X, const uint64_t* rows, int32_t pwo
                                   int64_t n_reads, bmbs_result* results, uint32_t* cigar_pool, int64_t cigar_cap, int64_t* n_cigar_used)
 {
     if (X && (!rows || !qual || pwords <= 0)) { X->err = "packed reads: NULL rows / qualities or pwords <= 0"; return BMBS_EINVAL; }
-    HostIn in = {nullptr, qual, nullptr, nullptr, len, nullptr};
-    in.rows1 = rows; in.hw = pwords;
+    HostIn in; in.hw = pwords; in.m[0].rows = rows; in.m[0].qual = qual; in.m[0].len = len;
     return dispatch_host(X, false, in, L_max, stride, n_reads, results, cigar_pool, cigar_cap, n_cigar_used);
 }
 extern "C" int bmbs_map_pe_packed(bmbs_ctx* X, const uint64_t* rows1, const uint64_t* rows2, int32_t pwords, const char* qual1, const char* qual2,
@@ -1829,8 +1829,9 @@ extern "C" int bmbs_map_pe_packed(bmbs_ctx* X, const uint64_t* rows1, const uint
                                   uint32_t* cigar_pool, int64_t cigar_cap, int64_t* n_cigar_used)
 {
     if (X && (!rows1 || !rows2 || !qual1 || !qual2 || pwords <= 0 || (len1 != nullptr) != (len2 != nullptr))) { X->err = "packed reads: NULL rows / qualities, pwords <= 0, or only one of len1 / len2"; return BMBS_EINVAL; }
-    HostIn in = {nullptr, qual1, nullptr, qual2, len1, len2};
-    in.rows1 = rows1; in.rows2 = rows2; in.hw = pwords;
+    HostIn in; in.hw = pwords;
+    in.m[0].rows = rows1; in.m[0].qual = qual1; in.m[0].len = len1;
+    in.m[1].rows = rows2; in.m[1].qual = qual2; in.m[1].len = len2;
     return dispatch_host(X, true, in, L_max, stride, n_pairs, results, cigar_pool, cigar_cap, n_cigar_used);
 }
 // ---- packed quality classes (include/bmbs.h): a 4-bit penalty class per base instead of the quality byte ------------------------------------
@@ -1847,8 +1848,7 @@ extern "C" int bmbs_map_se_packedq(bmbs_ctx* X, const uint64_t* rows, int32_t pw
 {
     if (X && (!rows || !qrows || pwords <= 0 || qwords <= 0)) { X->err = "packed reads: NULL rows / quality classes or pwords / qwords <= 0"; return BMBS_EINVAL; }
     if (X && L_max > 0 && qwords < (L_max + 15) / 16) { X->err = "packed quality classes: qwords is smaller than a row of this length takes"; return BMBS_EINVAL; }
-    HostIn in = {nullptr, nullptr, nullptr, nullptr, len, nullptr};
-    in.rows1 = rows; in.hw = pwords; in.qrows1 = qrows; in.qw = qwords;
+    HostIn in; in.hw = pwords; in.qw = qwords; in.m[0].rows = rows; in.m[0].qrows = qrows; in.m[0].len = len;
     return dispatch_host(X, false, in, L_max, std::max(L_max, 0), n_reads, results, cigar_pool, cigar_cap, n_cigar_used);
 }
 extern "C" int bmbs_map_pe_packedq(bmbs_ctx* X, const uint64_t* rows1, const uint64_t* rows2, int32_t pwords, const uint64_t* qrows1, const uint64_t* qrows2,
@@ -1859,8 +1859,9 @@ extern "C" int bmbs_map_pe_packedq(bmbs_ctx* X, const uint64_t* rows1, const uin
         X->err = "packed reads: NULL rows / quality classes, pwords / qwords <= 0, or only one of len1 / len2"; return BMBS_EINVAL;
     }
     if (X && L_max > 0 && qwords < (L_max + 15) / 16) { X->err = "packed quality classes: qwords is smaller than a row of this length takes"; return BMBS_EINVAL; }
-    HostIn in = {nullptr, nullptr, nullptr, nullptr, len1, len2};
-    in.rows1 = rows1; in.rows2 = rows2; in.hw = pwords; in.qrows1 = qrows1; in.qrows2 = qrows2; in.qw = qwords;
+    HostIn in; in.hw = pwords; in.qw = qwords;
+    in.m[0].rows = rows1; in.m[0].qrows = qrows1; in.m[0].len = len1;
+    in.m[1].rows = rows2; in.m[1].qrows = qrows2; in.m[1].len = len2;
     return dispatch_host(X, true, in, L_max, std::max(L_max, 0), n_pairs, results, cigar_pool, cigar_cap, n_cigar_used);
 }
 // quality bytes -> packed classes on the host's threads (once per batch, like bmbs_pack_rows).  -> BMBS_OK, or BMBS_EINVAL with *bad_row = the
@@ -1949,7 +1950,6 @@ extern "C" int bmbs_pack_rows(const char* seq, int32_t L_max, int32_t stride, in
     for (int t = 0; t < T; t++) if (bad[(size_t)t] >= 0) { if (bad_row) *bad_row = bad[(size_t)t]; return BMBS_EINVAL; }
     return BMBS_OK;
 }
-
 
 // ------------------------------------------------------------------------------------------------
 static int lane_locate_batch(Lane* c, const uint64_t* row, int64_t n_rows, uint64_t* pos)

@@ -325,6 +325,9 @@ struct Lane {
 // create them (it ignores the result)
 inline hipStream_t up_stream_of(const Lane* c) { return c->up_stream ? c->up_stream : c->stream; }
 inline hipStream_t down_stream_of(const Lane* c) { return c->down_stream ? c->down_stream : c->stream; }
+// the host-buffer mapping calls tie their copies to the kernels with the lane's two events: they use the copy streams only when both
+// streams AND both events exist -- otherwise everything goes on the kernel stream and no event is recorded
+inline bool copy_streams(const Lane* c) { return c->up_stream && c->down_stream && c->ev_up && c->ev_k; }
 
 // the public handle: parameters + the lanes (lane 0 owns the index unless the context shares another one's)
 struct bmbs_ctx {
