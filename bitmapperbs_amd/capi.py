@@ -268,7 +268,7 @@ def lib() -> C.CDLL:
 
 
 LIB_SRCS = ("bmbs_api.hip", "bmbs_kernels.hip", "k_index.hip", "k_rows.hip", "k_qualpack.hip", "k_attach.hip", "k_scan.hip", "k_seed.hip", "k_vote.hip", "k_filter.hip", "k_reduce.hip", "k_align.hip", "k_finalize.hip", "k_pe_fast.hip", "k_pe_sensitive.hip",
-            "bmbs_textpath.hip", "bmbs_text.hip", "bmbs_bam.hip", "bmbs_inflate.hip", "k_bamsort.hip", "bmbs_bytes.h", "bmbs_records.hip", "k_bai.hip", "k_markdup.hip", "k_methyl.hip", "bmbs_host.h", "bmbs_dev.h", "bmbs_words.h", "bmbs_sort.h", "../../include/bmbs.h",
+            "bmbs_textpath.hip", "bmbs_text.hip", "bmbs_bam.hip", "bmbs_inflate.hip", "k_bamsort.hip", "bmbs_bytes.h", "bmbs_records.hip", "k_bai.hip", "k_markdup.hip", "k_methyl.hip", "bmbs_host.h", "bmbs_dev.h", "bmbs_words.h", "bmbs_sort.h", "bmbs_rowpitch.h", "../../include/bmbs.h",
             "index_io.cpp", "index_io.h", "index_build_gpu.hip", "build_id.cpp")
 
 

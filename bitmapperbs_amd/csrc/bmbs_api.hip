@@ -463,7 +463,7 @@ int launch_seeding(Lane* c, const char* d_seq, const ReadGeom& gm, int stride, u
     const unsigned chunks = nblk(n, SEED_CHUNK);
     const unsigned chunks_min = nblk(n, SEED_CHUNK_MIN);      // grid for the device-sized chunks of the two work lists
     const int target_waves = c->kn.seed_waves;
-    // packed copy of the rows (2 bits per base + a not-ACGT bit plane, 64 bytes for 150 bases): what the seeding engine and
+    // packed copy of the rows (2 bits per base + a not-ACGT bit plane, whole 64-byte lines: one for 150 bases): what the seeding engine and
     // k_seed_decide read instead of the ASCII rows; BMBS_LEGACY=1 keeps the round-1 forms (A/B runs)
     const bool packed = use_packed_rows(c);
     if (packed && !prepacked) {

@@ -56,12 +56,14 @@ k_pe_prepare(const char* __restrict__ s1, const char* __restrict__ s2raw, ReadGe
     if (!sparse_ascii) reinterpret_cast<uint4*>(seq_all)[i16] = v1;                           // the qualities stay where they are (qual_row)
     // the packed copy of both rows (what k_pack_rows would write), from the pieces this thread holds anyway
     auto pack_out = [&](const uint4& pv, long row_id, int Lr, uint4* ascii) {
-        const int piece = j0 / 16;
-        if (!prow || piece * 16 >= ((Lr + 63) & ~63)) return;
-        u32 bases, mask;
-        pack_piece(pv, Lr - piece * 16, bases, mask);
+        const int piece = j0 / 16, ppr = stride / 16;
+        if (!prow) return;
         u64* row = prow + (size_t)row_id * pwords;
-        if (piece * 16 < ((Lr + 31) & ~31)) reinterpret_cast<u32*>(row)[piece] = bases;
+        if (piece == ppr - 1) pack_row_tail(row, pwords, W, ppr);
+        if (piece >= 4 * ((W + 1) / 2)) return;                 // beyond the row's last mask word
+        u32 bases, mask;
+        pack_piece(pv, Lr - piece * 16, bases, mask);           // zeros at and beyond the read's end
+        if (piece < 2 * W) reinterpret_cast<u32*>(row)[piece] = bases;
         reinterpret_cast<u16*>(row + W)[piece] = (u16)mask;
         if (mask) {
             atomicOr(&dirty32[row_id >> 2], 1u << (8 * (int)(row_id & 3)));
@@ -120,6 +122,7 @@ k_pe_prepare_p(const char* __restrict__ s1, const char* __restrict__ s2raw, Read
     extern __shared__ u32 lds_pp[];
     const int ppr = stride / 16, rpb = 256 / ppr;
     const int bufw = rpb * (ppr + 1);                   // words of one plane of one buffer
+    const int M4 = 4 * ((W + 1) / 2);                   // 16-bit pieces of a row's mask plane
     const int tid = threadIdx.x, rl = tid / ppr, piece = tid - rl * ppr;
     const long total = n * stride;
     const long step = (long)gridDim.x * rpb;
@@ -145,15 +148,17 @@ k_pe_prepare_p(const char* __restrict__ s1, const char* __restrict__ s2raw, Read
             pack_piece(v2, L2 - piece * 16, b2, m2);
             lb[rl * (ppr + 1) + piece] = b2; lm[rl * (ppr + 1) + piece] = m2;
             if (piece == 0) { lb[rl * (ppr + 1) + ppr] = 0; lm[rl * (ppr + 1) + ppr] = 0; }
-            if (piece * 16 < ((L1 + 63) & ~63)) {
-                u64* row = prow + (size_t)r * pwords;
-                if (piece * 16 < ((L1 + 31) & ~31)) reinterpret_cast<u32*>(row)[piece] = b1;
+            // every word of both rows is written, whatever the reads' lengths: the pieces up to the planes' ends, the rest by pack_row_tail
+            u64* row = prow + (size_t)r * pwords;
+            if (piece == ppr - 1) { pack_row_tail(row, pwords, W, ppr); pack_row_tail(prow + (size_t)(n + r) * pwords, pwords, W, ppr); }
+            if (piece < M4) {
+                if (piece < 2 * W) reinterpret_cast<u32*>(row)[piece] = b1;
                 reinterpret_cast<u16*>(row + W)[piece] = (u16)m1;
                 if (m1) { atomicOr(&dirty32[r >> 2], 1u << (8 * (int)(r & 3))); reinterpret_cast<uint4*>(seq_all)[i16] = v1; }
             }
         }
         __syncthreads();
-        if (on && piece * 16 < ((L2 + 63) & ~63)) {
+        if (on && piece < M4) {
             const int j0 = piece * 16, lo = L2 - 16 - j0;       // forward positions lo .. lo+15, reversed, are rc positions j0 .. j0+15
             const u32* fb = lb + rl * (ppr + 1); const u32* fm = lm + rl * (ppr + 1);
             u32 win, bad, inr;
@@ -175,7 +180,7 @@ k_pe_prepare_p(const char* __restrict__ s1, const char* __restrict__ s2raw, Read
             const u32 om = __brev(bad & inr) >> 16;
             const long row_id = n + r;
             u64* row = prow + (size_t)row_id * pwords;
-            if (j0 < ((L2 + 31) & ~31)) reinterpret_cast<u32*>(row)[piece] = rv;
+            if (piece < 2 * W) reinterpret_cast<u32*>(row)[piece] = rv;
             reinterpret_cast<u16*>(row + W)[piece] = (u16)om;
             if (om) {
                 atomicOr(&dirty32[row_id >> 2], 1u << (8 * (int)(row_id & 3)));

@@ -7,20 +7,29 @@
 // per-lane load is a request of its own to the memory pipeline (a row load costs 3/4 of a random gather, tools/gather_bench):
 // with ASCII rows that is two or three 16-byte requests per seed start plus one per 16 characters walked.  k_pack_rows
 // therefore writes, once per batch, a packed copy of every row -- 2 bits per base (A0 C1 G2 T3, LSB first like gen2) followed by
-// one bit per base that says "this character is not one of ACGT" (then the base bits are 0): 64 bytes for a 150-base read,
-// ONE sector -- and a `dirty` byte per read that tells whether any such character exists at all.  A seed start is then one
-// 16-byte request (64 bases from the word that holds its first base), the walk one 8-byte request per 32 bases, the 16-mer key
-// falls out of the 2-bit codes with a few logic ops, and the comparisons with the 2-bit genome are XORs of whole words.  Only
-// what asks for the letter 'N' itself (penalty np, determine_seed_offset_unmatch) still looks at the ASCII row, and only for
-// dirty reads.
+// one bit per base that says "this character is not one of ACGT" (then the base bits are 0) -- and a `dirty` byte per read that
+// tells whether any such character exists at all.  Rows are whole 64-byte lines apart (pack_words: the two planes rounded up to a
+// multiple of 8 words), and the buffer is line-aligned: a 100- or 150-base row IS one line, a 250-base row two, so a whole-row
+// fetch touches no line it shares with a neighbour.  A seed start is then one 16-byte request (64 bases from the word that holds
+// its first base), the walk one 8-byte request per 32 bases, the 16-mer key falls out of the 2-bit codes with a few logic ops, and
+// the comparisons with the 2-bit genome are XORs of whole words.  Only what asks for the letter 'N' itself (penalty np,
+// determine_seed_offset_unmatch) still looks at the ASCII row, and only for dirty reads.
+//
+// What a reader may rely on (the writers: k_pack_rows, k_pe_prepare, k_pe_prepare_p, k_rows_from_packed; as include/bmbs.h says of
+// the caller's rows): every word of a row is written in every call -- base and mask bits at and beyond the read's length, and the
+// words between the two planes' end (W + M) and the pitch, are 0 whatever an earlier call with another read length left there.
+// There is NO spare word behind a row: where W + M is a multiple of 8 (129-160 bases, 481-512, ...) the word after the last mask
+// word is the next row's first base word (after the last row: the 64 bytes of slack the buffer carries).  The two-word loads below
+// (load2 at a row's last word: prow_mask32) therefore bring in bits that belong to no position of this read -- in the LDS copies of
+// k_seed_decide_p and k_seed_extra the slot's pad word, which nobody writes: UNINITIALISED LDS, not zeros; every consumer masks by
+// the read's length (field_range, len / steps bounds) and none may let them reach a result.
 struct PackedRows {
     const u64* base;      // row r at base + r * pwords
     const u8*  dirty;     // [n] 1 = the row holds a character outside ACGT
-    int pwords;           // u64 words per row (even: rows are 16-byte aligned)
+    int pwords;           // u64 words per row (a multiple of 8: rows are whole 64-byte lines)
     int W;                // words of bases; the mask words follow
 };
-__host__ __device__ inline int pack_base_words(int L) { return (L + 31) / 32; }
-__host__ __device__ inline int pack_words(int L) { const int w = (L + 31) / 32 + (L + 63) / 64 + 1; return (w + 1) & ~1; }   // + one spare word for two-word loads at the end
+#include "bmbs_rowpitch.h"      // pack_base_words, pack_words: W + M up to whole lines (150 -> 8, 100 -> 8, 250 -> 16)
 
 // two consecutive words from an 8-byte aligned address: one 16-byte request
 DEVI void load2(const u64* p, u64& a, u64& b)
@@ -161,6 +170,22 @@ DEVI void pack_piece(const uint4& v, int valid, u32& bases, u32& mask)
     bases = out & (k | (k << 1));
 }
 
+// What the pieces of a packed row do not cover, zeroed by the thread of the row's last piece (ppr pieces of 16 characters per row):
+// piece p writes u32 p of the base plane (p < 2 W) and u16 p of the mask plane (p < 4 M, M = (W + 1) / 2), pack_piece leaving 0 at
+// and beyond the read's length.  Left over are the upper half of the last base word (ppr odd: at most one u32), the mask plane
+// beyond the last piece and the words from W + M to the pitch -- for 150 bases one u32, bits 160-191 of the mask plane.
+DEVI void pack_row_tail(u64* row, int pwords, int W, int ppr)
+{
+    if (ppr < 2 * W) reinterpret_cast<u32*>(row)[ppr] = 0;
+    u16* m = reinterpret_cast<u16*>(row + W);
+    const int M4 = 4 * ((W + 1) / 2), e = 4 * (pwords - W);          // u16 units: the mask plane's end, the row's end (both multiples of 4)
+    int q = ppr < M4 ? ppr : M4;
+    if (q >= e) return;
+    if (q & 1) m[q++] = 0;
+    if (q & 2) { *reinterpret_cast<u32*>(m + q) = 0; q += 2; }
+    for (; q < e; q += 4) *reinterpret_cast<u64*>(m + q) = 0;
+}
+
 // one thread per 16-byte piece of an ASCII row
 __global__ void __launch_bounds__(256)
 k_pack_rows(const char* __restrict__ seq, ReadGeom gm, int stride, long n, u64* __restrict__ prow, int pwords, int W, u32* __restrict__ dirty32)
@@ -171,12 +196,13 @@ k_pack_rows(const char* __restrict__ seq, ReadGeom gm, int stride, long n, u64* 
     const long r = i16 / per_row;
     const int piece = (int)(i16 - r * per_row);
     const int L = gm.rl(r);
-    if (piece * 16 >= ((L + 63) & ~63)) return;                 // beyond the row's last mask word: nothing to write
-    const uint4 v = reinterpret_cast<const uint4*>(seq)[i16];
-    u32 bases, mask;
-    pack_piece(v, L - piece * 16, bases, mask);
     u64* row = prow + (size_t)r * pwords;
-    if (piece * 16 < ((L + 31) & ~31)) reinterpret_cast<u32*>(row)[piece] = bases;
+    if (piece == per_row - 1) pack_row_tail(row, pwords, W, per_row);
+    const int M4 = 4 * ((W + 1) / 2);
+    if (piece >= M4) return;                                    // beyond the row's last mask word: nothing to write
+    u32 bases = 0, mask = 0;                                    // a piece at or beyond the read's end (shorter reads of a mixed batch): zeros
+    if (piece * 16 < L) pack_piece(reinterpret_cast<const uint4*>(seq)[i16], L - piece * 16, bases, mask);
+    if (piece < 2 * W) reinterpret_cast<u32*>(row)[piece] = bases;
     reinterpret_cast<u16*>(row + W)[piece] = (u16)mask;
     if (mask) atomicOr(&dirty32[r >> 2], 1u << (8 * (int)(r & 3)));
 }
@@ -185,7 +211,7 @@ k_pack_rows(const char* __restrict__ seq, ReadGeom gm, int stride, long n, u64* 
 // Host format of a row (include/bmbs.h): W = ceil(L_max / 32) words of bases (base j in bits 2 (j % 32) .. +1 of word j / 32, A0 C1 G2 T3),
 // then M = ceil(L_max / 64) words of marks (bit j % 64 of word j / 64: the character at j is 'N', its base bits are 0), rows `hw` words
 // apart: 64 bytes for 150 bases where the ASCII row takes 160.  This kernel makes the lane's own packed rows of them (pack_words(L_max)
-// words: the same two planes and the spare words the two-word loads read), sets the rows' dirty bytes, rebuilds the ASCII text of every
+// words: the same two planes and zeros up to the pitch, whole 64-byte lines), sets the rows' dirty bytes, rebuilds the ASCII text of every
 // 16-character piece that holds an 'N' (the only pieces whose text a kernel ever asks for) -- and, RC, reverse-complements the row on
 // the way: mate 2 comes in FASTQ orientation and is mapped as its reverse complement (Process_Reads.cpp:262-267).  It replaces
 // k_pe_prepare / k_pack_rows for such callers: 2 x 64 bytes read per pair instead of 2 x 160.
@@ -245,7 +271,7 @@ k_rows_from_packed(const u64* __restrict__ src, int hw, ReadGeom gm, long row0, 
     // marks: this thread's 32 bits are one half of mask word k / 2
     reinterpret_cast<u32*>(out + W)[k] = mk;
     if ((W & 1) && k == W - 1) reinterpret_cast<u32*>(out + W)[W] = 0;                       // (the upper half of the last mask word when W is odd)
-    if (k == 0) for (int q = W + M; q < pwords; q++) out[q] = 0;                             // the spare words
+    if (k == 0) for (int q = W + M; q < pwords; q++) out[q] = 0;                             // the words up to the pitch (none where W + M is a multiple of 8)
     if (mk) {
         atomicOr(&dirty32[row_id >> 2], 1u << (8 * (int)(row_id & 3)));
         // the text of the pieces that hold an 'N'

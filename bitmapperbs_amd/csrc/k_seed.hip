@@ -706,7 +706,7 @@ k_seed_decide_p(DevIndex ix, const char* __restrict__ seq, PackedRows pr, ReadGe
     __shared__ unsigned int shc[2];
     if (threadIdx.x < 2) shc[threadIdx.x] = 0;
     extern __shared__ __align__(16) char lds_prows[];
-    const int lw = pr.pwords + 1;                                   // row stride in words, odd against bank conflicts
+    const int lw = pr.pwords + 1;                                   // row stride in words, odd against bank conflicts (the pad word stays uninitialised)
     u64* lrows = reinterpret_cast<u64*>(lds_prows);
     const long row0 = (long)blockIdx.x * blockDim.x;
     const long rows = n - row0 < (long)blockDim.x ? n - row0 : (long)blockDim.x;
@@ -985,7 +985,9 @@ k_seed_second(DevIndex ix, const char* __restrict__ seq, PackedRows pr, ReadGeom
 // ROWS_LDS: ASCII rows staged in LDS (small indexes); PACKED: packed rows read from global memory (64 bytes per read)
 // PLDS (with PACKED): the packed row of a lane's read (pwords x 8 bytes) is copied into the lane's LDS slot when the lane takes the
 // read -- coalesced 16-byte loads along the rows -- and every seed start and cursor refill reads LDS: one request to the memory
-// pipeline per seed start less (of about five), at 64 x (pwords + 1) x 8 = 4.6 KB of LDS per wave for 150-base reads
+// pipeline per seed start less (of about five), at 64 x (pwords + 1) x 8 = 4.6 KB of LDS per wave for 150-base reads (pwords = 8, one
+// line per row; the slot's pad word is never written -- a two-word load at the row's last mask word brings in UNINITIALISED LDS there,
+// bits of no position of the read, which every user of prow_mask32 masks away by length)
 template <bool ROWS_LDS, bool PACKED = false, bool PLDS = false, bool KG = false>
 __global__ void __launch_bounds__(64)
 k_seed_extra(DevIndex ix, const char* __restrict__ seq, PackedRows pr, ReadGeom gm, int stride, const u64* __restrict__ count_ptr, int target_waves,
@@ -1067,7 +1069,7 @@ k_seed_extra(DevIndex ix, const char* __restrict__ seq, PackedRows pr, ReadGeom 
                 if (pending && !have && it < chunk_end) { take_row[rank] = sc.list_d[it]; take_lane[rank] = (u8)(threadIdx.x & 63); }
                 __syncthreads();
                 if constexpr (PLDS) {
-                    const int per_row = pr.pwords / 2, pieces = n_take * per_row;         // rows are 16-byte aligned, pwords is even
+                    const int per_row = pr.pwords / 2, pieces = n_take * per_row;         // rows are whole 64-byte lines: 4 lanes per line
                     u64* lr = reinterpret_cast<u64*>(lds_rows);
                     for (int t = threadIdx.x & 63; t < pieces; t += 64) {
                         const int w = t / per_row, cc = t - w * per_row;
