@@ -28,6 +28,7 @@ SYMBOLS = [
     "bmbs_bam_dup_sigs", "bmbs_text_sorted_dup", "bmbs_dup_select",
     "bmbs_text_sorted_clip", "bmbs_bam_methyl", "bmbs_bam_sort_methyl", "bmbs_methyl_sites",
     "bmbs_bam_methyl_opts", "bmbs_bam_sort_methyl_opts", "bmbs_methyl_mbias",
+    "bmbs_bam_methyl_opposite", "bmbs_bam_sort_methyl_opposite", "bmbs_methyl_opposite", "bmbs_methyl_drop_variants",
     "bmbs_outcome_index",
 ]
 
@@ -243,6 +244,15 @@ def lib() -> C.CDLL:
         L.bmbs_bam_sort_methyl_opts.restype = C.c_int
         L.bmbs_methyl_mbias.argtypes = [vp, vp, i64, C.POINTER(i64)]
         L.bmbs_methyl_mbias.restype = C.c_int
+    if hasattr(L, "bmbs_methyl_opposite"):               # (the opposite-strand observation and the variant filter; BMBS_LIB may name an older build, as above)
+        L.bmbs_bam_methyl_opposite.argtypes = [vp, vp, u64, vp, i64, vp, C.POINTER(MethylOpts), C.POINTER(i64)]
+        L.bmbs_bam_methyl_opposite.restype = C.c_int
+        L.bmbs_bam_sort_methyl_opposite.argtypes = [vp, vp, C.POINTER(MethylOpts), C.POINTER(i64)]
+        L.bmbs_bam_sort_methyl_opposite.restype = C.c_int
+        L.bmbs_methyl_opposite.argtypes = [vp, vp, i64, C.POINTER(i64)]
+        L.bmbs_methyl_opposite.restype = C.c_int
+        L.bmbs_methyl_drop_variants.argtypes = [vp, i64, vp, i64, C.c_int32, C.c_int32, C.POINTER(i64)]
+        L.bmbs_methyl_drop_variants.restype = C.c_int
     L.bmbs_map_pe_text.argtypes = [vp, vp, u64, vp, u64, i64, i32, vp, u64, C.POINTER(u64), C.POINTER(i64)]
     L.bmbs_map_pe_text.restype = C.c_int
     L.bmbs_retries.argtypes = [vp]

@@ -249,9 +249,11 @@ struct Lane {
     std::vector<std::pair<u64, u64>> mt_slice;
     int mt_cus = 0;
     // the last methyl call: `sites` of them in mt_site (bmbs_methyl_sites; -1: none); has_mbias: it made the M-bias table
-    // (bmbs_methyl_mbias) -- in mt_mbias, or (mbias_zero) a call without records: the table is all zero and not on the device
+    // (bmbs_methyl_mbias) -- in mt_mbias, or (mbias_zero) a call without records: the table is all zero and not on the device.
+    // An opposite call (bmbs_bam_methyl_opposite / bmbs_bam_sort_methyl_opposite) leaves `opp` entries in mt_site instead
+    // (bmbs_methyl_opposite; -1: none): a context holds one result at a time, so at most one of `sites` and `opp` is not -1
     struct MethylCall {
-        int64_t sites = -1;
+        int64_t sites = -1, opp = -1;
         bool has_mbias = false, mbias_zero = false;
     } mc;
     // What is about to be rewritten or begun -> the results that end with it.  A result that stayed would hand another call's bytes to
@@ -285,8 +287,8 @@ struct Lane {
         case SORT_KEYS: st.n = -1; break;
         // what bmbs_text_sorted_dup keeps behind a size query: it computes again (bam_raw is still there)
         case DUP_SIGS: st.sigs_done = false; break;
-        // bmbs_methyl_sites / bmbs_methyl_mbias describe the LAST methyl call
-        case METHYL_CALL: mc.sites = -1; mc.has_mbias = mc.mbias_zero = false; break;
+        // bmbs_methyl_sites / bmbs_methyl_mbias / bmbs_methyl_opposite describe the LAST methyl call, of either kind
+        case METHYL_CALL: mc.sites = mc.opp = -1; mc.has_mbias = mc.mbias_zero = false; break;
         }
     }
     DevBuf z_comp, z_off, z_text, z_err, z_nl, z_comp2, z_off2, z_err2;         // bmbs_inflate_bgzf; (…2: mate 2 of bmbs_text_open_bgzf)

@@ -435,14 +435,16 @@ static int methyl_params_as_opts(Lane* c, const bmbs_methyl_params* par, bmbs_me
     return BMBS_OK;
 }
 
-// the options of a call: *opts if given (the _opts calls), else the old calls' parameters with no flags and no trim (NULL: the defaults)
-static int methyl_get_opts(Lane* c, const bmbs_methyl_params* par, const bmbs_methyl_opts* opts, bmbs_methyl_opts* out)
+// the options of a call: *opts if given (the _opts calls), else the old calls' parameters with no flags and no trim (NULL: the defaults).
+// opposite: an opposite call, which makes no M-bias table -- its flags must be 0
+static int methyl_get_opts(Lane* c, const bmbs_methyl_params* par, const bmbs_methyl_opts* opts, bool opposite, bmbs_methyl_opts* out)
 {
     if (!opts) return methyl_params_as_opts(c, par, out);
     const bmbs_methyl_opts& o = *out = *opts;
     bool bad = o.contexts < 1 || o.contexts > 7 || o.min_mapq < 0 || o.min_mapq > 255 || o.min_phred < 0 || o.min_phred > 255 || (o.flags & ~BMBS_METHYL_MBIAS);
     for (int m = 0; m < 2; m++) bad = bad || o.ignore_5p[m] < 0 || o.ignore_5p[m] > 65535 || o.ignore_3p[m] < 0 || o.ignore_3p[m] > 65535;
     if (bad) { c->err = "methyl: bad parameters (contexts 1..7, min_mapq and min_phred 0..255, flags BMBS_METHYL_MBIAS or 0, ignore values 0..65535)"; return BMBS_EINVAL; }
+    if (opposite && o.flags) { c->err = "methyl opposite: bad parameters (flags must be 0: an opposite call makes no M-bias table)"; return BMBS_EINVAL; }
     return BMBS_OK;
 }
 
@@ -464,14 +466,15 @@ static int meth_slice(Lane* c, const u64* eoff, u64 start, u64 n, u64 cap, u64* 
 
 // the records at raw / off / len (device; off = the exclusive scan of len), their clips (device, or NULL) -> c->mt_site, c->mc.sites;
 // with BMBS_METHYL_MBIAS the M-bias table of all n records -> c->mt_mbias too (once, whatever the slices).  Options: methyl_get_opts.
+// opposite: the walk is the opposite-strand observation (k_methyl.hip) and its entries -> c->mt_site, c->mc.opp; flags must be 0.
 // (The caller has ended the last methyl call's result: Lane::METHYL_CALL)
 static int methyl_device(Lane* c, const char* raw, const u64* off, const u32* len, const u32* clip, u64 n, const bmbs_methyl_params* par_in, const bmbs_methyl_opts* opts,
-                         int64_t* n_site)
+                         bool opposite, int64_t* n_site)
 {
     // BMBS_METHYL_EVENTS (test aid): the events a slice of records may hold
     static const u64 slice_cap = [] { const char* e = getenv("BMBS_METHYL_EVENTS"); const long long v = e ? atoll(e) : 0; return v > 0 ? (u64)v : (u64)1 << 26; }();
     bmbs_methyl_opts pp;
-    if (int rc = methyl_get_opts(c, par_in, opts, &pp)) return rc;
+    if (int rc = methyl_get_opts(c, par_in, opts, opposite, &pp)) return rc;
     MethPar par;
     par.contexts = (u32)pp.contexts; par.min_mapq = (u32)pp.min_mapq; par.min_phred = (u32)pp.min_phred; par.n_chrom = c->ix.n_chrom;
     for (int m = 0; m < 2; m++) { par.ig5[m] = (u32)pp.ignore_5p[m]; par.ig3[m] = (u32)pp.ignore_3p[m]; }
@@ -486,9 +489,13 @@ static int methyl_device(Lane* c, const char* raw, const u64* off, const u32* le
     HIPCHK(c, hipMemsetAsync(info, 0, TXI_HALF_WORDS * sizeof(u32), c->stream));
     const unsigned grid = nblk(n * METH_GROUP, 256);
     // (without a trim: the kernels as they were before there was one)
-    const auto k_count = trim ? k_meth_events<false, true> : k_meth_events<false, false>;
-    const auto k_emit = trim ? k_meth_events<true, true> : k_meth_events<true, false>;
-    prof_begin(c, "k_meth_count");
+    auto k_count = trim ? k_meth_events<false, true> : k_meth_events<false, false>;
+    auto k_emit = trim ? k_meth_events<true, true> : k_meth_events<true, false>;
+    if (opposite) {
+        k_count = trim ? k_meth_events<false, true, true> : k_meth_events<false, false, true>;
+        k_emit = trim ? k_meth_events<true, true, true> : k_meth_events<true, false, true>;
+    }
+    prof_begin(c, opposite ? "k_meth_opp_count" : "k_meth_count");
     hipLaunchKernelGGL(k_count, dim3(grid), dim3(256), 0, c->stream, c->ix.gen2p, c->ix.chrom_start, raw, off, len, clip, 0l,
                        (long)n, par, c->mt_cnt.as<u32>(), (const u64*)nullptr, (u64*)nullptr, (u64*)nullptr, info);
     prof_end(c);
@@ -531,7 +538,7 @@ static int methyl_device(Lane* c, const char* raw, const u64* off, const u32* le
         if (ne >= (1ull << 32)) { c->err = "methyl: a record with 2^32 events and more"; return BMBS_EINVAL; }
         if (ne) {
             if ((rc = meth_events(c, ne, e))) return rc;
-            prof_begin(c, "k_meth_emit");
+            prof_begin(c, opposite ? "k_meth_opp_emit" : "k_meth_emit");
             hipLaunchKernelGGL(k_emit, dim3(nblk((end - start) * METH_GROUP, 256)), dim3(256), 0, c->stream, c->ix.gen2p,
                                c->ix.chrom_start, raw, off, len, clip, (long)start, (long)(end - start), par, (u32*)nullptr, eoff + start, e.ka, e.va, info + TXI_METH_EMIT);
             prof_end(c);
@@ -575,14 +582,15 @@ static int methyl_device(Lane* c, const char* raw, const u64* off, const u32* le
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
-    c->mc.sites = (int64_t)n_sites;
-    c->mc.has_mbias = mbias;
+    if (opposite) c->mc.opp = (int64_t)n_sites;
+    else { c->mc.sites = (int64_t)n_sites; c->mc.has_mbias = mbias; }
     if (n_site) *n_site = (int64_t)n_sites;
     return BMBS_OK;
 }
 
+// opposite: bmbs_bam_methyl_opposite (opts NULL: the defaults)
 static int lane_bam_methyl(Lane* c, const char* records, uint64_t bytes, const uint32_t* len, int64_t n_in, const uint32_t* clip, const bmbs_methyl_params* par,
-                           const bmbs_methyl_opts* opts, int64_t* n_site)
+                           const bmbs_methyl_opts* opts, bool opposite, int64_t* n_site)
 {
     if (n_site) *n_site = 0;
     c->ends(Lane::METHYL_CALL);
@@ -593,18 +601,18 @@ static int lane_bam_methyl(Lane* c, const char* records, uint64_t bytes, const u
     if (!n) {
         // (no record: no device work; an _opts call still has its options checked, and its table is all zero)
         bmbs_methyl_opts pp;
-        if (opts) { if (int rc = methyl_get_opts(c, par, opts, &pp)) return rc; c->mc.has_mbias = c->mc.mbias_zero = (pp.flags & BMBS_METHYL_MBIAS) != 0; }
-        c->mc.sites = 0;
+        if (opts) { if (int rc = methyl_get_opts(c, par, opts, opposite, &pp)) return rc; c->mc.has_mbias = c->mc.mbias_zero = (pp.flags & BMBS_METHYL_MBIAS) != 0; }
+        (opposite ? c->mc.opp : c->mc.sites) = 0;
         return BMBS_OK;
     }
     if (bytes && !records) { c->err = "methyl: NULL buffer"; return BMBS_EINVAL; }
     HIPCHK(c, hipSetDevice(c->dev));
     RecIn& r = c->mt_in;
     if (int rc = records_stage(c, r, records, bytes, len, n, TOT_RECS_IN, clip, &c->mt_clip)) return rc;
-    return methyl_device(c, r.in.as<char>(), r.off.as<u64>(), r.len.as<u32>(), clip ? c->mt_clip.as<u32>() : nullptr, n, par, opts, n_site);
+    return methyl_device(c, r.in.as<char>(), r.off.as<u64>(), r.len.as<u32>(), clip ? c->mt_clip.as<u32>() : nullptr, n, par, opts, opposite, n_site);
 }
 
-static int lane_bam_sort_methyl(Lane* c, const uint32_t* clip, const bmbs_methyl_params* par, const bmbs_methyl_opts* opts, int64_t* n_site)
+static int lane_bam_sort_methyl(Lane* c, const uint32_t* clip, const bmbs_methyl_params* par, const bmbs_methyl_opts* opts, bool opposite, int64_t* n_site)
 {
     if (n_site) *n_site = 0;
     c->ends(Lane::METHYL_CALL);
@@ -624,19 +632,56 @@ static int lane_bam_sort_methyl(Lane* c, const uint32_t* clip, const bmbs_methyl
         HIPCHK(c, hipStreamSynchronize(us));
     }
     const RecIn& r = c->sc.in;
-    return methyl_device(c, r.in.as<char>(), r.off.as<u64>(), r.len.as<u32>(), clip ? c->mt_clip.as<u32>() : nullptr, n, par, opts, n_site);
+    return methyl_device(c, r.in.as<char>(), r.off.as<u64>(), r.len.as<u32>(), clip ? c->mt_clip.as<u32>() : nullptr, n, par, opts, opposite, n_site);
 }
 
 static int lane_methyl_sites(Lane* c, bmbs_methyl_site* site, int64_t cap, int64_t* n)
 {
     if (int rc = fetch_begin(c, "methyl sites", {{n, &c->mc.sites, cap, site}}, c->mc.sites >= 0,
-                             "the context's last bmbs_bam_methyl / bmbs_bam_sort_methyl call left no result",
+                             c->mc.opp >= 0 ? "the context's last methylation call was an opposite call: its entries are fetched with bmbs_methyl_opposite"
+                                            : "the context's last bmbs_bam_methyl / bmbs_bam_sort_methyl call left no result",
                              "the array is too small (n tells what is needed)")) return rc;
     if (!c->mc.sites) return BMBS_OK;
     HIPCHK(c, hipSetDevice(c->dev));
     hipStream_t ds = down_stream_of(c);
     HIPCHK(c, hipMemcpyAsync(site, c->mt_site.p, (size_t)c->mc.sites * sizeof(bmbs_methyl_site), hipMemcpyDeviceToHost, ds));
     HIPCHK(c, hipStreamSynchronize(ds));
+    return BMBS_OK;
+}
+
+static int lane_methyl_opposite(Lane* c, bmbs_methyl_site* entry, int64_t cap, int64_t* n)
+{
+    if (int rc = fetch_begin(c, "methyl opposite", {{n, &c->mc.opp, cap, entry}}, c->mc.opp >= 0,
+                             c->mc.sites >= 0 ? "the context's last methylation call was not an opposite call: its sites are fetched with bmbs_methyl_sites"
+                                              : "the context's last bmbs_bam_methyl_opposite / bmbs_bam_sort_methyl_opposite call left no result",
+                             "the array is too small (n tells what is needed)")) return rc;
+    if (!c->mc.opp) return BMBS_OK;
+    HIPCHK(c, hipSetDevice(c->dev));
+    hipStream_t ds = down_stream_of(c);
+    HIPCHK(c, hipMemcpyAsync(entry, c->mt_site.p, (size_t)c->mc.opp * sizeof(bmbs_methyl_site), hipMemcpyDeviceToHost, ds));
+    HIPCHK(c, hipStreamSynchronize(ds));
+    return BMBS_OK;
+}
+
+// bmbs_methyl_drop_variants (host only): the rule is in include/bmbs.h
+static int methyl_drop_variants(bmbs_methyl_site* site, int64_t n_site, const bmbs_methyl_site* opp, int64_t n_opp, int32_t min_depth, int32_t max_ppm, int64_t* n_kept)
+{
+    if (n_kept) *n_kept = 0;
+    if (n_site < 0 || n_opp < 0 || (n_site && !site) || (n_opp && !opp) || !n_kept || min_depth < 1 || max_ppm < 0 || max_ppm > 1000000) return BMBS_EINVAL;
+    const auto less = [](const bmbs_methyl_site& a, const bmbs_methyl_site& b) { return a.ref != b.ref ? a.ref < b.ref : a.pos < b.pos; };
+    for (int64_t i = 1; i < n_site; i++) if (!less(site[i - 1], site[i])) return BMBS_EINVAL;
+    for (int64_t j = 1; j < n_opp; j++) if (!less(opp[j - 1], opp[j])) return BMBS_EINVAL;
+    int64_t kept = 0, j = 0;
+    for (int64_t i = 0; i < n_site; i++) {
+        while (j < n_opp && less(opp[j], site[i])) j++;
+        bool drop = false;
+        if (j < n_opp && !less(site[i], opp[j])) {
+            const uint64_t variant = opp[j].meth, depth = (uint64_t)opp[j].meth + opp[j].unmeth;      // (below 2^33; times 10^6: below 2^53)
+            drop = depth >= (uint64_t)min_depth && variant * 1000000ull > (uint64_t)max_ppm * depth;
+        }
+        if (!drop) site[kept++] = site[i];
+    }
+    *n_kept = kept;
     return BMBS_OK;
 }
 
@@ -691,11 +736,17 @@ extern "C" int bmbs_text_sorted_dup(bmbs_ctx* X, bmbs_dup_sig* sig, int64_t sig_
 { ON_LANE0(lane_text_sorted_dup(c, sig, sig_cap, n_sig, tmpl, cap, n)); }
 extern "C" int bmbs_dup_select(bmbs_ctx* X, const bmbs_dup_sig* sig, int64_t n, uint8_t* dup, int64_t* n_dup) { ON_LANE0(lane_dup_select(c, sig, n, dup, n_dup)); }
 extern "C" int bmbs_bam_methyl(bmbs_ctx* X, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, const uint32_t* clip, const bmbs_methyl_params* par, int64_t* n_site)
-{ ON_LANE0(lane_bam_methyl(c, records, bytes, len, n, clip, par, nullptr, n_site)); }
-extern "C" int bmbs_bam_sort_methyl(bmbs_ctx* X, const uint32_t* clip, const bmbs_methyl_params* par, int64_t* n_site) { ON_LANE0(lane_bam_sort_methyl(c, clip, par, nullptr, n_site)); }
+{ ON_LANE0(lane_bam_methyl(c, records, bytes, len, n, clip, par, nullptr, false, n_site)); }
+extern "C" int bmbs_bam_sort_methyl(bmbs_ctx* X, const uint32_t* clip, const bmbs_methyl_params* par, int64_t* n_site) { ON_LANE0(lane_bam_sort_methyl(c, clip, par, nullptr, false, n_site)); }
 extern "C" int bmbs_bam_methyl_opts(bmbs_ctx* X, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, const uint32_t* clip, const bmbs_methyl_opts* opts, int64_t* n_site)
-{ ON_LANE0(lane_bam_methyl(c, records, bytes, len, n, clip, nullptr, opts, n_site)); }
-extern "C" int bmbs_bam_sort_methyl_opts(bmbs_ctx* X, const uint32_t* clip, const bmbs_methyl_opts* opts, int64_t* n_site) { ON_LANE0(lane_bam_sort_methyl(c, clip, nullptr, opts, n_site)); }
+{ ON_LANE0(lane_bam_methyl(c, records, bytes, len, n, clip, nullptr, opts, false, n_site)); }
+extern "C" int bmbs_bam_sort_methyl_opts(bmbs_ctx* X, const uint32_t* clip, const bmbs_methyl_opts* opts, int64_t* n_site) { ON_LANE0(lane_bam_sort_methyl(c, clip, nullptr, opts, false, n_site)); }
 extern "C" int bmbs_methyl_mbias(bmbs_ctx* X, uint64_t* table, int64_t cap, int64_t* n) { ON_LANE0(lane_methyl_mbias(c, table, cap, n)); }
 extern "C" int bmbs_methyl_sites(bmbs_ctx* X, bmbs_methyl_site* site, int64_t cap, int64_t* n) { ON_LANE0(lane_methyl_sites(c, site, cap, n)); }
+extern "C" int bmbs_bam_methyl_opposite(bmbs_ctx* X, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, const uint32_t* clip, const bmbs_methyl_opts* opts, int64_t* n_entry)
+{ ON_LANE0(lane_bam_methyl(c, records, bytes, len, n, clip, nullptr, opts, true, n_entry)); }
+extern "C" int bmbs_bam_sort_methyl_opposite(bmbs_ctx* X, const uint32_t* clip, const bmbs_methyl_opts* opts, int64_t* n_entry) { ON_LANE0(lane_bam_sort_methyl(c, clip, nullptr, opts, true, n_entry)); }
+extern "C" int bmbs_methyl_opposite(bmbs_ctx* X, bmbs_methyl_site* entry, int64_t cap, int64_t* n) { ON_LANE0(lane_methyl_opposite(c, entry, cap, n)); }
+extern "C" int bmbs_methyl_drop_variants(bmbs_methyl_site* site, int64_t n_site, const bmbs_methyl_site* opp, int64_t n_opp, int32_t min_opposite_depth, int32_t max_variant_ppm, int64_t* n_kept)
+{ return methyl_drop_variants(site, n_site, opp, n_opp, min_opposite_depth, max_variant_ppm, n_kept); }
 extern "C" int bmbs_text_sorted_clip(bmbs_ctx* X, uint32_t* clip, int64_t cap, int64_t* n) { ON_LANE0(lane_text_sorted_clip(c, clip, cap, n)); }

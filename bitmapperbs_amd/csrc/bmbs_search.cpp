@@ -21,6 +21,10 @@
 //          --methyl ... [--methyl-ignore n] [--methyl-ignore-3prime n] [--methyl-ignore-r2 n] [--methyl-ignore-3prime-r2 n] (cycles left
 //          out of the calls at the 5' / 3' end of read 1 (or a single-end read) / read 2: Bismark's --ignore options) [--mbias]
 //          (<prefix>_mbias.tsv: the calls by context, strand, read and cycle, before the trim)
+//          --methyl ... [--methyl-min-opposite-depth n [--methyl-max-variant-frac f]] (a site is left out when at least n bases of the
+//          OTHER bisulfite strand's reads cover it and more than the fraction f of them is not the genome's letter: a C->T polymorphism
+//          of the sample, not an unmethylated cytosine; MethylDackel's --minOppositeDepth / --maxVariantFrac, a second walk on the device)
+//          [--methyl-merge-context] (one line per CpG / CHG, both strands added) [--methyl-min-depth n] (lines with fewer calls are left out)
 //
 // The reference has ONE reader thread and ONE fprintf sink (Process_Reads.cpp:2057-2260, Process_sam_out.cpp:954-1006), which is
 // what limits it.  Round 2 of this driver indexed the lines and formatted the SAM text with the host's
@@ -74,12 +78,17 @@ struct Options {
     bmbs_methyl_params mpar = {0, 10, 5, 0};     // --CpG (the default) --CHG --CHH, --methyl-min-mapq, --methyl-min-phred
     long ignore[4] = {0, 0, 0, 0};               // --methyl-ignore, --methyl-ignore-r2 (5' of mate 0, 1), --methyl-ignore-3prime, --methyl-ignore-3prime-r2 (3')
     bool ignore_given = false, mbias = false;    // --mbias: <prefix>_mbias.tsv
+    long min_opp_depth = 0;                      // --methyl-min-opposite-depth (0: no variant filter), --methyl-max-variant-frac in parts per million,
+    int32_t max_variant_ppm = 0;                 // --methyl-min-depth, --methyl-merge-context
+    long min_depth = 1;
+    bool variant_frac_given = false, site_opts_given = false, merge_context = false;
     double sort_mem_gib = 0;                     // --sort-mem: cap of the in-memory record store of --sort (0: half of the machine's memory)
     // derived once
     bool pe = false, gz_in = false, methyl_out = false;
     bool methyl_clip = false;                    // --methyl of pairs: the records carry their mate-overlap clips
     bool methyl_use_opts = false;                // a trim or --mbias: pass 2 calls bmbs_bam_sort_methyl_opts with mopt (else bmbs_bam_sort_methyl, as ever)
     bmbs_methyl_opts mopt = {1, 10, 5, 0, {0, 0}, {0, 0}};
+    bmbs_methyl_opts oopt = {1, 10, 5, 0, {0, 0}, {0, 0}};      // the variant filter: what pass 2 calls bmbs_bam_sort_methyl_opposite with (mopt without flags)
     std::string in1;                             // the first (or only) read file
     int live_parts = 1;                          // a .gz stream cannot be entered in the middle: everything goes through part 0, the other part files stay empty
     int32_t flags = 0;                           // BMBS_TEXT_* of every mapping call
@@ -179,6 +188,7 @@ struct Run {
 struct Slot {
     Pinned in, out; std::vector<uint32_t> len, clip; size_t unit = 0; uint64_t out_bytes = 0; BaiPieces bai; std::vector<bmbs_methyl_site> site; int64_t n_site = 0;
     std::vector<uint64_t> mbias;                 // --mbias: the call's table
+    std::vector<bmbs_methyl_site> opp; int64_t n_opp = 0;      // the variant filter: the call's opposite-strand entries
 };
 // (a slot belongs to one thread at a time: free_s -> stager -> staged_s -> a sorter -> done_s -> main)
 struct Pass2 {
@@ -190,6 +200,8 @@ struct Pass2 {
     std::vector<uint64_t> dup_bits;              // --markdup: a bit per template id, set for duplicates; dup_select_pass writes, the stager reads
     BaiIndex bai;                                // main alone (the calls' pieces, in call order)
     std::vector<bmbs_methyl_site> meth_sites;    // --methyl: the sites of the calls so far, merged; main alone
+    std::vector<bmbs_methyl_site> meth_opp;      // the variant filter: the opposite-strand entries of the calls so far, merged the same way; main alone
+    size_t meth_variants = 0, meth_shallow = 0;  // sites dropped as variants, lines left out below --methyl-min-depth
     std::vector<uint64_t> mbias;                 // --mbias: the tables of the calls so far, added up; main alone
     uint64_t mbias_calls = 0;                    // ... and its total
     size_t sort_calls = 0, select_calls = 0, n_dup = 0, bai_bytes = 0;
@@ -272,6 +284,20 @@ Options parse_options(int argc, char** argv)
             o.ignore_given = true;
         }
         else if (a == "--mbias") o.mbias = true;                      // --methyl ... --mbias: <prefix>_mbias.tsv
+        else if (a == "--methyl-min-opposite-depth" || a == "--methyl-min-depth") {      // MethylDackel's --minOppositeDepth, --minDepth
+            const bool opp = a == "--methyl-min-opposite-depth";
+            char* end = nullptr;
+            const char* v = val();
+            const long x = strtol(v, &end, 10);
+            if (end == v || *end || x < (opp ? 0 : 1) || x > (opp ? 65535 : 2147483647l)) { fprintf(stderr, "bmbs_search: %s takes %s\n", a.c_str(), opp ? "0..65535" : "1..2147483647"); exit(2); }
+            (opp ? o.min_opp_depth : o.min_depth) = x;
+            o.site_opts_given = true;
+        }
+        else if (a == "--methyl-max-variant-frac") {                  // MethylDackel's --maxVariantFrac
+            if (!methyl_parse_frac(val(), &o.max_variant_ppm)) refuse("bmbs_search: --methyl-max-variant-frac takes a plain decimal in 0..1 with at most 6 digits behind the point\n");
+            o.variant_frac_given = o.site_opts_given = true;
+        }
+        else if (a == "--methyl-merge-context") o.merge_context = o.site_opts_given = true;      // MethylDackel's --mergeContext
         else { fprintf(stderr, "bmbs_search: unsupported option %s\n", a.c_str()); exit(2); }
     }
     if (o.sort && !o.bam) refuse("bmbs_search: --sort needs --bam\n");
@@ -284,9 +310,13 @@ Options parse_options(int argc, char** argv)
     if (mpar.min_mapq < 0 || mpar.min_mapq > 255 || mpar.min_phred < 0 || mpar.min_phred > 255) refuse("bmbs_search: --methyl-min-mapq and --methyl-min-phred take 0..255\n");
     if (!o.methyl_out && o.ignore_given) refuse("bmbs_search: --methyl-ignore, --methyl-ignore-3prime, --methyl-ignore-r2 and --methyl-ignore-3prime-r2 need --methyl\n");
     if (!o.methyl_out && o.mbias) refuse("bmbs_search: --mbias needs --methyl\n");
+    if (!o.methyl_out && o.site_opts_given) refuse("bmbs_search: --methyl-min-opposite-depth, --methyl-max-variant-frac, --methyl-min-depth and --methyl-merge-context need --methyl\n");
+    if (o.variant_frac_given && o.min_opp_depth < 1) refuse("bmbs_search: --methyl-max-variant-frac needs --methyl-min-opposite-depth above 0\n");
     if (!mpar.contexts) mpar.contexts = 1;
+    if (o.merge_context && !(mpar.contexts & 3)) refuse("bmbs_search: --methyl-merge-context needs --CpG or --CHG (CHH is never merged)\n");
     o.methyl_use_opts = o.mbias || o.ignore[0] || o.ignore[1] || o.ignore[2] || o.ignore[3];
     o.mopt = bmbs_methyl_opts{mpar.contexts, mpar.min_mapq, mpar.min_phred, o.mbias ? BMBS_METHYL_MBIAS : 0, {(int32_t)o.ignore[0], (int32_t)o.ignore[1]}, {(int32_t)o.ignore[2], (int32_t)o.ignore[3]}};
+    o.oopt = o.mopt; o.oopt.flags = 0;
     if (o.bai) {
         // the index lies beside a file: a device or a pipe has no such place
         struct stat osb;
@@ -294,7 +324,7 @@ Options parse_options(int argc, char** argv)
     }
     if (!o.build_fasta.empty()) return o;            // --index: nothing below applies
     if (o.index.empty() || (o.seq.empty() && (o.seq1.empty() || o.seq2.empty())))
-        refuse("usage: bmbs_search --index <genome.fa> [--index_folder dir] [-t threads]\n       bmbs_search --search <index> (--seq r.fq | --seq1 a.fq --seq2 b.fq) [-o out.sam] [-e f] [--min n] [--max n] [--sensitive] [--pbat] [--unmapped_out] [--ambiguous_out] [--bam [--sort [--sort-mem GiB] [--markdup] [--bai] [--methyl prefix [--CpG] [--CHG] [--CHH] [--methyl-min-mapq n] [--methyl-min-phred n] [--methyl-ignore n] [--methyl-ignore-3prime n] [--methyl-ignore-r2 n] [--methyl-ignore-3prime-r2 n] [--mbias]]]] [--mapstats f] [-t io_threads] [--out-parts n]\n");
+        refuse("usage: bmbs_search --index <genome.fa> [--index_folder dir] [-t threads]\n       bmbs_search --search <index> (--seq r.fq | --seq1 a.fq --seq2 b.fq) [-o out.sam] [-e f] [--min n] [--max n] [--sensitive] [--pbat] [--unmapped_out] [--ambiguous_out] [--bam [--sort [--sort-mem GiB] [--markdup] [--bai] [--methyl prefix [--CpG] [--CHG] [--CHH] [--methyl-min-mapq n] [--methyl-min-phred n] [--methyl-ignore n] [--methyl-ignore-3prime n] [--methyl-ignore-r2 n] [--methyl-ignore-3prime-r2 n] [--mbias] [--methyl-min-opposite-depth n [--methyl-max-variant-frac f]] [--methyl-merge-context] [--methyl-min-depth n]]]] [--mapstats f] [-t io_threads] [--out-parts n]\n");
     if (o.batch < 1) o.batch = 1;
     if (o.io_threads <= 0) {
         // plain text needs few threads to read at memory speed; compressed input is inflated by them (csrc/pgz.h): more pay off
@@ -507,7 +537,8 @@ std::string sam_header_text(bool sorted, const std::vector<std::string>& chrom_n
         const std::string& a = args[i];
         if (a == "--methyl" || a == "--methyl-min-mapq" || a == "--methyl-min-phred") { i++; continue; }
         if (a == "--methyl-ignore" || a == "--methyl-ignore-r2" || a == "--methyl-ignore-3prime" || a == "--methyl-ignore-3prime-r2") { i++; continue; }
-        if (a == "--CpG" || a == "--CHG" || a == "--CHH" || a == "--mbias") continue;
+        if (a == "--methyl-min-opposite-depth" || a == "--methyl-max-variant-frac" || a == "--methyl-min-depth") { i++; continue; }
+        if (a == "--CpG" || a == "--CHG" || a == "--CHH" || a == "--mbias" || a == "--methyl-merge-context") continue;
         h += a; h += ' ';
     }
     h += '\n';
@@ -975,7 +1006,7 @@ void pass2_sorter(Run& R, Pass2& S, bmbs_ctx* ctx)
         }
         if (o.bai && !R.failed && !sl->bai.fetch(ctx)) { R.fail(bmbs_last_error(ctx)); sl->out_bytes = 0; }
         // --methyl: the call's records are still on the device (the staged copies: duplicates carry 0x400)
-        sl->n_site = 0;
+        sl->n_site = sl->n_opp = 0;
         if (o.mbias) std::fill(sl->mbias.begin(), sl->mbias.end(), 0);      // (a call that fails leaves no table of the call before)
         if (o.methyl_out && !R.failed) {
             int64_t ns = 0;
@@ -986,6 +1017,15 @@ void pass2_sorter(Run& R, Pass2& S, bmbs_ctx* ctx)
                 if (bmbs_methyl_sites(ctx, sl->site.data(), (int64_t)sl->site.size(), &sl->n_site)) { R.fail(bmbs_last_error(ctx)); sl->out_bytes = 0; sl->n_site = 0; }
                 int64_t nt = 0;
                 if (o.mbias && !R.failed && bmbs_methyl_mbias(ctx, sl->mbias.data(), (int64_t)sl->mbias.size(), &nt)) { R.fail(bmbs_last_error(ctx)); sl->out_bytes = 0; }
+            }
+            // the variant filter: the same records once more, for what they show of the other strand's cytosines
+            if (o.min_opp_depth > 0 && !R.failed) {
+                int64_t no = 0;
+                if (bmbs_bam_sort_methyl_opposite(ctx, clip, &o.oopt, &no)) { R.fail(bmbs_last_error(ctx)); sl->out_bytes = 0; }
+                else {
+                    if ((size_t)no > sl->opp.size()) sl->opp.resize((size_t)no + (size_t)no / 8);
+                    if (bmbs_methyl_opposite(ctx, sl->opp.data(), (int64_t)sl->opp.size(), &sl->n_opp)) { R.fail(bmbs_last_error(ctx)); sl->out_bytes = 0; sl->n_opp = 0; }
+                }
             }
         }
         S.done_s.put((long)sl->unit, sl);
@@ -1038,6 +1078,7 @@ void sort_pass2(Run& R, Pass2& S)
             if (!R.failed && !pwrite_all(pt.ofd, sl->out.p, (size_t)sl->out_bytes, pt.out_off)) R.fail(std::string("write error: ") + strerror(errno));
             if (o.bai && !R.failed && !S.bai.add(sl->bai, (uint64_t)pt.out_off)) R.fail("--bai: a record names a sequence the header does not have");
             if (o.methyl_out && !R.failed) methyl_merge(S.meth_sites, sl->site.data(), (size_t)sl->n_site);
+            if (o.min_opp_depth > 0 && !R.failed) methyl_merge(S.meth_opp, sl->opp.data(), (size_t)sl->n_opp);
             if (o.mbias && !R.failed) for (size_t k = 0; k < S.mbias.size(); k++) S.mbias[k] += sl->mbias[k];
             pt.out_off += (size_t)sl->out_bytes;
             S.free_s.put(sl);
@@ -1080,7 +1121,9 @@ void write_bai(Run& R, Pass2& S)
     if (fd < 0 || !pwrite_all(fd, ix.data(), ix.size(), 0) || ::close(fd) != 0) { fprintf(stderr, "bmbs_search: cannot write %s.bai: %s\n", o.out.c_str(), strerror(errno)); R.failed = true; }
 }
 
-// --methyl: the files, written once the BAM is complete; sites that touch a base the FASTA does not spell A, C, G or T are left out
+// --methyl: the files, written once the BAM is complete.  In this order: sites that touch a base the FASTA does not spell A, C, G or T
+// are left out; the variant filter drops the sites the opposite strand shows to be polymorphisms (bmbs_methyl_drop_variants);
+// --methyl-merge-context adds the two strands of a CpG / CHG; --methyl-min-depth leaves out the lines below it
 void write_methyl(Run& R, Pass2& S)
 {
     const Options& o = R.o;
@@ -1094,11 +1137,19 @@ void write_methyl(Run& R, Pass2& S)
         S.meth_dropped = sites.size() - kept;
         sites.resize(kept);
     }
+    if (o.min_opp_depth > 0) {
+        int64_t kept = 0;
+        if (bmbs_methyl_drop_variants(sites.data(), (int64_t)sites.size(), S.meth_opp.data(), (int64_t)S.meth_opp.size(), (int32_t)o.min_opp_depth, o.max_variant_ppm, &kept)) {
+            fprintf(stderr, "bmbs_search: --methyl: the sites or the opposite-strand entries are out of order\n"); R.failed = true; return;
+        }
+        S.meth_variants = sites.size() - (size_t)kept;
+        sites.resize((size_t)kept);
+    }
     for (const bmbs_methyl_site& s : sites) { S.meth_n[s.kind & 3u]++; S.meth_calls[s.kind & 3u] += (size_t)s.meth + s.unmeth; }
     for (unsigned x = 0; x < 3 && !R.failed; x++) {
         if (!((o.mpar.contexts >> x) & 1)) continue;
         const std::string path = o.methyl + "_" + ctx_names[x] + ".bedGraph";
-        if (!methyl_write(path, o.methyl, ctx_names[x], x, sites, R.ixf)) { fprintf(stderr, "bmbs_search: cannot write %s: %s\n", path.c_str(), strerror(errno)); R.failed = true; }
+        if (!methyl_write(path, o.methyl, ctx_names[x], x, sites, R.ixf, o.merge_context, (uint64_t)o.min_depth, &S.meth_shallow)) { fprintf(stderr, "bmbs_search: cannot write %s: %s\n", path.c_str(), strerror(errno)); R.failed = true; }
     }
     // --mbias: the table as the device made it (calls at bases the FASTA does not spell A, C, G or T are in it: only sites are filtered)
     if (o.mbias && !R.failed) {
@@ -1144,7 +1195,7 @@ void report(const Run& R, const Pass2& S)
             R.n_owner, o.contexts, o.parts);
     if (o.sort) {
         const SortStore& store = R.sort_store;
-        char ixs[640] = "";
+        char ixs[800] = "";
         if (o.bai) snprintf(ixs, sizeof ixs, ", index: chunks %zu, windows %zu, %zu bytes", S.bai.n_chunks(), S.bai.n_windows(), S.bai_bytes);
         if (o.markdup)
             snprintf(ixs + strlen(ixs), sizeof ixs - strlen(ixs), ", markdup: templates %ld, with signature %ld, duplicates %zu (select calls %zu, %.3fs of pass 2)", store.templates,
@@ -1152,6 +1203,8 @@ void report(const Run& R, const Pass2& S)
         if (o.methyl_out)
             snprintf(ixs + strlen(ixs), sizeof ixs - strlen(ixs), ", methyl: sites CpG %zu CHG %zu CHH %zu, calls CpG %zu CHG %zu CHH %zu, sites left out at bases other than ACGT %zu", S.meth_n[0],
                      S.meth_n[1], S.meth_n[2], S.meth_calls[0], S.meth_calls[1], S.meth_calls[2], S.meth_dropped);
+        if (o.methyl_out)
+            snprintf(ixs + strlen(ixs), sizeof ixs - strlen(ixs), ", sites dropped as variants %zu, lines left out below the minimum depth %zu", S.meth_variants, S.meth_shallow);
         if (o.mbias) snprintf(ixs + strlen(ixs), sizeof ixs - strlen(ixs), ", mbias calls %llu", (unsigned long long)S.mbias_calls);
         fprintf(stderr, "[bmbs_search] sort: bins %zu (one of them for records without a reference), pass-2 calls %zu, store bytes %zu (%ld records), pass 1 %.3fs (mapping, binning), pass 2 %.3fs (sort, deflate, write)%s\n",
                 store.bin.size(), S.sort_calls, store.bytes, store.records, R.t_pass1 - R.t_loaded, R.t_pass2 - R.t_pass1, ixs);

@@ -1,6 +1,7 @@
 // bitmapperbs_amd/csrc/k_methyl.hip -- per-cytosine methylation counts from BAM records on the device (`--bam --sort --methyl`,
-// bmbs_bam_methyl[_opts], bmbs_bam_sort_methyl[_opts], bmbs_methyl_sites, bmbs_methyl_mbias, bmbs_text_sorted_clip).  The rule is in
-// include/bmbs.h; tests/methyl_spec.py restates the sites, tests/mbias_spec.py the read-end trim and the M-bias table.
+// bmbs_bam_methyl[_opts], bmbs_bam_sort_methyl[_opts], bmbs_methyl_sites, bmbs_methyl_mbias, bmbs_text_sorted_clip,
+// bmbs_bam_methyl_opposite, bmbs_bam_sort_methyl_opposite, bmbs_methyl_opposite).  The rule is in include/bmbs.h; tests/methyl_spec.py
+// restates the sites, tests/mbias_spec.py the read-end trim and the M-bias table, tests/variant_spec.py the opposite-strand observation.
 //
 // Record i = len[i] bytes at raw + off[i] (len 0: no record), the layout of k_markdup.hip.  An EVENT is one call of one read base:
 // key = refID << pos_bits | pos, value = 1 << 32 (methylated) or 1 (unmethylated) -- the same (key, value) form a SITE has once its
@@ -8,6 +9,11 @@
 //   k_meth_events<false>  a group of METH_GROUP lanes per record: checks it, decides whether it counts, and counts its events
 //   (scan_u32)            where each record's events go
 //   k_meth_events<true>   the same walk again, writing the events  (<.., true>: both passes leave out the calls of trimmed cycles)
+//   k_meth_events<.., .., true>  the OPPOSITE-strand observation (bmbs_bam_methyl_opposite, bmbs_bam_sort_methyl_opposite; tests/
+//                         variant_spec.py): the same two passes, but an OB record is looked at where the genome has a forward C of a
+//                         selected context and an OT record where it has a forward G -- where the other strand's records are called.  A
+//                         read base that passes the filters of a call is a MATCH (value 1) when its code is the genome's base there
+//                         (C = 2, G = 4), a VARIANT (value 1 << 32) when it is one of the other three of A C G T, else nothing
 //   k_meth_mbias          the same walk once more when the M-bias table is asked for: a histogram of the calls by (mate, strand,
 //                         context, methylated, cycle), trimmed or not
 //   k_meth_cut            where a slice of records ends that holds at most a given number of events
@@ -69,8 +75,12 @@ DEVI void meth_masks(const u64* __restrict__ gen2p, long W, long lo, long hi, u3
 // EMIT false: cnt[i - first] = the events of record i.  EMIT true: they are written at eoff[i - first] - eoff[0].
 // TRIM: a call of cycle c of a record of mate m is an event only if par.ig5[m] <= c < l_seq - par.ig3[m]; both passes of a call run
 // the same TRIM.  <.., false> is the kernel as it was before there was a trim: none of this is compiled into it.
+// OPP: the opposite-strand observation (the header of this file): the other half of the masks, and match / variant in the place of
+// unmethylated / methylated.  Its record checks are those of the calls and report through the same four words, nothing of its own.
+// <.., .., false> (the default) is the kernel as it was before there was one: none of this is compiled into it, and its code is the
+// same instruction for instruction -- which a template parameter guarantees and a walk shared through a function does not.
 // k_meth_mbias below holds a COPY of the record checks and of the walk: a change to the rule here has to be made there too.
-template <bool EMIT, bool TRIM>
+template <bool EMIT, bool TRIM, bool OPP = false>
 __global__ void __launch_bounds__(256)
 k_meth_events(const u64* __restrict__ gen2p, const u64* __restrict__ chrom_start, const char* __restrict__ raw, const u64* __restrict__ off,
               const u32* __restrict__ len, const u32* __restrict__ clip, long first, long n, MethPar par, u32* __restrict__ cnt,
@@ -123,7 +133,9 @@ k_meth_events(const u64* __restrict__ gen2p, const u64* __restrict__ chrom_start
     const bool all_m = counts && n_cig == 1 && ((0x181u >> (bs_ld32(cg) & 15u)) & 1u);      // one M, = or X: a constant shift
     const char* const sq = cg + 4 * (u64)n_cig;
     const char* const ql = sq + ((u64)l_seq + 1) / 2;
-    const u32 want_m = ob ? 4u : 2u, want_u = ob ? 1u : 8u;               // G / A for OB, C / T for OT (BAM's 4-bit codes)
+    // G / A for OB, C / T for OT (BAM's 4-bit codes); OPP: want_u = the genome's own base where the record is looked at, C for OB, G for OT
+    const u32 want_m = OPP ? 0u : ob ? 4u : 2u, want_u = OPP ? (ob ? 2u : 4u) : ob ? 1u : 8u;
+    const bool at_g = OPP ? !ob : ob;                                       // the record is looked at where the genome has a forward G
     const long W0 = a0 >> 5, W1 = counts && span ? (a1 - 1) >> 5 : W0 - 1;
     const long t_lo = TRIM ? (long)par.ig5[meth_mate(flag)] : 0, t_hi = TRIM ? (long)l_seq - (long)par.ig3[meth_mate(flag)] : 0;
     for (long base = W0; base <= W1; base += METH_GROUP) {                  // (uniform within the group)
@@ -134,7 +146,7 @@ k_meth_events(const u64* __restrict__ gen2p, const u64* __restrict__ chrom_start
             meth_masks(gen2p, W, s_lo, s_hi, m);
             u32 sel = 0;
 #pragma unroll
-            for (int x = 0; x < 3; x++) if ((par.contexts >> x) & 1u) sel |= m[(ob ? 3 : 0) + x];
+            for (int x = 0; x < 3; x++) if ((par.contexts >> x) & 1u) sel |= m[(at_g ? 3 : 0) + x];
             sel &= (u32)meth_range(32 * W, a0, a1, 32) & ~(u32)meth_range(32 * W, c_lo, c_hi, 32);
             // the read base against each position that is left: bits ascend, so the CIGAR is walked once per word
             u32 k = 0; long r_at = 0, i_at = 0;
@@ -161,7 +173,11 @@ k_meth_events(const u64* __restrict__ gen2p, const u64* __restrict__ chrom_start
                 if ((q == 255u ? 0u : q) < par.min_phred) continue;
                 const u32 by = (u32)(unsigned char)sq[ri >> 1];
                 const u32 code = (ri & 1) ? (by & 15u) : (by >> 4);
-                if (code == want_m) mb |= 1u << b;
+                if (OPP) {                                                   // a match, or one of the other three of A C G T: a variant
+                    if (code == want_u) ub |= 1u << b;
+                    else if ((0x116u >> code) & 1u) mb |= 1u << b;
+                }
+                else if (code == want_m) mb |= 1u << b;
                 else if (code == want_u) ub |= 1u << b;
             }
         }

@@ -374,17 +374,55 @@ inline bool methyl_touches(const std::vector<std::pair<int64_t, int64_t>>& runs,
     auto it = std::upper_bound(runs.begin(), runs.end(), std::make_pair(hi, INT64_MAX));                 // the first run that begins behind hi
     return it != runs.begin() && (it - 1)->second > lo;
 }
-// <prefix>_<context>.bedGraph in MethylDackel's column layout; the percentage is rounded half up in integers
-inline bool methyl_write(const std::string& path, const std::string& prefix, const char* ctx_name, unsigned ctx, const std::vector<bmbs_methyl_site>& sites, const bmbs_index_file* ixf)
+// --methyl-max-variant-frac: a plain decimal in [0, 1] -> parts per million without floating point.  Digits, or digits '.' digits with
+// the first digits optional; at most 6 digits behind the point; no sign, no exponent, nothing else
+inline bool methyl_parse_frac(const char* text, int32_t* ppm)
+{
+    const char* q = text;
+    uint64_t whole = 0, frac = 0;
+    int nw = 0, nf = 0;
+    for (; *q >= '0' && *q <= '9'; q++, nw++) whole = std::min<uint64_t>(whole * 10 + (uint64_t)(*q - '0'), 1000);
+    if (*q == '.') {
+        for (q++; *q >= '0' && *q <= '9'; q++, nf++) { if (nf >= 6) return false; frac = frac * 10 + (uint64_t)(*q - '0'); }
+        if (!nf) return false;
+    }
+    if (*q || nw + nf == 0) return false;
+    for (int k = nf; k < 6; k++) frac *= 10;
+    const uint64_t v = whole * 1000000 + frac;
+    if (v > 1000000) return false;
+    *ppm = (int32_t)v;
+    return true;
+}
+// <prefix>_<context>.bedGraph in MethylDackel's column layout; the percentage is rounded half up in integers.
+// merge (--methyl-merge-context): a CpG site is written with the interval of its dinucleotide (strand 0 at p: [p, p + 2), strand 1:
+// [p - 1, p + 1)), a CHG site with that of its trinucleotide ([p, p + 3) / [p - 2, p + 1)), and the sites of the context with the same
+// interval -- the two strands of one CpG or CHG -- are added; a site without its partner (absent, dropped before, or of another context:
+// in CCG the G is a CpG cytosine) stands alone with its interval; CHH is never merged.  Among the sites of ONE context in (ref, pos)
+// order the intervals ascend and only partners share one (a C directly in front of a G is a CpG on both strands, so no CHG of strand 0
+// lies between a CHG of strand 1 and its interval's start): one pending line is enough.
+// min_depth (--methyl-min-depth): a line is written iff meth + unmeth >= min_depth, *shallow += the lines that are not
+inline bool methyl_write(const std::string& path, const std::string& prefix, const char* ctx_name, unsigned ctx, const std::vector<bmbs_methyl_site>& sites, const bmbs_index_file* ixf,
+                         bool merge, uint64_t min_depth, size_t* shallow)
 {
     FILE* f = fopen(path.c_str(), "wb");
     if (!f) return false;
     fprintf(f, "track type=\"bedGraph\" description=\"%s %s methylation levels\"\n", prefix.c_str(), ctx_name);
+    struct Line { int32_t ref; int64_t beg, end; uint64_t m, u; } cur = {-1, 0, 0, 0, 0};
+    const auto flush = [&] {
+        if (cur.ref < 0) return;
+        if (cur.m + cur.u < min_depth) { ++*shallow; return; }
+        fprintf(f, "%s\t%lld\t%lld\t%llu\t%llu\t%llu\n", bmbs_index_file_chrom_name(ixf, cur.ref), (long long)cur.beg, (long long)cur.end,
+                (unsigned long long)((200 * cur.m + cur.m + cur.u) / (2 * (cur.m + cur.u))), (unsigned long long)cur.m, (unsigned long long)cur.u);
+    };
+    const int64_t w = !merge || ctx == 2 ? 1 : ctx == 0 ? 2 : 3;
     for (const bmbs_methyl_site& s : sites) {
         if ((s.kind & 3u) != ctx) continue;
-        const uint64_t m = s.meth, u = s.unmeth;
-        fprintf(f, "%s\t%d\t%d\t%llu\t%u\t%u\n", bmbs_index_file_chrom_name(ixf, s.ref), s.pos, s.pos + 1, (unsigned long long)((200 * m + m + u) / (2 * (m + u))), s.meth, s.unmeth);
+        const int64_t beg = (s.kind & 4u) ? (int64_t)s.pos - w + 1 : (int64_t)s.pos;
+        if (cur.ref == s.ref && cur.beg == beg) { cur.m += s.meth; cur.u += s.unmeth; continue; }
+        flush();
+        cur = Line{s.ref, beg, beg + w, s.meth, s.unmeth};
     }
+    flush();
     const bool ok = !ferror(f);
     return fclose(f) == 0 && ok;
 }

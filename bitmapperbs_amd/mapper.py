@@ -485,6 +485,49 @@ class Mapper:
         self._chk(call(self._ctx, capi.ptr(cl) if cl is not None and cl.size else None, C.byref(par if opts is None else opts), C.byref(n)))
         return self.methyl_sites()
 
+    def methyl_opposite(self) -> np.ndarray:
+        """the entries (capi.METHYL_SITE_DTYPE: meth = variants, unmeth = matches) the last bam_methyl_opposite / bam_sort_methyl_opposite
+        call left on the device (bmbs_methyl_opposite)"""
+        n = C.c_int64(0)
+        rc = self._lib.bmbs_methyl_opposite(self._ctx, None, 0, C.byref(n))
+        if rc and rc != -12:
+            self._chk(rc)
+        entry = np.zeros(max(1, n.value), dtype=capi.METHYL_SITE_DTYPE)
+        self._chk(self._lib.bmbs_methyl_opposite(self._ctx, capi.ptr(entry), n.value, C.byref(n)))
+        return entry[:n.value]
+
+    @staticmethod
+    def _opposite_opts(contexts, min_mapq, min_phred, ignore_5p, ignore_3p):
+        i5, i3 = tuple(int(x) for x in ignore_5p), tuple(int(x) for x in ignore_3p)
+        if len(i5) != 2 or len(i3) != 2:
+            raise ValueError("ignore_5p and ignore_3p: one value per mate")
+        return capi.MethylOpts(int(contexts), int(min_mapq), int(min_phred), 0, (C.c_int32 * 2)(*i5), (C.c_int32 * 2)(*i3))
+
+    def bam_methyl_opposite(self, records: bytes, lens, clip=None, contexts: int = 1, min_mapq: int = 10, min_phred: int = 5, ignore_5p=(0, 0),
+                            ignore_3p=(0, 0)) -> np.ndarray:
+        """the records of bam_methyl -> what they show of the OTHER strand's cytosines: per (ref, pos) where an OB record lies over a
+        forward C of a selected context or an OT record over a forward G, the read bases that are another letter (meth) and the genome's
+        own (unmeth), ordered by (ref, pos) (bmbs_bam_methyl_opposite); drop_variants() filters a call's sites with them"""
+        ln = np.ascontiguousarray(lens, dtype=np.uint32)
+        a = np.frombuffer(records, dtype=np.uint8) if len(records) else np.zeros(1, dtype=np.uint8)
+        cl = None if clip is None else np.ascontiguousarray(clip, dtype=np.uint32)
+        if cl is not None and cl.size != ln.size:
+            raise ValueError("bam_methyl_opposite: one clip per record")
+        opts = self._opposite_opts(contexts, min_mapq, min_phred, ignore_5p, ignore_3p)
+        n = C.c_int64(0)
+        self._chk(self._lib.bmbs_bam_methyl_opposite(self._ctx, capi.ptr(a), len(records), capi.ptr(ln) if ln.size else None, ln.size,
+                                                     capi.ptr(cl) if cl is not None and cl.size else None, C.byref(opts), C.byref(n)))
+        return self.methyl_opposite()
+
+    def bam_sort_methyl_opposite(self, clip=None, contexts: int = 1, min_mapq: int = 10, min_phred: int = 5, ignore_5p=(0, 0), ignore_3p=(0, 0)) -> np.ndarray:
+        """the same for the records of the last bam_sort call, which are still on the device; clip in that call's input order
+        (bmbs_bam_sort_methyl_opposite)"""
+        cl = None if clip is None else np.ascontiguousarray(clip, dtype=np.uint32)
+        opts = self._opposite_opts(contexts, min_mapq, min_phred, ignore_5p, ignore_3p)
+        n = C.c_int64(0)
+        self._chk(self._lib.bmbs_bam_sort_methyl_opposite(self._ctx, capi.ptr(cl) if cl is not None and cl.size else None, C.byref(opts), C.byref(n)))
+        return self.methyl_opposite()
+
     def sync(self):
         self._chk(self._lib.bmbs_sync(self._ctx))
 
@@ -634,6 +677,21 @@ def pack_quals(params, qual: np.ndarray, L: int, lens: np.ndarray | None = None,
     if rc:
         raise ValueError("bmbs_pack_quals: row %d cannot be packed (rc %d)" % (bad.value, rc))
     return qrows
+
+
+# ---- the variant filter of the methylation calls (host arithmetic only: no device, no Mapper needed) ----
+def drop_variants(site: np.ndarray, opp: np.ndarray, min_opposite_depth: int, max_variant_ppm: int) -> np.ndarray:
+    """bmbs_methyl_drop_variants: the sites (capi.METHYL_SITE_DTYPE, ordered by (ref, pos)) without those where the opposite-strand
+    entries `opp` (Mapper.methyl_opposite) show at least min_opposite_depth bases of which more than max_variant_ppm / 10^6 are a
+    variant; a new array, the arguments stay as they are"""
+    s = np.array(site, dtype=capi.METHYL_SITE_DTYPE, copy=True, ndmin=1)
+    o = np.ascontiguousarray(opp, dtype=capi.METHYL_SITE_DTYPE)
+    kept = C.c_int64(0)
+    rc = capi.lib().bmbs_methyl_drop_variants(capi.ptr(s) if s.size else None, s.size, capi.ptr(o) if o.size else None, o.size,
+                                              int(min_opposite_depth), int(max_variant_ppm), C.byref(kept))
+    if rc:
+        raise ValueError("bmbs_methyl_drop_variants: a list out of order, min_opposite_depth < 1 or max_variant_ppm outside 0..1000000 (rc %d)" % rc)
+    return s[:kept.value]
 
 
 # ---- SAM text (host emit) --------------------------------------------------------------------------

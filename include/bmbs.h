@@ -506,6 +506,37 @@ int bmbs_bam_sort_methyl_opts(bmbs_ctx*, const uint32_t* clip, const bmbs_methyl
 int bmbs_methyl_sites(bmbs_ctx*, bmbs_methyl_site* site, int64_t cap, int64_t* n);
 int bmbs_methyl_mbias(bmbs_ctx*, uint64_t* table, int64_t cap, int64_t* n);
 
+/* ---- the opposite strand: what tells a C->T polymorphism of the sample from an unmethylated cytosine (tests/variant_spec.py) --------------
+ * On the reads of its own bisulfite strand a C->T variant looks like an unmethylated C; the reads of the OTHER strand show the position
+ * unconverted, so only they can tell the two apart (MethylDackel's --minOppositeDepth / --maxVariantFrac).
+ * The opposite-strand OBSERVATION.  Every record that COUNTS under the rule above (flags, n_cigar_op > 0, MAPQ >= min_mapq, proper pair
+ * when paired) is walked with the same CIGAR pairing (M = X).  An OB record is looked at where the genome has a forward C of a selected
+ * context, an OT record where it has a forward G of a selected context: the positions the other strand's records are called at.  A read
+ * base passes exactly the filters a call passes: quality >= min_phred (0xff counts as 0), not inside the record's mate-overlap clip,
+ * ignore_5p[m] <= cycle < l_seq - ignore_3p[m].  Its BAM code against the genome's base there (C = 2, G = 4): equal -- a MATCH; one of
+ * the other three of {1, 2, 4, 8} -- a VARIANT; any other code (=, N, the ambiguity codes) -- nothing.
+ * bmbs_bam_methyl_opposite / bmbs_bam_sort_methyl_opposite (the records as for bmbs_bam_methyl_opts / bmbs_bam_sort_methyl_opts; the
+ * latter works on the records of the context's last bmbs_bam_sort call, directly before or behind a bmbs_bam_sort_methyl[_opts] call on
+ * the same records as well) leave one entry per (ref, pos) with match + variant > 0 on the device, ordered by (ref, pos), *n_entry of
+ * them, as bmbs_methyl_site: meth = the VARIANT count, unmeth = the MATCH count (each saturates at 2^32 - 1), kind = context |
+ * strand << 2 of the cytosine at that position (strand 0 where an OB record was looked at), pad = 0.  opts NULL: the defaults (CpG,
+ * MAPQ 10, quality 5, no trim); opts->flags must be 0 (BMBS_METHYL_MBIAS there: BMBS_EINVAL); every other check and error is that of
+ * bmbs_bam_methyl_opts; n = 0 is valid.  A context holds ONE methylation result at a time: an opposite call ends the sites and table of
+ * the call before it, a bmbs_bam_methyl* / bmbs_bam_sort_methyl* call ends the entries.  bmbs_methyl_opposite fetches the entries
+ * (BMBS_ENOMEM with *n set when cap is smaller; a cap of 0: the size query); it and bmbs_methyl_sites return BMBS_ESTATE, and say so,
+ * when the context's last methylation call was of the other kind.
+ * The FILTER (bmbs_methyl_drop_variants: host only -- no context, no device).  site[0 .. n_site) and opp[0 .. n_opp) are ordered by
+ * (ref, pos), each position once.  A site is dropped iff an entry of opp has its (ref, pos) with match + variant >= min_opposite_depth and
+ * variant * 1000000 > max_variant_ppm * (match + variant) (strict, in 64 bits).  A site without an entry is kept; an entry without a
+ * site does nothing.  `site` is compacted in place, *n_kept = what is left.  BMBS_EINVAL: a list out of order, min_opposite_depth < 1,
+ * max_variant_ppm outside 0..1000000, a NULL argument.                                                                            */
+int bmbs_bam_methyl_opposite(bmbs_ctx*, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, const uint32_t* clip,
+                             const bmbs_methyl_opts* opts, int64_t* n_entry);
+int bmbs_bam_sort_methyl_opposite(bmbs_ctx*, const uint32_t* clip, const bmbs_methyl_opts* opts, int64_t* n_entry);
+int bmbs_methyl_opposite(bmbs_ctx*, bmbs_methyl_site* entry, int64_t cap, int64_t* n);
+int bmbs_methyl_drop_variants(bmbs_methyl_site* site, int64_t n_site, const bmbs_methyl_site* opp, int64_t n_opp,
+                              int32_t min_opposite_depth, int32_t max_variant_ppm, int64_t* n_kept);
+
 /* a21: per-ctx counters of the batches mapped so far = {reads, unique, ambiguous, mapped bases,
  * error bases} (Schema.cpp:25141-25146); bmbs_stats_allreduce sums them over the ctxs one process
  * drives (get_mapping_informations, Schema.cpp:451-476).  Multi-process jobs sum the five int64 with

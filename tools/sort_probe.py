@@ -18,10 +18,14 @@ and k_meth_mbias's kernel time beside the counting pass's (k_meth_events<false, 
 --other-driver <bmbs_search of another build> (with --methyl): that build's `--methyl` leg alternates with this build's, to show that
 a run which asks for neither the table nor a trim costs what it did: this build's median against the other's median and spread.
 (The other build's runs write the same sortp_y.bam and bedGraphs as this build's --methyl leg, one after the other.)
+--variant (with --methyl): a leg `--methyl ... --methyl-min-opposite-depth 3 --methyl-max-variant-frac 0.5` beside the --methyl leg --
+its walls beside that leg's, the numbers of sites dropped as variants, and the opposite passes' kernel time (k_meth_events<.., .., true>)
+beside the calling passes' (k_meth_events<.., .., false>: k_meth_count / k_meth_emit) in the trace (then a run with the filter on).  The
+report goes to profiles/variant_probe.txt and the kernel rows to profiles/variant_kernel_stats.csv unless --out / --stats-out say otherwise.
 With --mbias the report goes to profiles/mbias_probe.txt and the kernel rows to profiles/mbias_kernel_stats.csv unless --out /
 --stats-out name other files.
 
-  python tools/sort_probe.py [--reads 4000000] [--loop 8] [--pe] [--runs 3] [--bai] [--markdup] [--methyl [--mbias] [--other-driver path]] [--out profiles/sorted_bam_probe.txt | profiles/mbias_probe.txt]
+  python tools/sort_probe.py [--reads 4000000] [--loop 8] [--pe] [--runs 3] [--bai] [--markdup] [--methyl [--mbias] [--variant] [--other-driver path]] [--out profiles/sorted_bam_probe.txt | profiles/mbias_probe.txt]
 """
 import argparse
 import csv
@@ -36,6 +40,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
+
+
+VARIANT_ARGS = ["--methyl-min-opposite-depth", "3", "--methyl-max-variant-frac", "0.5"]
 
 
 def step(cmd, limit, **kw):
@@ -62,6 +69,9 @@ def verbose_numbers(err):
     m = re.search(r"(methyl: sites CpG \d+ CHG \d+ CHH \d+, calls CpG \d+ CHG \d+ CHH \d+)", err)
     if m:
         out["methyl"] = m.group(1)
+    m = re.search(r"sites dropped as variants (\d+), lines left out below the minimum depth (\d+)", err)
+    if m:
+        out["variants"] = int(m.group(1))
     m = re.search(r"mbias calls (\d+)", err)
     if m:
         out["mbias"] = int(m.group(1))
@@ -85,13 +95,14 @@ def main():
     ap.add_argument("--markdup", action="store_true", help="also measure --bam --sort --markdup (PCR duplicates flagged in the same run)")
     ap.add_argument("--methyl", action="store_true", help="also measure --bam --sort --methyl (methylation counts per cytosine from the same run)")
     ap.add_argument("--mbias", action="store_true", help="with --methyl: also measure --methyl ... --mbias (the M-bias table from the same run)")
+    ap.add_argument("--variant", action="store_true", help="with --methyl: also measure --methyl with the opposite-strand variant filter on")
     ap.add_argument("--other-driver", default="", help="with --methyl: bmbs_search of another build, whose --methyl leg alternates with this build's")
     ap.add_argument("--driver-args", default="")
     ap.add_argument("--workdir", default=os.environ.get("BMBS_BENCH_DIR", "/tmp/bmbs_bench"))
     ap.add_argument("--out", default="")
     ap.add_argument("--stats-out", default="")
     args = ap.parse_args()
-    stem = "mbias" if args.methyl and args.mbias else "sorted_bam"
+    stem = "variant" if args.methyl and args.variant else "mbias" if args.methyl and args.mbias else "sorted_bam"
     args.out = args.out or os.path.join(ROOT, "profiles", stem + "_probe.txt")
     args.stats_out = args.stats_out or os.path.join(ROOT, "profiles", stem + "_kernel_stats.csv")
     import torch
@@ -136,6 +147,9 @@ def main():
         if args.mbias:
             runs["mbias"] = []
             legs.append(("mbias", os.path.join(wd, "sortp_y.bam"), ["--sort"] + meth_args + ["--mbias"]))
+        if args.variant:
+            runs["variant"] = []
+            legs.append(("variant", os.path.join(wd, "sortp_y.bam"), ["--sort"] + meth_args + VARIANT_ARGS))
         if args.other_driver:
             runs["methyl_other"] = []
             legs.append(("methyl_other", os.path.join(wd, "sortp_y.bam"), ["--sort"] + meth_args))
@@ -156,7 +170,7 @@ def main():
         % (args.reads, "pairs" if args.pe else "SE reads", L, args.loop, n_reads, args.genome, args.batch, " ".join(base[3:])))
     med = {}
     label = {"bam": "--bam", "sort": "--bam --sort", "bai": "--bam --sort --bai", "markdup": "--bam --sort --markdup", "methyl": "--bam --sort --methyl",
-             "mbias": "... --methyl --mbias", "methyl_other": "--methyl, other build"}
+             "mbias": "... --methyl --mbias", "variant": "... --methyl, filter", "methyl_other": "--methyl, other build"}
     for kind in runs:
         w = [r["wall"] for r in runs[kind]]
         med[kind] = statistics.median(w)
@@ -195,6 +209,11 @@ def main():
         mw = [r["wall"] for r in runs["methyl"]]
         say("--mbias: mbias calls %s; median wall %.3f s against %.3f s of --methyl without it = %+.3f s; spread (max - min) of the --methyl runs %.3f s; pass 2 %s s"
             % (runs["mbias"][-1].get("mbias", "?"), med["mbias"], med["methyl"], med["mbias"] - med["methyl"], max(mw) - min(mw), " ".join("%.3f" % r["pass2"] for r in runs["mbias"])))
+    if args.methyl and args.variant:
+        mw = [r["wall"] for r in runs["methyl"]]
+        say("variant filter (%s): sites dropped as variants %s; median wall %.3f s against %.3f s of --methyl without it = %+.3f s; spread (max - min) of the --methyl runs %.3f s; pass 2 %s s"
+            % (" ".join(VARIANT_ARGS), runs["variant"][-1].get("variants", "?"), med["variant"], med["methyl"], med["variant"] - med["methyl"], max(mw) - min(mw),
+               " ".join("%.3f" % r["pass2"] for r in runs["variant"])))
     if args.methyl and args.other_driver:
         ow = [r["wall"] for r in runs["methyl_other"]]
         say("--methyl on this build against the other build (%s): median wall %.3f s against %.3f s = %+.3f s; the other build's own spread (max - min) %.3f s: %s"
@@ -205,7 +224,7 @@ def main():
     shutil.rmtree(tr, ignore_errors=True)
     if os.path.exists(out_s):
         os.unlink(out_s)
-    step(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tr, "--"] + base + ["--sort"] + (["--bai"] if args.bai else []) + (["--markdup"] if args.markdup else []) + (meth_args if args.methyl else []) + (["--mbias"] if args.methyl and args.mbias else []) + ["-o", out_s], 900)
+    step(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tr, "--"] + base + ["--sort"] + (["--bai"] if args.bai else []) + (["--markdup"] if args.markdup else []) + (meth_args if args.methyl else []) + (["--mbias"] if args.methyl and args.mbias else []) + (VARIANT_ARGS if args.methyl and args.variant else []) + ["-o", out_s], 900)
     f = glob.glob(os.path.join(tr, "**", "*kernel_stats.csv"), recursive=True)
     if f:
         rows = list(csv.DictReader(open(f[0])))
@@ -252,6 +271,47 @@ def main():
             if args.mbias:
                 mb, cnt = total_ns(lambda n: "k_meth_mbias" in n), total_ns(lambda n: "k_meth_events<false" in n)
                 say("  k_meth_mbias %.3f ms beside the counting pass k_meth_events<false, ..> %.3f ms (the same walk; the tally adds one LDS or global add per call)" % (mb / 1e6, cnt / 1e6))
+            if args.variant:
+                opp, own = total_ns(lambda n: re.search(r"k_meth_events<\w+, \w+, true>", n)), total_ns(lambda n: re.search(r"k_meth_events<\w+, \w+, false>", n))
+                if not opp or not own:
+                    say("  the trace has no rows named k_meth_events<.., .., true> or none named k_meth_events<.., .., false> (%d and %d ns): the opposite passes cannot be set beside the calling passes"
+                        % (opp, own))
+                else:
+                    say("  the opposite passes k_meth_events<.., .., true> %.3f ms beside the calling passes k_meth_events<.., .., false> (k_meth_count + k_meth_emit) %.3f ms = %.2f x (the same walk over the other half of the masks)"
+                        % (opp / 1e6, own / 1e6, opp / own))
+    # ---- --variant with --other-driver: a plain --methyl run of either build under the kernel trace -- do they launch the same kernels?
+    if args.methyl and args.variant and args.other_driver:
+        seen = {}
+        for who, drv_w in (("this build", drv), ("the other build", args.other_driver)):
+            shutil.rmtree(tr, ignore_errors=True)
+            if os.path.exists(out_s):
+                os.unlink(out_s)
+            step(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tr, "--", drv_w] + base[1:] + ["--sort"] + meth_args + ["-o", out_s], 900)
+            f = glob.glob(os.path.join(tr, "**", "*kernel_stats.csv"), recursive=True)
+            seen[who] = {r["Name"]: (int(r["Calls"]), int(r["TotalDurationNs"])) for r in csv.DictReader(open(f[0]))} if f else {}
+        a, b = seen["this build"], seen["the other build"]
+        if not a or not b:
+            say("--methyl without the filter under the kernel trace: no kernel rows for %s -- nothing to compare" % " and ".join(w for w in seen if not seen[w]))
+        else:
+            def calls(rows, plain):
+                """name -> calls; plain: k_meth_events<x, y, false> counted as k_meth_events<x, y> (a defaulted third template argument)"""
+                out = {}
+                for n, (c, _ns) in rows.items():
+                    n = re.sub(r"(k_meth_events<\w+, \w+), false>", r"\1>", n) if plain else n
+                    out[n] = out.get(n, 0) + c
+                return out
+            for plain in (False, True):
+                ca, cb = calls(a, plain), calls(b, plain)
+                differ = sorted(n for n in set(ca) | set(cb) if ca.get(n, 0) != cb.get(n, 0))
+                say("--methyl without the filter under the kernel trace, this build against the other%s: %d and %d kernel names; names and call counts %s"
+                    % (", k_meth_events<x, y, false> read as k_meth_events<x, y>" if plain else "", len(ca), len(cb), "identical" if not differ else "differ in %d rows:" % len(differ)))
+                for n in differ:
+                    say("  %s: %d calls here, %d there" % (n.split("(")[0], ca.get(n, 0), cb.get(n, 0)))
+                if not differ:
+                    break
+            for n in sorted(set(a) | set(b)):
+                if "k_meth_" in n:
+                    say("  %-40s here %d calls %.3f ms, there %d calls %.3f ms" % (n.split("(")[0], a.get(n, (0, 0))[0], a.get(n, (0, 0))[1] / 1e6, b.get(n, (0, 0))[0], b.get(n, (0, 0))[1] / 1e6))
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as o:
         o.write("\n".join(lines) + "\n")
