@@ -28,7 +28,7 @@ SYMBOLS = [
     "bmbs_bam_dup_sigs", "bmbs_text_sorted_dup", "bmbs_dup_select",
     "bmbs_text_sorted_clip", "bmbs_bam_methyl", "bmbs_bam_sort_methyl", "bmbs_methyl_sites",
     "bmbs_bam_methyl_opts", "bmbs_bam_sort_methyl_opts", "bmbs_methyl_mbias",
-    "bmbs_bam_methyl_opposite", "bmbs_bam_sort_methyl_opposite", "bmbs_methyl_opposite", "bmbs_methyl_drop_variants",
+    "bmbs_bam_methyl_opposite", "bmbs_bam_sort_methyl_opposite", "bmbs_methyl_opposite", "bmbs_methyl_drop_variants", "bmbs_methyl_report",
     "bmbs_outcome_index",
 ]
 
@@ -94,6 +94,7 @@ class MethylOpts(C.Structure):
 
 assert C.sizeof(MethylOpts) == 32
 METHYL_MBIAS = 1             # in MethylOpts.flags
+REPORT_OMIT = 8              # in a site's kind, for bmbs_methyl_report only: the position gets no line
 MBIAS_CYCLES = 1024
 MBIAS_SHAPE = (2, 2, 3, 2, MBIAS_CYCLES)      # mate, strand (0 OT, 1 OB), context, (0 unmethylated, 1 methylated), cycle
 
@@ -253,6 +254,9 @@ def lib() -> C.CDLL:
         L.bmbs_methyl_opposite.restype = C.c_int
         L.bmbs_methyl_drop_variants.argtypes = [vp, i64, vp, i64, C.c_int32, C.c_int32, C.POINTER(i64)]
         L.bmbs_methyl_drop_variants.restype = C.c_int
+    if hasattr(L, "bmbs_methyl_report"):                 # (the genome-wide cytosine report; BMBS_LIB may name an older build, as above)
+        L.bmbs_methyl_report.argtypes = [vp, i32, i64, i64, vp, i64, vp, i64, i32, vp, u64, C.POINTER(u64), C.POINTER(i64)]
+        L.bmbs_methyl_report.restype = C.c_int
     L.bmbs_map_pe_text.argtypes = [vp, vp, u64, vp, u64, i64, i32, vp, u64, C.POINTER(u64), C.POINTER(i64)]
     L.bmbs_map_pe_text.restype = C.c_int
     L.bmbs_retries.argtypes = [vp]
@@ -278,7 +282,7 @@ def lib() -> C.CDLL:
 
 
 LIB_SRCS = ("bmbs_api.hip", "bmbs_kernels.hip", "k_index.hip", "k_rows.hip", "k_qualpack.hip", "k_attach.hip", "k_scan.hip", "k_seed.hip", "k_vote.hip", "k_filter.hip", "k_reduce.hip", "k_align.hip", "k_finalize.hip", "k_pe_fast.hip", "k_pe_sensitive.hip",
-            "bmbs_textpath.hip", "bmbs_text.hip", "bmbs_bam.hip", "bmbs_inflate.hip", "k_bamsort.hip", "bmbs_bytes.h", "bmbs_records.hip", "k_bai.hip", "k_markdup.hip", "k_methyl.hip", "bmbs_host.h", "bmbs_dev.h", "bmbs_words.h", "bmbs_sort.h", "bmbs_rowpitch.h", "../../include/bmbs.h",
+            "bmbs_textpath.hip", "bmbs_text.hip", "bmbs_bam.hip", "bmbs_inflate.hip", "k_bamsort.hip", "bmbs_bytes.h", "bmbs_records.hip", "k_bai.hip", "k_markdup.hip", "k_methyl.hip", "k_cytosine.hip", "bmbs_host.h", "bmbs_dev.h", "bmbs_words.h", "bmbs_sort.h", "bmbs_rowpitch.h", "../../include/bmbs.h",
             "index_io.cpp", "index_io.h", "index_build_gpu.hip", "build_id.cpp")
 
 

@@ -248,6 +248,9 @@ struct Lane {
     DevBuf mt_clip, mt_cnt, mt_eoff, mt_ev, mt_work, mt_acc, mt_site, mt_cl2, mt_mbias;
     std::vector<std::pair<u64, u64>> mt_slice;
     int mt_cus = 0;
+    // the cytosine report (k_cytosine.hip, bmbs_methyl_report): the caller's sites and runs as uploaded, the bytes of each genome word of
+    // the window and their scan, the text.  Nothing of it outlives the call, and nothing of a methyl call's is touched
+    DevBuf cy_site, cy_run, cy_cnt, cy_off, cy_out;
     // the last methyl call: `sites` of them in mt_site (bmbs_methyl_sites; -1: none); has_mbias: it made the M-bias table
     // (bmbs_methyl_mbias) -- in mt_mbias, or (mbias_zero) a call without records: the table is all zero and not on the device.
     // An opposite call (bmbs_bam_methyl_opposite / bmbs_bam_sort_methyl_opposite) leaves `opp` entries in mt_site instead

@@ -2,7 +2,8 @@
 // on the device already (a sorted text call's, the last bmbs_bam_sort call's) or come from the host, and sort them (bmbs_bam_sort), index
 // them (k_bai.hip: bmbs_bam_sort_index), sign them for duplicate marking (k_markdup.hip: bmbs_bam_dup_sigs, bmbs_text_sorted_dup,
 // bmbs_dup_select) or call cytosines in them (k_methyl.hip: bmbs_bam_methyl[_opts], bmbs_bam_sort_methyl[_opts], bmbs_methyl_sites,
-// bmbs_methyl_mbias, bmbs_text_sorted_clip); bmbs_text_sorted_index hands out a sorted text call's keys.  The sort itself, the deflater
+// bmbs_methyl_mbias, bmbs_text_sorted_clip) or write the genome-wide cytosine report from the sites of such calls (k_cytosine.hip:
+// bmbs_methyl_report); bmbs_text_sorted_index hands out a sorted text call's keys.  The sort itself, the deflater
 // and the download are bmbs_textpath.hip's, which the text calls run too (bmbs_host.h).  What a call leaves on the device for a later one,
 // and which call ends that, is Lane::ends (bmbs_host.h).
 #include "bmbs_host.h"
@@ -18,6 +19,7 @@ DEVI u32 bs_ld32(const char* p)
 #include "k_bai.hip"
 #include "k_markdup.hip"
 #include "k_methyl.hip"
+#include "k_cytosine.hip"
 
 // ---- what the stages share -------------------------------------------------------------------------------------------------------------------
 // Entries the host describes: n_in of them, entry i = len[i] bytes of `records`, `bytes` in all.  An entry is a BAM record (36 bytes and
@@ -723,6 +725,82 @@ static int lane_text_sorted_clip(Lane* c, uint32_t* clip, int64_t cap, int64_t* 
     return BMBS_OK;
 }
 
+// ---- the genome-wide cytosine report (k_cytosine.hip): the rule is in include/bmbs.h ------------------------------------------------------------
+// The sites and runs go up, k_cyt_check looks at the sites, k_cyt_count at every genome word of the window, the scan says where each
+// word's text goes (64-bit offsets: a window's text may pass 4 GB), and one wait brings back the refusals, the bytes and the lines.
+// k_cyt_emit runs only when the caller's buffer holds the text.  Nothing of a methyl call's is read or written (Lane::mc, mt_*)
+static int lane_methyl_report(Lane* c, int32_t ref, int64_t beg, int64_t end, const bmbs_methyl_site* site, int64_t n_site, const int64_t* run, int64_t n_run,
+                              int32_t contexts, char* out, uint64_t cap, uint64_t* out_bytes, int64_t* n_line)
+{
+    if (out_bytes) *out_bytes = 0;
+    if (n_line) *n_line = 0;
+    if (!c->attached) { c->err = "methyl report: no index attached"; return BMBS_ESTATE; }
+    if (c->n_refs != c->ix.n_chrom) { c->err = "methyl report: bmbs_sam_refs has not been given the index's reference names"; return BMBS_ESTATE; }
+    if (!out_bytes || !n_line || n_site < 0 || n_run < 0 || (n_site && !site) || (n_run && !run)) { c->err = "methyl report: bad argument"; return BMBS_EINVAL; }
+    if (ref < 0 || ref >= c->ix.n_chrom) { c->err = "methyl report: ref " + std::to_string(ref) + " is outside the " + std::to_string(c->ix.n_chrom) + " sequences of the index"; return BMBS_EINVAL; }
+    HIPCHK(c, hipSetDevice(c->dev));
+    u64 cs[2] = {0, 0}; u32 co[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(cs, c->ix.chrom_start + ref, sizeof cs, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(co, c->chrom_off.as<u32>() + ref, sizeof co, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int64_t length = (int64_t)(cs[1] - cs[0]);
+    if (beg < 0 || beg > end || end > length) {
+        c->err = "methyl report: the window [" + std::to_string(beg) + ", " + std::to_string(end) + ") does not lie in the " + std::to_string(length) + " bases of sequence " + std::to_string(ref);
+        return BMBS_EINVAL;
+    }
+    if (contexts < 1 || contexts > 7) { c->err = "methyl report: contexts " + std::to_string(contexts) + " is outside 1..7 (1 CpG | 2 CHG | 4 CHH)"; return BMBS_EINVAL; }
+    for (int64_t r = 0; r < n_run; r++)
+        if (run[2 * r] >= run[2 * r + 1] || run[2 * r] < (r ? run[2 * r - 1] : 0)) { c->err = "methyl report: run " + std::to_string(r) + " is empty, out of order or overlaps its predecessor"; return BMBS_EINVAL; }
+    if (n_site >= (1ll << 31)) { c->err = "methyl report: 2^31 sites and more"; return BMBS_EINVAL; }
+    CytPar P;
+    P.gen2p = c->ix.gen2p; P.s_lo = (long)cs[0]; P.s_hi = (long)cs[1]; P.a0 = P.s_lo + beg; P.a1 = P.s_lo + end;
+    P.W0 = P.a0 >> 5; P.nW = end > beg ? ((P.a1 - 1) >> 5) - P.W0 + 1 : 0;
+    P.n_site = n_site; P.n_run = n_run; P.name = c->chrom_chars.as<char>() + co[0]; P.name_len = co[1] - co[0]; P.contexts = (u32)contexts;
+    const u64 nW = (u64)P.nW;
+    ENS(c, c->cy_site, (u64)n_site * sizeof(bmbs_methyl_site) + 64); ENS(c, c->cy_run, (u64)n_run * 16 + 64);
+    ENS(c, c->cy_cnt, nW * 4 + 64); ENS(c, c->cy_off, (nW + 1) * 8 + 64);
+    P.site = c->cy_site.as<bmbs_methyl_site>(); P.run = c->cy_run.as<long>();
+    if (n_site || n_run) {
+        std::lock_guard<std::mutex> up(g_h2d_mu[c->dev & 15]);
+        hipStream_t us = up_stream_of(c);
+        if (n_site) HIPCHK(c, hipMemcpyAsync(c->cy_site.p, site, (size_t)n_site * sizeof(bmbs_methyl_site), hipMemcpyHostToDevice, us));
+        if (n_run) HIPCHK(c, hipMemcpyAsync(c->cy_run.p, run, (size_t)n_run * 16, hipMemcpyHostToDevice, us));
+        HIPCHK(c, hipStreamSynchronize(us));
+    }
+    u32* const info = stage_info(c);
+    HostInfo* const hi = c->h_info;
+    HIPCHK(c, hipMemsetAsync(info, 0, TXI_HALF_WORDS * sizeof(u32), c->stream));
+    HIPCHK(c, hipMemsetAsync(tot_at(c, TOT_CYT_BYTES), 0, sizeof hi->cyt, c->stream));
+    if (n_site) hipLaunchKernelGGL(k_cyt_check, dim3(nblk((u64)n_site, 256)), dim3(256), 0, c->stream, P, (int)ref, info);
+    if (nW) {
+        hipLaunchKernelGGL(k_cyt_count, dim3(nblk(nW, 256)), dim3(256), 0, c->stream, P, c->cy_cnt.as<u32>(), reinterpret_cast<unsigned long long*>(tot_at(c, TOT_CYT_LINES)));
+        if (int rc = scan_u32(c, c->cy_cnt.as<u32>(), nW, c->cy_off.as<u64>(), TOT_CYT_BYTES)) return rc;
+    }
+    HIPCHK(c, hipMemcpyAsync(hi->stage, info, TXI_CYT_WORDS * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hi->cyt, tot_at(c, TOT_CYT_BYTES), sizeof hi->cyt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    // the first offender among the sites, and of its faults the first in the order of the list
+    static const char* const fault[TXI_CYT_WORDS] = {
+        "has another ref than the call", "lies outside the window [beg, end)", "does not sit at a larger pos than its predecessor",
+        "has a kind that is not what the genome says at its position", "is of a context that is not selected", "has a window that touches a run"};
+    int64_t bad = -1; int why = 0;
+    for (int x = 0; x < TXI_CYT_WORDS; x++) if (hi->stage[x] && (bad < 0 || (int64_t)~hi->stage[x] < bad)) { bad = (int64_t)~hi->stage[x]; why = x; }
+    if (bad >= 0) { c->err = "methyl report: site " + std::to_string(bad) + " " + fault[why]; return BMBS_EINVAL; }
+    const u64 total = hi->cyt[0];
+    *out_bytes = total; *n_line = (int64_t)hi->cyt[1];
+    if (total > cap) { c->err = "methyl report: the output buffer is too small (out_bytes tells what is needed)"; return BMBS_ENOMEM; }
+    if (!total) return BMBS_OK;
+    if (!out) { c->err = "methyl report: NULL buffer"; return BMBS_EINVAL; }
+    ENS(c, c->cy_out, total + 64);
+    hipLaunchKernelGGL(k_cyt_emit, dim3(nblk(nW, CYT_WPB)), dim3(256), 0, c->stream, P, c->cy_off.as<u64>(), c->cy_out.as<char>());
+    HIPCHK(c, hipGetLastError());
+    return download_locked(c, out, c->cy_out.as<char>(), total, c->stream, nullptr);
+}
+
+extern "C" int bmbs_methyl_report(bmbs_ctx* X, int32_t ref, int64_t beg, int64_t end, const bmbs_methyl_site* site, int64_t n_site, const int64_t* run, int64_t n_run,
+                                  int32_t contexts, char* out, uint64_t cap, uint64_t* out_bytes, int64_t* n_line)
+{ ON_LANE0(lane_methyl_report(c, ref, beg, end, site, n_site, run, n_run, contexts, out, cap, out_bytes, n_line)); }
 extern "C" int bmbs_text_sorted_index(bmbs_ctx* X, uint64_t* key, uint32_t* len, int64_t cap, int64_t* n) { ON_LANE0(lane_text_sorted_index(c, key, len, cap, n)); }
 extern "C" int bmbs_bam_sort(bmbs_ctx* X, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, int32_t flags, char* out, uint64_t out_cap, uint64_t* out_bytes)
 { ON_LANE0(lane_bam_sort(c, records, bytes, len, n, flags, out, out_cap, out_bytes)); }

@@ -25,6 +25,10 @@
 //          OTHER bisulfite strand's reads cover it and more than the fraction f of them is not the genome's letter: a C->T polymorphism
 //          of the sample, not an unmethylated cytosine; MethylDackel's --minOppositeDepth / --maxVariantFrac, a second walk on the device)
 //          [--methyl-merge-context] (one line per CpG / CHG, both strands added) [--methyl-min-depth n] (lines with fewer calls are left out)
+//          --methyl ... --cytosine-report [--methyl-report-window bases] (<prefix>.cytosine_report.txt: one line for EVERY cytosine of the
+//          selected contexts in the genome, both strands, covered or not -- Bismark's CX_report; the lines are made on the device window
+//          by window, see "--cytosine-report" below.  --methyl-merge-context and --methyl-min-depth shape the bedGraphs only: the report
+//          stays per strand and includes depth 0)
 //
 // The reference has ONE reader thread and ONE fprintf sink (Process_Reads.cpp:2057-2260, Process_sam_out.cpp:954-1006), which is
 // what limits it.  Round 2 of this driver indexed the lines and formatted the SAM text with the host's
@@ -82,6 +86,8 @@ struct Options {
     int32_t max_variant_ppm = 0;                 // --methyl-min-depth, --methyl-merge-context
     long min_depth = 1;
     bool variant_frac_given = false, site_opts_given = false, merge_context = false;
+    bool cytosine_report = false;                // --cytosine-report: <prefix>.cytosine_report.txt, every cytosine of the selected contexts
+    long report_window = 0;                      // --methyl-report-window: bases per bmbs_methyl_report call (0: what fits the buffers, write_report)
     double sort_mem_gib = 0;                     // --sort-mem: cap of the in-memory record store of --sort (0: half of the machine's memory)
     // derived once
     bool pe = false, gz_in = false, methyl_out = false;
@@ -202,6 +208,8 @@ struct Pass2 {
     std::vector<bmbs_methyl_site> meth_sites;    // --methyl: the sites of the calls so far, merged; main alone
     std::vector<bmbs_methyl_site> meth_opp;      // the variant filter: the opposite-strand entries of the calls so far, merged the same way; main alone
     size_t meth_variants = 0, meth_shallow = 0;  // sites dropped as variants, lines left out below --methyl-min-depth
+    uint64_t report_lines = 0, report_bytes = 0; // --cytosine-report: what the file holds; the seconds it took, of which inside the device
+    double t_report = 0, t_report_calls = 0, t_report_wait = 0;      // calls, and waiting for the writer to hand a buffer back
     std::vector<uint64_t> mbias;                 // --mbias: the tables of the calls so far, added up; main alone
     uint64_t mbias_calls = 0;                    // ... and its total
     size_t sort_calls = 0, select_calls = 0, n_dup = 0, bai_bytes = 0;
@@ -212,6 +220,9 @@ const char* const ctx_names[3] = {"CpG", "CHG", "CHH"};
 
 // ================ the command line ===============================================================================================
 [[noreturn]] void refuse(const char* msg) { fputs(msg, stderr); exit(2); }
+
+const char* const USAGE =
+    "usage: bmbs_search --index <genome.fa> [--index_folder dir] [-t threads]\n       bmbs_search --search <index> (--seq r.fq | --seq1 a.fq --seq2 b.fq) [-o out.sam] [-e f] [--min n] [--max n] [--sensitive] [--pbat] [--unmapped_out] [--ambiguous_out] [--bam [--sort [--sort-mem GiB] [--markdup] [--bai] [--methyl prefix [--CpG] [--CHG] [--CHH] [--methyl-min-mapq n] [--methyl-min-phred n] [--methyl-ignore n] [--methyl-ignore-3prime n] [--methyl-ignore-r2 n] [--methyl-ignore-3prime-r2 n] [--mbias] [--methyl-min-opposite-depth n [--methyl-max-variant-frac f]] [--methyl-merge-context] [--methyl-min-depth n] [--cytosine-report [--methyl-report-window bases]]]]] [--mapstats f] [-t io_threads] [--out-parts n]\n       --cytosine-report: <prefix>.cytosine_report.txt, one line per cytosine of the selected contexts on both strands, covered or not; --methyl-merge-context and --methyl-min-depth shape the bedGraphs only, the report stays per strand and includes depth 0\n";
 
 Options parse_options(int argc, char** argv)
 {
@@ -298,6 +309,15 @@ Options parse_options(int argc, char** argv)
             o.variant_frac_given = o.site_opts_given = true;
         }
         else if (a == "--methyl-merge-context") o.merge_context = o.site_opts_given = true;      // MethylDackel's --mergeContext
+        else if (a == "--help" || a == "-h") { fputs(USAGE, stdout); exit(0); }
+        else if (a == "--cytosine-report") o.cytosine_report = true;  // --methyl ... --cytosine-report: Bismark's CX_report, from the device
+        else if (a == "--methyl-report-window") {
+            char* end = nullptr;
+            const char* v = val();
+            const long x = strtol(v, &end, 10);
+            if (end == v || *end || x < 1 || x > 2147483647l) refuse("bmbs_search: --methyl-report-window takes 1..2147483647 (bases)\n");
+            o.report_window = x;
+        }
         else { fprintf(stderr, "bmbs_search: unsupported option %s\n", a.c_str()); exit(2); }
     }
     if (o.sort && !o.bam) refuse("bmbs_search: --sort needs --bam\n");
@@ -311,6 +331,8 @@ Options parse_options(int argc, char** argv)
     if (!o.methyl_out && o.ignore_given) refuse("bmbs_search: --methyl-ignore, --methyl-ignore-3prime, --methyl-ignore-r2 and --methyl-ignore-3prime-r2 need --methyl\n");
     if (!o.methyl_out && o.mbias) refuse("bmbs_search: --mbias needs --methyl\n");
     if (!o.methyl_out && o.site_opts_given) refuse("bmbs_search: --methyl-min-opposite-depth, --methyl-max-variant-frac, --methyl-min-depth and --methyl-merge-context need --methyl\n");
+    if (!o.methyl_out && (o.cytosine_report || o.report_window)) refuse("bmbs_search: --cytosine-report and --methyl-report-window need --methyl\n");
+    if (o.report_window && !o.cytosine_report) refuse("bmbs_search: --methyl-report-window needs --cytosine-report\n");
     if (o.variant_frac_given && o.min_opp_depth < 1) refuse("bmbs_search: --methyl-max-variant-frac needs --methyl-min-opposite-depth above 0\n");
     if (!mpar.contexts) mpar.contexts = 1;
     if (o.merge_context && !(mpar.contexts & 3)) refuse("bmbs_search: --methyl-merge-context needs --CpG or --CHG (CHH is never merged)\n");
@@ -324,7 +346,7 @@ Options parse_options(int argc, char** argv)
     }
     if (!o.build_fasta.empty()) return o;            // --index: nothing below applies
     if (o.index.empty() || (o.seq.empty() && (o.seq1.empty() || o.seq2.empty())))
-        refuse("usage: bmbs_search --index <genome.fa> [--index_folder dir] [-t threads]\n       bmbs_search --search <index> (--seq r.fq | --seq1 a.fq --seq2 b.fq) [-o out.sam] [-e f] [--min n] [--max n] [--sensitive] [--pbat] [--unmapped_out] [--ambiguous_out] [--bam [--sort [--sort-mem GiB] [--markdup] [--bai] [--methyl prefix [--CpG] [--CHG] [--CHH] [--methyl-min-mapq n] [--methyl-min-phred n] [--methyl-ignore n] [--methyl-ignore-3prime n] [--methyl-ignore-r2 n] [--methyl-ignore-3prime-r2 n] [--mbias] [--methyl-min-opposite-depth n [--methyl-max-variant-frac f]] [--methyl-merge-context] [--methyl-min-depth n]]]] [--mapstats f] [-t io_threads] [--out-parts n]\n");
+        refuse(USAGE);
     if (o.batch < 1) o.batch = 1;
     if (o.io_threads <= 0) {
         // plain text needs few threads to read at memory speed; compressed input is inflated by them (csrc/pgz.h): more pay off
@@ -538,7 +560,8 @@ std::string sam_header_text(bool sorted, const std::vector<std::string>& chrom_n
         if (a == "--methyl" || a == "--methyl-min-mapq" || a == "--methyl-min-phred") { i++; continue; }
         if (a == "--methyl-ignore" || a == "--methyl-ignore-r2" || a == "--methyl-ignore-3prime" || a == "--methyl-ignore-3prime-r2") { i++; continue; }
         if (a == "--methyl-min-opposite-depth" || a == "--methyl-max-variant-frac" || a == "--methyl-min-depth") { i++; continue; }
-        if (a == "--CpG" || a == "--CHG" || a == "--CHH" || a == "--mbias" || a == "--methyl-merge-context") continue;
+        if (a == "--methyl-report-window") { i++; continue; }
+        if (a == "--CpG" || a == "--CHG" || a == "--CHH" || a == "--mbias" || a == "--methyl-merge-context" || a == "--cytosine-report") continue;
         h += a; h += ' ';
     }
     h += '\n';
@@ -1121,6 +1144,78 @@ void write_bai(Run& R, Pass2& S)
     if (fd < 0 || !pwrite_all(fd, ix.data(), ix.size(), 0) || ::close(fd) != 0) { fprintf(stderr, "bmbs_search: cannot write %s.bai: %s\n", o.out.c_str(), strerror(errno)); R.failed = true; }
 }
 
+// --cytosine-report: <prefix>.cytosine_report.txt, every cytosine of the selected contexts of every sequence, in index order, no header
+// line.  The genome is walked in windows of `window` bases, one bmbs_methyl_report call each, with the window's sites and the runs that
+// reach into it; a window never spans two sequences.  The default window is what a 256 MiB page-locked buffer holds whatever the genome
+// says: a line has at most name + 44 bytes (six tabs, strand, three letters, newline: 11; three numbers of at most ten digits; CHG).
+// Two buffers: a writer thread puts one window into the file while the device makes the next.  `sites` are those the bedGraphs start
+// from (behind the non-ACGT filter), the ones the variant filter dropped marked BMBS_REPORT_OMIT; --methyl-merge-context and
+// --methyl-min-depth do not touch the report
+void write_report(Run& R, Pass2& S, const std::vector<bmbs_methyl_site>& sites, const std::vector<std::vector<std::pair<int64_t, int64_t>>>& runs)
+{
+    const Options& o = R.o;
+    const double t_begin = now();
+    const std::string path = o.methyl + ".cytosine_report.txt";
+    const int fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (fd < 0) { fprintf(stderr, "bmbs_search: cannot write %s: %s\n", path.c_str(), strerror(errno)); R.failed = true; return; }
+    size_t name_max = 0;
+    for (const std::string& n : R.chrom_names) name_max = std::max(name_max, n.size());
+    const uint64_t buf_bytes = 256ull << 20;
+    const int64_t window = o.report_window ? (int64_t)o.report_window : std::max<int64_t>(32, (int64_t)(buf_bytes / (name_max + 44)) & ~31ll);
+    bmbs_ctx* const ctx = R.ctxs[0];
+    Pinned buf[2];
+    struct Job { int b; uint64_t bytes, off; };      // (b < 0: the last)
+    Chan<Job> full; Chan<int> empty;
+    empty.put(0); empty.put(1);
+    std::atomic<bool> write_failed{false};
+    std::thread writer([&] {
+        for (Job j = full.get(); j.b >= 0; j = full.get()) {
+            if (!write_failed && !pwrite_all(fd, buf[j.b].p, (size_t)j.bytes, (size_t)j.off)) write_failed = true;
+            empty.put(j.b);
+        }
+    });
+    uint64_t off = 0;
+    size_t s0 = 0;
+    for (int32_t ref = 0; ref < R.view.n_chrom && !R.failed && !write_failed; ref++) {
+        const int64_t len = (int64_t)R.view.chrom_len[ref];
+        static const std::vector<std::pair<int64_t, int64_t>> none;
+        const auto& rr = (size_t)ref < runs.size() ? runs[(size_t)ref] : none;
+        size_t r0 = 0;
+        for (int64_t beg = 0; beg < len && !R.failed && !write_failed; beg += window) {
+            const int64_t end = std::min(len, beg + window);
+            size_t s1 = s0;
+            while (s1 < sites.size() && sites[s1].ref == ref && sites[s1].pos < end) s1++;
+            // the runs that reach into [beg - 2, end + 2): what a context window of this window's cytosines can touch
+            while (r0 < rr.size() && rr[r0].second <= beg - 2) r0++;
+            size_t r1 = r0;
+            while (r1 < rr.size() && rr[r1].first < end + 2) r1++;
+            const double t_w = now();
+            const int b = empty.get();
+            const double t_c = now();
+            S.t_report_wait += t_c - t_w;
+            uint64_t bytes = 0; int64_t lines = 0;
+            int rc = BMBS_ENOMEM;
+            for (int attempt = 0; attempt < 2 && rc == BMBS_ENOMEM; attempt++) {
+                if (!buf[b].need(attempt ? (size_t)bytes : (size_t)std::min<uint64_t>(buf_bytes, (uint64_t)(end - beg) * (name_max + 44)))) { rc = BMBS_ENOMEM; break; }
+                rc = bmbs_methyl_report(ctx, ref, beg, end, sites.data() + s0, (int64_t)(s1 - s0), r1 > r0 ? &rr[r0].first : nullptr, (int64_t)(r1 - r0), o.mpar.contexts,
+                                        buf[b].p, buf[b].cap, &bytes, &lines);
+            }
+            S.t_report_calls += now() - t_c;
+            if (rc) { fprintf(stderr, "bmbs_search: --cytosine-report: %s\n", rc == BMBS_ENOMEM ? "no page-locked memory for a window's text" : bmbs_last_error(ctx)); R.failed = true; empty.put(b); break; }
+            full.put(Job{b, bytes, off});
+            off += bytes; S.report_lines += (uint64_t)lines;
+            s0 = s1;
+        }
+        while (s0 < sites.size() && sites[s0].ref == ref) s0++;              // (none: every site lies in its sequence)
+    }
+    full.put(Job{-1, 0, 0});
+    writer.join();
+    if (write_failed || ::close(fd) != 0) { fprintf(stderr, "bmbs_search: cannot write %s: %s\n", path.c_str(), strerror(errno)); R.failed = true; }
+    buf[0].release(); buf[1].release();
+    S.report_bytes = off;
+    S.t_report = now() - t_begin;
+}
+
 // --methyl: the files, written once the BAM is complete.  In this order: sites that touch a base the FASTA does not spell A, C, G or T
 // are left out; the variant filter drops the sites the opposite strand shows to be polymorphisms (bmbs_methyl_drop_variants);
 // --methyl-merge-context adds the two strands of a CpG / CHG; --methyl-min-depth leaves out the lines below it
@@ -1130,13 +1225,18 @@ void write_methyl(Run& R, Pass2& S)
     const std::string& index = R.index;
     std::vector<bmbs_methyl_site>& sites = S.meth_sites;
     std::vector<std::vector<std::pair<int64_t, int64_t>>> runs;
-    if (!non_acgt_runs(index, R.view, runs)) fprintf(stderr, "bmbs_search: --methyl: cannot read the sequences of the index from %s: sites at bases other than A, C, G and T are not filtered out\n", index.c_str());
-    else {
+    if (!non_acgt_runs(index, R.view, runs)) {
+        fprintf(stderr, "bmbs_search: --methyl: cannot read the sequences of the index from %s: sites at bases other than A, C, G and T are not filtered out\n", index.c_str());
+        runs.clear();                                                        // (--cytosine-report: no runs either, so that it agrees with the sites)
+    } else {
         size_t kept = 0;
         for (const bmbs_methyl_site& s : sites) if (runs[(size_t)s.ref].empty() || !methyl_touches(runs[(size_t)s.ref], s)) sites[kept++] = s;
         S.meth_dropped = sites.size() - kept;
         sites.resize(kept);
     }
+    // --cytosine-report: the sites as they are now; those the variant filter drops stay in this list, marked
+    std::vector<bmbs_methyl_site> rsites;
+    if (o.cytosine_report && o.min_opp_depth > 0) rsites = sites;
     if (o.min_opp_depth > 0) {
         int64_t kept = 0;
         if (bmbs_methyl_drop_variants(sites.data(), (int64_t)sites.size(), S.meth_opp.data(), (int64_t)S.meth_opp.size(), (int32_t)o.min_opp_depth, o.max_variant_ppm, &kept)) {
@@ -1150,6 +1250,12 @@ void write_methyl(Run& R, Pass2& S)
         if (!((o.mpar.contexts >> x) & 1)) continue;
         const std::string path = o.methyl + "_" + ctx_names[x] + ".bedGraph";
         if (!methyl_write(path, o.methyl, ctx_names[x], x, sites, R.ixf, o.merge_context, (uint64_t)o.min_depth, &S.meth_shallow)) { fprintf(stderr, "bmbs_search: cannot write %s: %s\n", path.c_str(), strerror(errno)); R.failed = true; }
+    }
+    if (o.cytosine_report && !R.failed) {
+        // (a merge walk of the lists before and behind the filter: what is missing behind it was dropped)
+        size_t k = 0;
+        for (bmbs_methyl_site& s : rsites) { if (k < sites.size() && sites[k].ref == s.ref && sites[k].pos == s.pos) k++; else s.kind |= BMBS_REPORT_OMIT; }
+        write_report(R, S, o.min_opp_depth > 0 ? rsites : sites, runs);
     }
     // --mbias: the table as the device made it (calls at bases the FASTA does not spell A, C, G or T are in it: only sites are filtered)
     if (o.mbias && !R.failed) {
@@ -1166,6 +1272,7 @@ int give_up(Run& R)
     const Options& o = R.o;
     if (o.methyl_out) for (unsigned x = 0; x < 3; x++) if ((o.mpar.contexts >> x) & 1) ::unlink((o.methyl + "_" + ctx_names[x] + ".bedGraph").c_str());
     if (o.mbias) ::unlink((o.methyl + "_mbias.tsv").c_str());
+    if (o.cytosine_report) ::unlink((o.methyl + ".cytosine_report.txt").c_str());
     if (o.sort && R.parts[0]->regular) ::unlink(o.out.c_str());      // a sorted file is whole or absent (a device or a pipe is left alone)
     if (o.bai && R.parts[0]->regular) ::unlink((o.out + ".bai").c_str());      // ... and so is its index
     fprintf(stderr, "bmbs_search: failed\n");
@@ -1195,7 +1302,7 @@ void report(const Run& R, const Pass2& S)
             R.n_owner, o.contexts, o.parts);
     if (o.sort) {
         const SortStore& store = R.sort_store;
-        char ixs[800] = "";
+        char ixs[1000] = "";
         if (o.bai) snprintf(ixs, sizeof ixs, ", index: chunks %zu, windows %zu, %zu bytes", S.bai.n_chunks(), S.bai.n_windows(), S.bai_bytes);
         if (o.markdup)
             snprintf(ixs + strlen(ixs), sizeof ixs - strlen(ixs), ", markdup: templates %ld, with signature %ld, duplicates %zu (select calls %zu, %.3fs of pass 2)", store.templates,
@@ -1206,6 +1313,7 @@ void report(const Run& R, const Pass2& S)
         if (o.methyl_out)
             snprintf(ixs + strlen(ixs), sizeof ixs - strlen(ixs), ", sites dropped as variants %zu, lines left out below the minimum depth %zu", S.meth_variants, S.meth_shallow);
         if (o.mbias) snprintf(ixs + strlen(ixs), sizeof ixs - strlen(ixs), ", mbias calls %llu", (unsigned long long)S.mbias_calls);
+        if (o.cytosine_report) snprintf(ixs + strlen(ixs), sizeof ixs - strlen(ixs), ", report lines %llu bytes %llu in %.3fs (device calls %.3fs, waiting for the file %.3fs)", (unsigned long long)S.report_lines, (unsigned long long)S.report_bytes, S.t_report, S.t_report_calls, S.t_report_wait);
         fprintf(stderr, "[bmbs_search] sort: bins %zu (one of them for records without a reference), pass-2 calls %zu, store bytes %zu (%ld records), pass 1 %.3fs (mapping, binning), pass 2 %.3fs (sort, deflate, write)%s\n",
                 store.bin.size(), S.sort_calls, store.bytes, store.records, R.t_pass1 - R.t_loaded, R.t_pass2 - R.t_pass1, ixs);
     }

@@ -71,7 +71,9 @@ enum Tot : int {
     // offsets, nobody reads either total.
     TOT_METH_M = 31,
     TOT_METH_U = 31,
-    TOT_WORDS = 32
+    TOT_CYT_BYTES = 32,      // bmbs_methyl_report: the text of the   the scan behind k_cyt_count    lane_methyl_report (the two words, one copy)
+    TOT_CYT_LINES = 33,      // window, and its lines                 memset, then k_cyt_count's adds (a counter, not a scan)
+    TOT_WORDS = 34
 };
 // the word of file f (0, 1) of a pair of words: TOT_LINES_1, TOT_NL_ADDED_1
 constexpr Tot tot_file(Tot first, int f) { return (Tot)(first + f); }
@@ -79,7 +81,8 @@ static_assert(TOT_LINES_2 == TOT_LINES_1 + 1 && TOT_NL_ADDED_2 == TOT_NL_ADDED_1
 static_assert(TOT_RCAND == TOT_RESEED + 1, "verify_sensitive copies the two as one");
 static_assert(TOT_CHAIN_EXT == TOT_CHAIN_LOOKUPS + 1, "k_call_chain_counts writes the two from one base");
 static_assert(TOT_BAI_WINS == TOT_BAI_HEADS + 1 && TOT_BAI_REFS == TOT_BAI_HEADS + 2, "bai_compute copies the three as one");
-static_assert(TOT_CHAIN_EXT < TOT_CALL_WORDS && TOT_CALL_WORDS <= TOT_LINES_1 && TOT_METH_U < TOT_WORDS, "the groups fit the array");
+static_assert(TOT_CYT_LINES == TOT_CYT_BYTES + 1, "lane_methyl_report copies the two as one");
+static_assert(TOT_CHAIN_EXT < TOT_CALL_WORDS && TOT_CALL_WORDS <= TOT_LINES_1 && TOT_CYT_LINES < TOT_WORDS, "the groups fit the array");
 
 // ---- the guard flags of a mapping call (Lane::flags, u32; k_reduce.hip: the guards raise them, k_stats_commit and lane_settle read them) --
 #define BMBS_FLAG_CAND   0   // candidate slots > capacity
@@ -103,7 +106,7 @@ static_assert(sizeof(CallWords) == BMBS_SLOT_WORDS * 8 && offsetof(CallWords, fl
 //   the stage half  one kernel family at a time, zeroed by the stage that is about to use it: k_bam_keys (bam_sort_device),
 //                   k_bai_records, k_dup_sig, k_dup_bits + k_dup_heads (words 0..5 as three u64, word TXI_DUP_COUNT),
 //                   k_meth_events (the emitting pass is handed words TXI_METH_EMIT.. and writes none), k_meth_cut (words 0..1 as
-//                   one u64), k_meth_clip.  Every stage waits for its words before it returns or launches the next family.
+//                   one u64), k_meth_clip, k_cyt_check (TXI_CYT_WORDS words).  Every stage waits for its words before it returns or launches the next family.
 #define TXI_HALF_WORDS 8
 #define TXI_LINE       0
 #define TXI_STAGE      TXI_HALF_WORDS
@@ -111,7 +114,8 @@ static_assert(sizeof(CallWords) == BMBS_SLOT_WORDS * 8 && offsetof(CallWords, fl
 #define TXI_FQ_WORDS   4
 #define TXI_DUP_COUNT  6     // k_dup_heads: the duplicates it marked
 #define TXI_METH_EMIT  4
-static_assert(2 * TXI_FQ_WORDS <= TXI_HALF_WORDS && TXI_DUP_COUNT >= 3 * 2 && TXI_DUP_COUNT < TXI_HALF_WORDS && TXI_METH_EMIT + 4 <= TXI_HALF_WORDS, "the halves hold their kernels' words");
+#define TXI_CYT_WORDS  6     // k_cyt_check: one word per kind of refusal
+static_assert(2 * TXI_FQ_WORDS <= TXI_HALF_WORDS && TXI_DUP_COUNT >= 3 * 2 && TXI_DUP_COUNT < TXI_HALF_WORDS && TXI_METH_EMIT + 4 <= TXI_HALF_WORDS && TXI_CYT_WORDS <= TXI_HALF_WORDS, "the halves hold their kernels' words");
 
 // ---- Lane::h_info: the page-locked block the text calls and the record stages read their words from.  No kernel sees it; one field
 // per use.  The uses that share bytes: `line` (one text call's k_fq_records, then its k_bam_len), `stage` (every stage's u32 words),
@@ -132,5 +136,6 @@ struct HostInfo {
     uint64_t bai_nwin;                  // TOT_BAI_NWIN
     uint64_t meth_events;               // TOT_METH_EVENTS
     uint64_t meth_heads;                // TOT_METH_HEADS
+    uint64_t cyt[2];                    // TOT_CYT_BYTES, _LINES
 };
 #endif

@@ -528,6 +528,23 @@ class Mapper:
         self._chk(self._lib.bmbs_bam_sort_methyl_opposite(self._ctx, capi.ptr(cl) if cl is not None and cl.size else None, C.byref(opts), C.byref(n)))
         return self.methyl_opposite()
 
+    def methyl_report(self, ref: int, beg: int, end: int, sites, runs=None, contexts: int = 1) -> bytes:
+        """the cytosine-report lines of forward positions [beg, end) of sequence ref (bmbs_methyl_report): one line per cytosine of a
+        selected context, covered or not.  sites: capi.METHYL_SITE_DTYPE, those of that window in position order (kind | capi.REPORT_OMIT:
+        no line there); runs: the [beg, end) runs of that sequence that the FASTA does not spell A, C, G or T.  The size query, then the call"""
+        self._set_refs()
+        st = np.ascontiguousarray(sites, dtype=capi.METHYL_SITE_DTYPE)
+        rn = np.ascontiguousarray(runs if runs is not None else [], dtype=np.int64).reshape(-1, 2)
+        args = (self._ctx, int(ref), int(beg), int(end), capi.ptr(st) if st.size else None, st.size, capi.ptr(rn) if rn.size else None, rn.shape[0], int(contexts))
+        used = C.c_uint64(0); lines = C.c_int64(0)
+        rc = self._lib.bmbs_methyl_report(*args, None, 0, C.byref(used), C.byref(lines))
+        if rc and rc != -12:
+            self._chk(rc)
+        out = np.empty(max(1, used.value), dtype=np.uint8)
+        self._chk(self._lib.bmbs_methyl_report(*args, capi.ptr(out), used.value, C.byref(used), C.byref(lines)))
+        self.report_lines = lines.value
+        return out[:used.value].tobytes()
+
     def sync(self):
         self._chk(self._lib.bmbs_sync(self._ctx))
 

@@ -537,6 +537,38 @@ int bmbs_methyl_opposite(bmbs_ctx*, bmbs_methyl_site* entry, int64_t cap, int64_
 int bmbs_methyl_drop_variants(bmbs_methyl_site* site, int64_t n_site, const bmbs_methyl_site* opp, int64_t n_opp,
                               int32_t min_opposite_depth, int32_t max_variant_ppm, int64_t* n_kept);
 
+/* ---- the genome-wide cytosine report (csrc/k_cytosine.hip; `--methyl <prefix> --cytosine-report`; tests/cytosine_spec.py) -----------------
+ * One line of text for every cytosine of a selected context, on both strands, whether a read covered it or not (Bismark's CX_report,
+ * MethylDackel's --cytosine_report): what tells "not covered" from "no cytosine there".  bmbs_methyl_report writes the lines of the
+ * forward positions p in [beg, end) of sequence `ref`, ascending.  A position gets a line iff the rule above gives it a context and a
+ * strand (a forward C: strand +, a forward G: strand -), the context is in `contexts`, and its WINDOW -- the cytosine and the one
+ * (CpG) or two (CHG, CHH) positions behind it on its strand: [p, p + w] for +, [p - w, p] for - -- touches none of the runs.  run[2 r],
+ * run[2 r + 1] = [beg, end) of the r-th run of bases of this sequence that the FASTA does not spell A, C, G or T (the index holds a
+ * pseudo-random letter there): the rule bmbs_search filters the sites of its bedGraphs with, so both agree on which cytosines exist.
+ * The line is
+ *     name \t p + 1 \t strand \t meth \t unmeth \t context \t tri \n
+ * name = the sequence's (bmbs_sam_refs), meth / unmeth = the counts of the site with pos = p, 0 and 0 when there is none, context = CG,
+ * CHG or CHH, tri = three letters read on the cytosine's own strand from the cytosine on: the letters of p, p + 1, p + 2 for +, the
+ * complements of those of p, p - 1, p - 2 for -; a position off the sequence's ends or inside a run is written N (this can only be the
+ * third letter, and only of a CpG: one on the last two bases of a sequence, or directly in front of a run).  The decimal numbers have no
+ * sign and no padding; nothing is rounded; there is no percent column and no header line.
+ * A site whose kind has BMBS_REPORT_OMIT set takes the line of its position away: bmbs_search marks the sites its variant filter
+ * dropped this way -- such a position is a polymorphism of the sample, not an uncovered cytosine.
+ * site[0 .. n_site) (host memory): all of sequence `ref`, beg <= pos < end, pos strictly ascending, kind & 7 = context | strand << 2 as
+ * the genome has it, the context selected, the window clear of the runs (the caller filters such sites first, as bmbs_search does).
+ * run (host memory): n_run pairs, ascending and disjoint; NULL with n_run 0.
+ * BMBS_ESTATE: no index attached, or bmbs_sam_refs has not been given the index's names.  BMBS_EINVAL (bmbs_last_error names the first
+ * offender): ref outside the index's sequences; not 0 <= beg <= end <= the sequence's length; contexts outside 1..7; a run out of order
+ * or overlapping; a site with another ref, outside [beg, end), not behind its predecessor, with a kind the genome does not have there,
+ * of a context that is not selected, or whose window touches a run.  BMBS_ENOMEM with *out_bytes and *n_line set when cap is smaller
+ * than the text, a cap of 0 being the size query; nothing is written behind out + cap or out + *out_bytes.  beg == end is valid: 0
+ * bytes.  The call leaves the context's methylation result (sites, M-bias table, opposite-strand entries) as it is.
+ * Unlike Bismark: a CpG whose third letter is unknown is written, with N (Bismark skips it); the caller gets one text, not one per
+ * chromosome; positions are 1-based always (no --zero_based); no gzip; no CpG-merged report.                                       */
+#define BMBS_REPORT_OMIT 8             /* in bmbs_methyl_site.kind, for bmbs_methyl_report only */
+int bmbs_methyl_report(bmbs_ctx*, int32_t ref, int64_t beg, int64_t end, const bmbs_methyl_site* site, int64_t n_site,
+                       const int64_t* run, int64_t n_run, int32_t contexts, char* out, uint64_t cap, uint64_t* out_bytes, int64_t* n_line);
+
 /* a21: per-ctx counters of the batches mapped so far = {reads, unique, ambiguous, mapped bases,
  * error bases} (Schema.cpp:25141-25146); bmbs_stats_allreduce sums them over the ctxs one process
  * drives (get_mapping_informations, Schema.cpp:451-476).  Multi-process jobs sum the five int64 with

@@ -22,10 +22,15 @@ a run which asks for neither the table nor a trim costs what it did: this build'
 its walls beside that leg's, the numbers of sites dropped as variants, and the opposite passes' kernel time (k_meth_events<.., .., true>)
 beside the calling passes' (k_meth_events<.., .., false>: k_meth_count / k_meth_emit) in the trace (then a run with the filter on).  The
 report goes to profiles/variant_probe.txt and the kernel rows to profiles/variant_kernel_stats.csv unless --out / --stats-out say otherwise.
+--report (with --methyl): a leg `--methyl ... --cytosine-report` beside the --methyl leg -- its walls beside that leg's, the report's
+lines and bytes and the seconds the driver spent on it (inside the device calls, and waiting for the file), what the file system takes
+for as many bytes, the k_cyt_* rows of the trace (then a run with the report), and k_cyt_emit's bytes written per second beside
+k_line_write<true>'s.  With --other-driver the plain --methyl run of either build goes under the kernel trace too, as with --variant.
+The report goes to profiles/cytosine_report_probe.txt and the kernel rows to profiles/cytosine_report_kernel_stats.csv.
 With --mbias the report goes to profiles/mbias_probe.txt and the kernel rows to profiles/mbias_kernel_stats.csv unless --out /
 --stats-out name other files.
 
-  python tools/sort_probe.py [--reads 4000000] [--loop 8] [--pe] [--runs 3] [--bai] [--markdup] [--methyl [--mbias] [--variant] [--other-driver path]] [--out profiles/sorted_bam_probe.txt | profiles/mbias_probe.txt]
+  python tools/sort_probe.py [--reads 4000000] [--loop 8] [--pe] [--runs 3] [--bai] [--markdup] [--methyl [--mbias] [--variant] [--report] [--other-driver path]] [--out profiles/sorted_bam_probe.txt | profiles/mbias_probe.txt]
 """
 import argparse
 import csv
@@ -72,6 +77,9 @@ def verbose_numbers(err):
     m = re.search(r"sites dropped as variants (\d+), lines left out below the minimum depth (\d+)", err)
     if m:
         out["variants"] = int(m.group(1))
+    m = re.search(r"report lines (\d+) bytes (\d+) in ([\d.]+)s \(device calls ([\d.]+)s, waiting for the file ([\d.]+)s\)", err)
+    if m:
+        out["report"] = (int(m.group(1)), int(m.group(2)), float(m.group(3)), float(m.group(4)), float(m.group(5)))
     m = re.search(r"mbias calls (\d+)", err)
     if m:
         out["mbias"] = int(m.group(1))
@@ -96,13 +104,14 @@ def main():
     ap.add_argument("--methyl", action="store_true", help="also measure --bam --sort --methyl (methylation counts per cytosine from the same run)")
     ap.add_argument("--mbias", action="store_true", help="with --methyl: also measure --methyl ... --mbias (the M-bias table from the same run)")
     ap.add_argument("--variant", action="store_true", help="with --methyl: also measure --methyl with the opposite-strand variant filter on")
+    ap.add_argument("--report", action="store_true", help="with --methyl: also measure --methyl ... --cytosine-report (the genome-wide cytosine report)")
     ap.add_argument("--other-driver", default="", help="with --methyl: bmbs_search of another build, whose --methyl leg alternates with this build's")
     ap.add_argument("--driver-args", default="")
     ap.add_argument("--workdir", default=os.environ.get("BMBS_BENCH_DIR", "/tmp/bmbs_bench"))
     ap.add_argument("--out", default="")
     ap.add_argument("--stats-out", default="")
     args = ap.parse_args()
-    stem = "variant" if args.methyl and args.variant else "mbias" if args.methyl and args.mbias else "sorted_bam"
+    stem = "cytosine_report" if args.methyl and args.report else "variant" if args.methyl and args.variant else "mbias" if args.methyl and args.mbias else "sorted_bam"
     args.out = args.out or os.path.join(ROOT, "profiles", stem + "_probe.txt")
     args.stats_out = args.stats_out or os.path.join(ROOT, "profiles", stem + "_kernel_stats.csv")
     import torch
@@ -150,6 +159,9 @@ def main():
         if args.variant:
             runs["variant"] = []
             legs.append(("variant", os.path.join(wd, "sortp_y.bam"), ["--sort"] + meth_args + VARIANT_ARGS))
+        if args.report:
+            runs["report"] = []
+            legs.append(("report", os.path.join(wd, "sortp_y.bam"), ["--sort"] + meth_args + ["--cytosine-report"]))
         if args.other_driver:
             runs["methyl_other"] = []
             legs.append(("methyl_other", os.path.join(wd, "sortp_y.bam"), ["--sort"] + meth_args))
@@ -170,7 +182,7 @@ def main():
         % (args.reads, "pairs" if args.pe else "SE reads", L, args.loop, n_reads, args.genome, args.batch, " ".join(base[3:])))
     med = {}
     label = {"bam": "--bam", "sort": "--bam --sort", "bai": "--bam --sort --bai", "markdup": "--bam --sort --markdup", "methyl": "--bam --sort --methyl",
-             "mbias": "... --methyl --mbias", "variant": "... --methyl, filter", "methyl_other": "--methyl, other build"}
+             "mbias": "... --methyl --mbias", "variant": "... --methyl, filter", "report": "... --cytosine-report", "methyl_other": "--methyl, other build"}
     for kind in runs:
         w = [r["wall"] for r in runs[kind]]
         med[kind] = statistics.median(w)
@@ -214,6 +226,26 @@ def main():
         say("variant filter (%s): sites dropped as variants %s; median wall %.3f s against %.3f s of --methyl without it = %+.3f s; spread (max - min) of the --methyl runs %.3f s; pass 2 %s s"
             % (" ".join(VARIANT_ARGS), runs["variant"][-1].get("variants", "?"), med["variant"], med["methyl"], med["variant"] - med["methyl"], max(mw) - min(mw),
                " ".join("%.3f" % r["pass2"] for r in runs["variant"])))
+    if args.methyl and args.report:
+        mw = [r["wall"] for r in runs["methyl"]]
+        n_l, n_b = runs["report"][-1]["report"][:2]
+        say("cytosine report: %d lines, %d bytes (%.1f bytes a line); median wall %.3f s against %.3f s of --methyl without it = %+.3f s; spread (max - min) of the --methyl runs %.3f s"
+            % (n_l, n_b, n_b / max(1, n_l), med["report"], med["methyl"], med["report"] - med["methyl"], max(mw) - min(mw)))
+        say("  the driver's own clock, each run: report %s s, of which inside bmbs_methyl_report %s s and waiting for the writer thread to hand a buffer back %s s"
+            % tuple(" ".join("%.3f" % r["report"][k] for r in runs["report"]) for k in (2, 3, 4)))
+        # what the file system takes for as many bytes, written the way the driver writes them (pwrite of 64 MiB pieces into a new file)
+        import time
+        scratch = os.path.join(wd, "sortp_meth.write_probe")
+        piece = bytes(64 << 20)
+        t0 = time.time()
+        fd = os.open(scratch, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
+        at = 0
+        while at < n_b:
+            at += os.pwrite(fd, piece[:min(len(piece), n_b - at)], at)
+        os.close(fd)
+        t_fs = time.time() - t0
+        os.unlink(scratch)
+        say("  the file system alone: %d bytes into a new file in %.3f s = %.2f GB/s" % (n_b, t_fs, n_b / t_fs / 1e9))
     if args.methyl and args.other_driver:
         ow = [r["wall"] for r in runs["methyl_other"]]
         say("--methyl on this build against the other build (%s): median wall %.3f s against %.3f s = %+.3f s; the other build's own spread (max - min) %.3f s: %s"
@@ -224,7 +256,7 @@ def main():
     shutil.rmtree(tr, ignore_errors=True)
     if os.path.exists(out_s):
         os.unlink(out_s)
-    step(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tr, "--"] + base + ["--sort"] + (["--bai"] if args.bai else []) + (["--markdup"] if args.markdup else []) + (meth_args if args.methyl else []) + (["--mbias"] if args.methyl and args.mbias else []) + (VARIANT_ARGS if args.methyl and args.variant else []) + ["-o", out_s], 900)
+    step(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tr, "--"] + base + ["--sort"] + (["--bai"] if args.bai else []) + (["--markdup"] if args.markdup else []) + (meth_args if args.methyl else []) + (["--mbias"] if args.methyl and args.mbias else []) + (VARIANT_ARGS if args.methyl and args.variant else []) + (["--cytosine-report"] if args.methyl and args.report else []) + ["-o", out_s], 900)
     f = glob.glob(os.path.join(tr, "**", "*kernel_stats.csv"), recursive=True)
     if f:
         rows = list(csv.DictReader(open(f[0])))
@@ -279,8 +311,18 @@ def main():
                 else:
                     say("  the opposite passes k_meth_events<.., .., true> %.3f ms beside the calling passes k_meth_events<.., .., false> (k_meth_count + k_meth_emit) %.3f ms = %.2f x (the same walk over the other half of the masks)"
                         % (opp / 1e6, own / 1e6, opp / own))
-    # ---- --variant with --other-driver: a plain --methyl run of either build under the kernel trace -- do they launch the same kernels?
-    if args.methyl and args.variant and args.other_driver:
+            if args.report:
+                for r in rows:
+                    if "k_cyt_" in r["Name"]:
+                        say("  %-14s %.3f ms in %s calls" % (r["Name"].split("(")[0], int(r["TotalDurationNs"]) / 1e6, r["Calls"]))
+                em = total_ns(lambda n: "k_cyt_emit" in n)
+                n_b = runs["report"][-1]["report"][1]
+                if em and lw:
+                    say("  k_cyt_emit writes %d bytes of text in %.3f ms = %.0f GB/s; k_line_write<true> writes %d record bytes in %.2f ms = %.0f GB/s (bytes written only, same trace)"
+                        % (n_b, em / 1e6, n_b / em, rec_bytes, lw / 1e6, rec_bytes / lw))
+                say("  k_cyt_* together %.3f ms for the whole genome of %d bp" % (total_ns(lambda n: "k_cyt_" in n) / 1e6, args.genome))
+    # ---- --variant or --report with --other-driver: a plain --methyl run of either build under the kernel trace -- do they launch the same kernels?
+    if args.methyl and (args.variant or args.report) and args.other_driver:
         seen = {}
         for who, drv_w in (("this build", drv), ("the other build", args.other_driver)):
             shutil.rmtree(tr, ignore_errors=True)
