@@ -29,6 +29,7 @@ SYMBOLS = [
     "bmbs_text_sorted_clip", "bmbs_bam_methyl", "bmbs_bam_sort_methyl", "bmbs_methyl_sites",
     "bmbs_bam_methyl_opts", "bmbs_bam_sort_methyl_opts", "bmbs_methyl_mbias",
     "bmbs_bam_methyl_opposite", "bmbs_bam_sort_methyl_opposite", "bmbs_methyl_opposite", "bmbs_methyl_drop_variants", "bmbs_methyl_report",
+    "bmbs_bam_nonconv", "bmbs_text_sorted_nonconv",
     "bmbs_outcome_index",
 ]
 
@@ -97,6 +98,15 @@ METHYL_MBIAS = 1             # in MethylOpts.flags
 REPORT_OMIT = 8              # in a site's kind, for bmbs_methyl_report only: the position gets no line
 MBIAS_CYCLES = 1024
 MBIAS_SHAPE = (2, 2, 3, 2, MBIAS_CYCLES)      # mate, strand (0 OT, 1 OB), context, (0 unmethylated, 1 methylated), cycle
+
+
+# bmbs_nonconv_params, and the numpy view of bmbs_nonconv_count (the non-conversion filter: bmbs_bam_nonconv / bmbs_text_sorted_nonconv)
+class NonconvParams(C.Structure):
+    _fields_ = [("threshold", C.c_int32), ("percent", C.c_int32), ("min_count", C.c_int32), ("min_phred", C.c_int32)]
+
+
+NONCONV_COUNT_DTYPE = np.dtype([("meth", "<u4"), ("unmeth", "<u4")])
+NONCONV_TOTALS_SHAPE = (2, 3, 2)              # strand (0 OT, 1 OB), context, (0 unmethylated, 1 methylated)
 
 ST_UNMAPPED, ST_UNIQUE, ST_AMBIG, ST_OFFEND = 0, 1, 2, 3
 
@@ -257,6 +267,11 @@ def lib() -> C.CDLL:
     if hasattr(L, "bmbs_methyl_report"):                 # (the genome-wide cytosine report; BMBS_LIB may name an older build, as above)
         L.bmbs_methyl_report.argtypes = [vp, i32, i64, i64, vp, i64, vp, i64, i32, vp, u64, C.POINTER(u64), C.POINTER(i64)]
         L.bmbs_methyl_report.restype = C.c_int
+    if hasattr(L, "bmbs_bam_nonconv"):                   # (the non-conversion filter; BMBS_LIB may name an older build, as above)
+        L.bmbs_bam_nonconv.argtypes = [vp, vp, u64, vp, i64, i32, C.POINTER(NonconvParams), vp, vp, i64, C.POINTER(i64), C.POINTER(i64), vp]
+        L.bmbs_bam_nonconv.restype = C.c_int
+        L.bmbs_text_sorted_nonconv.argtypes = [vp, C.POINTER(NonconvParams), vp, i64, C.POINTER(i64), C.POINTER(i64), vp]
+        L.bmbs_text_sorted_nonconv.restype = C.c_int
     L.bmbs_map_pe_text.argtypes = [vp, vp, u64, vp, u64, i64, i32, vp, u64, C.POINTER(u64), C.POINTER(i64)]
     L.bmbs_map_pe_text.restype = C.c_int
     L.bmbs_retries.argtypes = [vp]
@@ -282,7 +297,7 @@ def lib() -> C.CDLL:
 
 
 LIB_SRCS = ("bmbs_api.hip", "bmbs_kernels.hip", "k_index.hip", "k_rows.hip", "k_qualpack.hip", "k_attach.hip", "k_scan.hip", "k_seed.hip", "k_vote.hip", "k_filter.hip", "k_reduce.hip", "k_align.hip", "k_finalize.hip", "k_pe_fast.hip", "k_pe_sensitive.hip",
-            "bmbs_textpath.hip", "bmbs_text.hip", "bmbs_bam.hip", "bmbs_inflate.hip", "k_bamsort.hip", "bmbs_bytes.h", "bmbs_records.hip", "k_bai.hip", "k_markdup.hip", "k_methyl.hip", "k_cytosine.hip", "bmbs_host.h", "bmbs_dev.h", "bmbs_words.h", "bmbs_sort.h", "bmbs_rowpitch.h", "../../include/bmbs.h",
+            "bmbs_textpath.hip", "bmbs_text.hip", "bmbs_bam.hip", "bmbs_inflate.hip", "k_bamsort.hip", "bmbs_bytes.h", "bmbs_records.hip", "k_bai.hip", "k_markdup.hip", "k_methyl.hip", "k_nonconv.hip", "k_cytosine.hip", "bmbs_host.h", "bmbs_dev.h", "bmbs_words.h", "bmbs_sort.h", "bmbs_rowpitch.h", "../../include/bmbs.h",
             "index_io.cpp", "index_io.h", "index_build_gpu.hip", "build_id.cpp")
 
 

@@ -251,6 +251,10 @@ struct Lane {
     // the cytosine report (k_cytosine.hip, bmbs_methyl_report): the caller's sites and runs as uploaded, the bytes of each genome word of
     // the window and their scan, the text.  Nothing of it outlives the call, and nothing of a methyl call's is touched
     DevBuf cy_site, cy_run, cy_cnt, cy_off, cy_out;
+    // the non-conversion filter (k_nonconv.hip, bmbs_bam_nonconv / bmbs_text_sorted_nonconv): the records of bmbs_bam_nonconv as uploaded;
+    // the tally, the records' counts, the templates' verdicts and those in a sorted text call's order.  Nothing of it outlives the call
+    RecIn nc_in;
+    DevBuf nc_work;
     // the last methyl call: `sites` of them in mt_site (bmbs_methyl_sites; -1: none); has_mbias: it made the M-bias table
     // (bmbs_methyl_mbias) -- in mt_mbias, or (mbias_zero) a call without records: the table is all zero and not on the device.
     // An opposite call (bmbs_bam_methyl_opposite / bmbs_bam_sort_methyl_opposite) leaves `opp` entries in mt_site instead

@@ -2,7 +2,8 @@
 // on the device already (a sorted text call's, the last bmbs_bam_sort call's) or come from the host, and sort them (bmbs_bam_sort), index
 // them (k_bai.hip: bmbs_bam_sort_index), sign them for duplicate marking (k_markdup.hip: bmbs_bam_dup_sigs, bmbs_text_sorted_dup,
 // bmbs_dup_select) or call cytosines in them (k_methyl.hip: bmbs_bam_methyl[_opts], bmbs_bam_sort_methyl[_opts], bmbs_methyl_sites,
-// bmbs_methyl_mbias, bmbs_text_sorted_clip) or write the genome-wide cytosine report from the sites of such calls (k_cytosine.hip:
+// bmbs_methyl_mbias, bmbs_text_sorted_clip), find the reads the bisulfite treatment did not convert (k_nonconv.hip: bmbs_bam_nonconv,
+// bmbs_text_sorted_nonconv) or write the genome-wide cytosine report from the sites of such calls (k_cytosine.hip:
 // bmbs_methyl_report); bmbs_text_sorted_index hands out a sorted text call's keys.  The sort itself, the deflater
 // and the download are bmbs_textpath.hip's, which the text calls run too (bmbs_host.h).  What a call leaves on the device for a later one,
 // and which call ends that, is Lane::ends (bmbs_host.h).
@@ -19,6 +20,7 @@ DEVI u32 bs_ld32(const char* p)
 #include "k_bai.hip"
 #include "k_markdup.hip"
 #include "k_methyl.hip"
+#include "k_nonconv.hip"
 #include "k_cytosine.hip"
 
 // ---- what the stages share -------------------------------------------------------------------------------------------------------------------
@@ -725,6 +727,118 @@ static int lane_text_sorted_clip(Lane* c, uint32_t* clip, int64_t cap, int64_t* 
     return BMBS_OK;
 }
 
+// ---- reads the bisulfite treatment did not convert (k_nonconv.hip): the rule is in include/bmbs.h -------------------------------------------------
+// Neither call touches a methyl call's result (Lane::mc, mt_*) or what a sort left (Lane::st, Lane::sc): the records of bmbs_bam_nonconv
+// go to nc_in, everything the kernels write to nc_work.
+static int nonconv_get_params(Lane* c, const bmbs_nonconv_params* in, NonconvPar* out)
+{
+    const bmbs_nonconv_params p = in ? *in : bmbs_nonconv_params{3, 0, 5, 0};
+    if (p.threshold < 0 || p.percent < 0 || p.percent > 100 || p.min_count < 0 || p.min_phred < 0 || p.min_phred > 255) {
+        c->err = "nonconv: bad parameters (threshold and min_count 0 and above, percent 0..100, min_phred 0..255)"; return BMBS_EINVAL;
+    }
+    out->threshold = (u32)p.threshold; out->percent = (u32)p.percent; out->min_count = (u32)p.min_count; out->min_phred = (u32)p.min_phred;
+    out->n_chrom = c->ix.n_chrom;
+    return BMBS_OK;
+}
+
+// the n entries at raw / off / len (device; off = the exclusive scan of len), n_tmpl templates of them -> in c->nc_work the counts (if
+// wanted), the templates' verdicts and the tally; n_out more bytes are carved for the caller (the verdicts in sorted order).  The tally
+// comes back in tally[NONCONV_TALLY]; the refusals are those of methyl_device, word for word
+struct NonconvOut { bmbs_nonconv_count* count; uint8_t* fail; uint8_t* out; };
+static int nonconv_device(Lane* c, const char* raw, const u64* off, const u32* len, u64 n, bool paired, u64 n_tmpl, const NonconvPar& par, bool want_count, u64 n_out,
+                          NonconvOut* o, u64 tally[NONCONV_TALLY])
+{
+    Carve A;
+    if (int rc = A.make(c, c->nc_work, {NONCONV_TALLY * 8, want_count ? n * sizeof(bmbs_nonconv_count) : 0, n_tmpl, n_out})) return rc;
+    unsigned long long* const d_tally = A.get<unsigned long long>();
+    o->count = A.get<bmbs_nonconv_count>(); o->fail = A.get<uint8_t>(); o->out = A.get<uint8_t>();
+    if (!want_count) o->count = nullptr;
+    u32* const info = stage_info(c);
+    HIPCHK(c, hipMemsetAsync(info, 0, TXI_HALF_WORDS * sizeof(u32), c->stream));
+    HIPCHK(c, hipMemsetAsync(d_tally, 0, NONCONV_TALLY * 8, c->stream));
+    // as many blocks as stay resident (7 per CU: the 7 waves per SIMD the kernel's registers allow -- the walk waits on memory most of its
+    // time, as k_meth_mbias does), each with its own tally, striding over the records
+    if (!c->mt_cus) { int cus = 0; HIPCHK(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->dev)); c->mt_cus = cus > 0 ? cus : 1; }
+    const unsigned grid = (unsigned)std::min<u64>((u64)c->mt_cus * 7, nblk(n * METH_GROUP, 256));
+    prof_begin(c, "k_nonconv_walk");
+    hipLaunchKernelGGL(k_nonconv_walk, dim3(grid), dim3(256), 0, c->stream, c->ix.gen2p, c->ix.chrom_start, raw, off, len, (long)n, paired ? 1 : 0, par, o->count, o->fail,
+                       d_tally, info);
+    prof_end(c);
+    const u32* const got = c->h_info->stage;
+    HIPCHK(c, hipMemcpyAsync(c->h_info->stage, info, 4 * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(tally, d_tally, NONCONV_TALLY * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    if (got[0]) { c->err = "nonconv: the length given for record " + std::to_string(~got[0]) + " is not its block_size + 4 (or is below the 36 bytes every BAM record has)"; return BMBS_EINVAL; }
+    if (got[1]) { c->err = "nonconv: the read name, CIGAR, sequence and qualities of record " + std::to_string(~got[1]) + " do not fit its length"; return BMBS_EINVAL; }
+    if (got[2]) { c->err = "nonconv: the refID of record " + std::to_string(~got[2]) + " is beyond the " + std::to_string(c->ix.n_chrom) + " sequences of the index"; return BMBS_EINVAL; }
+    if (got[3]) { c->err = "nonconv: the reference span of record " + std::to_string(~got[3]) + " runs off its sequence"; return BMBS_EINVAL; }
+    return BMBS_OK;
+}
+
+static int lane_bam_nonconv(Lane* c, const char* records, uint64_t bytes, const uint32_t* len, int64_t n_in, int32_t paired, const bmbs_nonconv_params* par_in,
+                            bmbs_nonconv_count* count, uint8_t* fail, int64_t fail_cap, int64_t* n_tmpl, int64_t* n_fail, uint64_t* totals)
+{
+    if (!n_tmpl || !n_fail) { c->err = "nonconv: NULL argument"; return BMBS_EINVAL; }
+    *n_tmpl = *n_fail = 0;
+    if (totals) memset(totals, 0, 12 * sizeof(uint64_t));
+    if (!c->attached) { c->err = "nonconv: no index attached"; return BMBS_ESTATE; }
+    NonconvPar par;
+    if (int rc = nonconv_get_params(c, par_in, &par)) return rc;
+    if (int rc = records_check(c, "nonconv", records, bytes, len, n_in, true, paired != 0)) return rc;
+    const u64 n = (u64)n_in, nt = paired ? n / 2 : n;
+    *n_tmpl = (int64_t)nt;
+    if ((int64_t)nt > fail_cap) { c->err = "nonconv: the array is too small (n_tmpl tells what is needed)"; return BMBS_ENOMEM; }
+    if (!nt) return BMBS_OK;
+    if (!fail || (bytes && !records)) { c->err = "nonconv: NULL buffer"; return BMBS_EINVAL; }
+    HIPCHK(c, hipSetDevice(c->dev));
+    RecIn& r = c->nc_in;
+    if (int rc = records_stage(c, r, records, bytes, len, n, TOT_RECS_IN)) return rc;
+    NonconvOut o;
+    u64 tally[NONCONV_TALLY];
+    if (int rc = nonconv_device(c, r.in.as<char>(), r.off.as<u64>(), r.len.as<u32>(), n, paired != 0, nt, par, count != nullptr, 0, &o, tally)) return rc;
+    hipStream_t ds = down_stream_of(c);
+    if (count) HIPCHK(c, hipMemcpyAsync(count, o.count, n * sizeof(bmbs_nonconv_count), hipMemcpyDeviceToHost, ds));
+    HIPCHK(c, hipMemcpyAsync(fail, o.fail, nt, hipMemcpyDeviceToHost, ds));
+    HIPCHK(c, hipStreamSynchronize(ds));
+    *n_fail = (int64_t)tally[12];
+    if (totals) memcpy(totals, tally, 12 * sizeof(uint64_t));
+    return BMBS_OK;
+}
+
+static int lane_text_sorted_nonconv(Lane* c, const bmbs_nonconv_params* par_in, uint8_t* fail, int64_t cap, int64_t* n, int64_t* n_tmpl_failed, uint64_t* totals)
+{
+    if (!n || !n_tmpl_failed) { c->err = "sorted nonconv: NULL argument"; return BMBS_EINVAL; }
+    *n = *n_tmpl_failed = 0;
+    if (totals) memset(totals, 0, 12 * sizeof(uint64_t));
+    if (!c->attached) { c->err = "sorted nonconv: no index attached"; return BMBS_ESTATE; }
+    NonconvPar par;
+    if (int rc = nonconv_get_params(c, par_in, &par)) return rc;
+    const Lane::SortedText& t = c->st;
+    if (t.lines < 0 || t.n < 0) {
+        c->err = "sorted nonconv: the context's last text call was not a BMBS_TEXT_BAM_SORTED call that returned records, or another call has used its buffers since";
+        return BMBS_ESTATE;
+    }
+    *n = t.n;
+    if (t.n > cap) { c->err = "sorted nonconv: the array is too small (n tells what is needed)"; return BMBS_ENOMEM; }
+    const u64 nr = (u64)t.n, lines = (u64)t.lines, nt = lines >> (t.pe ? 1 : 0);
+    if (!nr || !nt) return BMBS_OK;
+    if (!fail) { c->err = "sorted nonconv: NULL argument"; return BMBS_EINVAL; }
+    HIPCHK(c, hipSetDevice(c->dev));
+    NonconvOut o;
+    u64 tally[NONCONV_TALLY];
+    if (int rc = nonconv_device(c, c->bam_raw.as<char>(), c->sam_off.as<u64>(), c->sam_len.as<u32>(), lines, t.pe, nt, par, false, nr, &o, tally)) return rc;
+    prof_begin(c, "k_nonconv_order");
+    hipLaunchKernelGGL(k_nonconv_order, dim3(nblk(nr, 256)), dim3(256), 0, c->stream, o.fail, c->bs_idx2.as<u32>(), (long)nr, t.pe ? 1 : 0, o.out);
+    prof_end(c);
+    HIPCHK(c, hipMemcpyAsync(fail, o.out, nr, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    *n_tmpl_failed = (int64_t)tally[12];
+    if (totals) memcpy(totals, tally, 12 * sizeof(uint64_t));
+    return BMBS_OK;
+}
+
 // ---- the genome-wide cytosine report (k_cytosine.hip): the rule is in include/bmbs.h ------------------------------------------------------------
 // The sites and runs go up, k_cyt_check looks at the sites, k_cyt_count at every genome word of the window, the scan says where each
 // word's text goes (64-bit offsets: a window's text may pass 4 GB), and one wait brings back the refusals, the bytes and the lines.
@@ -828,3 +942,8 @@ extern "C" int bmbs_methyl_opposite(bmbs_ctx* X, bmbs_methyl_site* entry, int64_
 extern "C" int bmbs_methyl_drop_variants(bmbs_methyl_site* site, int64_t n_site, const bmbs_methyl_site* opp, int64_t n_opp, int32_t min_opposite_depth, int32_t max_variant_ppm, int64_t* n_kept)
 { return methyl_drop_variants(site, n_site, opp, n_opp, min_opposite_depth, max_variant_ppm, n_kept); }
 extern "C" int bmbs_text_sorted_clip(bmbs_ctx* X, uint32_t* clip, int64_t cap, int64_t* n) { ON_LANE0(lane_text_sorted_clip(c, clip, cap, n)); }
+extern "C" int bmbs_bam_nonconv(bmbs_ctx* X, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, int32_t paired, const bmbs_nonconv_params* par,
+                                bmbs_nonconv_count* count, uint8_t* fail, int64_t fail_cap, int64_t* n_tmpl, int64_t* n_fail, uint64_t* totals)
+{ ON_LANE0(lane_bam_nonconv(c, records, bytes, len, n, paired, par, count, fail, fail_cap, n_tmpl, n_fail, totals)); }
+extern "C" int bmbs_text_sorted_nonconv(bmbs_ctx* X, const bmbs_nonconv_params* par, uint8_t* fail, int64_t cap, int64_t* n, int64_t* n_tmpl_failed, uint64_t* totals)
+{ ON_LANE0(lane_text_sorted_nonconv(c, par, fail, cap, n, n_tmpl_failed, totals)); }

@@ -29,6 +29,11 @@
 //          selected contexts in the genome, both strands, covered or not -- Bismark's CX_report; the lines are made on the device window
 //          by window, see "--cytosine-report" below.  --methyl-merge-context and --methyl-min-depth shape the bedGraphs only: the report
 //          stays per strand and includes depth 0)
+//          --bam --sort --filter-non-conversion [--non-conversion-threshold n] [--non-conversion-percent p] [--non-conversion-min-count m]
+//          (templates with a read the bisulfite treatment did not convert -- n methylated calls outside CpG, or p percent of at least m
+//          such calls -- get flag 0x200 in every record: Bismark's filter_non_conversion, decided on the device in pass 1; every later
+//          stage, --methyl included, leaves flagged records out) [--conversion-report file] (the calls of all examined records by strand
+//          and context and the non-CpG conversion rate; alone it flags nothing)
 //
 // The reference has ONE reader thread and ONE fprintf sink (Process_Reads.cpp:2057-2260, Process_sam_out.cpp:954-1006), which is
 // what limits it.  Round 2 of this driver indexed the lines and formatted the SAM text with the host's
@@ -88,6 +93,12 @@ struct Options {
     bool variant_frac_given = false, site_opts_given = false, merge_context = false;
     bool cytosine_report = false;                // --cytosine-report: <prefix>.cytosine_report.txt, every cytosine of the selected contexts
     long report_window = 0;                      // --methyl-report-window: bases per bmbs_methyl_report call (0: what fits the buffers, write_report)
+    // --filter-non-conversion: templates with unconverted reads get flag 0x200 (--non-conversion-threshold, -percent, -min-count set the
+    // rule and imply the switch); --conversion-report <file>: the calls of all examined records and the non-CpG conversion rate
+    bool nonconv_filter = false;
+    bmbs_nonconv_params ncpar = {3, 0, 5, 0};
+    std::string conversion_report;
+    bool nonconv = false;                        // derived: pass 1 calls bmbs_text_sorted_nonconv (the filter, the report or both)
     double sort_mem_gib = 0;                     // --sort-mem: cap of the in-memory record store of --sort (0: half of the machine's memory)
     // derived once
     bool pe = false, gz_in = false, methyl_out = false;
@@ -114,6 +125,7 @@ struct Batch {
     std::vector<uint64_t> skey; std::vector<uint32_t> slen; int64_t n_sorted = 0;      // --sort: key and length of each record in `sam`
     std::vector<bmbs_dup_sig> sig; std::vector<uint32_t> tmpl; int64_t n_sig = 0;      // --markdup: the batch's signatures, the template of each record in `sam`
     std::vector<uint32_t> clip;                                                         // --methyl of pairs: the mate-overlap clip of each record in `sam`
+    std::vector<uint8_t> ncfail;                                                        // --filter-non-conversion: 1 for each record in `sam` whose template failed
     std::vector<uint32_t> counts1, counts2;
     bmbs_ctx* open_ctx = nullptr;                // compressed input kept on the device: the context that holds this batch's open window
 };
@@ -168,6 +180,9 @@ struct Run {
     std::mutex err_mu;                           // the first failure's message
     std::mutex g_mu;                             // t_gpu and t_wait_g: the gpu workers add under it, main reads after their join
     double t_gpu = 0, t_wait_g = 0;
+    // --filter-non-conversion / --conversion-report: the batches' totals, templates and failed templates added up (under g_mu, as t_gpu)
+    uint64_t nc_totals[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    long nc_templates = 0, nc_failed = 0;
     double t_start = 0, t_loaded = 0, t_pass1 = 0, t_pass2 = 0, t_joined = 0;      // main alone
 
     explicit Run(const Options& opt) : o(opt), batches((size_t)(opt.live_parts + opt.n_ctx() + 2))
@@ -222,7 +237,7 @@ const char* const ctx_names[3] = {"CpG", "CHG", "CHH"};
 [[noreturn]] void refuse(const char* msg) { fputs(msg, stderr); exit(2); }
 
 const char* const USAGE =
-    "usage: bmbs_search --index <genome.fa> [--index_folder dir] [-t threads]\n       bmbs_search --search <index> (--seq r.fq | --seq1 a.fq --seq2 b.fq) [-o out.sam] [-e f] [--min n] [--max n] [--sensitive] [--pbat] [--unmapped_out] [--ambiguous_out] [--bam [--sort [--sort-mem GiB] [--markdup] [--bai] [--methyl prefix [--CpG] [--CHG] [--CHH] [--methyl-min-mapq n] [--methyl-min-phred n] [--methyl-ignore n] [--methyl-ignore-3prime n] [--methyl-ignore-r2 n] [--methyl-ignore-3prime-r2 n] [--mbias] [--methyl-min-opposite-depth n [--methyl-max-variant-frac f]] [--methyl-merge-context] [--methyl-min-depth n] [--cytosine-report [--methyl-report-window bases]]]]] [--mapstats f] [-t io_threads] [--out-parts n]\n       --cytosine-report: <prefix>.cytosine_report.txt, one line per cytosine of the selected contexts on both strands, covered or not; --methyl-merge-context and --methyl-min-depth shape the bedGraphs only, the report stays per strand and includes depth 0\n";
+    "usage: bmbs_search --index <genome.fa> [--index_folder dir] [-t threads]\n       bmbs_search --search <index> (--seq r.fq | --seq1 a.fq --seq2 b.fq) [-o out.sam] [-e f] [--min n] [--max n] [--sensitive] [--pbat] [--unmapped_out] [--ambiguous_out] [--bam [--sort [--sort-mem GiB] [--markdup] [--bai] [--methyl prefix [--CpG] [--CHG] [--CHH] [--methyl-min-mapq n] [--methyl-min-phred n] [--methyl-ignore n] [--methyl-ignore-3prime n] [--methyl-ignore-r2 n] [--methyl-ignore-3prime-r2 n] [--mbias] [--methyl-min-opposite-depth n [--methyl-max-variant-frac f]] [--methyl-merge-context] [--methyl-min-depth n] [--cytosine-report [--methyl-report-window bases]]] [--filter-non-conversion] [--non-conversion-threshold n] [--non-conversion-percent p] [--non-conversion-min-count m] [--conversion-report file]]] [--mapstats f] [-t io_threads] [--out-parts n]\n       --cytosine-report: <prefix>.cytosine_report.txt, one line per cytosine of the selected contexts on both strands, covered or not; --methyl-merge-context and --methyl-min-depth shape the bedGraphs only, the report stays per strand and includes depth 0\n       --filter-non-conversion: flag 0x200 on every record of a template with a read that has 3 (--non-conversion-threshold) methylated calls outside CpG, or --non-conversion-percent of at least 5 (--non-conversion-min-count) such calls; --conversion-report: the calls of all examined records and the non-CpG conversion rate\n";
 
 Options parse_options(int argc, char** argv)
 {
@@ -309,6 +324,17 @@ Options parse_options(int argc, char** argv)
             o.variant_frac_given = o.site_opts_given = true;
         }
         else if (a == "--methyl-merge-context") o.merge_context = o.site_opts_given = true;      // MethylDackel's --mergeContext
+        else if (a == "--filter-non-conversion") o.nonconv_filter = true;      // --bam --sort --filter-non-conversion: flag 0x200 on unconverted templates, decided on the device
+        else if (a == "--non-conversion-threshold" || a == "--non-conversion-percent" || a == "--non-conversion-min-count") {      // Bismark's --threshold, --percentage_cutoff, --minimum_count
+            const bool pct = a == "--non-conversion-percent";
+            char* end = nullptr;
+            const char* v = val();
+            const long x = strtol(v, &end, 10);
+            if (end == v || *end || x < 0 || x > (pct ? 100 : 2147483647l)) { fprintf(stderr, "bmbs_search: %s takes %s\n", a.c_str(), pct ? "0..100" : "0..2147483647"); exit(2); }
+            (pct ? o.ncpar.percent : a == "--non-conversion-threshold" ? o.ncpar.threshold : o.ncpar.min_count) = (int32_t)x;
+            o.nonconv_filter = true;
+        }
+        else if (a == "--conversion-report") o.conversion_report = val();      // the calls of all examined records, the non-CpG conversion rate
         else if (a == "--help" || a == "-h") { fputs(USAGE, stdout); exit(0); }
         else if (a == "--cytosine-report") o.cytosine_report = true;  // --methyl ... --cytosine-report: Bismark's CX_report, from the device
         else if (a == "--methyl-report-window") {
@@ -324,6 +350,10 @@ Options parse_options(int argc, char** argv)
     if (o.sort && o.parts > 1) refuse("bmbs_search: --sort writes one file (--out-parts 1)\n");
     if (o.bai && !o.sort) refuse("bmbs_search: --bai needs --sort\n");
     if (o.markdup && !o.sort) refuse("bmbs_search: --markdup needs --sort\n");
+    if (o.nonconv_filter && !o.sort) refuse("bmbs_search: --filter-non-conversion, --non-conversion-threshold, --non-conversion-percent and --non-conversion-min-count need --sort\n");
+    if (!o.conversion_report.empty() && !o.sort) refuse("bmbs_search: --conversion-report needs --sort\n");
+    o.nonconv = o.nonconv_filter || !o.conversion_report.empty();
+    if (!o.nonconv_filter) o.ncpar.threshold = o.ncpar.percent = 0;      // (--conversion-report alone: nothing fails, the totals are still produced)
     o.methyl_out = !o.methyl.empty();
     if (o.methyl_out && !o.sort) refuse("bmbs_search: --methyl needs --sort\n");
     if (!o.methyl_out && (mpar.contexts || mpar.min_mapq != 10 || mpar.min_phred != 5)) refuse("bmbs_search: --CpG, --CHG, --CHH, --methyl-min-mapq and --methyl-min-phred need --methyl\n");
@@ -560,7 +590,7 @@ std::string sam_header_text(bool sorted, const std::vector<std::string>& chrom_n
         if (a == "--methyl" || a == "--methyl-min-mapq" || a == "--methyl-min-phred") { i++; continue; }
         if (a == "--methyl-ignore" || a == "--methyl-ignore-r2" || a == "--methyl-ignore-3prime" || a == "--methyl-ignore-3prime-r2") { i++; continue; }
         if (a == "--methyl-min-opposite-depth" || a == "--methyl-max-variant-frac" || a == "--methyl-min-depth") { i++; continue; }
-        if (a == "--methyl-report-window") { i++; continue; }
+        if (a == "--methyl-report-window" || a == "--conversion-report") { i++; continue; }      // (the filter's own options set flags in this file: they stay)
         if (a == "--CpG" || a == "--CHG" || a == "--CHH" || a == "--mbias" || a == "--methyl-merge-context" || a == "--cytosine-report") continue;
         h += a; h += ' ';
     }
@@ -946,6 +976,21 @@ void gpu_worker(Run& R, bmbs_ctx* own_ctx)
                         if (bmbs_text_sorted_clip(ctx, b->clip.data(), lines, &nc)) { R.fail(bmbs_last_error(ctx)); b->sam_bytes = 0; }
                         else if (nc != b->n_sorted) { R.fail("--methyl: the batch's clips do not match its records"); b->sam_bytes = 0; }
                     }
+                    if (o.nonconv && !R.failed) {
+                        // the verdicts of the batch's templates, per record; the records of a failed one get flag 0x200 (byte 19 |= 0x02) here,
+                        // in the batch's own buffer: the store, pass 2 and every later stage see flagged records
+                        int64_t nv = 0, nf = 0;
+                        uint64_t tot[12];
+                        b->ncfail.resize((size_t)lines + 1);
+                        if (bmbs_text_sorted_nonconv(ctx, &o.ncpar, b->ncfail.data(), lines, &nv, &nf, tot)) { R.fail(bmbs_last_error(ctx)); b->sam_bytes = 0; }
+                        else if (nv != b->n_sorted) { R.fail("--filter-non-conversion: the batch's verdicts do not match its records"); b->sam_bytes = 0; }
+                        else {
+                            if (nf) { size_t at = 0; for (int64_t j = 0; j < nv; at += b->slen[(size_t)j], j++) if (b->ncfail[(size_t)j]) b->sam.p[at + 19] |= 0x02; }
+                            std::lock_guard<std::mutex> l(R.g_mu);
+                            for (int x = 0; x < 12; x++) R.nc_totals[x] += tot[x];
+                            R.nc_templates += b->n; R.nc_failed += (long)nf;
+                        }
+                    }
                 }
                 break;
             }
@@ -1266,10 +1311,34 @@ void write_methyl(Run& R, Pass2& S)
     }
 }
 
+// --conversion-report <file>: the calls of all examined records by strand and context, the non-CpG conversion rate (unmethylated CHG and
+// CHH calls of all such calls, in hundredths of a percent, rounded half up), the templates and how many failed the filter.  Exact
+// integers; tests/nonconv_spec.py::report_text defines the text
+void write_conversion_report(Run& R)
+{
+    const Options& o = R.o;
+    FILE* f = fopen(o.conversion_report.c_str(), "w");
+    if (!f) { fprintf(stderr, "bmbs_search: cannot write %s: %s\n", o.conversion_report.c_str(), strerror(errno)); R.failed = true; return; }
+    fputs("#strand\tcontext\tmethylated\tunmethylated\tpercent\n", f);
+    unsigned long long nm = 0, nu = 0;
+    for (int s = 0; s < 2; s++)
+        for (int x = 0; x < 3; x++) {
+            const unsigned long long u = R.nc_totals[(s * 3 + x) * 2], m = R.nc_totals[(s * 3 + x) * 2 + 1];
+            if (x) { nm += m; nu += u; }
+            if (m + u) fprintf(f, "%s\t%s\t%llu\t%llu\t%llu\n", s ? "OB" : "OT", ctx_names[x], m, u, (200 * m + m + u) / (2 * (m + u)));
+            else fprintf(f, "%s\t%s\t0\t0\tNA\n", s ? "OB" : "OT", ctx_names[x]);
+        }
+    if (nm + nu) { const unsigned long long bp = (20000 * nu + nm + nu) / (2 * (nm + nu)); fprintf(f, "non-CpG conversion rate\t%llu\t%llu\t%llu.%02llu\n", nu, nm + nu, bp / 100, bp % 100); }
+    else fputs("non-CpG conversion rate\t0\t0\tNA\n", f);
+    fprintf(f, "templates\t%ld\tfailed\t%ld\n", R.nc_templates, R.nc_failed);
+    if (fclose(f)) { fprintf(stderr, "bmbs_search: cannot write %s: %s\n", o.conversion_report.c_str(), strerror(errno)); R.failed = true; }
+}
+
 // a failed run leaves no half-made sorted file, index or bedGraph behind
 int give_up(Run& R)
 {
     const Options& o = R.o;
+    if (!o.conversion_report.empty()) ::unlink(o.conversion_report.c_str());
     if (o.methyl_out) for (unsigned x = 0; x < 3; x++) if ((o.mpar.contexts >> x) & 1) ::unlink((o.methyl + "_" + ctx_names[x] + ".bedGraph").c_str());
     if (o.mbias) ::unlink((o.methyl + "_mbias.tsv").c_str());
     if (o.cytosine_report) ::unlink((o.methyl + ".cytosine_report.txt").c_str());
@@ -1307,6 +1376,7 @@ void report(const Run& R, const Pass2& S)
         if (o.markdup)
             snprintf(ixs + strlen(ixs), sizeof ixs - strlen(ixs), ", markdup: templates %ld, with signature %ld, duplicates %zu (select calls %zu, %.3fs of pass 2)", store.templates,
                      store.with_sig, S.n_dup, S.select_calls, S.t_select - R.t_pass1);
+        if (o.nonconv) snprintf(ixs + strlen(ixs), sizeof ixs - strlen(ixs), ", nonconv: templates %ld, failed %ld", R.nc_templates, R.nc_failed);
         if (o.methyl_out)
             snprintf(ixs + strlen(ixs), sizeof ixs - strlen(ixs), ", methyl: sites CpG %zu CHG %zu CHH %zu, calls CpG %zu CHG %zu CHH %zu, sites left out at bases other than ACGT %zu", S.meth_n[0],
                      S.meth_n[1], S.meth_n[2], S.meth_calls[0], S.meth_calls[1], S.meth_calls[2], S.meth_dropped);
@@ -1372,6 +1442,7 @@ int main(int argc, char** argv)
     finish_files(R);
     if (o.bai && !R.failed) write_bai(R, S);
     if (o.methyl_out && !R.failed) write_methyl(R, S);
+    if (!o.conversion_report.empty() && !R.failed) write_conversion_report(R);
     if (R.failed) return give_up(R);
     report(R, S);
     teardown(R);

@@ -80,6 +80,7 @@ DEVI void meth_masks(const u64* __restrict__ gen2p, long W, long lo, long hi, u3
 // <.., .., false> (the default) is the kernel as it was before there was one: none of this is compiled into it, and its code is the
 // same instruction for instruction -- which a template parameter guarantees and a walk shared through a function does not.
 // k_meth_mbias below holds a COPY of the record checks and of the walk: a change to the rule here has to be made there too.
+// k_nonconv_walk (k_nonconv.hip) holds a third copy, with the non-conversion filter's own rule for which records it looks at.
 template <bool EMIT, bool TRIM, bool OPP = false>
 __global__ void __launch_bounds__(256)
 k_meth_events(const u64* __restrict__ gen2p, const u64* __restrict__ chrom_start, const char* __restrict__ raw, const u64* __restrict__ off,

@@ -421,6 +421,41 @@ class Mapper:
         return clip[:n.value]
 
     @staticmethod
+    def _nonconv_params(threshold, percent, min_count, min_phred):
+        return capi.NonconvParams(int(threshold), int(percent), int(min_count), int(min_phred))
+
+    def bam_nonconv(self, records: bytes, lens, paired: bool = False, threshold: int = 3, percent: int = 0, min_count: int = 5, min_phred: int = 0):
+        """concatenated BAM records in input order + their sizes (0: no record here) -> (count NONCONV_COUNT_DTYPE[records]: the non-CpG
+        calls of each, fail u8[templates]: 1 where a template failed the non-conversion filter, their number, totals u64
+        NONCONV_TOTALS_SHAPE: the calls of all examined records); a template is one record, or with paired=True the entries 2p and
+        2p + 1 (bmbs_bam_nonconv)"""
+        ln = np.ascontiguousarray(lens, dtype=np.uint32)
+        a = np.frombuffer(records, dtype=np.uint8) if len(records) else np.zeros(1, dtype=np.uint8)
+        par = self._nonconv_params(threshold, percent, min_count, min_phred)
+        nt = C.c_int64(0); nf = C.c_int64(0)
+        cap = ln.size // 2 if paired else ln.size
+        count = np.zeros(max(1, ln.size), dtype=capi.NONCONV_COUNT_DTYPE)
+        fail = np.zeros(max(1, cap), dtype=np.uint8)
+        totals = np.zeros(capi.NONCONV_TOTALS_SHAPE, dtype=np.uint64)
+        self._chk(self._lib.bmbs_bam_nonconv(self._ctx, capi.ptr(a), len(records), capi.ptr(ln) if ln.size else None, ln.size, int(paired), C.byref(par),
+                                             capi.ptr(count), capi.ptr(fail), cap, C.byref(nt), C.byref(nf), capi.ptr(totals)))
+        return count[:ln.size], fail[:nt.value], int(nf.value), totals
+
+    def sorted_nonconv(self, threshold: int = 3, percent: int = 0, min_count: int = 5, min_phred: int = 0):
+        """(fail u8[records], failed templates, totals u64 NONCONV_TOTALS_SHAPE) of the last map_text / text_map_open call with TEXT_BAM |
+        TEXT_BAM_SORTED: fail[j] = 1 where the template of the j-th record that call returned failed the non-conversion filter
+        (bmbs_text_sorted_nonconv)"""
+        par = self._nonconv_params(threshold, percent, min_count, min_phred)
+        n = C.c_int64(0); nf = C.c_int64(0)
+        rc = self._lib.bmbs_text_sorted_nonconv(self._ctx, C.byref(par), None, 0, C.byref(n), C.byref(nf), None)
+        if rc and rc != -12:
+            self._chk(rc)
+        fail = np.zeros(max(1, n.value), dtype=np.uint8)
+        totals = np.zeros(capi.NONCONV_TOTALS_SHAPE, dtype=np.uint64)
+        self._chk(self._lib.bmbs_text_sorted_nonconv(self._ctx, C.byref(par), capi.ptr(fail), n.value, C.byref(n), C.byref(nf), capi.ptr(totals)))
+        return fail[:n.value], int(nf.value), totals
+
+    @staticmethod
     def _methyl_params(contexts, min_mapq, min_phred):
         return capi.MethylParams(int(contexts), int(min_mapq), int(min_phred), 0)
 

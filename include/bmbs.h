@@ -569,6 +569,44 @@ int bmbs_methyl_drop_variants(bmbs_methyl_site* site, int64_t n_site, const bmbs
 int bmbs_methyl_report(bmbs_ctx*, int32_t ref, int64_t beg, int64_t end, const bmbs_methyl_site* site, int64_t n_site,
                        const int64_t* run, int64_t n_run, int32_t contexts, char* out, uint64_t cap, uint64_t* out_bytes, int64_t* n_line);
 
+/* ---- reads the bisulfite treatment did not convert (csrc/k_nonconv.hip; `--bam --sort --filter-non-conversion`; tests/nonconv_spec.py) ------
+ * A read that carries several methylated cytosines outside CpG context is, in a mammalian sample, almost always a conversion failure
+ * (Bismark's filter_non_conversion, MethylDackel's --minConversionEfficiency).  Exact integers throughout.
+ * A record is EXAMINED when it is there (len != 0), refID >= 0, flag 4 is clear, flags 0x100 and 0x800 are clear and n_cigar_op > 0.
+ * MAPQ, the proper-pair flag, 0x200 and 0x400 are not looked at: the filter sees every aligned read.  Its CALLS are those of the rule
+ * above with the strand from the flags, M = X, the context from the genome alone, no mate-overlap clip, no trim, a base quality
+ * >= min_phred (a quality byte 0xff is 0).  nm / nu = the methylated / unmethylated calls in CHG and CHH together; CpG calls are
+ * counted for the totals only.  params NULL: threshold 3, percent 0, min_count 5, min_phred 0 (Bismark's --threshold and
+ * --minimum_count, no quality bound as there).  A record FAILS iff
+ *     threshold > 0 && nm >= threshold,  or  percent > 0 && nm + nu >= min_count && 100 * nm >= percent * (nm + nu)   (64-bit).
+ * Both switches 0 is valid: nothing fails, counts and totals are still produced.  BMBS_EINVAL ("bad parameters") for a negative value,
+ * percent > 100 or min_phred > 255.  A TEMPLATE is one entry, or with `paired` the entries 2p and 2p + 1; it fails iff any of its
+ * records fails (either read fails the pair, as in Bismark).  A caller marks a failed template by `flag |= 0x200` (QC fail) in EVERY
+ * record of it, the mate that is unmapped or was not examined too: record byte 19 |= 0x02, the byte --markdup uses; nothing else in a
+ * record changes.  Every methylation call above, samtools and MethylDackel then leave such records out.
+ * totals[2 strand (0 OT, 1 OB)][3 context][2 (0 unmethylated, 1 methylated)] = the calls of all examined records, failed or not: the
+ * run's conversion estimate comes from them.
+ * bmbs_bam_nonconv: `records` = n entries in host memory, len[i] their sizes (0: no record here).  count (n entries, or NULL): the
+ * non-CpG calls of each record, 0 and 0 when it is not examined.  fail[t] = 1 when template t fails, else 0; *n_tmpl = the templates
+ * (n, or n / 2), *n_fail = those that fail.  BMBS_ENOMEM with *n_tmpl set when fail_cap is smaller (a cap of 0: the size query; nothing
+ * is computed then).  totals: 12 entries, or NULL.
+ * bmbs_text_sorted_nonconv: the same for the context's last BMBS_TEXT_BAM_SORTED call, computed from the buffers that call left on the
+ * device, a pair's two output lines being its template: fail[j] = 1 when the template of the j-th record the call returned failed
+ * (*n = their number, that of bmbs_text_sorted_index), *n_tmpl_failed = the templates of the batch that failed.  BMBS_ENOMEM with *n
+ * set when cap is smaller.
+ * BMBS_ESTATE: no index attached; bmbs_text_sorted_nonconv: there was no such call, or another call on the context has rewritten the
+ * buffers since.  BMBS_EINVAL (bmbs_last_error names the record): the length, refID and span checks of bmbs_bam_methyl; an odd n with
+ * `paired`.  n = 0 is valid.  Both calls leave the context's methylation result and what a sort left on the device as they are.
+ * Not done: Bismark's --consecutive; removing records (they are flagged); per-strand thresholds; any interaction with --markdup
+ * (signatures and scores are computed as before, and a template may carry both flags).                                           */
+typedef struct bmbs_nonconv_params { int32_t threshold, percent, min_count, min_phred; } bmbs_nonconv_params;
+typedef struct bmbs_nonconv_count { uint32_t meth, unmeth; } bmbs_nonconv_count;   /* non-CpG calls of one record; 0, 0 when not examined */
+int bmbs_bam_nonconv(bmbs_ctx*, const char* records, uint64_t bytes, const uint32_t* len, int64_t n, int32_t paired,
+                     const bmbs_nonconv_params* params, bmbs_nonconv_count* count, uint8_t* fail, int64_t fail_cap,
+                     int64_t* n_tmpl, int64_t* n_fail, uint64_t totals[12]);
+int bmbs_text_sorted_nonconv(bmbs_ctx*, const bmbs_nonconv_params* params, uint8_t* fail, int64_t cap, int64_t* n,
+                             int64_t* n_tmpl_failed, uint64_t totals[12]);
+
 /* a21: per-ctx counters of the batches mapped so far = {reads, unique, ambiguous, mapped bases,
  * error bases} (Schema.cpp:25141-25146); bmbs_stats_allreduce sums them over the ctxs one process
  * drives (get_mapping_informations, Schema.cpp:451-476).  Multi-process jobs sum the five int64 with

@@ -27,10 +27,15 @@ lines and bytes and the seconds the driver spent on it (inside the device calls,
 for as many bytes, the k_cyt_* rows of the trace (then a run with the report), and k_cyt_emit's bytes written per second beside
 k_line_write<true>'s.  With --other-driver the plain --methyl run of either build goes under the kernel trace too, as with --variant.
 The report goes to profiles/cytosine_report_probe.txt and the kernel rows to profiles/cytosine_report_kernel_stats.csv.
+--nonconv (with --methyl): a leg `--methyl ... --filter-non-conversion` beside the --methyl leg -- its walls beside that leg's and its
+own spread, the templates examined and failed, the k_nonconv_* rows of the trace (then a run with the filter), and k_nonconv_walk's
+kernel time beside the counting pass k_meth_events<false, false>'s of the same run (the same walk over the same records with one context
+fewer and a clip).  With --other-driver the plain --methyl run of either build goes under the kernel trace too, as with --variant.  The
+report goes to profiles/nonconv_probe.txt and the kernel rows to profiles/nonconv_kernel_stats.csv.
 With --mbias the report goes to profiles/mbias_probe.txt and the kernel rows to profiles/mbias_kernel_stats.csv unless --out /
 --stats-out name other files.
 
-  python tools/sort_probe.py [--reads 4000000] [--loop 8] [--pe] [--runs 3] [--bai] [--markdup] [--methyl [--mbias] [--variant] [--report] [--other-driver path]] [--out profiles/sorted_bam_probe.txt | profiles/mbias_probe.txt]
+  python tools/sort_probe.py [--reads 4000000] [--loop 8] [--pe] [--runs 3] [--bai] [--markdup] [--methyl [--mbias] [--variant] [--report] [--nonconv] [--other-driver path]] [--out profiles/sorted_bam_probe.txt | profiles/mbias_probe.txt]
 """
 import argparse
 import csv
@@ -80,6 +85,9 @@ def verbose_numbers(err):
     m = re.search(r"report lines (\d+) bytes (\d+) in ([\d.]+)s \(device calls ([\d.]+)s, waiting for the file ([\d.]+)s\)", err)
     if m:
         out["report"] = (int(m.group(1)), int(m.group(2)), float(m.group(3)), float(m.group(4)), float(m.group(5)))
+    m = re.search(r"nonconv: templates (\d+), failed (\d+)", err)
+    if m:
+        out["nonconv"] = (int(m.group(1)), int(m.group(2)))
     m = re.search(r"mbias calls (\d+)", err)
     if m:
         out["mbias"] = int(m.group(1))
@@ -105,13 +113,14 @@ def main():
     ap.add_argument("--mbias", action="store_true", help="with --methyl: also measure --methyl ... --mbias (the M-bias table from the same run)")
     ap.add_argument("--variant", action="store_true", help="with --methyl: also measure --methyl with the opposite-strand variant filter on")
     ap.add_argument("--report", action="store_true", help="with --methyl: also measure --methyl ... --cytosine-report (the genome-wide cytosine report)")
+    ap.add_argument("--nonconv", action="store_true", help="with --methyl: also measure --methyl ... --filter-non-conversion (unconverted templates flagged in pass 1)")
     ap.add_argument("--other-driver", default="", help="with --methyl: bmbs_search of another build, whose --methyl leg alternates with this build's")
     ap.add_argument("--driver-args", default="")
     ap.add_argument("--workdir", default=os.environ.get("BMBS_BENCH_DIR", "/tmp/bmbs_bench"))
     ap.add_argument("--out", default="")
     ap.add_argument("--stats-out", default="")
     args = ap.parse_args()
-    stem = "cytosine_report" if args.methyl and args.report else "variant" if args.methyl and args.variant else "mbias" if args.methyl and args.mbias else "sorted_bam"
+    stem = "nonconv" if args.methyl and args.nonconv else "cytosine_report" if args.methyl and args.report else "variant" if args.methyl and args.variant else "mbias" if args.methyl and args.mbias else "sorted_bam"
     args.out = args.out or os.path.join(ROOT, "profiles", stem + "_probe.txt")
     args.stats_out = args.stats_out or os.path.join(ROOT, "profiles", stem + "_kernel_stats.csv")
     import torch
@@ -162,6 +171,9 @@ def main():
         if args.report:
             runs["report"] = []
             legs.append(("report", os.path.join(wd, "sortp_y.bam"), ["--sort"] + meth_args + ["--cytosine-report"]))
+        if args.nonconv:
+            runs["nonconv"] = []
+            legs.append(("nonconv", os.path.join(wd, "sortp_y.bam"), ["--sort"] + meth_args + ["--filter-non-conversion"]))
         if args.other_driver:
             runs["methyl_other"] = []
             legs.append(("methyl_other", os.path.join(wd, "sortp_y.bam"), ["--sort"] + meth_args))
@@ -182,7 +194,7 @@ def main():
         % (args.reads, "pairs" if args.pe else "SE reads", L, args.loop, n_reads, args.genome, args.batch, " ".join(base[3:])))
     med = {}
     label = {"bam": "--bam", "sort": "--bam --sort", "bai": "--bam --sort --bai", "markdup": "--bam --sort --markdup", "methyl": "--bam --sort --methyl",
-             "mbias": "... --methyl --mbias", "variant": "... --methyl, filter", "report": "... --cytosine-report", "methyl_other": "--methyl, other build"}
+             "mbias": "... --methyl --mbias", "variant": "... --methyl, filter", "report": "... --cytosine-report", "nonconv": "... --filter-non-conv.", "methyl_other": "--methyl, other build"}
     for kind in runs:
         w = [r["wall"] for r in runs[kind]]
         med[kind] = statistics.median(w)
@@ -246,6 +258,11 @@ def main():
         t_fs = time.time() - t0
         os.unlink(scratch)
         say("  the file system alone: %d bytes into a new file in %.3f s = %.2f GB/s" % (n_b, t_fs, n_b / t_fs / 1e9))
+    if args.methyl and args.nonconv:
+        mw, nw = [r["wall"] for r in runs["methyl"]], [r["wall"] for r in runs["nonconv"]]
+        n_t, n_f = runs["nonconv"][-1].get("nonconv", (0, 0))
+        say("--filter-non-conversion: templates %d, failed %d; median wall %.3f s against %.3f s of --methyl without it = %+.3f s; spread (max - min) of this leg %.3f s, of the --methyl runs %.3f s; pass 1 %s s"
+            % (n_t, n_f, med["nonconv"], med["methyl"], med["nonconv"] - med["methyl"], max(nw) - min(nw), max(mw) - min(mw), " ".join("%.3f" % r["pass1"] for r in runs["nonconv"])))
     if args.methyl and args.other_driver:
         ow = [r["wall"] for r in runs["methyl_other"]]
         say("--methyl on this build against the other build (%s): median wall %.3f s against %.3f s = %+.3f s; the other build's own spread (max - min) %.3f s: %s"
@@ -256,7 +273,7 @@ def main():
     shutil.rmtree(tr, ignore_errors=True)
     if os.path.exists(out_s):
         os.unlink(out_s)
-    step(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tr, "--"] + base + ["--sort"] + (["--bai"] if args.bai else []) + (["--markdup"] if args.markdup else []) + (meth_args if args.methyl else []) + (["--mbias"] if args.methyl and args.mbias else []) + (VARIANT_ARGS if args.methyl and args.variant else []) + (["--cytosine-report"] if args.methyl and args.report else []) + ["-o", out_s], 900)
+    step(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tr, "--"] + base + ["--sort"] + (["--bai"] if args.bai else []) + (["--markdup"] if args.markdup else []) + (meth_args if args.methyl else []) + (["--mbias"] if args.methyl and args.mbias else []) + (VARIANT_ARGS if args.methyl and args.variant else []) + (["--cytosine-report"] if args.methyl and args.report else []) + (["--filter-non-conversion"] if args.methyl and args.nonconv else []) + ["-o", out_s], 900)
     f = glob.glob(os.path.join(tr, "**", "*kernel_stats.csv"), recursive=True)
     if f:
         rows = list(csv.DictReader(open(f[0])))
@@ -311,6 +328,14 @@ def main():
                 else:
                     say("  the opposite passes k_meth_events<.., .., true> %.3f ms beside the calling passes k_meth_events<.., .., false> (k_meth_count + k_meth_emit) %.3f ms = %.2f x (the same walk over the other half of the masks)"
                         % (opp / 1e6, own / 1e6, opp / own))
+            if args.nonconv:
+                for r in rows:
+                    if "k_nonconv_" in r["Name"]:
+                        say("  %-14s %.3f ms in %s calls" % (r["Name"].split("(")[0], int(r["TotalDurationNs"]) / 1e6, r["Calls"]))
+                nw, cnt = total_ns(lambda n: "k_nonconv_walk" in n), total_ns(lambda n: "k_meth_events<false, false" in n)
+                if nw and cnt:
+                    say("  k_nonconv_walk %.3f ms beside the counting pass k_meth_events<false, false> %.3f ms of the same run = %.2f x (the same walk: pass 1 over every record of the batches, all three contexts, no clip; the counting pass over the records that are left, without those the filter flagged)"
+                        % (nw / 1e6, cnt / 1e6, nw / cnt))
             if args.report:
                 for r in rows:
                     if "k_cyt_" in r["Name"]:
@@ -321,8 +346,8 @@ def main():
                     say("  k_cyt_emit writes %d bytes of text in %.3f ms = %.0f GB/s; k_line_write<true> writes %d record bytes in %.2f ms = %.0f GB/s (bytes written only, same trace)"
                         % (n_b, em / 1e6, n_b / em, rec_bytes, lw / 1e6, rec_bytes / lw))
                 say("  k_cyt_* together %.3f ms for the whole genome of %d bp" % (total_ns(lambda n: "k_cyt_" in n) / 1e6, args.genome))
-    # ---- --variant or --report with --other-driver: a plain --methyl run of either build under the kernel trace -- do they launch the same kernels?
-    if args.methyl and (args.variant or args.report) and args.other_driver:
+    # ---- --variant, --report or --nonconv with --other-driver: a plain --methyl run of either build under the kernel trace -- do they launch the same kernels?
+    if args.methyl and (args.variant or args.report or args.nonconv) and args.other_driver:
         seen = {}
         for who, drv_w in (("this build", drv), ("the other build", args.other_driver)):
             shutil.rmtree(tr, ignore_errors=True)
