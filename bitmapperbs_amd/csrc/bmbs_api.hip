@@ -108,6 +108,15 @@ int mismatch_penalty(const bmbs_params& P, int Q)
     return (int)(phred * (P.mp_max - P.mp_min)) + P.mp_min;
 }
 
+// The smallest and the largest penalty a mismatching cell can take: mismatch_penalty over all 256 quality bytes.  Not [mp_min, mp_max]:
+// nothing keeps mp_min below mp_max (then the largest is mp_min or more), and a byte below q_base (--phred64 on Phred+33 data) takes
+// the formula outside both ends, below zero too -- such a mismatch RAISES the score.
+void mismatch_penalty_range(const bmbs_params& P, int* lo, int* hi)
+{
+    *lo = *hi = mismatch_penalty(P, 0);
+    for (int b = 1; b < 256; b++) { const int p = mismatch_penalty(P, b); *lo = std::min(*lo, p); *hi = std::max(*hi, p); }
+}
+
 // The penalty classes of the quality bytes (bmbs_qual_classes): the distinct values of mismatch_penalty over the 256 bytes, largest
 // first, the 16 largest numbered 0..15; class_of[b] = 0xFF for a byte whose penalty is not among them.  rep[c] (may be null) = the
 // smallest byte of class c, what k_qual_expand writes for it (classes that do not exist: rep[0]).
@@ -174,7 +183,11 @@ int threshold_k(const bmbs_params& P, int L)
 int cigar_ops_bound(const bmbs_params& P, int L, int k)
 {
     const long goe = (long)P.gap_open + P.gap_ext;
-    const long worst = std::max<long>(std::max<long>(P.mp_max, P.np), goe);
+    // the dearest mismatch is the largest entry of the penalty table, which is mp_max only while mp_min <= mp_max (the default penalties
+    // and every set with mp_min <= mp_max give the same bound as before)
+    int pen_lo, pen_hi;
+    mismatch_penalty_range(P, &pen_lo, &pen_hi);
+    const long worst = std::max<long>(std::max<long>(pen_hi, P.np), goe);
     long gaps = (long)L + 2 * k;
     if (goe > 0) gaps = std::min<long>(gaps, (long)k * worst / goe);
     return (int)std::min<long>(2 * gaps + 8, 1 << 20);
@@ -183,7 +196,7 @@ int cigar_ops_bound(const bmbs_params& P, int L, int k)
 #define BMBS_MAX_RECORD_OPS 254
 
 // MAP_Calculation tables for every error_threshold 0..62 (k for single-end, k1+k2 for pairs), concatenated:
-// table t = (t+2) x (unit*t+1) bytes at mapq_off[t]; plus klut[L] = the threshold of a read of length L.  Built once.
+// table t = (t+2) x (unit*t+2) bytes at mapq_off[t]; plus klut[L] = the threshold of a read of length L.  Built once.
 int prepare_luts(Lane* c)
 {
     if (c->luts_ready) return BMBS_OK;
@@ -195,11 +208,13 @@ int prepare_luts(Lane* c)
     for (int k = 0; k <= 62; k++) {
         const int range = unit * k;
         off[k] = (u32)lut.size();
-        lut.resize(lut.size() + (size_t)(k + 2) * (range + 1));
+        // column range + 1 stands for every score above 0 (mismatches whose penalty is negative): all of them reach every rank cut
+        // as score 0 does, but none is "perfect", so one column serves them all
+        lut.resize(lut.size() + (size_t)(k + 2) * (range + 2));
         u8* t = lut.data() + off[k];
         for (int ed = 0; ed <= k + 1; ed++)
-            for (int sd = 0; sd <= range; sd++)
-                t[(size_t)ed * (range + 1) + sd] = (u8)map_calculation(c->prm, (unsigned)ed, (unsigned)k, sd - range);
+            for (int sd = 0; sd <= range + 1; sd++)
+                t[(size_t)ed * (range + 2) + sd] = (u8)map_calculation(c->prm, (unsigned)ed, (unsigned)k, sd - range);
     }
     std::vector<u8> kl(1002);
     for (int L = 0; L <= 1001; L++) kl[L] = (u8)threshold_k(c->prm, L);
@@ -322,7 +337,14 @@ int run_align(Lane* c, const char* d_seq, const char* d_qual, const char* d_qual
     //        its DPP wait states), so it only pays when there are too few jobs to fill the lanes.
     const int swm = c->kn.sw_form;
     const bool wave_form = swm == 3;
-    int maxpen = std::max(std::max(c->prm.mp_max, c->prm.np), c->prm.gap_open + c->prm.gap_ext);
+    // what one cell can move a score by, either way: the extremes of the penalty table (not mp_max: mismatch_penalty_range), np, one gap
+    int pen_lo, pen_hi;
+    mismatch_penalty_range(c->prm, &pen_lo, &pen_hi);
+    int maxpen = std::max(std::max(std::max(pen_hi, -pen_lo), c->prm.np), c->prm.gap_open + c->prm.gap_ext);
+    // The bound holds for ANY job, a stage call's with a window that fits nowhere included (every cell then costs np): L * maxpen.  Jobs
+    // the filter accepted stay far inside it (H is a maximum over paths next to one with <= k edits), so a set like mp_max 2, mp_min 60
+    // at 998 bases takes the 32-bit form although its accepted jobs would fit.  (gap_ext < 256 keeps the packed gap constants in their
+    // halves; with gap_open >= 0 the product test already excludes it, it decides only if that test is ever loosened.)
     const bool packed = !wave_form && swm != 1 && (k >= 5 || swm == 2) && !gm.len && c->prm.gap_ext < 256 && (L + 64) * maxpen < 12000 &&
                         c->prm.mp_min >= 0 && c->prm.gap_ext >= 0 && c->prm.gap_open >= 0 && c->prm.np >= 0;
     const bool reg_form = !wave_form;
@@ -2023,6 +2045,19 @@ static int lane_window_batch(Lane* c, const uint64_t* site, int64_t n_sites, int
     return BMBS_OK;
 }
 
+// the packed stage entries (bmbs_filter_batch_packed, bmbs_align_batch_packed): the uploaded rows c->in_seq packed on the device
+// exactly as the mapping calls pack them (k_pack_rows: 2 bits per base + the not-ACGT plane and the per-row dirty byte)
+static int pack_stage_rows(Lane* c, const ReadGeom& gm, int stride, u64 n_reads, PackedRows* pr)
+{
+    const int pwords = pack_words(gm.L), W = pack_base_words(gm.L);
+    { int rz_ = ensure(c, c->prow, n_reads * (u64)pwords * 8 + 64, true); if (rz_) return rz_; } ENS(c, c->prow_dirty, n_reads + 64);
+    HIPCHK(c, hipMemsetAsync(c->prow_dirty.p, 0, n_reads + 64, c->stream));
+    hipLaunchKernelGGL(k_pack_rows, dim3(nblk(n_reads * (u64)(stride / 16), 256)), dim3(256), 0, c->stream, c->in_seq.as<char>(), gm, stride, (long)n_reads,
+                       c->prow.as<u64>(), pwords, W, c->prow_dirty.as<u32>());
+    pr->base = c->prow.as<u64>(); pr->dirty = c->prow_dirty.as<u8>(); pr->pwords = pwords; pr->W = W;
+    return BMBS_OK;
+}
+
 static int lane_filter_batch(Lane* c, const char* seq, int32_t L, int32_t stride, int64_t n_reads,
                                  const uint32_t* read_of, const uint64_t* site, int64_t n_cand, uint32_t* err,
                                  int32_t* end_site, bool packed)
@@ -2042,17 +2077,8 @@ static int lane_filter_batch(Lane* c, const char* seq, int32_t L, int32_t stride
     HIPCHK(c, hipMemcpyAsync(c->in_b.p, site, m * 8, hipMemcpyHostToDevice, c->stream));
     PackedRows pr = {nullptr, nullptr, 0, 0};
     const ReadGeom gm = geom(c, L, nullptr);
-    if (packed) {
-        // the rows packed on the device exactly as the mapping calls pack them (k_pack_rows: 2 bits per base + the not-ACGT plane and the
-        // per-row dirty byte), then the Myers form those calls run (bpm_planes<W, true>)
-        const u64 nrd = (u64)n_reads;
-        const int pwords = pack_words(gm.L), W = pack_base_words(gm.L);
-        { int rz_ = ensure(c, c->prow, nrd * (u64)pwords * 8 + 64, true); if (rz_) return rz_; } ENS(c, c->prow_dirty, nrd + 64);
-        HIPCHK(c, hipMemsetAsync(c->prow_dirty.p, 0, nrd + 64, c->stream));
-        hipLaunchKernelGGL(k_pack_rows, dim3(nblk(nrd * (u64)(stride / 16), 256)), dim3(256), 0, c->stream, c->in_seq.as<char>(), gm, stride, (long)nrd,
-                           c->prow.as<u64>(), pwords, W, c->prow_dirty.as<u32>());
-        pr.base = c->prow.as<u64>(); pr.dirty = c->prow_dirty.as<u8>(); pr.pwords = pwords; pr.W = W;
-    }
+    // packed: the Myers form the mapping calls run (bpm_planes<W, true>)
+    if (packed) { const int rp = pack_stage_rows(c, gm, stride, (u64)n_reads, &pr); if (rp) return rp; }
     hipLaunchKernelGGL(k_filter_pairs, dim3(nblk(m, 256)), dim3(256), 0, c->stream, c->ix, c->in_seq.as<char>(), pr, gm, stride, m,
                        c->in_a.as<u32>(), c->in_b.as<u64>(), c->ferr.as<u32>(), c->fend.as<int>());
     HIPCHK(c, hipMemcpyAsync(err, c->ferr.p, m * 4, hipMemcpyDeviceToHost, c->stream));
@@ -2064,7 +2090,7 @@ static int lane_filter_batch(Lane* c, const char* seq, int32_t L, int32_t stride
 static int lane_align_batch(Lane* c, const char* seq, const char* qual, int32_t L, int32_t stride, int64_t n_reads,
                                 const uint32_t* read_of, const uint64_t* site, const int32_t* end_site_in,
                                 const uint32_t* err_in, int64_t n_jobs, int32_t* start_site, int32_t* end_site,
-                                uint32_t* nm, int32_t* score, uint32_t* cigar_ops, int32_t* n_ops, int32_t max_ops)
+                                uint32_t* nm, int32_t* score, uint32_t* cigar_ops, int32_t* n_ops, int32_t max_ops, bool packed, uint32_t rev_from)
 {
     if (!c) return BMBS_EINVAL;
     if (!c->attached) { c->err = "no index attached"; return BMBS_ESTATE; }
@@ -2090,8 +2116,11 @@ static int lane_align_batch(Lane* c, const char* seq, const char* qual, int32_t 
     HIPCHK(c, hipMemsetAsync(c->cig_pool.p, 0, m * (u64)max_ops * 4, c->stream));
     c->cur_slot = 0; c->prof_used[0] = 0;
     Jobs jobs = {c->in_a.as<u32>(), c->in_b.as<u64>(), c->in_c.as<int>(), c->in_d.as<u32>()};
-    int rc = run_align(c, c->in_seq.as<char>(), c->in_qual.as<char>(), nullptr, geom(c, L, nullptr), stride, m, jobs, 0xffffffffu, c->cig_pool.as<u32>(), max_ops,
-                       PackedRows{nullptr, nullptr, 0, 0}, nullptr, ~0ull);          // on the ASCII rows
+    PackedRows pr = {nullptr, nullptr, 0, 0};                                        // the empty one: on the ASCII rows
+    const ReadGeom gm = geom(c, L, nullptr);
+    if (packed) { const int rp = pack_stage_rows(c, gm, stride, (u64)n_reads, &pr); if (rp) return rp; }
+    int rc = run_align(c, c->in_seq.as<char>(), c->in_qual.as<char>(), nullptr, gm, stride, m, jobs, packed ? rev_from : 0xffffffffu, c->cig_pool.as<u32>(),
+                       max_ops, pr, nullptr, ~0ull);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(start_site, c->a_start.p, m * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(end_site, c->a_end.p, m * 4, hipMemcpyDeviceToHost, c->stream));
@@ -2320,7 +2349,11 @@ extern "C" int bmbs_filter_batch_packed(bmbs_ctx* X, const char* seq, int32_t L,
 extern "C" int bmbs_align_batch(bmbs_ctx* X, const char* seq, const char* qual, int32_t L, int32_t stride, int64_t n_reads, const uint32_t* read_of,
                                 const uint64_t* site, const int32_t* end_site_in, const uint32_t* err_in, int64_t n_jobs, int32_t* start_site,
                                 int32_t* end_site, uint32_t* nm, int32_t* score, uint32_t* cigar_ops, int32_t* n_ops, int32_t max_ops)
-{ ON_LANE0(lane_align_batch(c, seq, qual, L, stride, n_reads, read_of, site, end_site_in, err_in, n_jobs, start_site, end_site, nm, score, cigar_ops, n_ops, max_ops)); }
+{ ON_LANE0(lane_align_batch(c, seq, qual, L, stride, n_reads, read_of, site, end_site_in, err_in, n_jobs, start_site, end_site, nm, score, cigar_ops, n_ops, max_ops, false, 0xffffffffu)); }
+extern "C" int bmbs_align_batch_packed(bmbs_ctx* X, const char* seq, const char* qual, int32_t L, int32_t stride, int64_t n_reads, const uint32_t* read_of,
+                                       const uint64_t* site, const int32_t* end_site_in, const uint32_t* err_in, int64_t n_jobs, int32_t* start_site,
+                                       int32_t* end_site, uint32_t* nm, int32_t* score, uint32_t* cigar_ops, int32_t* n_ops, int32_t max_ops, uint32_t rev_from)
+{ ON_LANE0(lane_align_batch(c, seq, qual, L, stride, n_reads, read_of, site, end_site_in, err_in, n_jobs, start_site, end_site, nm, score, cigar_ops, n_ops, max_ops, true, rev_from)); }
 extern "C" int bmbs_seed_batch(bmbs_ctx* X, const char* seq, int32_t L, int32_t stride, int64_t n_reads, uint8_t* verdict, uint64_t* exit_site,
                                uint64_t* seg_off, uint32_t* n_votes, uint64_t* vote_site, uint32_t* vote_cnt, int64_t vote_cap, int64_t* total_slots)
 { ON_LANE0(lane_seed_batch(c, seq, L, stride, n_reads, verdict, exit_site, seg_off, n_votes, vote_site, vote_cnt, vote_cap, total_slots)); }

@@ -681,11 +681,12 @@ DEVI int group_prefix_max(int x, int minf)
 }
 
 #define SWW_CG_WORDS 260
-// LDS words per job: row constants (u16 per read position, padded to 4) + trace + CIGAR ops; even, so that jobs stay 8-byte aligned
+// LDS words per job: row constants (one word per read position, padded to 2) + trace + CIGAR ops; rounded up to even, so that jobs
+// stay 8-byte aligned
 __host__ __device__ inline int sww_lds_words(int L, int k)
 {
     const int rw = (2 * k + 1 + 7) / 8;
-    return ((L + 3) / 4) * 2 + L * rw + SWW_CG_WORDS;
+    return (((L + 1) / 2) * 2 + L * rw + SWW_CG_WORDS + 1) & ~1;
 }
 
 template <int LANES>
@@ -718,11 +719,13 @@ k_align_sw_wave(DevIndex ix, ScoreParams sp, const int* __restrict__ pen_lut, co
     const int MINUS_INF = -0x40000000;
     const int gapoe = sp.gap_open + sp.gap_ext, gape = sp.gap_ext;
     u32* base = sww_lds + (size_t)grp * sww_lds_words(gm.L, gm.k);
-    u16* rc = reinterpret_cast<u16*>(base);                        // row constants: read code | penalty << 3
-    u32* tr = base + ((gm.L + 3) / 4) * 2;                         // trace, RW words per row
+    // row constants: read code | penalty << 3 in a whole word each -- 29 signed bits of penalty: a negative one (a quality byte below
+    // q_base) and one above 8191 (mp_min far above mp_max) fit, which the 16 bits this used to be cut both off
+    u32* rc = base;
+    u32* tr = base + ((gm.L + 1) / 2) * 2;                         // trace, RW words per row
     u32* cg = tr + (size_t)gm.L * RW;                              // CIGAR ops of the traceback
-    for (int i = b; i < ((L + 3) & ~3); i += LANES) {
-        u16 v = 4;
+    for (int i = b; i < ((L + 1) & ~1); i += LANES) {
+        u32 v = 4;
         if (i < L) {
             int ta;
             if (pr.base) {
@@ -732,7 +735,7 @@ k_align_sw_wave(DevIndex ix, ScoreParams sp, const int* __restrict__ pen_lut, co
             } else ta = code4(rd[i]);
             const unsigned char qc = (unsigned char)ql[rev ? L - 1 - i : i];
             const int pen = ta == 4 ? sp.np : pen_lut[qc];
-            v = (u16)(ta | (pen << 3));
+            v = (u32)ta | ((u32)pen << 3);
         }
         rc[i] = v;
     }
@@ -747,11 +750,11 @@ k_align_sw_wave(DevIndex ix, ScoreParams sp, const int* __restrict__ pen_lut, co
     const int gb = gape * b;
     const bool in_band = b < band;
     int hprev = 0, e_next = -gapoe;
-    u64 rc4 = 0;
+    u64 rc2 = 0;
     for (int i = 0; i < Lmax; ++i) {
-        if ((i & 3) == 0) rc4 = *reinterpret_cast<const u64*>(rc + (i < L ? i : 0));
-        const u32 x = (u32)(rc4 >> (16 * (i & 3))) & 0xffffu;
-        const int ta = (int)(x & 7), mis = -(int)(x >> 3);
+        if ((i & 1) == 0) rc2 = *reinterpret_cast<const u64*>(rc + (i < L ? i : 0));
+        const u32 x = (u32)(rc2 >> (32 * (i & 1)));
+        const int ta = (int)(x & 7), mis = -((int)x >> 3);
         const int wb = wr.next();
         const int sc = ((ta == wb && ta < 4) || (ta == 3 && wb == 1)) ? 0 : (wb == 4 ? -sp.np : mis);   // mat[] of Schema.cpp:830-850
         const int m = hprev + sc, e = e_next;

@@ -5,8 +5,8 @@
 // ================================================================================================
 DEVI u16 sat16(u32 v) { return v > 0xffffu ? (u16)0xffffu : (u16)v; }
 
-// mapq_lut[(ed) * (range+1) + sd]: MAP_Calculation (Schema.cpp:168-405) tabulated on the host in
-// IEEE double for this k: ed = min(second_best_diff, k+1), sd = clamp(score + range, 0, range).
+// mapq_lut[(ed) * (range+2) + sd]: MAP_Calculation (Schema.cpp:168-405) tabulated on the host in
+// IEEE double for this k: ed = min(second_best_diff, k+1), sd = max(score + range, 0), range + 1 for every score above 0.
 __global__ void __launch_bounds__(256)
 k_finalize(DevIndex ix, ScoreParams sp, const int* __restrict__ pen_lut, const u8* __restrict__ mapq_lut,
            const u32* __restrict__ mapq_off, int unit, const char* __restrict__ seq, const char* __restrict__ qual, ReadGeom gm,
@@ -78,9 +78,9 @@ k_finalize(DevIndex ix, ScoreParams sp, const int* __restrict__ pen_lut, const u
         }
         if (have) {
             if (verdict != 1) {
-                int sd = score + range; if (sd < 0) sd = 0; if (sd > range) sd = range;
+                int sd = score + range; if (sd < 0) sd = 0; if (sd > range) sd = range + 1;          // range + 1: any score above 0
                 const u32 ed = sbd > (u32)k ? (u32)k + 1 : sbd;
-                mapq = mapq_lut[(size_t)ed * (range + 1) + sd];
+                mapq = mapq_lut[(size_t)ed * (range + 2) + sd];
             }
             // output_sam_end_to_end placement (Schema.cpp:11941-11986)
             u64 loc = site; int flag;

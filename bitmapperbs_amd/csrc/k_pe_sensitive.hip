@@ -617,9 +617,9 @@ k_finalize_pe(DevIndex ix, ScoreParams sp, const int* __restrict__ pen_lut, cons
                 const int L1 = gm.rl(p), L2 = gm.rl(p + n);
                 const u32 kk = (u32)(gm.rk(L1) + gm.rk(L2)), sb = ps.sbd[p];
                 const int range = unit * (int)kk;
-                int sd = score[0] + score[1] + range; if (sd < 0) sd = 0; if (sd > range) sd = range;
+                int sd = score[0] + score[1] + range; if (sd < 0) sd = 0; if (sd > range) sd = range + 1;          // as in k_finalize
                 const u32 ed = sb > kk ? kk + 1 : sb;
-                const int mapq = mapq_lut[mapq_off[kk] + (size_t)ed * (range + 1) + sd];
+                const int mapq = mapq_lut[mapq_off[kk] + (size_t)ed * (range + 2) + sd];
                 for (int m = 0; m < 2; m++) {
                     o[m].pos = (u64)site_pos[m]; o[m].chrom = chrom[m]; o[m].mapq = (u8)mapq; o[m].nm = (u16)nm[m];
                     o[m].score = (int16_t)score[m]; o[m].tlen = (u32)tlen; o[m].path = 3;

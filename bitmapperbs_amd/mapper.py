@@ -620,7 +620,10 @@ class Mapper:
                                               capi.ptr(site), m, capi.ptr(err), capi.ptr(end)))
         return err, end
 
-    def align(self, seq, qual, L, read_of, site, end_in, err_in):
+    def align(self, seq, qual, L, read_of, site, end_in, err_in, packed: bool = False, rev_from: int | None = None):
+        """K11-K13 on (read, site, end, err) jobs; ops[j][:n_ops[j]] = the operations of job j (n_ops 0: all M).  packed: the rows are
+        packed on the device first and the DP form is chosen as in a mapping call (bmbs_align_batch_packed); rev_from (packed only):
+        reads from this index on read their qualities mirrored"""
         seq = np.ascontiguousarray(seq, dtype=np.uint8)
         qual = np.ascontiguousarray(qual, dtype=np.uint8)
         read_of = np.ascontiguousarray(read_of, dtype=np.uint32)
@@ -628,14 +631,20 @@ class Mapper:
         end_in = np.ascontiguousarray(end_in, dtype=np.int32)
         err_in = np.ascontiguousarray(err_in, dtype=np.uint32)
         m = read_of.size
-        max_ops = 2 * self.threshold(L) + 8
+        if rev_from is not None and not packed:
+            raise ValueError("rev_from needs packed=True (bmbs_align_batch has no such argument)")
+        max_ops = self.max_cigar_ops(L)
         out = {k: np.zeros(m, dtype=t) for k, t in (("start", np.int32), ("end", np.int32), ("nm", np.uint32),
                                                      ("score", np.int32), ("n_ops", np.int32))}
         ops = np.zeros((m, max_ops), dtype=np.uint32)
-        self._chk(self._lib.bmbs_align_batch(self._ctx, capi.ptr(seq), capi.ptr(qual), L, seq.shape[1], seq.shape[0],
-                                             capi.ptr(read_of), capi.ptr(site), capi.ptr(end_in), capi.ptr(err_in), m,
-                                             capi.ptr(out["start"]), capi.ptr(out["end"]), capi.ptr(out["nm"]),
-                                             capi.ptr(out["score"]), capi.ptr(ops), capi.ptr(out["n_ops"]), max_ops))
+        args = (self._ctx, capi.ptr(seq), capi.ptr(qual), L, seq.shape[1], seq.shape[0],
+                capi.ptr(read_of), capi.ptr(site), capi.ptr(end_in), capi.ptr(err_in), m,
+                capi.ptr(out["start"]), capi.ptr(out["end"]), capi.ptr(out["nm"]),
+                capi.ptr(out["score"]), capi.ptr(ops), capi.ptr(out["n_ops"]), max_ops)
+        if packed:
+            self._chk(self._lib.bmbs_align_batch_packed(*args, 0xFFFFFFFF if rev_from is None else int(rev_from)))
+        else:
+            self._chk(self._lib.bmbs_align_batch(*args))
         out["ops"] = ops
         return out
 

@@ -168,6 +168,16 @@ int bmbs_align_batch(bmbs_ctx*, const char* seq, const char* qual, int32_t L, in
                      int32_t* start_site, int32_t* end_site, uint32_t* nm, int32_t* score,
                      uint32_t* cigar_ops, int32_t* n_ops, int32_t max_ops);
 
+/* the same call on the form the mapping calls run: the rows are packed on the device first (as bmbs_filter_batch_packed does), the
+ * un-gapped recheck and the DP kernels take the read letters from the packed words, and the form of the DP is chosen as in a
+ * mapping call.  Jobs whose read index is >= rev_from read their quality row mirrored (what a mapping call does for mate 2);
+ * 0xffffffff: none.  Same results as bmbs_align_batch for every input (tests/test_align_forms.py).                              */
+int bmbs_align_batch_packed(bmbs_ctx*, const char* seq, const char* qual, int32_t L, int32_t stride,
+                            int64_t n_reads, const uint32_t* read_of, const uint64_t* site,
+                            const int32_t* end_site_in, const uint32_t* err_in, int64_t n_jobs,
+                            int32_t* start_site, int32_t* end_site, uint32_t* nm, int32_t* score,
+                            uint32_t* cigar_ops, int32_t* n_ops, int32_t max_ops, uint32_t rev_from);
+
 /* K1-K6 (+a8-a10): the seeding state machine of Map_Single_Seq_end_to_end (Schema.cpp:24588-24986).
  * verdict[i]: 0 no candidate, 1 exact-unique exit (exit_site), 2 one-mismatch exit (exit_site),
  * 3 general path, 4 exact but ambiguous.  For verdict 3 the read's votes, in the reference's visiting
