@@ -31,6 +31,7 @@ SYMBOLS = [
     "bmbs_bam_methyl_opposite", "bmbs_bam_sort_methyl_opposite", "bmbs_methyl_opposite", "bmbs_methyl_drop_variants", "bmbs_methyl_report",
     "bmbs_bam_nonconv", "bmbs_text_sorted_nonconv",
     "bmbs_outcome_index",
+    "bmbs_set_trim", "bmbs_text_trim_counts", "bmbs_trim_text",
 ]
 
 
@@ -107,6 +108,20 @@ class NonconvParams(C.Structure):
 
 NONCONV_COUNT_DTYPE = np.dtype([("meth", "<u4"), ("unmeth", "<u4")])
 NONCONV_TOTALS_SHAPE = (2, 3, 2)              # strand (0 OT, 1 OB), context, (0 unmethylated, 1 methylated)
+
+
+# bmbs_trim_opts and bmbs_trim_counts (trimming in the text calls: bmbs_set_trim / bmbs_text_trim_counts / bmbs_trim_text)
+class TrimOpts(C.Structure):
+    _fields_ = [("quality", C.c_int32), ("min_overlap", C.c_int32), ("error_permille", C.c_int32), ("min_length", C.c_int32),
+                ("clip_5p", C.c_int32 * 2), ("clip_3p", C.c_int32 * 2), ("adapter", (C.c_char * 33) * 2)]
+
+
+TRIM_COUNTERS = ("records_in", "bases_in", "bases_out", "quality_records", "quality_bases", "adapter_records", "adapter_bases", "clip_records", "clip_bases")
+
+
+class TrimCounts(C.Structure):
+    _fields_ = [(k, C.c_int64 * 2) for k in TRIM_COUNTERS] + [("templates_dropped", C.c_int64)]
+
 
 ST_UNMAPPED, ST_UNIQUE, ST_AMBIG, ST_OFFEND = 0, 1, 2, 3
 
@@ -275,6 +290,13 @@ def lib() -> C.CDLL:
         L.bmbs_bam_nonconv.restype = C.c_int
         L.bmbs_text_sorted_nonconv.argtypes = [vp, C.POINTER(NonconvParams), vp, i64, C.POINTER(i64), C.POINTER(i64), vp]
         L.bmbs_text_sorted_nonconv.restype = C.c_int
+    if hasattr(L, "bmbs_set_trim"):                      # (trimming in the text calls; BMBS_LIB may name an older build, as above)
+        L.bmbs_set_trim.argtypes = [vp, C.POINTER(TrimOpts)]
+        L.bmbs_set_trim.restype = C.c_int
+        L.bmbs_text_trim_counts.argtypes = [vp, C.POINTER(TrimCounts), C.POINTER(i64)]
+        L.bmbs_text_trim_counts.restype = C.c_int
+        L.bmbs_trim_text.argtypes = [vp, vp, u64, i64, i32, vp, vp, vp, vp]
+        L.bmbs_trim_text.restype = C.c_int
     L.bmbs_map_pe_text.argtypes = [vp, vp, u64, vp, u64, i64, i32, vp, u64, C.POINTER(u64), C.POINTER(i64)]
     L.bmbs_map_pe_text.restype = C.c_int
     L.bmbs_retries.argtypes = [vp]
@@ -300,7 +322,7 @@ def lib() -> C.CDLL:
 
 
 LIB_SRCS = ("bmbs_api.hip", "bmbs_kernels.hip", "k_index.hip", "k_rows.hip", "k_qualpack.hip", "k_attach.hip", "k_scan.hip", "k_seed.hip", "k_vote.hip", "k_filter.hip", "k_reduce.hip", "k_align.hip", "k_finalize.hip", "k_pe_fast.hip", "k_pe_sensitive.hip",
-            "bmbs_textpath.hip", "bmbs_text.hip", "bmbs_bam.hip", "bmbs_inflate.hip", "k_bamsort.hip", "bmbs_bytes.h", "bmbs_records.hip", "k_bai.hip", "k_markdup.hip", "k_methyl.hip", "k_nonconv.hip", "k_cytosine.hip", "bmbs_host.h", "bmbs_dev.h", "bmbs_words.h", "bmbs_sort.h", "bmbs_rowpitch.h", "../../include/bmbs.h",
+            "bmbs_textpath.hip", "bmbs_text.hip", "bmbs_bam.hip", "bmbs_inflate.hip", "k_bamsort.hip", "bmbs_bytes.h", "k_trim.hip", "bmbs_records.hip", "k_bai.hip", "k_markdup.hip", "k_methyl.hip", "k_nonconv.hip", "k_cytosine.hip", "bmbs_host.h", "bmbs_dev.h", "bmbs_words.h", "bmbs_sort.h", "bmbs_rowpitch.h", "../../include/bmbs.h",
             "index_io.cpp", "index_io.h", "index_build_gpu.hip", "build_id.cpp")
 
 

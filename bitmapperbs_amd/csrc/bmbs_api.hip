@@ -779,7 +779,8 @@ void lane_destroy(Lane* c)
                      &c->bs_key, &c->bs_key2, &c->bs_idx, &c->bs_idx2, &c->bs_slen, &c->bs_soff, &c->bs_tmp, &c->sc.in.in, &c->sc.in.len, &c->sc.in.off, &c->bs_sorted, &c->bai_a, &c->bai_b, &c->bai_out,
                      &c->dp_in.in, &c->dp_in.len, &c->dp_in.off, &c->dp_sig, &c->dp_key, &c->dp_key2, &c->dp_idx, &c->dp_idx2, &c->dp_dup, &c->dp_tmpl,
                      &c->mt_in.in, &c->mt_in.len, &c->mt_in.off, &c->mt_clip, &c->mt_cnt, &c->mt_eoff, &c->mt_ev, &c->mt_work, &c->mt_acc, &c->mt_site, &c->mt_cl2, &c->mt_mbias,
-                     &c->cy_site, &c->cy_run, &c->cy_cnt, &c->cy_off, &c->cy_out, &c->nc_in.in, &c->nc_in.len, &c->nc_in.off, &c->nc_work};
+                     &c->cy_site, &c->cy_run, &c->cy_cnt, &c->cy_off, &c->cy_out, &c->nc_in.in, &c->nc_in.len, &c->nc_in.off, &c->nc_work,
+                     &c->tr_rec[0], &c->tr_rec[1], &c->tr_keep, &c->tr_flag, &c->tr_off, &c->tr_words};
       for (DevBuf* b : tx) release(*b); }
     if (c->ev_up) (void)hipEventDestroy(c->ev_up);
     if (c->ev_k) (void)hipEventDestroy(c->ev_k);

@@ -207,6 +207,16 @@ struct Lane {
     // bmbs_map_*_text: newline index built on the device, SAM text written on the device
     DevBuf tx_tilecnt, tx_tileoff, tx_nl[2], tx_rec[2], tx_info, sam_len, sam_off, sam_out, chrom_chars, chrom_off;
     DevBuf bam_raw, bam_slots, bam_slot_len, bam_off, stats_snap;      // --bam: record stream, deflate scratch, BGZF slots
+    // the trim stage of the text calls (k_trim.hip; bmbs_set_trim).  on / opts: what the context was told; tr_rec: the second set of the
+    // files' record arrays (the records that stay), tr_keep: the files' keep bytes, tr_flag / tr_off: the templates' flags and their scan,
+    // tr_words: the counters (bmbs_words.h).  counted: the last text call trimmed -- cnt and kept are its counters (bmbs_text_trim_counts)
+    struct Trim {
+        bool on = false, counted = false;
+        bmbs_trim_opts opts = {};
+        bmbs_trim_counts cnt = {};
+        int64_t kept = 0;
+    } trim;
+    DevBuf tr_rec[2], tr_keep, tr_flag, tr_off, tr_words;
     // ---- the record stages behind the sorted BAM (bmbs_records.hip).  Each group: what a call left on the device for the calls that
     // fetch it, beside the buffers it lives in; `ends` (below the struct) is the one place that says which call takes it away again.
     // coordinate sort (k_bamsort.hip): keys / record numbers before and behind the pair sort, the sorted records' lengths and offsets, the

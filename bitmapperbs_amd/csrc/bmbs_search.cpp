@@ -34,6 +34,14 @@
 //          such calls -- get flag 0x200 in every record: Bismark's filter_non_conversion, decided on the device in pass 1; every later
 //          stage, --methyl included, leaves flagged records out) [--conversion-report file] (the calls of all examined records by strand
 //          and context and the non-CpG conversion rate; alone it flags nothing)
+//          --trim (adapter and quality trimming of every read on the device, in front of the mapping: what a pipeline otherwise runs
+//          trim_galore for; its defaults -- quality 20, adapter AGATCGGAAGAGC on both mates, overlap 1, error rate 0.1, length 20; the rule
+//          and its departures from cutadapt: include/bmbs.h, bmbs_set_trim) [--trim-quality n] (0: off) [--trim-adapter SEQ] (both mates
+//          unless --trim-adapter2 SEQ names mate 2's; `none`: off) [--trim-stringency n] [--trim-error-rate f] [--trim-min-length n]
+//          [--trim-clip-r1 n] [--trim-clip-r2 n] [--trim-three-prime-clip-r1 n] [--trim-three-prime-clip-r2 n] [--trim-report file] (the
+//          totals of all batches, one line per counter and mate).  Templates that end up shorter than the minimum length (pairs: either
+//          mate) are dropped: they reach no output and no statistic but the "removed by trimming" line.  M-bias cycles and
+//          --methyl-ignore* count from the trimmed read's first base, as Bismark's do behind trim_galore
 //
 // The reference has ONE reader thread and ONE fprintf sink (Process_Reads.cpp:2057-2260, Process_sam_out.cpp:954-1006), which is
 // what limits it.  Round 2 of this driver indexed the lines and formatted the SAM text with the host's
@@ -99,6 +107,10 @@ struct Options {
     bmbs_nonconv_params ncpar = {3, 0, 5, 0};
     std::string conversion_report;
     bool nonconv = false;                        // derived: pass 1 calls bmbs_text_sorted_nonconv (the filter, the report or both)
+    // --trim: the reads are trimmed on the device before they are mapped (bmbs_set_trim); the --trim-* refinements need it
+    bool trim = false, trim_opt_given = false, trim_a2_given = false;
+    bmbs_trim_opts tpar = {20, 1, 100, 20, {0, 0}, {0, 0}, {"AGATCGGAAGAGC", "AGATCGGAAGAGC"}};
+    std::string trim_report;
     double sort_mem_gib = 0;                     // --sort-mem: cap of the in-memory record store of --sort (0: half of the machine's memory)
     // derived once
     bool pe = false, gz_in = false, methyl_out = false;
@@ -183,6 +195,9 @@ struct Run {
     // --filter-non-conversion / --conversion-report: the batches' totals, templates and failed templates added up (under g_mu, as t_gpu)
     uint64_t nc_totals[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     long nc_templates = 0, nc_failed = 0;
+    // --trim: the batches' counters and kept templates added up (under g_mu, as t_gpu)
+    bmbs_trim_counts trim_cnt = {};
+    long trim_in = 0, trim_kept = 0;
     double t_start = 0, t_loaded = 0, t_pass1 = 0, t_pass2 = 0, t_joined = 0;      // main alone
 
     explicit Run(const Options& opt) : o(opt), batches((size_t)(opt.live_parts + opt.n_ctx() + 2))
@@ -237,7 +252,7 @@ const char* const ctx_names[3] = {"CpG", "CHG", "CHH"};
 [[noreturn]] void refuse(const char* msg) { fputs(msg, stderr); exit(2); }
 
 const char* const USAGE =
-    "usage: bmbs_search --index <genome.fa> [--index_folder dir] [-t threads]\n       bmbs_search --search <index> (--seq r.fq | --seq1 a.fq --seq2 b.fq) [-o out.sam] [-e f] [--min n] [--max n] [--sensitive] [--pbat] [--unmapped_out] [--ambiguous_out] [--bam [--sort [--sort-mem GiB] [--markdup] [--bai] [--methyl prefix [--CpG] [--CHG] [--CHH] [--methyl-min-mapq n] [--methyl-min-phred n] [--methyl-ignore n] [--methyl-ignore-3prime n] [--methyl-ignore-r2 n] [--methyl-ignore-3prime-r2 n] [--mbias] [--methyl-min-opposite-depth n [--methyl-max-variant-frac f]] [--methyl-merge-context] [--methyl-min-depth n] [--cytosine-report [--methyl-report-window bases]]] [--filter-non-conversion] [--non-conversion-threshold n] [--non-conversion-percent p] [--non-conversion-min-count m] [--conversion-report file]]] [--mapstats f] [-t io_threads] [--out-parts n]\n       --cytosine-report: <prefix>.cytosine_report.txt, one line per cytosine of the selected contexts on both strands, covered or not; --methyl-merge-context and --methyl-min-depth shape the bedGraphs only, the report stays per strand and includes depth 0\n       --filter-non-conversion: flag 0x200 on every record of a template with a read that has 3 (--non-conversion-threshold) methylated calls outside CpG, or --non-conversion-percent of at least 5 (--non-conversion-min-count) such calls; --conversion-report: the calls of all examined records and the non-CpG conversion rate\n";
+    "usage: bmbs_search --index <genome.fa> [--index_folder dir] [-t threads]\n       bmbs_search --search <index> (--seq r.fq | --seq1 a.fq --seq2 b.fq) [-o out.sam] [-e f] [--min n] [--max n] [--sensitive] [--pbat] [--unmapped_out] [--ambiguous_out] [--bam [--sort [--sort-mem GiB] [--markdup] [--bai] [--methyl prefix [--CpG] [--CHG] [--CHH] [--methyl-min-mapq n] [--methyl-min-phred n] [--methyl-ignore n] [--methyl-ignore-3prime n] [--methyl-ignore-r2 n] [--methyl-ignore-3prime-r2 n] [--mbias] [--methyl-min-opposite-depth n [--methyl-max-variant-frac f]] [--methyl-merge-context] [--methyl-min-depth n] [--cytosine-report [--methyl-report-window bases]]] [--filter-non-conversion] [--non-conversion-threshold n] [--non-conversion-percent p] [--non-conversion-min-count m] [--conversion-report file]]] [--trim [--trim-quality n] [--trim-adapter SEQ] [--trim-adapter2 SEQ] [--trim-stringency n] [--trim-error-rate f] [--trim-min-length n] [--trim-clip-r1 n] [--trim-clip-r2 n] [--trim-three-prime-clip-r1 n] [--trim-three-prime-clip-r2 n] [--trim-report file]] [--mapstats f] [-t io_threads] [--out-parts n]\n       --trim: quality (20) and adapter (AGATCGGAAGAGC, overlap 1, error rate 0.1) trimming of every read on the device before it is mapped, reads below 20 bases (pairs: either mate) dropped -- trim_galore's defaults; the leftmost accepted adapter start without indels, not cutadapt's best alignment; --trim-adapter sets both mates unless --trim-adapter2 is given, `none` turns the adapter step off, --trim-quality 0 the quality step; --trim-report: the counters of the run, one line per counter and mate\n       --cytosine-report: <prefix>.cytosine_report.txt, one line per cytosine of the selected contexts on both strands, covered or not; --methyl-merge-context and --methyl-min-depth shape the bedGraphs only, the report stays per strand and includes depth 0\n       --filter-non-conversion: flag 0x200 on every record of a template with a read that has 3 (--non-conversion-threshold) methylated calls outside CpG, or --non-conversion-percent of at least 5 (--non-conversion-min-count) such calls; --conversion-report: the calls of all examined records and the non-CpG conversion rate\n";
 
 Options parse_options(int argc, char** argv)
 {
@@ -334,6 +349,35 @@ Options parse_options(int argc, char** argv)
             (pct ? o.ncpar.percent : a == "--non-conversion-threshold" ? o.ncpar.threshold : o.ncpar.min_count) = (int32_t)x;
             o.nonconv_filter = true;
         }
+        else if (a == "--trim") o.trim = true;                         // trim_galore's defaults, on the device (bmbs_set_trim)
+        else if (a == "--trim-adapter" || a == "--trim-adapter2") {
+            std::string v = val();
+            if (v == "none") v.clear();
+            if (v.size() > 32) { fprintf(stderr, "bmbs_search: %s takes at most 32 letters\n", a.c_str()); exit(2); }
+            const bool second = a == "--trim-adapter2";
+            if (second) o.trim_a2_given = true;
+            for (int m = second ? 1 : 0; m < 2; m++) if (m == (second ? 1 : 0) || !o.trim_a2_given) { memset(o.tpar.adapter[m], 0, sizeof o.tpar.adapter[m]); memcpy(o.tpar.adapter[m], v.data(), v.size()); }
+            o.trim_opt_given = true;
+        }
+        else if (a == "--trim-error-rate") {
+            int32_t ppm = 0;
+            if (!methyl_parse_frac(val(), &ppm) || ppm % 1000) refuse("bmbs_search: --trim-error-rate takes a plain decimal in 0..1 with at most 3 digits behind the point\n");
+            o.tpar.error_permille = ppm / 1000;
+            o.trim_opt_given = true;
+        }
+        else if (a == "--trim-report") { o.trim_report = val(); o.trim_opt_given = true; }
+        else if (a == "--trim-quality" || a == "--trim-stringency" || a == "--trim-min-length" || a == "--trim-clip-r1" || a == "--trim-clip-r2" || a == "--trim-three-prime-clip-r1" ||
+                 a == "--trim-three-prime-clip-r2") {
+            const bool q = a == "--trim-quality", len = a == "--trim-min-length", ov = a == "--trim-stringency";
+            const long lo = len || ov ? 1 : 0, hi = q ? 255 : 65535;
+            char* end = nullptr;
+            const char* v = val();
+            const long x = strtol(v, &end, 10);
+            if (end == v || *end || x < lo || x > hi) { fprintf(stderr, "bmbs_search: %s takes %ld..%ld\n", a.c_str(), lo, hi); exit(2); }
+            const int mate = a.back() == '2' ? 1 : 0;                 // (of the four clips)
+            (q ? o.tpar.quality : len ? o.tpar.min_length : ov ? o.tpar.min_overlap : a.find("three-prime") != std::string::npos ? o.tpar.clip_3p[mate] : o.tpar.clip_5p[mate]) = (int32_t)x;
+            o.trim_opt_given = true;
+        }
         else if (a == "--conversion-report") o.conversion_report = val();      // the calls of all examined records, the non-CpG conversion rate
         else if (a == "--help" || a == "-h") { fputs(USAGE, stdout); exit(0); }
         else if (a == "--cytosine-report") o.cytosine_report = true;  // --methyl ... --cytosine-report: Bismark's CX_report, from the device
@@ -354,6 +398,10 @@ Options parse_options(int argc, char** argv)
     if (!o.conversion_report.empty() && !o.sort) refuse("bmbs_search: --conversion-report needs --sort\n");
     o.nonconv = o.nonconv_filter || !o.conversion_report.empty();
     if (!o.nonconv_filter) o.ncpar.threshold = o.ncpar.percent = 0;      // (--conversion-report alone: nothing fails, the totals are still produced)
+    if (o.trim_opt_given && !o.trim) refuse("bmbs_search: --trim-quality, --trim-adapter, --trim-adapter2, --trim-stringency, --trim-error-rate, --trim-min-length, --trim-clip-r1, --trim-clip-r2, --trim-three-prime-clip-r1, --trim-three-prime-clip-r2 and --trim-report need --trim\n");
+    for (int m = 0; m < 2; m++)
+        for (const char* q = o.tpar.adapter[m]; *q; q++)
+            if (!strchr("ACGTacgt", *q)) { fprintf(stderr, "bmbs_search: --trim-adapter%s takes letters of ACGT (or `none`)\n", m ? "2" : ""); exit(2); }
     o.methyl_out = !o.methyl.empty();
     if (o.methyl_out && !o.sort) refuse("bmbs_search: --methyl needs --sort\n");
     if (!o.methyl_out && (mpar.contexts || mpar.min_mapq != 10 || mpar.min_phred != 5)) refuse("bmbs_search: --CpG, --CHG, --CHH, --methyl-min-mapq and --methyl-min-phred need --methyl\n");
@@ -402,6 +450,8 @@ Options parse_options(int argc, char** argv)
     // Process_Reads.cpp:986-1075; Schema.cpp:15102 need_reverse_quality = 1); paired-end input files swap roles
     // (exchange_two_reads, Process_Reads.cpp:1628, called from Bitmapper_main.cpp:169)
     if (o.pbat && o.pe) std::swap(o.seq1, o.seq2);
+    // (... and with them what --trim is told about read 1 and read 2)
+    if (o.pbat && o.pe) { std::swap(o.tpar.clip_5p[0], o.tpar.clip_5p[1]); std::swap(o.tpar.clip_3p[0], o.tpar.clip_3p[1]); std::swap(o.tpar.adapter[0], o.tpar.adapter[1]); }
     o.in1 = o.pe ? o.seq1 : o.seq;
     o.gz_in = Source::is_gz(o.in1.c_str()) || (o.pe && Source::is_gz(o.seq2.c_str()));
     o.live_parts = o.gz_in ? 1 : o.parts;
@@ -553,6 +603,8 @@ int load_index_and_contexts(Run& R)
         for (const auto& s : R.chrom_names) nm.push_back(s.c_str());
         for (bmbs_ctx* c : R.ctxs) if (bmbs_sam_refs(c, nm.data(), (int32_t)nm.size())) { fprintf(stderr, "%s\n", bmbs_last_error(c)); return 1; }
     }
+    if (o.trim)
+        for (bmbs_ctx* c : R.ctxs) if (bmbs_set_trim(c, &o.tpar)) { fprintf(stderr, "bmbs_search: %s\n", bmbs_last_error(c)); return 2; }
     // device memory for the work buffers of a batch, taken while the index loads instead of inside the first calls
     for (bmbs_ctx* c : R.ctxs) (void)bmbs_reserve(c, (uint64_t)o.batch * (uint64_t)o.nf() * (1200 + 3 * (uint64_t)std::max<size_t>(R.est0 / 2, 100)));
     return 0;
@@ -591,6 +643,9 @@ std::string sam_header_text(bool sorted, const std::vector<std::string>& chrom_n
         if (a == "--methyl-ignore" || a == "--methyl-ignore-r2" || a == "--methyl-ignore-3prime" || a == "--methyl-ignore-3prime-r2") { i++; continue; }
         if (a == "--methyl-min-opposite-depth" || a == "--methyl-max-variant-frac" || a == "--methyl-min-depth") { i++; continue; }
         if (a == "--methyl-report-window" || a == "--conversion-report") { i++; continue; }      // (the filter's own options set flags in this file: they stay)
+        // (--trim and its options: a run on trimmed files names none of them, and its output is this run's)
+        if (a == "--trim") continue;
+        if (a.compare(0, 7, "--trim-") == 0) { i++; continue; }
         if (a == "--CpG" || a == "--CHG" || a == "--CHH" || a == "--mbias" || a == "--methyl-merge-context" || a == "--cytosine-report") continue;
         h += a; h += ' ';
     }
@@ -960,6 +1015,20 @@ void gpu_worker(Run& R, bmbs_ctx* own_ctx)
                 if (rc == BMBS_ENOMEM && bytes > b->sam.cap && attempt == 0 && b->sam.need((size_t)bytes + 64)) continue;   // reads longer than guessed
                 if (rc) R.fail(bmbs_last_error(ctx));
                 b->sam_bytes = rc ? 0 : bytes;
+                if (o.trim && !rc) {
+                    // the batch is what trimming left of it, before anything else looks at it
+                    bmbs_trim_counts tc; int64_t kept = 0;
+                    if (bmbs_text_trim_counts(ctx, &tc, &kept)) { R.fail(bmbs_last_error(ctx)); b->sam_bytes = 0; break; }
+                    {
+                        std::lock_guard<std::mutex> l(R.g_mu);
+                        static_assert(sizeof(bmbs_trim_counts) == 19 * sizeof(int64_t), "bmbs_trim_counts is int64_t words and nothing else: they are added up as such");
+                        int64_t* const sum = reinterpret_cast<int64_t*>(&R.trim_cnt); const int64_t* const add = reinterpret_cast<const int64_t*>(&tc);
+                        for (size_t x = 0; x < sizeof tc / sizeof(int64_t); x++) sum[x] += add[x];
+                        R.trim_in += b->n; R.trim_kept += (long)kept;
+                    }
+                    b->n = (long)kept;
+                    if (!kept) { b->sam_bytes = 0; b->n_sorted = 0; b->n_sig = 0; break; }
+                }
                 if (o.sort && !rc) {
                     b->skey.resize((size_t)lines + 1); b->slen.resize((size_t)lines + 1);
                     if (bmbs_text_sorted_index(ctx, b->skey.data(), b->slen.data(), lines, &b->n_sorted)) { R.fail(bmbs_last_error(ctx)); b->sam_bytes = 0; }
@@ -1334,11 +1403,29 @@ void write_conversion_report(Run& R)
     if (fclose(f)) { fprintf(stderr, "bmbs_search: cannot write %s: %s\n", o.conversion_report.c_str(), strerror(errno)); R.failed = true; }
 }
 
+// --trim-report: the counters of all batches, one line per counter and mate (mate 0: the line counts templates)
+void write_trim_report(Run& R)
+{
+    const Options& o = R.o;
+    FILE* f = fopen(o.trim_report.c_str(), "w");
+    if (!f) { fprintf(stderr, "bmbs_search: cannot write %s: %s\n", o.trim_report.c_str(), strerror(errno)); R.failed = true; return; }
+    const bmbs_trim_counts& t = R.trim_cnt;
+    const struct { const char* name; const int64_t* v; } rows[] = {{"records_in", t.records_in}, {"bases_in", t.bases_in}, {"bases_out", t.bases_out},
+        {"quality_records", t.quality_records}, {"quality_bases", t.quality_bases}, {"adapter_records", t.adapter_records}, {"adapter_bases", t.adapter_bases},
+        {"clip_records", t.clip_records}, {"clip_bases", t.clip_bases}};
+    // (--pbat pairs: the files went in swapped; the report speaks of read 1 and read 2 as the command line does)
+    const bool swapped = o.pbat && o.pe;
+    for (const auto& r : rows) for (int m = 0; m < o.nf(); m++) fprintf(f, "%s\t%d\t%lld\n", r.name, m + 1, (long long)r.v[swapped ? 1 - m : m]);
+    fprintf(f, "templates_in\t0\t%ld\ntemplates_kept\t0\t%ld\ntemplates_dropped\t0\t%lld\n", R.trim_in, R.trim_kept, (long long)t.templates_dropped);
+    if (fclose(f)) { fprintf(stderr, "bmbs_search: cannot write %s: %s\n", o.trim_report.c_str(), strerror(errno)); R.failed = true; }
+}
+
 // a failed run leaves no half-made sorted file, index or bedGraph behind
 int give_up(Run& R)
 {
     const Options& o = R.o;
     if (!o.conversion_report.empty()) ::unlink(o.conversion_report.c_str());
+    if (!o.trim_report.empty()) ::unlink(o.trim_report.c_str());
     if (o.methyl_out) for (unsigned x = 0; x < 3; x++) if ((o.mpar.contexts >> x) & 1) ::unlink((o.methyl + "_" + ctx_names[x] + ".bedGraph").c_str());
     if (o.mbias) ::unlink((o.methyl + "_mbias.tsv").c_str());
     if (o.cytosine_report) ::unlink((o.methyl + ".cytosine_report.txt").c_str());
@@ -1354,8 +1441,11 @@ void report(const Run& R, const Pass2& S)
     const Options& o = R.o;
     int64_t st[5];
     bmbs_stats_allreduce(const_cast<bmbs_ctx**>(R.ctxs.data()), (int)R.ctxs.size(), st);      // get_mapping_informations: the counters of every worker summed
+    // (--trim: the statistics count what was mapped; the reads of the dropped templates get a line of their own)
+    const long long trimmed_away = (long long)R.trim_cnt.templates_dropped * o.nf();
     print_stats(stderr, st);
-    if (!o.mapstats.empty()) { FILE* m = fopen(o.mapstats.c_str(), "w"); if (m) { print_stats(m, st); fclose(m); } }
+    if (o.trim) fprintf(stderr, "%-48s%lld\n", "No. of Reads Removed by Trimming:", trimmed_away);
+    if (!o.mapstats.empty()) { FILE* m = fopen(o.mapstats.c_str(), "w"); if (m) { print_stats(m, st); if (o.trim) fprintf(m, "%-48s%lld\n", "No. of Reads Removed by Trimming:", trimmed_away); fclose(m); } }
     const double t_end = now();
     if (!o.verbose) return;
     long total_records = 0;
@@ -1443,6 +1533,7 @@ int main(int argc, char** argv)
     if (o.bai && !R.failed) write_bai(R, S);
     if (o.methyl_out && !R.failed) write_methyl(R, S);
     if (!o.conversion_report.empty() && !R.failed) write_conversion_report(R);
+    if (!o.trim_report.empty() && !R.failed) write_trim_report(R);
     if (R.failed) return give_up(R);
     report(R, S);
     teardown(R);

@@ -7,6 +7,7 @@
 #include "bmbs_host.h"
 #define DEVI __device__ __forceinline__
 #include "bmbs_text.hip"
+#include "k_trim.hip"
 #include "bmbs_bam.hip"
 #include "bmbs_inflate.hip"
 #include "k_bamsort.hip"
@@ -140,15 +141,91 @@ int text_index(Lane* c, DevBuf& dtext, u64 bytes, u64 n_cap, int f)
     hipLaunchKernelGGL(k_fq_lines, dim3((unsigned)tiles), dim3(FQ_TILE_THREADS), 0, c->stream, dtext.as<char>(), bytes, c->tx_tileoff.as<u64>(), 4 * n_cap, c->tx_nl[f].as<u32>());
     return BMBS_OK;
 }
-// the per-record field arrays of n records of file f
-int fq_rec_setup(Lane* c, u64 n, int f, FqRec& rec)
+// the per-record field arrays of n records, in `buf`; fq_rec_setup: those of file f that k_fq_records writes
+static int fq_rec_carve(Lane* c, DevBuf& buf, u64 n, FqRec& rec)
 {
     const u64 n4 = (n * 4 + 63) & ~63ull, n2 = (n * 2 + 63) & ~63ull;
-    ENS(c, c->tx_rec[f], 3 * n4 + 3 * n2 + 64);
-    char* b = c->tx_rec[f].as<char>();
+    ENS(c, buf, 3 * n4 + 3 * n2 + 64);
+    char* b = buf.as<char>();
     rec.seq_off = reinterpret_cast<u32*>(b); rec.qual_off = reinterpret_cast<u32*>(b + n4); rec.name_off = reinterpret_cast<u32*>(b + 2 * n4);
     rec.seq_len = reinterpret_cast<u16*>(b + 3 * n4); rec.qual_len = reinterpret_cast<u16*>(b + 3 * n4 + n2); rec.name_len = reinterpret_cast<u16*>(b + 3 * n4 + 2 * n2);
     return BMBS_OK;
+}
+int fq_rec_setup(Lane* c, u64 n, int f, FqRec& rec) { return fq_rec_carve(c, c->tx_rec[f], n, rec); }
+
+// ---- the trim stage of a text call (k_trim.hip; bmbs_set_trim): behind k_fq_records, in front of everything that reads a record
+// A 5' clip moves a line's start by up to a read's length, behind the end of a quality line that is shorter than that: while trimming
+// is on, the text buffers carry 1 KiB more beyond the window, so that a range computed from such a start (k_line_write's staging) stays
+// inside them.  With trimming off they are sized as ever.
+#define TEXT_PAD 64
+#define TEXT_PAD_TRIM 1024
+static u64 text_pad(const Lane* c) { return TEXT_PAD + (c->trim.on ? TEXT_PAD_TRIM : 0); }
+// what k_fq_trim is told about the records of mate m
+static TrimArgs trim_args(const Lane* c, int m, int min_length)
+{
+    const bmbs_trim_opts& o = c->trim.opts;
+    TrimArgs a = {};
+    char ad[32] = {};
+    a.alen = (int)strlen(o.adapter[m]);
+    for (int j = 0; j < a.alen; j++) ad[j] = (char)(o.adapter[m][j] & ~32);
+    memcpy(a.ad, ad, sizeof ad);
+    a.quality = o.quality; a.base = c->prm.q_base; a.min_overlap = o.min_overlap; a.error_permille = o.error_permille;
+    a.clip5 = o.clip_5p[m]; a.clip3 = o.clip_3p[m]; a.min_length = min_length;
+    return a;
+}
+// the counters zeroed, then the records of one file (mate m) trimmed in place: their keep bytes in tr_keep (file f: behind file 0's)
+static int trim_begin(Lane* c, u64 n)
+{
+    ENS(c, c->tr_words, TRW_WORDS * sizeof(u64)); ENS(c, c->tr_keep, 2 * ((n + 63) & ~63ull) + 64);
+    HIPCHK(c, hipMemsetAsync(c->tr_words.p, 0, TRW_WORDS * sizeof(u64), c->stream));
+    return BMBS_OK;
+}
+static u8* trim_keep_of(Lane* c, u64 n, int f) { return c->tr_keep.as<u8>() + (f ? (n + 63) & ~63ull : 0); }
+static void trim_file(Lane* c, const char* text, const FqRec& rec, u64 n, int f, int m, int min_length)
+{
+    prof_begin(c, "k_fq_trim");
+    hipLaunchKernelGGL(k_fq_trim, dim3(nblk(n, TRIM_RECS)), dim3(TRIM_BLOCK), 0, c->stream, text, rec, (long)n, trim_args(c, m, min_length), trim_keep_of(c, n, f),
+                       c->tr_words.as<unsigned long long>() + TRW_PER_MATE * m);
+    prof_end(c);
+}
+// every record trimmed, the templates that stay compacted into the second set of arrays, which `rec` names from here on; the kept
+// count is left in TOT_TRIM_KEPT, the counters and the two lengths in tr_words.  No wait
+static int trim_stage(Lane* c, bool pe, u64 n, FqRec* rec)
+{
+    const int nf = pe ? 2 : 1;
+    int rc = trim_begin(c, n);
+    if (rc) return rc;
+    ENS(c, c->tr_flag, n * 4 + 64); ENS(c, c->tr_off, (n + 1) * 8 + 64);
+    const char* const text[2] = {c->fq_text1.as<char>(), c->fq_text2.as<char>()};
+    for (int f = 0; f < nf; f++) trim_file(c, text[f], rec[f], n, f, f, c->trim.opts.min_length);
+    hipLaunchKernelGGL(k_trim_keep, dim3(nblk(n, 256)), dim3(256), 0, c->stream, trim_keep_of(c, n, 0), pe ? trim_keep_of(c, n, 1) : (const u8*)nullptr, (long)n, c->tr_flag.as<u32>());
+    rc = scan_u32(c, c->tr_flag.as<u32>(), n, c->tr_off.as<u64>(), TOT_TRIM_KEPT);
+    if (rc) return rc;
+    unsigned long long* const w = c->tr_words.as<unsigned long long>();
+    for (int f = 0; f < nf; f++) {
+        FqRec dst;
+        rc = fq_rec_carve(c, c->tr_rec[f], n, dst);
+        if (rc) return rc;
+        prof_begin(c, "k_fq_compact");
+        hipLaunchKernelGGL(k_fq_compact, dim3(nblk(n, 256)), dim3(256), 0, c->stream, rec[f], dst, c->tr_flag.as<u32>(), c->tr_off.as<u64>(), (long)n,
+                           w + TRW_PER_MATE * f + TRW_BASES_OUT, w + TRW_MAX_LEN);
+        prof_end(c);
+        rec[f] = dst;
+    }
+    return BMBS_OK;
+}
+// the counters of a call as the device left them (h_info->trim) -> the caller's form
+static void trim_counts_from(const u64* w, bool pe, u64 n_in, u64 kept, bmbs_trim_counts* o)
+{
+    memset(o, 0, sizeof *o);
+    for (int m = 0; m < (pe ? 2 : 1); m++) {
+        const u64* x = w + TRW_PER_MATE * m;
+        o->records_in[m] = (int64_t)x[TRW_RECORDS_IN]; o->bases_in[m] = (int64_t)x[TRW_BASES_IN]; o->bases_out[m] = (int64_t)x[TRW_BASES_OUT];
+        o->quality_records[m] = (int64_t)x[TRW_Q_RECORDS]; o->quality_bases[m] = (int64_t)x[TRW_Q_BASES];
+        o->adapter_records[m] = (int64_t)x[TRW_A_RECORDS]; o->adapter_bases[m] = (int64_t)x[TRW_A_BASES];
+        o->clip_records[m] = (int64_t)x[TRW_C_RECORDS]; o->clip_bases[m] = (int64_t)x[TRW_C_BASES];
+    }
+    o->templates_dropped = (int64_t)(n_in - kept);
 }
 // D2H in pieces: one 2 GiB device-to-host copy ran at a quarter of the link rate on the MI355X boxes (tools/pcie_probe)
 int d2h_chunked(Lane* c, char* dst, const char* src, u64 bytes, hipStream_t st)
@@ -299,6 +376,15 @@ struct TextCall {
         if (lines[0] < 4 * n || (pe && lines[1] < 4 * n)) { c->err = "text call: a window holds fewer than 4 lines per record"; return BMBS_EINVAL; }
         for (int f = 0; f < (pe ? 2 : 1); f++)
             hipLaunchKernelGGL(k_fq_records, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->tx_nl[f].as<u32>(), (long)n, rec[f], line_info(c) + TXI_FQ_WORDS * f);
+        // trimming (bmbs_set_trim): the records rewritten and compacted before anybody reads them; its words come back with k_fq_records'
+        const bool trim = c->trim.on;
+        c->trim.counted = false;
+        if (trim) {
+            const int rc = trim_stage(c, pe, n, rec);
+            if (rc) return rc;
+            HIPCHK(c, hipMemcpyAsync(&c->h_info->trim_kept, tot_at(c, TOT_TRIM_KEPT), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(c->h_info->trim, c->tr_words.p, sizeof c->h_info->trim, hipMemcpyDeviceToHost, c->stream));
+        }
         HIPCHK(c, hipMemcpyAsync(c->h_info->line, line_info(c), sizeof c->h_info->line, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         t.records = wall();
@@ -310,6 +396,14 @@ struct TextCall {
             }
         *maxL = (int)inf[0]; *minL = (int)~inf[1];
         if (pe) { *maxL = std::max(*maxL, (int)inf2[0]); *minL = std::min(*minL, (int)~inf2[1]); }
+        if (trim) {
+            // the batch is the templates that stay, from here on
+            const u64 kept = c->h_info->trim_kept;
+            trim_counts_from(c->h_info->trim, pe, n, kept, &c->trim.cnt);
+            c->trim.kept = (int64_t)kept; c->trim.counted = true;
+            n = kept; n2 = pe ? 2 * kept : kept;
+            *maxL = (int)c->h_info->trim[TRW_MAX_LEN]; *minL = (int)~(u32)c->h_info->trim[TRW_MIN_LEN_C];
+        }
         return BMBS_OK;
     }
     // rows and mapping: the records are in out_res / cig_pool when this returns, and `in` names them for the kernels of every ending
@@ -465,6 +559,8 @@ int lane_text_finish(Lane* c, bool pe, u64 bytes1, u64 bytes2, int64_t n_records
     TextCall T = {c, pe, bytes1 + bytes2, n, pe ? 2 * n : n, flags_in, sam, sam_cap, sam_bytes, n_lines_out, t0, {}, 0, {}};
     int maxL = 0, minL = 0;
     int rc = T.records(&maxL, &minL);
+    // trimming left nothing: as a call without records (no mapping launch sees an empty batch)
+    if (!rc && !T.n) { if (flags_in & BMBS_TEXT_BAM_SORTED) c->st.holds(0, 0, pe); return BMBS_OK; }
     if (!rc) rc = T.map(maxL, minL == maxL);
     if (rc) return rc;
     if (!(flags_in & BMBS_TEXT_BAM)) return T.emit_sam();
@@ -480,6 +576,7 @@ static int text_call_begin(Lane* c, int32_t flags_in, u64* sam_bytes, int64_t* n
 {
     if (sam_bytes) *sam_bytes = 0;
     if (n_lines_out) *n_lines_out = 0;
+    c->trim.counted = false;                            // (bmbs_text_trim_counts describes THIS call from here on, whatever becomes of it)
     if ((flags_in & BMBS_TEXT_BAM_SORTED) && !(flags_in & BMBS_TEXT_BAM)) { c->err = "text call: BMBS_TEXT_BAM_SORTED is only valid together with BMBS_TEXT_BAM"; return BMBS_EINVAL; }
     if (flags_in & BMBS_TEXT_BAM_SORTED) c->ends(Lane::SORTED_TEXT_CALL);
     return BMBS_OK;
@@ -500,8 +597,8 @@ int lane_map_text(Lane* c, bool pe, const char* text1, u64 bytes1, const char* t
     c->open_text.valid = false;
     TextClock t; t.start = wall();
     HIPCHK(c, hipMemsetAsync(c->tx_info.p, 0, TXI_WORDS * sizeof(u32), c->stream));
-    ENS(c, c->fq_text1, bytes1 + 64);
-    if (pe) ENS(c, c->fq_text2, bytes2 + 64);
+    ENS(c, c->fq_text1, bytes1 + text_pad(c));
+    if (pe) ENS(c, c->fq_text2, bytes2 + text_pad(c));
     {
         // the link is claimed for the copies alone: the kernels behind them may have to queue behind other contexts' kernels
         std::lock_guard<std::mutex> up(g_h2d_mu[c->dev & 15]);
@@ -648,7 +745,7 @@ int lane_text_open_bgzf(Lane* c, const bmbs_ztext* z1, const bmbs_ztext* z2, int
         // window from its 16-byte aligned start)
         a.bytes = z->prefix_bytes + (nb ? z->out_off[nb] : 0);
         if (a.bytes + 1 >= (1ull << 32)) { c->err = "a text window has to be smaller than 4 GiB (32-bit offsets)"; return BMBS_EINVAL; }
-        ENS(c, *a.text, a.bytes + 64 + 16);
+        ENS(c, *a.text, a.bytes + text_pad(c) + 16);
         if (nb) { ENS(c, *a.comp, z->comp_bytes + 1024); ENS(c, *a.off, 2 * (nb + 1) * 8 + 64); ENS(c, *a.err, nb * 4 + 64); }
     }
     for (int f = 0; f < (pe ? 2 : 1); f++) { const int rc = ztext_inflate(c, A[f], f, last[f], fs[f]); if (rc) return rc; }
@@ -675,6 +772,9 @@ int lane_text_map_open(Lane* c, int32_t flags_in, char* sam, u64 sam_cap, u64* s
     if (!c->open_text.valid) { c->err = "text map: no open batch (bmbs_text_open_bgzf first)"; return BMBS_ESTATE; }
     if (c->n_refs != c->ix.n_chrom) { c->err = "bmbs_sam_refs has not been given the index's reference names"; return BMBS_ESTATE; }
     if (!sam) { c->err = "text call: NULL buffer"; return BMBS_EINVAL; }
+    if (c->trim.on && (c->fq_text1.cap < c->open_text.bytes1 + text_pad(c) || (c->open_text.pe && c->fq_text2.cap < c->open_text.bytes2 + text_pad(c)))) {
+        c->err = "text map: the batch was opened before trimming was turned on (bmbs_set_trim comes before bmbs_text_open_bgzf)"; return BMBS_ESTATE;
+    }
     HIPCHK(c, hipSetDevice(c->dev));
     TextClock t; t.start = t.uploaded = wall();
     // (an output buffer that turns out too small leaves the batch open: the call can be repeated)
@@ -682,6 +782,77 @@ int lane_text_map_open(Lane* c, int32_t flags_in, char* sam, u64 sam_cap, u64* s
     if (rc != BMBS_ENOMEM) c->open_text.valid = false;
     return rc;
 }
+
+// ---- trimming: the options, the last call's counters, the stage alone
+static int trim_opts_check(std::string& err, const bmbs_trim_opts* o)
+{
+    if (o->quality < 0 || o->min_overlap < 0 || o->error_permille < 0 || o->min_length < 0 || o->clip_5p[0] < 0 || o->clip_5p[1] < 0 || o->clip_3p[0] < 0 || o->clip_3p[1] < 0) {
+        err = "trim options: a negative value"; return BMBS_EINVAL;
+    }
+    if (o->min_length < 1) { err = "trim options: min_length has to be at least 1"; return BMBS_EINVAL; }
+    if (o->error_permille > 1000) { err = "trim options: error_permille outside 0..1000"; return BMBS_EINVAL; }
+    if (o->quality > 255) { err = "trim options: quality above 255"; return BMBS_EINVAL; }
+    for (int m = 0; m < 2; m++) {
+        if (o->clip_5p[m] > 65535 || o->clip_3p[m] > 65535) { err = "trim options: a clip above 65535"; return BMBS_EINVAL; }
+        if (!memchr(o->adapter[m], 0, sizeof o->adapter[m])) { err = "trim options: an adapter of more than 32 letters"; return BMBS_EINVAL; }
+        for (const char* p = o->adapter[m]; *p; p++)
+            if (!strchr("ACGTacgt", *p)) { err = std::string("trim options: adapter letter '") + *p + "' of mate " + std::to_string(m + 1) + " is not one of ACGT"; return BMBS_EINVAL; }
+    }
+    return BMBS_OK;
+}
+extern "C" int bmbs_set_trim(bmbs_ctx* X, const bmbs_trim_opts* opts)
+{
+    if (!X) return BMBS_EINVAL;
+    if (opts) { const int rc = trim_opts_check(X->err, opts); if (rc) return rc; }
+    for (Lane* c : X->lanes) { c->trim.on = opts != nullptr; if (opts) c->trim.opts = *opts; }
+    return BMBS_OK;
+}
+extern "C" int bmbs_text_trim_counts(bmbs_ctx* X, bmbs_trim_counts* counts, int64_t* n_kept)
+{
+    Lane* c = lane0(X);
+    if (!c) return BMBS_EINVAL;
+    if (!c->trim.counted) { c->err = "trim counts: the context has made no text call with trimming on"; return fin(X, c, BMBS_ESTATE); }
+    if (counts) *counts = c->trim.cnt;
+    if (n_kept) *n_kept = c->trim.kept;
+    return BMBS_OK;
+}
+static int lane_trim_text(Lane* c, const char* text, u64 bytes, int64_t n_records, int32_t mate, uint32_t* seq_off, uint32_t* qual_off, uint16_t* seq_len, uint16_t* qual_len)
+{
+    if (!c->trim.on) { c->err = "trim text: trimming is off (bmbs_set_trim)"; return BMBS_ESTATE; }
+    if (n_records <= 0) return BMBS_OK;
+    if (!text || !seq_off || !qual_off || !seq_len || !qual_len || mate < 0 || mate > 1) { c->err = "trim text: bad argument"; return BMBS_EINVAL; }
+    if (bytes >= (1ull << 32)) { c->err = "a text window has to be smaller than 4 GiB (32-bit offsets)"; return BMBS_EINVAL; }
+    HIPCHK(c, hipSetDevice(c->dev));
+    { const int rs = lane_settle(c); if (rs) return rs; }
+    c->open_text.valid = false;                     // (the window of an open batch is overwritten)
+    const u64 n = (u64)n_records;
+    HIPCHK(c, hipMemsetAsync(c->tx_info.p, 0, TXI_WORDS * sizeof(u32), c->stream));
+    ENS(c, c->fq_text1, bytes + text_pad(c));
+    HIPCHK(c, hipMemcpyAsync(c->fq_text1.p, text, bytes, hipMemcpyHostToDevice, c->stream));
+    int rc = text_index(c, c->fq_text1, bytes, n, 0);
+    if (rc) return rc;
+    FqRec rec;
+    rc = fq_rec_setup(c, n, 0, rec);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->h_info->lines, tot_at(c, TOT_LINES_1), sizeof c->h_info->lines, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->h_info->lines[0] < 4 * n) { c->err = "trim text: the text holds fewer than 4 lines per record"; return BMBS_EINVAL; }
+    hipLaunchKernelGGL(k_fq_records, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->tx_nl[0].as<u32>(), (long)n, rec, line_info(c));
+    rc = trim_begin(c, n);
+    if (rc) return rc;
+    trim_file(c, c->fq_text1.as<char>(), rec, n, 0, mate, 1);
+    HIPCHK(c, hipMemcpyAsync(c->h_info->line, line_info(c), sizeof c->h_info->line, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(seq_off, rec.seq_off, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(qual_off, rec.qual_off, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(seq_len, rec.seq_len, n * 2, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(qual_len, rec.qual_len, n * 2, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->h_info->line[2]) { c->err = "record " + std::to_string(c->h_info->line[2] - 1) + " of this text has an empty or longer-than-" + std::to_string(BMBS_MAX_READ) + "-character sequence line"; return BMBS_EINVAL; }
+    return BMBS_OK;
+}
+extern "C" int bmbs_trim_text(bmbs_ctx* X, const char* text, uint64_t text_bytes, int64_t n_records, int32_t mate, uint32_t* seq_off, uint32_t* qual_off,
+                              uint16_t* seq_len, uint16_t* qual_len)
+{ ON_LANE0(lane_trim_text(c, text, text_bytes, n_records, mate, seq_off, qual_off, seq_len, qual_len)); }
 
 // RNAME table of the SAM text: the names behind the index's sequences, in index order
 int lane_sam_refs(Lane* c, const char* const* names, int n_names)

@@ -50,6 +50,11 @@ enum Tot : int {
     TOT_LINES_2 = 17,        // file 1 / file 2 (tot_file)
     TOT_SAM_BYTES = 18,      // SAM text of the batch               k_sam_len's scan               lane_text_finish
     TOT_BAM_BYTES = 19,      // BAM records of the batch            k_bam_len's scan               lane_text_finish; k_bgzf_block (bgzf_deflate's total_ptr)
+    // One word, two uses, one behind the other in a text call.  --trim: the templates the length filter keeps -- written by the scan of
+    // k_trim_keep's flags (trim_stage), read by TextCall::records behind the wait it has anyway, with the lane's trim words.  Then the
+    // compressed bytes of the call's blocks: bgzf_deflate runs behind the mapping, long after records() has read the first use.  (The
+    // array keeps its size and every other word its place: a call with trimming off must not differ from what it was.)
+    TOT_TRIM_KEPT = 20,
     TOT_BGZF_BYTES = 20,     // compressed bytes of the blocks      bgzf_deflate's scan            bgzf_deflate
     TOT_NL_ADDED_1 = 21,     // 1: the window of file 1 / file 2    k_close_last_line or a         lane_text_open_bgzf (both words, one copy, behind a wait for
     TOT_NL_ADDED_2 = 22,     // got a last newline (tot_file)       memset, on the FILE's stream   file 2's stream)
@@ -117,6 +122,27 @@ static_assert(sizeof(CallWords) == BMBS_SLOT_WORDS * 8 && offsetof(CallWords, fl
 #define TXI_CYT_WORDS  6     // k_cyt_check: one word per kind of refusal
 static_assert(2 * TXI_FQ_WORDS <= TXI_HALF_WORDS && TXI_DUP_COUNT >= 3 * 2 && TXI_DUP_COUNT < TXI_HALF_WORDS && TXI_METH_EMIT + 4 <= TXI_HALF_WORDS && TXI_CYT_WORDS <= TXI_HALF_WORDS, "the halves hold their kernels' words");
 
+// ---- Lane::tr_words: what the trim stage of a text call (k_trim.hip; bmbs_set_trim) counts.  trim_stage zeroes the array on the lane's
+// stream before its first kernel; k_fq_trim (one launch per file: mate m adds to the words TRW_PER_MATE * m + ...) and k_fq_compact add
+// to it with 64-bit atomics; TextCall::records copies it to h_info->trim behind the wait it has anyway.  The counters belong to the call:
+// a call repeated after BMBS_ENOMEM starts from zero again.
+enum TrimWord : int {
+    TRW_RECORDS_IN = 0,      // records k_fq_trim saw
+    TRW_BASES_IN = 1,        // ... and their bases
+    TRW_Q_RECORDS = 2,       // records the quality step shortened, and by how many bases
+    TRW_Q_BASES = 3,
+    TRW_A_RECORDS = 4,       // ... the adapter step
+    TRW_A_BASES = 5,
+    TRW_C_RECORDS = 6,       // ... the fixed clips
+    TRW_C_BASES = 7,
+    TRW_TRIM_COUNTERS = 8,   // (what k_fq_trim tallies in LDS)
+    TRW_BASES_OUT = 8,       // k_fq_compact: bases of the records that stay
+    TRW_PER_MATE = 9,
+    TRW_MAX_LEN = 2 * TRW_PER_MATE,          // k_fq_compact, both files: the longest read that stays (atomic max),
+    TRW_MIN_LEN_C = 2 * TRW_PER_MATE + 1,    // and the complement of the shortest (atomic max; 0: nothing stays)
+    TRW_WORDS = 2 * TRW_PER_MATE + 2
+};
+
 // ---- Lane::h_info: the page-locked block the text calls and the record stages read their words from.  No kernel sees it; one field
 // per use.  The uses that share bytes: `line` (one text call's k_fq_records, then its k_bam_len), `stage` (every stage's u32 words),
 // `out_bytes` (SAM or BAM), `z_bytes` (two callers of bgzf_deflate), `meth_eoff` (two reads of one slice).  That is safe because each
@@ -137,5 +163,7 @@ struct HostInfo {
     uint64_t meth_events;               // TOT_METH_EVENTS
     uint64_t meth_heads;                // TOT_METH_HEADS
     uint64_t cyt[2];                    // TOT_CYT_BYTES, _LINES
+    uint64_t trim_kept;                 // TOT_TRIM_KEPT
+    uint64_t trim[TRW_WORDS];           // Lane::tr_words as a text call's trim stage left them
 };
 #endif

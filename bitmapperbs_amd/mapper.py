@@ -332,6 +332,54 @@ class Mapper:
         self._chk(self._lib.bmbs_text_map_open(self._ctx, flags, capi.ptr(out), cap, C.byref(used), C.byref(lines)))
         return out[:used.value].tobytes()
 
+    # trim_galore's defaults (bmbs_search --trim)
+    TRIM_DEFAULTS = dict(quality=20, adapter="AGATCGGAAGAGC", adapter2=None, min_overlap=1, error_permille=100, min_length=20,
+                         clip_5p=(0, 0), clip_3p=(0, 0))
+
+    def set_trim(self, **opts):
+        """adapter and quality trimming in map_text / text_map_open (bmbs_set_trim; the rule: include/bmbs.h, tests/trim_spec.py).
+        set_trim(off=True) turns it off; otherwise the keywords of TRIM_DEFAULTS replace trim_galore's defaults: quality (0: no
+        quality step), adapter / adapter2 (mate 1 / mate 2; adapter2 None: mate 1's; "": no adapter step), min_overlap,
+        error_permille, min_length, clip_5p / clip_3p (a pair, or one number for both mates)"""
+        if opts.pop("off", False):
+            assert not opts
+            self._chk(self._lib.bmbs_set_trim(self._ctx, None))
+            return
+        o = dict(self.TRIM_DEFAULTS)
+        for k, v in opts.items():
+            if k not in o:
+                raise TypeError("set_trim: unknown option %r" % k)
+            o[k] = v
+        t = capi.TrimOpts()
+        t.quality, t.min_overlap, t.error_permille, t.min_length = int(o["quality"]), int(o["min_overlap"]), int(o["error_permille"]), int(o["min_length"])
+        for name in ("clip_5p", "clip_3p"):
+            v = o[name] if isinstance(o[name], (tuple, list)) else (o[name], o[name])
+            getattr(t, name)[0], getattr(t, name)[1] = int(v[0]), int(v[1])
+        ads = (o["adapter"] or "", o["adapter"] or "" if o["adapter2"] is None else o["adapter2"])
+        for m, a in enumerate(ads):
+            if len(a) > 32:
+                raise ValueError("set_trim: an adapter has at most 32 letters (bmbs_trim_opts holds no more)")
+            t.adapter[m].value = a.encode()
+        self._chk(self._lib.bmbs_set_trim(self._ctx, C.byref(t)))
+
+    def trim_counts(self):
+        """(counters, kept) of the last map_text / text_map_open call with trimming on (bmbs_text_trim_counts): counters = a dict of
+        capi.TRIM_COUNTERS -> (mate 1, mate 2) and "templates_dropped"; kept = the templates that were mapped"""
+        cnt = capi.TrimCounts(); kept = C.c_int64(0)
+        self._chk(self._lib.bmbs_text_trim_counts(self._ctx, C.byref(cnt), C.byref(kept)))
+        d = {k: (int(getattr(cnt, k)[0]), int(getattr(cnt, k)[1])) for k in capi.TRIM_COUNTERS}
+        d["templates_dropped"] = int(cnt.templates_dropped)
+        return d, int(kept.value)
+
+    def trim_text(self, text: bytes, n: int, mate: int = 0):
+        """the trim stage alone (bmbs_trim_text): (seq_off u32[n], qual_off u32[n], seq_len u16[n], qual_len u16[n]) of the n records of
+        `text`, read as mate `mate`, after the quality, adapter and clip steps and before the length filter"""
+        a = np.frombuffer(text, dtype=np.uint8)
+        so = np.zeros(max(1, n), dtype=np.uint32); qo = np.zeros(max(1, n), dtype=np.uint32)
+        sl = np.zeros(max(1, n), dtype=np.uint16); ql = np.zeros(max(1, n), dtype=np.uint16)
+        self._chk(self._lib.bmbs_trim_text(self._ctx, capi.ptr(a), a.size, n, int(mate), capi.ptr(so), capi.ptr(qo), capi.ptr(sl), capi.ptr(ql)))
+        return so[:n], qo[:n], sl[:n], ql[:n]
+
     def sorted_index(self):
         """(keys u64[n], lengths u32[n]) of the records the last map_text / text_map_open call with TEXT_BAM | TEXT_BAM_SORTED returned, in
         the order returned (bmbs_text_sorted_index)"""

@@ -375,6 +375,54 @@ int bmbs_text_open_bgzf(bmbs_ctx*, const bmbs_ztext* mate1, const bmbs_ztext* ma
  * also carried a device form of that scheme, bmbs_inflate_gzip / bmbs_text_open_gzip: exact, and slower than the host's; removed in round 5.) */
 int bmbs_text_map_open(bmbs_ctx*, int32_t flags, char* sam, uint64_t sam_cap, uint64_t* sam_bytes, int64_t* n_lines);
 
+/* ---- adapter and quality trimming of the reads of a text call, on the device (csrc/k_trim.hip; bmbs_search --trim) ------------------
+ * What a pipeline otherwise runs trim_galore / cutadapt for before it maps.  bmbs_set_trim turns it on for the text calls of the context
+ * (bmbs_map_se_text, bmbs_map_pe_text, bmbs_text_map_open; NULL turns it off): every record of a batch is trimmed behind the line index,
+ * templates that end up too short are dropped, and the rows, the mapping, the statistics, the SAM / BAM records, the sort and everything
+ * that describes the last sorted call (bmbs_text_sorted_index / _dup / _clip / _nonconv) see the remaining batch: the output is byte for
+ * byte what the same call without trimming gives on a FASTQ text from which a host trimmer following the rule below removed and
+ * shortened those records.  *n_lines counts the remaining templates' lines.  A batch that bmbs_text_open_bgzf opened while trimming was
+ * off cannot be mapped with it on (BMBS_ESTATE: the window's buffer is sized when it is opened): bmbs_set_trim comes first.  The calls whose caller owns the read lengths (the row,
+ * packed and bmbs_map_*_fastq calls) are not touched.  M-bias cycles and methylation read-end trimming count from the trimmed read's
+ * first base, as Bismark's do behind trim_galore.
+ * The rule, for a record of mate m (0 / 1) with L sequence characters (exact integer arithmetic; bases are upper-cased for comparison
+ * only, a quality character missing from a short quality line counts as ' '); the steps in this order:
+ *   1. quality (quality = c > 0; cutadapt -q, the BWA rule, 3' end only): s = 0, best = 0, stop = L; for i = L-1 down to 0:
+ *      s += c - (q[i] - q_base); if s < 0 stop looking; if s > best { best = s; stop = i }.  L = stop.  q_base: bmbs_params.q_base
+ *   2. 3' adapter (adapter[m] = 1..32 letters of ACGT; empty: no adapter step for that mate): a start i in [0, L) has the overlap
+ *      o = min(|A|, L - i) and mm = the number of j < o with upper(s[i + j]) != A[j] (a read's N matches nothing); it is accepted iff
+ *      o >= min_overlap and mm <= o * error_permille / 1000 (integer division).  L = the SMALLEST accepted i.
+ *      Not cutadapt's choice: cutadapt takes the best-scoring alignment and allows indels by default; here it is the leftmost
+ *      accepted start, without indels
+ *   3. fixed clips: L -= min(L, clip_3p[m]); k = min(L, clip_5p[m]): both lines begin k characters later, L -= k, and the quality
+ *      line keeps clamp(qual_len - k, 0, L) characters
+ *   4. length filter (trim_galore --length without --retain_unpaired; min_length >= 1): a single-end record with L < min_length is
+ *      dropped, a pair when either mate is
+ * Not done: adapter auto-detection, 5' and anchored adapters, indels, --nextseq poly-G trimming, RRBS's two extra bases,
+ * --retain_unpaired, writing trimmed FASTQ files.
+ * BMBS_EINVAL (bmbs_last_error says why): an adapter letter outside ACGT (lower case is accepted), an adapter of more than 32 letters,
+ * min_length < 1, error_permille outside 0..1000, a negative value, quality above 255 or a clip above 65535.                       */
+typedef struct bmbs_trim_opts {
+    int32_t quality, min_overlap, error_permille, min_length;
+    int32_t clip_5p[2], clip_3p[2];
+    char    adapter[2][33];        /* NUL-terminated */
+} bmbs_trim_opts;
+/* what the trim stage of the context's last text call did, per mate: the records it saw and their bases, the records each step
+ * shortened and by how many bases, the bases of the records that stayed; and the templates the length filter dropped.  The counters
+ * belong to the call, not to the running statistics: a call repeated after BMBS_ENOMEM counts anew.                                 */
+typedef struct bmbs_trim_counts {
+    int64_t records_in[2], bases_in[2], bases_out[2];
+    int64_t quality_records[2], quality_bases[2], adapter_records[2], adapter_bases[2], clip_records[2], clip_bases[2];
+    int64_t templates_dropped;
+} bmbs_trim_counts;
+int bmbs_set_trim(bmbs_ctx*, const bmbs_trim_opts* opts /* NULL: off */);
+/* *n_kept = the templates of that call that stayed.  BMBS_ESTATE when the context has made no text call or trimming was off in it. */
+int bmbs_text_trim_counts(bmbs_ctx*, bmbs_trim_counts* counts, int64_t* n_kept);
+/* The stage alone: the four fields of every record of `text` (n_records * 4 lines, read as mate `mate`) after steps 1-3 and BEFORE the
+ * filter -- a length of 0 is allowed here.  Needs no attached index; BMBS_ESTATE when trimming is off.                              */
+int bmbs_trim_text(bmbs_ctx*, const char* text, uint64_t text_bytes, int64_t n_records, int32_t mate, uint32_t* seq_off,
+                   uint32_t* qual_off, uint16_t* seq_len, uint16_t* qual_len);
+
 /* ---- coordinate-sorted BAM: the records are sorted on the device (csrc/k_bamsort.hip) ---------------------------------------------------
  * The sort key of a BAM record -- refID = the int32 at byte 4 of the record (counting its block_size word), pos = the int32 at byte 8,
  * flag = the uint16 at byte 18 -- is
